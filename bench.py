@@ -3,13 +3,18 @@
 discriminator forward + backward + Adam) at batch 64 per GPU, fp32, 12 RRDB -- BASELINE.json `metric`,
 config "1xMI355X full ESRGAN ... batch 64, fp32" (the reference has no VGG/perceptual branch: SURVEY.md section 0).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One rank per GPU; per-GPU work is fixed (weak scaling): rank r trains on its own 64 synthetic tiles
 (np.random.RandomState(42 + r).rand, the reference's fixture recipe, srgan_train.py:1101-1105) and gradients are
 summed with one RCCL all-reduce per optimizer step.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the benchmark
+measures (roofline brackets and per-shape tables, the inference sweep, one whole continent, the one-forward and per-minibatch
+read-back variants, the CPU baselines), all outside the timed region.  --dump-outputs DIR writes what the last timed step
+computed (last_step_outputs) as DIR/<name>.npy; inputs and initial weights are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import ctypes as C
@@ -42,6 +47,8 @@ TABLES_PATH = os.path.join(ROOT, "bench_tables.json")   # the per-shape tables o
 # environment switches of libdbm_measure.so (built by tools/build_measure.sh with -DDBM_MEASURE) that SKIP work: a run with
 # one of them set is not a measurement of the iteration and bench.py refuses it
 WORK_SKIPPING_ENV = ("DBM_ABL_SKIP", "DBM_NO_WGRAD", "DBM_TFB_ABL", "DBM_CL16_ABL", "DBM_ABL_NOPACK", "DBM_ITER_ABL", "DBM_LIB")
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs writes at most this much in all
+DUMP_MAX_VALUES = 7 << 20         # values kept of one dumped array (a fixed, seeded sample of a larger one): 2 x 29.4 MB of model tensors
 G_FWD_MAC_PER_TILE = 845360064  # generator forward, 12 RRDB, one 11x11 -> 36x36 tile (81 trunk pixels)
 BATCH_PER_GPU = 64
 N_RRDB = 12
@@ -61,6 +68,38 @@ def synthetic_batch(n, seed):
     r = lambda *s: np.random.RandomState(seed=seed).rand(*s).astype(np.float32)  # noqa: E731
     return {"X": r(n, 1, 11, 11), "W1": r(n, 1, 110, 110), "W2": r(n, 2, 22, 22), "W3": r(n, 1, 11, 11),
             "Y": r(n, 1, 36, 36)}
+
+
+def sample_values(a, n=DUMP_MAX_VALUES, seed=0):
+    """`a` flattened: whole if it has at most `n` values, else the values at `n` fixed positions (drawn with `seed`, sorted)."""
+    a = np.ascontiguousarray(a).reshape(-1)
+    if a.size <= n:
+        return a
+    return a[np.sort(np.random.RandomState(seed).choice(a.size, n, replace=False))]
+
+
+def last_step_outputs(g, d, metrics):
+    """What a caller of the timed training iteration holds after its last step: that step's five metrics (d_loss, d_accu, g_loss,
+    g_psnr, g_ssim) and the updated tensors of both models (weights, biases, BatchNorm running statistics), each model's
+    tensors flattened in serialize_dict() order and concatenated (then sample_values: the two models hold 77.1 MB)."""
+    out = {"metrics": np.asarray(metrics, np.float32).reshape(-1)[:5]}
+    for name, model in (("generator_tensors", g), ("discriminator_tensors", d)):
+        out[name] = sample_values(np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in model.serialize_dict().values()]))
+    return out
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays (name -> float32 / float64 array) -> out_dir/<name>.npy, at most `limit` bytes in all."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{k}: dtype {v.dtype}")
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:
+        raise ValueError(f"{total} bytes of outputs, more than {limit}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def _cpu_model():
@@ -376,11 +415,9 @@ def _r(v, n=4):
     return round(v, n) if isinstance(v, float) else v
 
 
-def compose_line(*, tiles, dt, steps, warmup, world, batch, ev_ms, config, fam, traffic=None, comm_stats=None, sweep=None, shared=None,
-                 cpu=None, continent=None, tables_path=None, env=None, sync_metrics_ms=None):
-    """The ONE JSON line rank 0 prints, as a dict: scalars only (the per-shape tables of the run go to bench_tables.json and to
-    stderr).  `fam`: one dict per kernel family of the roofline leg (key, ms_per_step, launches_per_step, flop, bytes per step,
-    standalone_ms_per_step).  json.dumps of the result stays below MAX_LINE_BYTES (fit_line enforces it)."""
+def roofline(fam, *, dt, steps, world, batch, traffic=None):
+    """The line's `roofline` (--full): the dominant kernel family of the roofline leg against the fp32 MFMA peak, in-step and
+    standalone, with the other families and the RRDB trunk forward beside it."""
     def tf(flop, ms):
         return flop / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
 
@@ -411,10 +448,21 @@ def compose_line(*, tiles, dt, steps, warmup, world, batch, ev_ms, config, fam, 
         k = max(fwd["launches_per_step"], 1)
         roof["rrdb_forward"] = {"form": fwd["key"], "ms_per_batch": _r(fwd["standalone_ms_per_step"] / k),
                                 "frac_standalone": _r(tf(fwd["flop"], fwd["standalone_ms_per_step"]) / PEAK_FP32_MFMA_TFLOPS)}
+    return roof
+
+
+def compose_line(*, tiles, dt, steps, warmup, world, batch, ev_ms, config, fam=None, traffic=None, comm_stats=None, sweep=None, shared=None,
+                 cpu=None, continent=None, tables_path=None, env=None, sync_metrics_ms=None):
+    """The ONE JSON line rank 0 prints, as a dict: scalars only (the per-shape tables of the run go to bench_tables.json and to
+    stderr).  `fam`: one dict per kernel family of the roofline leg (key, ms_per_step, launches_per_step, flop, bytes per step,
+    standalone_ms_per_step); without it (a run without --full) the line has no `roofline`.  json.dumps of the result stays below
+    MAX_LINE_BYTES (fit_line enforces it)."""
     out = {"metric": baseline_metric(), "value": _r(tiles / dt, 2), "unit": "tiles/s", "n_gpus": world, "steps": steps, "warmup": warmup,
            "ms_per_step": _r(1e3 * dt / steps), "ms_per_step_hip_events": _r(ev_ms / steps), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": dict(config, env=dbm_env() if env is None else env), "roofline": roof}
+           "config": dict(config, env=dbm_env() if env is None else env)}
+    if fam is not None:
+        out["roofline"] = roofline(fam, dt=dt, steps=steps, world=world, batch=batch, traffic=traffic)
     if comm_stats is not None:
         out["rccl_ranks"] = comm_stats.get("world")
         out["config"]["gradient_exchange"] = comm_stats
@@ -585,10 +633,19 @@ def main():
                          "to the ranks, grids resident in HBM, bf16), one compact line with s_per_continent")
     ap.add_argument("--sweep-scale", type=int, default=1, help="--sweep-continent on a 1/k-scale area (tests)")
     ap.add_argument("--tables", default=TABLES_PATH,
-                    help="where the per-shape tables of THIS run go (default bench_tables.json; profiling passes give their own path so "
+                    help="--full: where the per-shape tables of THIS run go (default bench_tables.json; profiling passes give their own path so "
                          "that they do not overwrite the tables of the unprofiled run)")
     ap.add_argument("--no-continent", action="store_true", help="skip extras.continent (one full 18000 x 22000 bf16 sweep on this GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beside the headline figure: roofline brackets and per-shape tables (--tables), "
+                         "extras.sweep / continent / one_generator_forward / sync_metrics_ms_per_step, cpu_baseline (the --no-* "
+                         "switches above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0: its five metrics, both models' updated tensors; "
+                         "bench.last_step_outputs) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.dump_outputs and (args.sweep_continent or args.selftest_launcher):
+        ap.error("--dump-outputs writes the training iteration's outputs: not with --sweep-continent / --selftest-launcher")
     if args.steps is None:
         args.steps = 1 if args.sweep_continent else 200
     if args.warmup is None:
@@ -670,7 +727,7 @@ def main():
     t0 = time.perf_counter()
     dbm._lib.check(lib.dbm_timer(ctx.handle, 0, None), ctx.handle)  # HIP events on the library's main stream as well
     for _ in range(args.steps):
-        step()
+        last = step()
     dbm._lib.check(lib.dbm_timer(ctx.handle, 1, None), ctx.handle)
     metrics_rows = log.fetch() if log is not None else None  # (inside the timed region: the epoch's single read-back)
     torch.cuda.synchronize()
@@ -688,34 +745,39 @@ def main():
         comm_stats = {"backend": comm.backend, "world": cw.value, "bytes_per_step": cb.value / max(args.steps + args.warmup, 1),
                       "collectives_per_step": cc.value / max(args.steps + args.warmup, 1)}
 
-    # ---- roofline leg (outside the timed region): hipEvent-bracketed launches of the dominant kernel ----
     assert metrics_rows is None or (len(metrics_rows) == args.steps + args.warmup and np.isfinite(metrics_rows[:, :5]).all())
-    dbm._lib.check(lib.dbm_profile_begin(ctx.handle), ctx.handle)
-    step()
-    recs = ctx.profile_records()
-    # the same brackets with the device synchronised around each launch: standalone durations
-    dbm._lib.check(lib.dbm_profile_begin_serial(ctx.handle), ctx.handle)
-    step()
-    recs_s = ctx.profile_records()
-    FAMILIES = [   # (key in the line, what it is) -- family index = KernelProfiler family (csrc/dbm_internal.h)
-        ("per_layer_conv_family", "every convolution that is one launch per layer, forward + data gradient: igemm_conv_kernel / igemm_pm_kernel / conv_tile_kernel / "
-                                  "input_block_fused_kernel / disc_deep_kernel + the fused deformable-convolution GEMMs (v_mfma_f32_32x32x2_f32)"),
-        ("wgrad_kernel", "weight gradients: wgrad_wave_dma_kernel, wgrad_band_dma_kernel, wgrad_direct_kernel, wgrad_kernel"),
-        ("trunk_fused_kernel<retained>", "RRDB trunk forward of a retained pass, one persistent launch"),
-        ("trunk_fused_bwd_kernel", "RRDB trunk data-gradient chain, persistent"),
-        ("trunk_fused_kernel<helper>", "RRDB trunk forward of a pass that keeps nothing (the D-step's fakes, inference): a helper workgroup per image"),
-    ]
-    fam = []
-    for i, (key, label) in enumerate(FAMILIES):
-        mine, mine_s = [r for r in recs if r["family"] == i], [r for r in recs_s if r["family"] == i]
-        fam.append({"key": key, "label": label, "ms_per_step": sum(r["ms"] for r in mine), "launches_per_step": len(mine),
-                    "flop": sum(r["flops"] for r in mine), "bytes": sum(r["bytes"] for r in mine),
-                    "standalone_ms_per_step": sum(r["ms"] for r in mine_s)})
-    per_shape = shape_table(recs, recs_s, [k for k, _ in FAMILIES])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(g, d, metrics_rows[-1] if metrics_rows is not None else last))
 
-    # ---- inference leg (outside the timed region, rank 0 of a single-GPU run): BASELINE config 5's unit of work ----
+    # ---- roofline leg (--full, outside the timed region): hipEvent-bracketed launches of the dominant kernel ----
+    fam = per_shape = None
+    if args.full:
+        dbm._lib.check(lib.dbm_profile_begin(ctx.handle), ctx.handle)
+        step()
+        recs = ctx.profile_records()
+        # the same brackets with the device synchronised around each launch: standalone durations
+        dbm._lib.check(lib.dbm_profile_begin_serial(ctx.handle), ctx.handle)
+        step()
+        recs_s = ctx.profile_records()
+        FAMILIES = [   # (key in the line, what it is) -- family index = KernelProfiler family (csrc/dbm_internal.h)
+            ("per_layer_conv_family", "every convolution that is one launch per layer, forward + data gradient: igemm_conv_kernel / igemm_pm_kernel / conv_tile_kernel / "
+                                      "input_block_fused_kernel / disc_deep_kernel + the fused deformable-convolution GEMMs (v_mfma_f32_32x32x2_f32)"),
+            ("wgrad_kernel", "weight gradients: wgrad_wave_dma_kernel, wgrad_band_dma_kernel, wgrad_direct_kernel, wgrad_kernel"),
+            ("trunk_fused_kernel<retained>", "RRDB trunk forward of a retained pass, one persistent launch"),
+            ("trunk_fused_bwd_kernel", "RRDB trunk data-gradient chain, persistent"),
+            ("trunk_fused_kernel<helper>", "RRDB trunk forward of a pass that keeps nothing (the D-step's fakes, inference): a helper workgroup per image"),
+        ]
+        fam = []
+        for i, (key, label) in enumerate(FAMILIES):
+            mine, mine_s = [r for r in recs if r["family"] == i], [r for r in recs_s if r["family"] == i]
+            fam.append({"key": key, "label": label, "ms_per_step": sum(r["ms"] for r in mine), "launches_per_step": len(mine),
+                        "flop": sum(r["flops"] for r in mine), "bytes": sum(r["bytes"] for r in mine),
+                        "standalone_ms_per_step": sum(r["ms"] for r in mine_s)})
+        per_shape = shape_table(recs, recs_s, [k for k, _ in FAMILIES])
+
+    # ---- inference leg (--full, outside the timed region, rank 0 of a single-GPU run): BASELINE config 5's unit of work ----
     sweep = None
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if args.full and rank == 0 and world == 1 and not args.no_sweep:
         try:
             sweep = sweep_leg(dbm, ctx, g)
         except Exception as e:  # pragma: no cover
@@ -723,7 +785,7 @@ def main():
 
     # ---- the same iteration with ONE generator forward (outside the timed region, single GPU; never the headline) ----
     shared = None
-    if rank == 0 and world == 1 and not args.share_generator_forward and not args.no_sweep:
+    if args.full and rank == 0 and world == 1 and not args.share_generator_forward and not args.no_sweep:
         try:
             log_s = dbm.MetricsLog(ctx, rows=64)
 
@@ -752,7 +814,7 @@ def main():
 
     # ---- the same iteration with the reference's per-minibatch read-back (outside the timed region, single GPU) ----
     sync_ms = None
-    if rank == 0 and world == 1 and not args.sync_metrics and not args.no_sweep:
+    if args.full and rank == 0 and world == 1 and not args.sync_metrics and not args.no_sweep:
         try:
             def step_sync():
                 return dbm.train_minibatch(batch, g, g_opt, d, d_opt, share_generator_forward=args.share_generator_forward,
@@ -771,7 +833,7 @@ def main():
 
     # ---- BASELINE config 5 as far as one GPU reaches (outside the timed region): ONE full 18000 x 22000 sweep, bf16, resident ----
     continent = None
-    if rank == 0 and world == 1 and not args.no_sweep and not args.no_continent:
+    if args.full and rank == 0 and world == 1 and not args.no_sweep and not args.no_continent:
         try:
             cl = continent_leg(dbm, ctx, argparse.Namespace(sweep_scale=1, warmup=1, steps=1), 0, 1, None)
             continent = {k: cl[k] for k in ("s_per_continent", "tiles_per_s", "canvas_check_ok")}
@@ -790,29 +852,29 @@ def main():
                                                (comm is None or (comm.exchanges_in_step(ctx) and not args.sync_batch_stats))),
                   "metrics_read_back": "every minibatch" if args.sync_metrics else "once per run",
                   "sync_batch_stats": bool(args.sync_batch_stats and world > 1)}
-        dom_key = max(fam, key=lambda f: f["ms_per_step"])["key"]
-        traffic = None
-        try:  # HBM bytes per launch of the dominant kernel: PMC FETCH_SIZE (x2, gfx950) + WRITE_SIZE, from the committed pass
-            with open(TRAFFIC_JSON) as f:
-                tjs = json.load(f)
-                tj = tjs.get(dom_key.split("<")[0]) or tjs[{"per_layer_conv_family": "igemm_conv_kernel"}[dom_key]]   # (key of the files up to round 5)
-                traffic = {"hbm_bytes_per_launch": tj["hbm_bytes_per_launch"], "traffic_over_algorithmic": tj.get("traffic_over_algorithmic"),
-                           "source": "static: " + os.path.relpath(TRAFFIC_JSON, ROOT) + " (rocprofv3 --pmc, separate passes; not this run)"}
-        except Exception:
-            pass
-        cpu = cpu_baseline() if (not args.no_cpu_baseline and world == 1) else None
-        tables = {"families": fam, "per_shape": per_shape, "sweep": sweep, "one_generator_forward": shared, "cpu_baseline": cpu,
-                  "continent": continent, "sync_metrics_ms_per_step": sync_ms,
-                  "note": "per_shape: every distinct launch shape of the step (tag = layer geometry), sorted by standalone time"}
-        tables_path = None
-        try:
-            with open(args.tables, "w") as f:
-                json.dump(tables, f, indent=1)
-            tables_path = args.tables
-        except OSError:
-            pass
-        if tables_path is None:   # (no writable directory: the tables go to stderr instead)
-            print("bench tables: " + json.dumps(tables), file=sys.stderr, flush=True)
+        traffic = cpu = tables_path = None
+        if args.full:
+            dom_key = max(fam, key=lambda f: f["ms_per_step"])["key"]
+            try:  # HBM bytes per launch of the dominant kernel: PMC FETCH_SIZE (x2, gfx950) + WRITE_SIZE, from the committed pass
+                with open(TRAFFIC_JSON) as f:
+                    tjs = json.load(f)
+                    tj = tjs.get(dom_key.split("<")[0]) or tjs[{"per_layer_conv_family": "igemm_conv_kernel"}[dom_key]]   # (key of the files up to round 5)
+                    traffic = {"hbm_bytes_per_launch": tj["hbm_bytes_per_launch"], "traffic_over_algorithmic": tj.get("traffic_over_algorithmic"),
+                               "source": "static: " + os.path.relpath(TRAFFIC_JSON, ROOT) + " (rocprofv3 --pmc, separate passes; not this run)"}
+            except Exception:
+                pass
+            cpu = cpu_baseline() if (not args.no_cpu_baseline and world == 1) else None
+            tables = {"families": fam, "per_shape": per_shape, "sweep": sweep, "one_generator_forward": shared, "cpu_baseline": cpu,
+                      "continent": continent, "sync_metrics_ms_per_step": sync_ms,
+                      "note": "per_shape: every distinct launch shape of the step (tag = layer geometry), sorted by standalone time"}
+            try:
+                with open(args.tables, "w") as f:
+                    json.dump(tables, f, indent=1)
+                tables_path = args.tables
+            except OSError:
+                pass
+            if tables_path is None:   # (no writable directory: the tables go to stderr instead)
+                print("bench tables: " + json.dumps(tables), file=sys.stderr, flush=True)
         out = compose_line(tiles=args.batch * world * args.steps, dt=dt, steps=args.steps, warmup=args.warmup, world=world, batch=args.batch,
                            ev_ms=ev_ms.value, config=config, fam=fam, traffic=traffic, comm_stats=comm_stats, sweep=sweep, shared=shared,
                            cpu=cpu, tables_path=tables_path, continent=continent, sync_metrics_ms=sync_ms)

@@ -1,4 +1,4 @@
-"""Regenerates tests/golden/esrgan_full.npz: oracle outputs at BASELINE.json's FULL configuration sizes.
+"""Regenerates tests/golden/esrgan_full.partNN.npz: oracle outputs at BASELINE.json's FULL configuration sizes.
 
     python tests/golden/make_golden_full.py            # ~5 minutes on 8 cores, ~12 GB peak
 
@@ -40,7 +40,7 @@ kernels is c3lin.
 
     python tests/golden/make_golden_full.py c3lin c2      # recompute only these, keep the rest of the file
 
-Round 3 -- tests/golden/esrgan_dem.npz (`python tests/golden/make_golden_full.py dem dem5 dlin`):
+Round 3 -- tests/golden/esrgan_dem.partNN.npz (`python tests/golden/make_golden_full.py dem dem5 dlin`):
 
   dem   the full iteration of config 3 at the REFERENCE'S DATA RANGE (SURVEY 8d "DEM-like"): the reference feeds raw metres,
         m/yr and kg/m2/yr (deepbedmap.py:164-169 gap-fills BEDMAP2 with -5000 m; paper/tc-2020-74.tex:192-197): X ~ U[-2000, 2000]
@@ -54,7 +54,7 @@ Round 3 -- tests/golden/esrgan_dem.npz (`python tests/golden/make_golden_full.py
         (no slope hangs on a rounding error, cf. c3lin): the float32 oracle is a tight reference for EVERY discriminator
         gradient, BatchNorm running statistic and the loss at batch 64; mid-size tensors are stored in full.
 
-Round 4 -- `python tests/golden/make_golden_full.py demlin` (also esrgan_dem.npz):
+Round 4 -- `python tests/golden/make_golden_full.py demlin` (also esrgan_dem):
 
   demlin  the G-step of config 3 at the DATA RANGE with a generator in the linear regime (c3lin carried to metres: the
           reference's HeNormal 0.1 weights, biases ~ N(0, 0.1 x 2000 m) so that every pre-activation is dominated by its bias
@@ -62,6 +62,7 @@ Round 4 -- `python tests/golden/make_golden_full.py demlin` (also esrgan_dem.npz
           5e-4 reference for EVERY generator gradient on inputs in metres (`dem` holds them to a multiple of the float32
           oracle's own deviation only).
 """
+import glob
 import os
 import sys
 import zlib
@@ -74,10 +75,42 @@ if ROOT not in sys.path:
 from oracle import model as omodel  # noqa: E402
 from oracle import train as otrain  # noqa: E402
 
-PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "esrgan_full.npz")
+# a fixture set is stored as <PATH>.partNN.npz, each part below 1 MiB: `load(PATH)` / `save(PATH, arrays)`
+PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "esrgan_full")
+PART_BYTES = 900_000   # uncompressed array bytes per part (float data barely compresses: the file stays below 1 MiB)
 NSAMPLE = 512   # entries kept per tensor (whole tensor if smaller)
 NPROJ = 4
 ALPHA, EPS = 1e-4, 1e-8
+
+
+def parts(path):
+    return sorted(glob.glob(glob.escape(path) + ".part[0-9][0-9].npz"))
+
+
+def load(path):
+    """Every array of the fixture set `path` (all of its parts), by key."""
+    out = {}
+    for p in parts(path):
+        with np.load(p) as f:
+            out.update({k: f[k] for k in f.files})
+    assert out, f"no {path}.partNN.npz"
+    return out
+
+
+def save(path, arrays):
+    """Writes `arrays` as the fixture set `path`, keys in order, a new part whenever PART_BYTES would be exceeded."""
+    for p in parts(path):
+        os.remove(p)
+    groups, n = [{}], 0
+    for k, v in arrays.items():
+        if groups[-1] and n + v.nbytes > PART_BYTES:
+            groups.append({})
+            n = 0
+        groups[-1][k] = v
+        n += v.nbytes
+    for i, g in enumerate(groups):
+        np.savez_compressed(f"{path}.part{i:02d}.npz", **g)
+        assert os.path.getsize(f"{path}.part{i:02d}.npz") < 1 << 20, (path, i, list(g))
 
 
 # ---- seeded inputs and weights (shared with tests/test_gpu_fullsize.py) ----
@@ -147,7 +180,7 @@ def target_c2():
 
 
 # ---- the reference's data range (SURVEY 8d "DEM-like"; deepbedmap.py:164-169, 663-665) ----
-PATH_DEM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "esrgan_dem.npz")
+PATH_DEM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "esrgan_dem")
 
 
 def arrays_dem(n, seed, h=11, w=11):
@@ -536,17 +569,17 @@ if __name__ == "__main__":
     import time
 
     todo = {"c3": compute_c3, "c3lin": compute_c3lin, "c2": compute_c2, "c5": compute_c5}
-    todo_dem = {"dem": compute_dem, "dem5": compute_dem5, "dlin": compute_dlin, "demlin": compute_demlin}  # rounds 3, 4: esrgan_dem.npz
+    todo_dem = {"dem": compute_dem, "dem5": compute_dem5, "dlin": compute_dlin, "demlin": compute_demlin}  # rounds 3, 4: esrgan_dem
     want = sys.argv[1:] or list(todo)
     for path, table in ((PATH, todo), (PATH_DEM, todo_dem)):
         mine = [n for n in want if n in table]
         if not mine:
             continue
-        out = dict(np.load(path)) if (sys.argv[1:] and os.path.exists(path)) else {}
+        out = load(path) if (sys.argv[1:] and parts(path)) else {}
         for name in mine:
             t0 = time.time()
             out = {k: v for k, v in out.items() if not k.startswith(name + "/")}
             out.update(table[name]())
             print(name, f"{time.time() - t0:.0f} s", flush=True)
-        np.savez_compressed(path, **out)
-        print("wrote", path, os.path.getsize(path), "bytes")
+        save(path, out)
+        print("wrote", path, [os.path.getsize(p) for p in parts(path)], "bytes")

@@ -25,13 +25,13 @@ def test_oracle_reproduces_golden_vectors():
 
 
 def test_full_size_fixture_belongs_to_this_oracle():
-    """tests/golden/esrgan_full.npz (batch 64 / 16 RRDB / 288 x 288: minutes of oracle time, made by make_golden_full.py)
+    """tests/golden/esrgan_full.partNN.npz (batch 64 / 16 RRDB / 288 x 288: minutes of oracle time, made by make_golden_full.py)
     is pinned to the current oracle code on the CPU through what is cheap: the generator has no cross-sample coupling, so
     the first two images of the stored forward outputs must be the oracle's outputs for the first two tiles; and every
     array of the three configurations is present with a consistent layout."""
     import make_golden_full as mgf
 
-    gold = dict(np.load(mgf.PATH))
+    gold = mgf.load(mgf.PATH)
     a = mgf.arrays(64, 4200)
     g, _ = mgf.models_c3()
     y = g.forward(*(a[k][:2] for k in ("X", "W1", "W2", "W3")))

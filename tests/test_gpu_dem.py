@@ -1,5 +1,5 @@
 """-m gpu: parity at the REFERENCE'S DATA RANGE and the tight full-size discriminator step, against
-tests/golden/esrgan_dem.npz (made by `python tests/golden/make_golden_full.py dlin dem dem5`).
+tests/golden/esrgan_dem.partNN.npz (made by `python tests/golden/make_golden_full.py dlin dem dem5`).
 
 The reference feeds raw physical units (deepbedmap.py:164-169 gap-fills BEDMAP2 with -5000 m): bed
 elevation X in metres, ice surface elevation W1 in metres, velocity W2 in m/yr, accumulation W3 in kg/m2/yr.  Rounds 1-2
@@ -28,7 +28,7 @@ DEV, DEV_G = 3.0, 5.0  # as in test_gpu_fullsize.py: multiples of the float32 or
 
 @pytest.fixture(scope="module")
 def gold():
-    return dict(np.load(mgf.PATH_DEM))
+    return mgf.load(mgf.PATH_DEM)
 
 
 @pytest.fixture(scope="module")
@@ -219,7 +219,7 @@ def test_demlin_generator_step_every_gradient_tight_at_the_data_range(dbm, gold)
     kernels at full occupancy; loss / PSNR / SSIM at 2e-4.  The float32 ORACLE is NOT that close on the layers behind the loss
     (its SSIM sigma^2 = E[x^2] - mu^2 loses its digits on 160 m +- 3 m tiles; `demlin/gradG/dev`): the HIP path must be."""
     if "demlin/g_step" not in gold:
-        pytest.skip("esrgan_dem.npz without the round-4 demlin fixture")
+        pytest.skip("esrgan_dem without the round-4 demlin fixture")
     og, od = mgf.models_demlin()
     g = copy_params(dbm.GeneratorModel(num_residual_blocks=12, initialize=False), og.params)
     d = copy_params(dbm.DiscriminatorModel(initialize=False), od.params, od.persistent)

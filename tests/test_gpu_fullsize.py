@@ -1,5 +1,5 @@
 """-m gpu: the HIP path at BASELINE.json's FULL configuration sizes against oracle outputs committed as
-tests/golden/esrgan_full.npz (made by tests/golden/make_golden_full.py; the oracle needs minutes at these sizes).
+tests/golden/esrgan_full.partNN.npz (made by tests/golden/make_golden_full.py; the oracle needs minutes at these sizes).
 
 This is the regime the benchmark runs: 64 images = 192 resident workgroups of the persistent trunk kernels with
 three bands per image and granule hand-offs, the prefetched G-step forward, merged discriminator weight-gradient
@@ -23,7 +23,7 @@ TOL_FWD, TOL_GRAD, TOL_BF16 = 1e-4, 5e-4, 3e-2
 
 @pytest.fixture(scope="module")
 def gold():
-    return dict(np.load(mgf.PATH))
+    return mgf.load(mgf.PATH)
 
 
 @pytest.fixture(scope="module")
@@ -319,3 +319,30 @@ def test_bench_sweep_continent_entry_on_a_reduced_area(dbm):
     assert d["ranks"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "bf16" and d["higher_is_better"] is False
     assert d["s_per_continent"] == d["value"] > 0 and d["canvas_check_ok"] is True
     assert "750 x 916" not in d["config"]["workload"] and "3000 x 3664" in d["config"]["workload"]
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(dbm, tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR` (no --full): ONE headline line with nothing a separate leg measures, and
+    the last timed step's outputs -- its five metrics and both models' updated tensors (sampled to bench.DUMP_MAX_VALUES) -- as
+    finite float32 .npy files within the byte budget."""
+    import json
+    import subprocess
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and abs(d["value"] - 64e3 / d["ms_per_step"]) < 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "extras", "tables"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ["discriminator_tensors.npy", "generator_tensors.npy", "metrics.npy"]
+    out = {k: np.load(tmp_path / (k + ".npy")) for k in ("metrics", "generator_tensors", "discriminator_tensors")}
+    assert out["metrics"].shape == (5,) and out["generator_tensors"].shape == out["discriminator_tensors"].shape == (bench.DUMP_MAX_VALUES,)
+    for k, v in out.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+    assert sum(v.nbytes for v in out.values()) <= bench.DUMP_LIMIT_BYTES

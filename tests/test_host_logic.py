@@ -1,11 +1,15 @@
 """CPU tests of the host-side logic that needs no GPU: iterator semantics (srgan_train.py:132-166, 1286-1288,
 1311-1313), tiling index arithmetic (deepbedmap.py:689-741), Chainer parameter ordering, config flags."""
+import os
+
 import numpy as np
 import pytest
 
 import deepbedmap_amd as dbm
 from deepbedmap_amd.srgan import _chainer_order
 from oracle import model as omodel
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_serial_iterator_full_batches_and_epochs():
@@ -155,7 +159,7 @@ def _canned_bench_inputs():
     return dict(tiles=64 * 200, dt=1.6288, steps=200, warmup=10, world=1, batch=64, ev_ms=1628.1, config=config, fam=fam,
                 traffic={"hbm_bytes_per_launch": 57.0e6, "source": "static: profiles/r4/traffic_pmc.json (rocprofv3 --pmc, separate passes; not this run)"},
                 sweep=sweep, shared={"ms_per_step": 7.46, "tiles_per_s": 8579.1, "steps": 40, "note": "n" * 500}, cpu=cpu,
-                tables_path="/root/repo/bench_tables.json")
+                tables_path=os.path.join(ROOT, "bench_tables.json"))
 
 
 def test_bench_line_is_short_and_complete():
@@ -208,6 +212,38 @@ def test_bench_line_sheds_detail_rather_than_grow():
     assert sorted(d["config"]["env"]) == sorted(f"DBM_SWITCH_{i}" for i in range(40))  # the names survive
     for k in ("value", "ms_per_step", "roofline", "cpu_baseline"):
         assert k in d
+
+
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full the line carries the timed figures and the configuration, and nothing a separate leg measures."""
+    import json
+
+    import bench
+
+    kw = {k: v for k, v in _canned_bench_inputs().items() if k in ("tiles", "dt", "steps", "warmup", "world", "batch", "ev_ms", "config")}
+    d = json.loads(bench.fit_line(bench.compose_line(env={}, **kw)))
+    assert d["metric"] == bench.baseline_metric() and d["unit"] == "tiles/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 64 * 200 / 1.6288) < 0.01 and abs(d["ms_per_step"] - 8.144) < 1e-3 and d["steps"] == 200
+    for k in ("roofline", "cpu_baseline", "extras", "tables"):
+        assert k not in d, k
+
+
+def test_bench_dump_outputs_sample_and_budget(tmp_path):
+    """--dump-outputs: arrays above the per-array cap are sampled at fixed positions (the same ones every run, in order), the
+    files are <name>.npy as given, and more than the byte budget or a non-float dtype is refused."""
+    import bench
+
+    a = np.arange(1000, dtype=np.float32)
+    s1, s2 = bench.sample_values(a, n=100), bench.sample_values(a.copy(), n=100)
+    assert s1.shape == (100,) and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+    assert np.array_equal(bench.sample_values(a.reshape(10, 100), n=1000), a)
+    bench.dump_outputs(str(tmp_path / "out"), {"metrics": np.ones(5, np.float32), "w": s1.astype(np.float64)})
+    assert np.load(tmp_path / "out" / "metrics.npy").dtype == np.float32 and np.array_equal(np.load(tmp_path / "out" / "w.npy"), s1)
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"w": a}, limit=a.nbytes - 1)
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "int"), {"w": np.arange(3)})
+    assert bench.DUMP_MAX_VALUES * 4 * 2 + 5 * 4 <= bench.DUMP_LIMIT_BYTES   # (metrics + both model dumps fit the budget)
 
 
 def test_bench_refuses_work_skipping_switches_and_prices_split_bf16_correctly():
