@@ -4,15 +4,10 @@
 
 static thread_local std::string g_last_error;
 
-static void run_deferred_eval(dbm_ctx* c, hipStream_t on);   // (dbm_ctx::DeferredEval; defined next to dbm_train_iteration)
-#define DBM_API_BEGIN_NOFLUSH(ctxptr) \
+#define DBM_API_BEGIN(ctxptr) \
   dbm_ctx* _ectx = (ctxptr);  \
   (void)_ectx;                \
   try {
-// every entry point but dbm_train_iteration first enqueues a pending deferred eval-mode pass on the main stream
-#define DBM_API_BEGIN(ctxptr) \
-  DBM_API_BEGIN_NOFLUSH(ctxptr) \
-  if (_ectx && _ectx->deferred.pending) run_deferred_eval(_ectx, _ectx->stream);
 // ---- a persistent trunk kernel that gives up (bounded spins: another process starving the GPU, a partitioned device) ----
 // It raises the context's error word (host-mapped) and a STICKY device flag.  While the flag is up, every kernel that commits
 // training state is a no-op: the optimizer launches (gated ONCE per launch by adam_gate_kernel, so an update is all or
@@ -234,9 +229,6 @@ int dbm_shutdown(dbm_ctx* ctx) {
   if (ctx->ev_comm_done) (void)hipEventDestroy(ctx->ev_comm_done);
   for (auto& e : ctx->comm_ev_pool) (void)hipEventDestroy(e);
   ctx->loss_tmp.release();
-  ctx->deferred.pending = false;   // (a pass nobody waited for: its metrics row dies with the context)
-  ctx->deferred.fakes.release(); ctx->deferred.scratch.release(); ctx->deferred.logits.release();
-  if (ctx->deferred.ev_ready) (void)hipEventDestroy(ctx->deferred.ev_ready);
   for (auto& b : ctx->stage) b.release();
   (void)hipStreamSynchronize(ctx->side);
   (void)hipStreamDestroy(ctx->side);
@@ -754,9 +746,9 @@ static void gen_loss_terms(dbm_ctx* ctx, const float* y, const float* t, const f
 }
 // adversarial term: calculate_discriminator_loss(real=ones, fake=D(fake) detached, targets swapped) (:874-879, :1233-1237)
 static void gen_loss_adv(dbm_ctx* ctx, const float* real_logits, const float* fake_logits, int N, int t_rf, int t_fr,
-                         const int* t_rf_arr = nullptr, const int* t_fr_arr = nullptr, float* base = nullptr) {
+                         const int* t_rf_arr = nullptr, const int* t_fr_arr = nullptr) {
   hipStream_t s = ctx->stream;
-  if (!base) base = ctx->loss_tmp.p;   // (the deferred eval-mode pass brings its own copy of the scratch)
+  float* base = ctx->loss_tmp.p;
   float* adv = base + 8;    // [8..9]
   float* ones = base + 16;  // N
   if (!real_logits) {
@@ -765,9 +757,9 @@ static void gen_loss_adv(dbm_ctx* ctx, const float* real_logits, const float* fa
   }
   launch_ragan_loss(real_logits, fake_logits, N, t_rf, t_fr, adv, nullptr, nullptr, s, t_rf_arr, t_fr_arr);
 }
-static void gen_loss_finish(dbm_ctx* ctx, int N, int H, int W, const float w[4], float* out3, const float* base = nullptr) {
+static void gen_loss_finish(dbm_ctx* ctx, int N, int H, int W, const float w[4], float* out3) {
   hipStream_t s = ctx->stream;
-  if (!base) base = ctx->loss_tmp.p;
+  const float* base = ctx->loss_tmp.p;
   const float* adv = base + 8;
   const float* sums = base + 16 + N;
   const float nhw = (float)N * H * W, npool = (float)N * (H / 4) * (W / 4), nwin = (float)N * (H - 8) * (W - 8);
@@ -1067,23 +1059,14 @@ int dbm_discriminator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, co
     d->comm_sent_lo = d->comm_sent_hi = 0;
     try {
       // The pass on the MAIN stream (real batch) is enqueued first: the main stream is the one the step's tail waits
-      // for (measured: D-step 5.72 -> 5.39 ms against enqueueing the fake batch's pass first); whichever pass is enqueued
-      // second launches the merged weight-gradient groups behind both passes' events.
-      static const bool fake_first = DBM_TUNE_GETENV("DBWD_ORDER") && atoi(DBM_TUNE_GETENV("DBWD_ORDER")) == 0;
+      // for (measured: D-step 5.72 -> 5.39 ms against enqueueing the fake batch's pass first); the fake batch's pass,
+      // enqueued second, launches the merged weight-gradient groups behind both passes' events.
       hipStream_t other = c->stream;  // chain[0] when two streams are used, else the main stream
-      if (fake_first) {
-        d->merge_launcher = 0;
-        d->backward(1, gf, false);
-        c->stream = s;
-        d->backward(0, gr, false);
-      } else {
-        d->merge_launcher = 1;
-        c->stream = s;
-        d->backward(0, gr, false);
-        c->stream = other;
-        d->backward(1, gf, false);
-        c->stream = s;
-      }
+      c->stream = s;
+      d->backward(0, gr, false);
+      c->stream = other;
+      d->backward(1, gf, false);
+      c->stream = s;
     } catch (...) {
       c->stream = s;
       d->merge_slots = false;
@@ -1214,22 +1197,9 @@ int dbm_generator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, const 
 // that stream carries, its remainder after the join, then the generator's buckets (tail, trunk groups, input block) as
 // its backward pass on chain[1] finishes them -- and both Adam launches take 1 / world.  Same collectives in the same order
 // as the two step calls, hence the same numbers bit for bit.
-static void run_deferred_eval(dbm_ctx* c, hipStream_t on) {
-  dbm_ctx::DeferredEval& q = c->deferred;
-  if (!q.pending) return;
-  q.pending = false;
-  struct Restore { dbm_ctx* c; hipStream_t s; ~Restore() { c->stream = s; } } restore{c, c->stream};
-  DBM_HIP(hipStreamWaitEvent(on, q.ev_ready, 0));
-  c->stream = on;
-  // (the discriminator's forward weight images were rebuilt behind its update; coefficients: prepare_eval_coeffs(2) at the snapshot)
-  q.d->forward(q.N, q.H4, q.W4, q.fakes.p, q.logits.p, false, false, 2, true);
-  gen_loss_adv(c, nullptr, q.logits.p, q.N, 0, 1, nullptr, nullptr, q.scratch.p);
-  gen_loss_finish(c, q.N, q.H4, q.W4, q.w, q.out3, q.scratch.p);
-}
-
 int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const float* X, const float* W1, const float* W2,
                         const float* W3, const float* Y, const float weights[4], int ssim_window, int flags, float* metrics) {
-  DBM_API_BEGIN_NOFLUSH(gm->ctx)
+  DBM_API_BEGIN(gm->ctx)
   DBM_CHECK(gm->type == 0 && dm->type == 1, "dbm_train_iteration: (generator, discriminator) expected");
   Generator* g = static_cast<Generator*>(gm);
   Discriminator* d = static_cast<Discriminator*>(dm);
@@ -1260,41 +1230,23 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   // metrics -- runs on the main stream.  Round 3 tried three alternatives (profiles/design_history_r1-r3.md): raising chain[1]'s
   // stream priority lost its A/B; moving the tail to chain[0] (DBM_ITER_TAIL) was NEVER validly measured -- DBM_API_BEGIN's
   // join cleared tail_pending, so both arms ran the same schedule -- and the path was deleted without a re-measurement;
-  // forking the twin's forward early is measured again in round 5: DBM_ITER_EARLY_TWIN below.)
+  // forking the twin's forward early, measured again in round 5, made the iteration later: profiles/r5/ab_twin.txt.)
   struct Scope {  // every helper below enqueues on ctx->stream / reads the exchange switches: restore them whatever happens
     dbm_ctx* c; hipStream_t s; Discriminator* d; Generator* t = nullptr;
     ~Scope() {
       c->stream = s; c->comm_in_step = false; c->comm_defer = false; c->comm_stream = nullptr; c->comm_pending.clear();
       d->merge_slots = false; d->borrow_images = false;
-      if (t) { t->grads_cleared = false; t->use_aux = true; t->max_split = 2; t->wgrad_inline = false; t->csr_early = false; t->csr_prebuilt = false; }
+      if (t) { t->grads_cleared = false; t->use_aux = true; t->max_split = 2; t->csr_early = false; t->csr_prebuilt = false; }
     }
   } scope{c, s, d};
   c->comm_in_step = dp;
   c->comm_stream = dp ? c->chain[0] : nullptr;
-  // (tuning switch, libdbm_measure.so only: DBM_DISC_BORROW=0 private image copies again.  profiles/r6/ab_disc_launch_trims.txt, three
-  //  alternations on one box, medians: all three trims of round 6 on 7.668 ms per step; the head as two launches per pass 7.695; image copies
-  //  7.681; the D-step's cleargrads at the head of the side stream instead of between the loss and the backward passes 7.668 against 7.656
-  //  WITHOUT it -- that one lost and is gone again: 77 MB of fills in front of D(real)'s forward cost more than 41 MB behind the loss.)
-  static const int borrow_env = DBM_TUNE_GETENV("DISC_BORROW") ? atoi(DBM_TUNE_GETENV("DISC_BORROW")) : 1;
-  d->borrow_images = borrow_env != 0;   // (Y and the generator's output buffers outlive this call; both backward passes run inside it)
+  // (profiles/r6/ab_disc_launch_trims.txt, three alternations on one box, medians: all three trims of round 6 on 7.668 ms per step; the
+  //  head as two launches per pass 7.695; private image copies 7.681; the D-step's cleargrads at the head of the side stream instead of
+  //  between the loss and the backward passes 7.668 against 7.656 WITHOUT it -- that one lost and is gone again: 77 MB of fills in front
+  //  of D(real)'s forward cost more than 41 MB behind the loss.)
+  d->borrow_images = true;   // (Y and the generator's output buffers outlive this call; both backward passes run inside it)
   DBM_MARK(s, "D:begin");
-  // DBM_ITER_DEFER_EVAL=1 (round 6; default 0): the G-step's detached eval-mode discriminator pass of THIS iteration is snapshotted at its
-  // end and enqueued by the next library call (dbm_ctx::DeferredEval); 0: inside this call, behind the discriminator's update.
-  // MEASURED (profiles/r6/ab_defer_eval.txt, two alternations on one box): inside the call 7.616-7.618 ms per step; deferred to the side
-  // stream beside D(fake)'s forward 7.68-7.69, in front of D(real)'s forward or first thing on the main stream 7.84-7.85, first thing on
-  // chain[0] 7.68-7.72 (7.66-7.69 with the weight repack left to D(real)'s forward).  Removing the pass is worth 0.32 ms (round 5's
-  // ablation), but every other place it can go costs more than the place it has: behind the update it runs on the main stream while that
-  // stream only waits for the generator's backward pass, squeezed into whatever the chain and the trunk's weight gradients leave; anywhere
-  // in the next iteration it competes with a forward pass on the critical path.  The mechanism stays (bitwise the same metrics:
-  // tests/test_gpu_round5.py) for callers whose next call is NOT a training iteration -- the pass then costs nothing until it is read.
-  // Where a pending pass of the PREVIOUS iteration goes (tuning switch, libdbm_measure.so only): 0 main stream, first thing; 1 side
-  // stream, in front of D(real)'s forward; 2 (default) side stream, behind D(real)'s forward and the weight-image rebuilds -- beside
-  // D(fake)'s forward, in the shadow of the retained trunk forward; 3 chain[0], first thing.
-  static const int defer_env = getenv("DBM_ITER_DEFER_EVAL") ? atoi(getenv("DBM_ITER_DEFER_EVAL")) : 0;
-  static const int defer_at = DBM_TUNE_GETENV("ITER_DEFER_AT") ? atoi(DBM_TUNE_GETENV("ITER_DEFER_AT")) : 2;
-  static const int defer_pack = DBM_TUNE_GETENV("ITER_DEFER_PACK") ? atoi(DBM_TUNE_GETENV("ITER_DEFER_PACK")) : 1;
-  if (c->deferred.pending && (defer_at == 0 || c->deferred.d != d)) run_deferred_eval(c, s);
-  if (c->deferred.pending && defer_at == 3) run_deferred_eval(c, c->chain[0]);
   // (libdbm_measure.so only; results are then wrong -- what a part of the iteration costs INSIDE it: 1 = no discriminator work at all
   //  (forwards, backward passes, weight gradients, update, repack, eval-mode pass), 2 = no trunk weight-gradient launch (generator.hip),
   //  4 = no weight gradients of the generator's tail, 8 = no eval-mode discriminator pass)
@@ -1307,22 +1259,12 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   // cleargrads of the G-step (:1255), early: nothing reads or writes the generator's gradient arena between the previous update and this
   // iteration's backward pass, and 35 MB of fill would otherwise sit between the loss and the backward pass on the critical path
   DBM_HIP(hipMemsetAsync(g->grads, 0, g->nparam * sizeof(float), c->side));
-  if (c->deferred.pending && defer_at == 1) run_deferred_eval(c, c->side);
   if (!no_d) d->forward(N, H4, W4, Y, lr, true, true, 0);
   c->stream = s;
   // (The G-step's own forward goes to chain[1] behind the first forward; one_fwd: it is the only forward, forked here.
   //  Round 4 measured releasing only its INPUT BLOCK early -- beside the first forward's tail, the trunk launch still behind it:
   //  8.073 against 8.027 ms, two alternations on one box: not kept.)
-  // DBM_ITER_EARLY_TWIN (round 5; persistent trunk path, single GPU): where the G-step's own forward is released.
-  //   0: behind the WHOLE first forward (its full-resolution tail included);
-  //   1: behind the first forward's TRUNK launch -- the persistent launches are serialised anyway (persist_begin), and the first
-  //      forward's tail (a serial chain of seven short kernels) then runs beside the second trunk's 192 workgroups instead of alone;
-  //   2: FIRST -- the retained forward's trunk precedes the D-step's in the chain of persistent launches: the generator's own
-  //      forward -> loss -> backward -> update path is the iteration's critical path, the D-step has slack behind it.
-  // Nothing is skipped and no number changes: the two forwards read the same weights and inputs and write separate workspaces.
-  static const int early_env = getenv("DBM_ITER_EARLY_TWIN") ? atoi(getenv("DBM_ITER_EARLY_TWIN")) : 0;
-  const int early = (!one_fwd && !dp && g->trunk_fused_ok(H - 2, W - 2)) ? early_env : 0;
-  if (one_fwd || early == 2) {
+  if (one_fwd) {
     g->ensure_packed();
     c->fork(s, pf, 6);
   }
@@ -1334,26 +1276,18 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   // (Generator::prebuild_csr; 7.69-7.70 against 7.77-7.78 ms.  On the side stream, which must then wait for the retained forward's
   // tail, the discriminator's weight gradients start late: 8.07)
   static const int csr_early_env = getenv("DBM_ITER_CSR_EARLY") ? atoi(getenv("DBM_ITER_CSR_EARLY")) : 1;
-  auto twin_forward = [&]() {  // the G-step's own forward (:1222-1227), retained graph, second workspace, on chain[1]
-    t->max_split = 1;
-    t->csr_early = csr_early_env != 0 && !dp;   // (data-parallel: chain[0] also carries the gradient exchange -- the lists stay on the backward pass's own path)
-    c->stream = pf;
-    t->forward(N, H, W, X, W1, W2, W3, t->yout.p, true);
-    DBM_HIP(hipEventRecord(g->ev_prefetch, pf));  // the twin's fakes are final (the G-step's eval-mode discriminator pass reads them)
-    c->stream = s;
-    t->max_split = 2;
-  };
-  if (early == 2) twin_forward();
   // ---- fakes under enable_backprop=False (:1131-1137) ----
-  if (!one_fwd) {
-    g->mark_trunk = early == 1;
-    g->forward(N, H, W, X, W1, W2, W3, g->yout.p, false);
-    g->mark_trunk = false;
-  }
+  if (!one_fwd) g->forward(N, H, W, X, W1, W2, W3, g->yout.p, false);
   DBM_MARK(s, "D:generator_forward");
-  if (early == 1) DBM_HIP(hipStreamWaitEvent(pf, g->ev_trunk, 0));  // weights packed, inputs final, the first trunk launch enqueued
-  else if (!one_fwd && early == 0) c->fork(s, pf, 6);
-  if (early != 2) twin_forward();
+  if (!one_fwd) c->fork(s, pf, 6);
+  // ---- the G-step's own forward (:1222-1227), retained graph, second workspace, on chain[1] ----
+  t->max_split = 1;
+  t->csr_early = csr_early_env != 0 && !dp;   // (data-parallel: chain[0] also carries the gradient exchange -- the lists stay on the backward pass's own path)
+  c->stream = pf;
+  t->forward(N, H, W, X, W1, W2, W3, t->yout.p, true);
+  DBM_HIP(hipEventRecord(g->ev_prefetch, pf));  // the twin's fakes are final (the G-step's eval-mode discriminator pass reads them)
+  c->stream = s;
+  t->max_split = 2;
   // ---- D(fake) forward, RaGAN loss, cleargrads (:1146-1162) ----
   c->join_side();
   // The data-gradient weight images of both models (stale since their updates; first read by this iteration's backward passes) are rebuilt
@@ -1364,7 +1298,6 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   DBM_HIP(hipEventRecord(c->ev_iter[2], c->side));   // (what the generator's backward pass on chain[1] waits for: cleargrads + images)
   d->ensure_packed_bwd(c->side);
   DBM_HIP(hipEventRecord(c->ev_iter[3], c->side));   // (what the discriminator's backward passes wait for)
-  if (c->deferred.pending) run_deferred_eval(c, c->side);   // (defer_at == 2; the main stream joins the side stream before the update below)
   if (one_fwd) DBM_HIP(hipStreamWaitEvent(s, g->ev_prefetch, 0));  // (the fakes are the retained forward's, written on chain[1])
   if (!no_d) d->forward(N, H4, W4, one_fwd ? t->yout.p : g->yout.p, lf, true, true, 1);
   launch_ragan_loss(lr, lf, N, 1, 0, metrics, gr, gf, s);
@@ -1375,7 +1308,6 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   DBM_HIP(hipStreamWaitEvent(s, c->ev_iter[3], 0));   // (before the fork: both passes read the data-gradient images)
   c->fork(s, c->chain[0], 7);
   d->merge_slots = true;
-  d->merge_launcher = 1;
   d->comm_sent_lo = d->comm_sent_hi = 0;
   c->comm_defer = dp;  // (chain[0] is the exchange stream AND carries the fake-batch pass: its bucket goes out behind the pass)
   if (!no_d) d->backward(0, gr, false);
@@ -1406,13 +1338,8 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   DBM_HIP(hipStreamWaitEvent(pf, c->ev_iter[2], 0));  // cleargrads (:1255): the fill at the head of the side stream (+ the weight images)
   mark_grads_cleared(g);
   t->grads_cleared = true;
-  // (chain[0] carries the discriminator's fake-batch pass and the gradient exchange.  DBM_ITER_AUX=1, single GPU only: the offset-
-  // gradient kernel of final_conv_layer2 goes there all the same, next to the input-gradient gather)
-  static const int iter_aux = DBM_TUNE_GETENV("ITER_AUX") ? atoi(DBM_TUNE_GETENV("ITER_AUX")) : 0;
-  t->use_aux = iter_aux && !dp;
-  t->wgrad_inline = early == 2;   // (the side stream carries the discriminator's weight gradients: see Generator::wgrad_inline)
+  t->use_aux = false;   // (chain[0] carries the discriminator's fake-batch pass and the gradient exchange)
   t->backward(t->g_y.p);
-  t->wgrad_inline = false;
   t->grads_cleared = false;
   t->use_aux = true;
   t->graph_version = -1;
@@ -1421,29 +1348,12 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   // ---- discriminator update (:1164), then the G-step's detached eval-mode discriminator pass (:1228-1237) ----
   if (!no_d) adam_update_impl(d, gscale);
   DBM_HIP(hipStreamWaitEvent(s, g->ev_prefetch, 0));  // the twin's fakes (written on chain[1]: nothing else orders this read)
-  if (defer_env && !no_d && !(iter_abl & 8)) {
-    // snapshot what the eval-mode pass reads; the pass itself goes out with the next library call (run_deferred_eval)
-    dbm_ctx::DeferredEval& q = c->deferred;
-    if (defer_pack) d->ensure_packed(s);   // (the forward weight images of the updated parameters: D(real)'s next forward needs them as well)
-    d->prepare_eval_coeffs(2, s);
-    const size_t nimg = (size_t)N * H4 * W4;
-    q.fakes.ensure(nimg); q.scratch.ensure(16 + 5 * (size_t)N); q.logits.ensure((size_t)N);
-    DBM_HIP(hipMemcpyAsync(q.fakes.p, t->yout.p, nimg * sizeof(float), hipMemcpyDeviceToDevice, s));
-    DBM_HIP(hipStreamWaitEvent(s, c->ev_iter[0], 0));  // the loss terms' partial sums (chain[1])
-    DBM_HIP(hipMemsetAsync(q.scratch.p, 0, 16 * sizeof(float), s));
-    DBM_HIP(hipMemcpyAsync(q.scratch.p + 16 + N, c->loss_tmp.p + 16 + N, 4 * (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (!q.ev_ready) DBM_HIP(hipEventCreateWithFlags(&q.ev_ready, hipEventDisableTiming));
-    DBM_HIP(hipEventRecord(q.ev_ready, s));
-    q.d = d; q.N = N; q.H4 = H4; q.W4 = W4; q.out3 = metrics + 2;
-    for (int k = 0; k < 4; ++k) q.w[k] = weights[k];
-    q.pending = true;
-  } else {
-    if (!no_d && !(iter_abl & 8)) d->forward(N, H4, W4, t->yout.p, lf_eval, false, false, 1);  // (repacks the updated weights first)
-    DBM_HIP(hipStreamWaitEvent(s, c->ev_iter[0], 0));  // the loss scratch was cleared on chain[1]
-    gen_loss_adv(c, nullptr, lf_eval, N, 0, 1);
-    gen_loss_finish(c, N, H4, W4, weights, metrics + 2);   // (the loss terms are final: not behind the backward pass's join -- it sat between the
-                                                           //  last weight gradient and the update, 12 us on the iteration's critical path)
-  }
+  // (Deferring this pass to the next library call, round 6, measured slower wherever it went: profiles/r6/ab_defer_eval.txt.)
+  if (!no_d && !(iter_abl & 8)) d->forward(N, H4, W4, t->yout.p, lf_eval, false, false, 1);  // (repacks the updated weights first)
+  DBM_HIP(hipStreamWaitEvent(s, c->ev_iter[0], 0));  // the loss scratch was cleared on chain[1]
+  gen_loss_adv(c, nullptr, lf_eval, N, 0, 1);
+  gen_loss_finish(c, N, H4, W4, weights, metrics + 2);   // (the loss terms are final: not behind the backward pass's join -- it sat between the
+                                                         //  last weight gradient and the update, 12 us on the iteration's critical path)
   DBM_HIP(hipStreamWaitEvent(s, c->ev_iter[1], 0));  // generator backward (and its weight gradients) done
   if (dp) {
     c->comm_join(s);  // ... and its last bucket summed over ranks
@@ -1626,8 +1536,7 @@ int dbm_op_deform_conv2d(dbm_ctx* ctx, const float* x, const float* off, const f
                          int N, int C, int H, int W, int O) {
   DBM_API_BEGIN(ctx)
   DBM_CHECK(C % 32 == 0, "deform conv op: C % 32 == 0");
-  static const int fused_env = DBM_TUNE_GETENV("DEFORM_FUSED") ? atoi(DBM_TUNE_GETENV("DEFORM_FUSED")) : 1;
-  const bool fused = fused_env && deform_conv_fused_ok(C, O);
+  const bool fused = deform_conv_fused_ok(C, O);
   DevBuf col;
   if (!fused) {
     col.ensure((size_t)N * C * 9 * H * W);
@@ -1673,8 +1582,7 @@ int dbm_op_deform_conv2d_backward(dbm_ctx* ctx, const float* x, const float* off
   DBM_CHECK(C % 32 == 0, "deform conv op: C % 32 == 0");
   hipStream_t s = ctx->stream;
   const long P = (long)H * W;
-  static const int fused_env = DBM_TUNE_GETENV("DEFORM_FUSED") ? atoi(DBM_TUNE_GETENV("DEFORM_FUSED")) : 1;
-  const bool fused = fused_env && deform_conv_fused_ok(C, O) && deform_input_grad_ok(C, H, W);
+  const bool fused = deform_conv_fused_ok(C, O) && deform_input_grad_ok(C, H, W);
   DevBuf col, gcol, xt, part, cws;
   if (fused) {
     cws.ensure(deform_csr_workspace_floats(N, H, W));

@@ -682,8 +682,6 @@ void launch_cl_to_nchw(const float* res, float* y, long ysn, int N, int plane, h
 
 // patches (of 2 rows) per tile: the plane in as few rounds of <= n_cus workgroups as possible, then the least work per SIMD
 static int cl16_choose_slots(int N, int H, int W, int n_cus, int maxs = CL_MAXSLOTS, int per_cu = 1) {
-  static const int forced = DBM_TUNE_GETENV("CL16_SLOTS") ? atoi(DBM_TUNE_GETENV("CL16_SLOTS")) : 0;
-  if (forced >= 1 && forced <= maxs) return forced;
   const int tilesX = (W + CL_TW - 1) / CL_TW;
   int best = 8;
   double best_cost = 1e30;
@@ -725,13 +723,11 @@ void launch_conv_cl16(const ClConvLaunch& L, hipStream_t s) {
   a.tilesX = (L.W + CL_TW - 1) / CL_TW;
   // (Tiles of at most eight patches with two workgroups per CU were measured in round 3, on that round's kernel, and bought nothing.)
   // (round 6, again: tiles of <= 8 patches with one output-channel tile -- 78 KB, two workgroups per CU -- for launches of several
-  //  rounds of tiles: crops batched per forward.  DBM_CL16_PAIR, libdbm_measure.so: 0 never)
-  static const int pair_env = DBM_TUNE_GETENV("CL16_PAIR") ? atoi(DBM_TUNE_GETENV("CL16_PAIR")) : 1;
-  // (DBM_CL16_PAIR_MIN: smallest number of 16-row tiles that takes the form.  A single crop -- 324 such tiles -- is slower with it:
+  //  rounds of tiles: crops batched per forward)
+  // (four rounds of 16-row tiles at the least.  A single crop -- 324 such tiles -- is slower with the form:
   //  4.51 against 4.47 ms; conv_layer5's 64 output channels as two workgroups of 32 per tile lost as well: continent 1.669 against 1.683 s
   //  without any pairing, where the 32-channel layers alone gain 3 %: round6_calls/40_conv_cl16_halves.patch)
-  static const long pair_min = DBM_TUNE_GETENV("CL16_PAIR_MIN") ? atol(DBM_TUNE_GETENV("CL16_PAIR_MIN")) : 4L * n_cus;
-  const bool pair = pair_env && MT == 1 && (long)L.N * a.tilesX * ((L.H + 15) / 16) >= pair_min;
+  const bool pair = MT == 1 && (long)L.N * a.tilesX * ((L.H + 15) / 16) >= 4L * n_cus;
   a.nslots = pair ? cl16_choose_slots(L.N, L.H, L.W, n_cus, 8, 2) : cl16_choose_slots(L.N, L.H, L.W, n_cus);
   a.tilesY = (L.H + 2 * a.nslots - 1) / (2 * a.nslots);
   size_t lds = 2 * (size_t)cl_act_bytes(pair ? 8 : CL_MAXSLOTS) + 2 * (size_t)18 * MT * 1024;
@@ -802,8 +798,7 @@ void launch_conv_cl16x3(const ClX3Launch& L, hipStream_t s) {
   const int MT = (L.Cout + 31) / 32;
   a.tilesX = (L.W + CL_TW - 1) / CL_TW;
   // two workgroups per CU (tiles of <= 8 patches, one output-channel tile) once the plane is several rounds of tiles anyway
-  static const int pair_env = DBM_TUNE_GETENV("CL16X3_PAIR") ? atoi(DBM_TUNE_GETENV("CL16X3_PAIR")) : 1;   // (0: one workgroup per CU -- A/B)
-  const bool pair = pair_env && MT == 1 && (long)L.N * a.tilesX * ((L.H + 15) / 16) >= 4L * n_cus;
+  const bool pair = MT == 1 && (long)L.N * a.tilesX * ((L.H + 15) / 16) >= 4L * n_cus;
   a.nslots = pair ? cl16_choose_slots(L.N, L.H, L.W, n_cus, 8, 2) : cl16_choose_slots(L.N, L.H, L.W, n_cus);
   a.tilesY = (L.H + 2 * a.nslots - 1) / (2 * a.nslots);
   const size_t lds = 2 * (size_t)cl_act_bytes(pair ? 8 : CL_MAXSLOTS) + 2 * (size_t)9 * MT * 2 * 1024;

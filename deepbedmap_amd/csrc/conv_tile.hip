@@ -411,9 +411,9 @@ int conv_tile_plan(ConvDesc& d, long* wgs) {
   // (51.6 -> 43.8 us, 56.3 -> 47.8 us standalone) cost + 0.04 ms per step when first measured and nothing on the final round-5 schedule
   // (7.66 / 7.68 against 7.67 / 7.69): on.  The 9 x 9 planes (34.4 -> 30.7 us standalone) cost + 0.02 then and + 0.23 ms now: these
   // discriminator layers run on the 64 CUs a persistent trunk launch leaves, where igemm_conv_kernel's small workgroups (up to eight
-  // per CU) use a CU better than 256 workgroups of four wavefronts.  Off; DBM_CONV_TILE_K4=0 / DBM_CONV_TILE_9=1 for the A/B.
+  // per CU) use a CU better than 256 workgroups of four wavefronts: they stay there (profiles/r5/ab_conv_tile_classes_late.txt).
+  // DBM_CONV_TILE_K4=0 for the A/B of the 4x4 class.
   static const int k4_enable = getenv("DBM_CONV_TILE_K4") ? atoi(getenv("DBM_CONV_TILE_K4")) : 1;
-  static const int p9_enable = getenv("DBM_CONV_TILE_9") ? atoi(getenv("DBM_CONV_TILE_9")) : 0;
   if (k4) {
     if (!k4_enable) return 0;
     if (d.OWl == 18 && x4) {   // 36 x 36 -> 18 x 18 (discriminator conv_layer1): two bands of nine output rows, six tiles each
@@ -439,11 +439,6 @@ int conv_tile_plan(ConvDesc& d, long* wgs) {
     *wgs = (long)d.N * 2 * mt;
     return 3;
   }
-  if (d.OWl == 9 && p9_enable && (long)d.N * mt >= 256) {   // 9 x 9 planes (discriminator conv_layer4): one image = three tiles
-    // (fewer workgroups than CUs: igemm_conv_kernel's K split over 8 / 16 wavefronts is faster -- 23.5 vs 29.6 us at 128)
-    *wgs = (long)d.N * mt;
-    return 7;
-  }
   return 0;
 }
 
@@ -458,7 +453,6 @@ void conv_tile_launch(const ConvDesc& d, int cfg, hipStream_t s) {
     case 4: launch_cfg<9, 1, 36, 9, 3, 8, 1>(d, s); break;    // (a folded x2 resize, or rows that are not 16-byte aligned)
     case 5: launch_cfg<16, 2, 18, 9, 2, 4, 4>(d, s); break;   // 4x4 stride 2 from 36-wide rows (16-byte pieces), four channels per chunk
     case 6: launch_cfg<16, 2, 9, 9, 1, 8, 1>(d, s); break;    // 4x4 stride 2 from 18-wide rows
-    case 7: launch_cfg<9, 1, 9, 9, 1, 8, 1>(d, s); break;     // 3x3 on 9 x 9 planes
     default: DBM_CHECK(false, "conv_tile_launch: unknown configuration");
   }
   DBM_HIP(hipGetLastError());

@@ -16,17 +16,6 @@ inline int dbm_measure_env(const char* name) { const char* v = getenv(name); ret
 #define DBM_ABL_BIT(a, m) false
 #endif
 inline int dbm_abl_skip() { static const int v = DBM_MEASURE_ENV("ABL_SKIP"); return v; }
-// TUNING switches (launch-size rules, kernel-form overrides, schedule variants whose A/Bs read "the default stands": profiles/r5/
-// ab_igemm_knobs_late.txt, ab_wgrad_knobs_late.txt, tune_igemm.txt): they select valid kernels, but nothing in the product or its tests
-// sets them -- round 6 moved them out of libdbm.so.  DBM_TUNE_GETENV("X") is getenv("DBM_X") in libdbm_measure.so (tools/tune_igemm.py,
-// tools/experiments/ab_env.sh with DBM_LIB) and a null pointer in the product library, where the defaults are compile-time constants and
-// the names do not occur (tests/test_abi.py lists the names the product library does read and fails on any nobody exercises).
-#ifdef DBM_MEASURE
-#define DBM_TUNE_GETENV(name) getenv("DBM_" name)
-#else
-inline const char* dbm_no_env() { return nullptr; }
-#define DBM_TUNE_GETENV(name) dbm_no_env()
-#endif
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -117,7 +106,7 @@ struct ConvDesc {
   int ksplit;          // set by the launcher: > 1 = blockIdx.z % ksplit owns Cin / ksplit input channels (few-tile, long-K
                        // layers: the deep discriminator convs).  Deterministic: every workgroup writes its partial tile to
                        // ks_part, the LAST one to arrive at the tile's counter sums the slices in index order and runs the
-                       // epilogue.  (DBM_IGEMM_KSPLIT=2: the older form, fp32 atomics onto a pre-zeroed y, plain layers only.)
+                       // epilogue.
   float* ks_part;      // set by the launcher: [tile][ksplit][32 x 32] partial tiles (workspace of the launch stream)
   unsigned* ks_cnt;    // set by the launcher: one arrival counter per tile, zero between launches
   // Merged phases of a stride-2 data gradient (T == 4): blockIdx.z / ksplit = phase ph = 2 py + px, whose four taps are
@@ -209,15 +198,14 @@ struct WgradPlan {
   int wave_task;          // 0: wgrad_kernel (workgroup form), 2: wgrad_wave_dma_kernel, 3: wgrad_band_dma_kernel,
                           // 4: wgrad_direct_kernel (Wst = segments per output row, nbands = segments, S = K slices)
   const float* zeros;     // >= 4 bytes of device zeros (out-of-image rows of the row-band DMA form)
-  // deterministic folding (no fp32 atomics): partial[slice][cout tile][group][wave][tap][16][64] in accumulator order,
-  // partial_b[slice][cout tile][32]; summed in slice order by wgrad_fold_kernel.  null = atomics.
+  // Slot partials: partial[slice][cout tile][group][wave][tap][16][64] in accumulator order, partial_b[slice][cout tile][32].  The
+  // planner always leaves them null (deterministic mode folds through the pair buffers below); the kernels' epilogue for them is kept
+  // because removing it changes the code hipcc emits for the LDS-DMA weight-gradient kernels.
   float* partial;
   float* partial_b;
   int fold_start;         // first workgroup of this layer in the fold launch
-  // wavefront slot w of a workgroup owns input tile grp * fold_ctmul + (w % fold_cts) (if (w % fold_cts) < fold_ctmul) and
-  // the fold_tpw taps from (w / fold_cts) * fold_tpw
-  int fold_slots, fold_cts, fold_ctmul, fold_tpw;
-  // Pair buffers (the other deterministic folding): K slices 2k and 2k + 1 add with atomics into buffer k, which is
+  int fold_slots, fold_cts, fold_ctmul, fold_tpw;   // (slot partials: which input tile / taps a wavefront slot owns)
+  // Pair buffers (deterministic folding, no fp32 atomics on the K split): K slices 2k and 2k + 1 add with atomics into buffer k, which is
   // zero and has gW's own layout (+ Cout bias floats): two contributions commute bit for bit.  pair_direct: pair 0 goes
   // straight to gW / gb (the gradient is known to be zero).  wgrad_pair_fold_kernel adds the buffers in order, clears them.
   float* pairW;
@@ -243,9 +231,8 @@ struct WgradBatch {
   int* d_starts[NCAT] = {};
   int nplans[NCAT] = {}, total_wg[NCAT] = {};
   size_t lds[NCAT] = {};
-  float* d_partial[NCAT] = {};   // scratch of the atomic-free folding (per category)
+  float* d_partial[NCAT] = {};   // pair buffers of the atomic-free folding (per category)
   int fold_wgs[NCAT] = {};
-  bool pair_mode[NCAT] = {};     // deterministic folding through pair buffers (WgradPlan::pairW)
   double flops[NCAT] = {};
   double abytes[NCAT] = {};      // algorithmic bytes of a category's launch: every layer's x, dy and gW once
   // 4x4 stride-2 layers on tiny planes (wgrad_s2tiny_kernel): their own plan table, outside the categories

@@ -1253,11 +1253,10 @@ __global__ __launch_bounds__(256) void deform1_premul_mfma_kernel(const float* _
 }
 
 static void launch_premul(const float* xt, const float* w, float* z, long total, int plane, int nz, hipStream_t s) {
-  static const int mfma_env = DBM_TUNE_GETENV("DEFORM1_PREMUL_MFMA") ? atoi(DBM_TUNE_GETENV("DEFORM1_PREMUL_MFMA")) : 1;   // (0: the vector-ALU kernel -- A/B)
   // (planes of the sweep only: on the training tile's 83 k positions the two kernels take the same time inside the iteration, and the
   //  discriminator's theoretically-zero linear_2/b gradient -- rounding noise of 128 cancelling terms, held to 3.2e-7 by
   //  tests/test_gpu_dem.py -- moves with the last bit of any fake: the training path keeps the summation order it was pinned with)
-  if (nz <= 16 && mfma_env && total >= (1L << 18) && total < (1L << 31)) {
+  if (nz <= 16 && total >= (1L << 18) && total < (1L << 31)) {
     const long ntile = (total + 15) / 16;
     const unsigned blocks = (unsigned)std::min<long>((ntile + 3) / 4, 4096);
     hipLaunchKernelGGL(deform1_premul_mfma_kernel, dim3(blocks), dim3(256), 0, s, xt, w, z, (int)total, plane, nz);

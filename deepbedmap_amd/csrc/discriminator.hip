@@ -53,9 +53,7 @@ static void layer_dims(int H, int W, int hs[11], int ws[11]) {
 }
 
 // Eval-mode coefficients of cache slot `slot` (scale = gamma / sqrt(avg_var + eps), shift = beta - avg_mean * scale for the nine
-// BatchNorm layers): ONE launch.  forward(bn_train = false) calls it itself unless the caller has done so (coef_ready) -- the deferred
-// eval-mode pass of dbm_train_iteration takes its coefficients right behind the discriminator's update, while the running statistics
-// and the parameters are still those the reference's call (srgan_train.py:1228) sees, and runs its convolutions later.
+// BatchNorm layers): ONE launch, at the head of every eval-mode forward.
 void Discriminator::prepare_eval_coeffs(int slot, hipStream_t s) {
   BnEvalJobs ej;
   memset(&ej, 0, sizeof(ej));
@@ -73,8 +71,8 @@ void Discriminator::prepare_eval_coeffs(int slot, hipStream_t s) {
   launch_bn_eval_coeffs(ej, 1e-5f, s);
 }
 
-void Discriminator::forward(int N, int H, int W, const float* img, float* logits, bool bn_train, bool keep, int slot, bool coef_ready) {
-  DBM_CHECK(slot >= 0 && slot <= 2 && (slot < 2 || !bn_train), "discriminator cache slot must be 0 or 1 (2: the library's own deferred eval-mode pass)");
+void Discriminator::forward(int N, int H, int W, const float* img, float* logits, bool bn_train, bool keep, int slot) {
+  DBM_CHECK(slot == 0 || slot == 1, "discriminator cache slot must be 0 or 1");
   int hs[11], ws[11];
   layer_dims(H, W, hs, ws);  // hs[i+1] = spatial size of h_i
   DBM_CHECK(hs[10] == 1 && ws[10] == 1, "discriminator input must reduce to 1x1 (linear_1 expects 512 features)");
@@ -98,7 +96,7 @@ void Discriminator::forward(int N, int H, int W, const float* img, float* logits
   BnEvalJobs ej;
   memset(&ej, 0, sizeof(ej));
   if (!bn_train) {
-    if (!coef_ready) prepare_eval_coeffs(slot, s);
+    prepare_eval_coeffs(slot, s);
     for (int i = 1; i < 10; ++i) {
       ej.start[i - 1] = ej.total;
       ej.total += DC_O[i];
@@ -141,21 +139,14 @@ void Discriminator::forward(int N, int H, int W, const float* img, float* logits
       launch_bn_train_fwd(c.z[i].p, c.h[i].p, P(T_bn[i][0]), P(T_bn[i][1]), c.mean[i].p, c.istd[i].p, S(T_bn[i][2]),
                           S(T_bn[i][3]), N, DC_O[i], ho * wo, 1e-5f, 0.9f, SLOPE, s, ctx->dev_err_flag);
   }
-  if ((c.N != N || c.H != H || c.W != W) && slot < 2) {
+  if (c.N != N || c.H != H || c.W != W) {
     for (auto& b : wb[slot]) b.reset();
     for (auto& b : wbm) b.reset();
   }  // buffers may move: re-plan the batched weight gradients
   c.l1.ensure(n * 100);
   if (!skip_deep) {
   // linear_1 -> LeakyReLU -> linear_2 (:693-696) as ONE launch (round 6: bitwise the two linear_fwd launches)
-  // (DBM_DISC_HEAD_FUSED=0, libdbm_measure.so only: the two-launch form -- A/B)
-  static const int head_fused = DBM_TUNE_GETENV("DISC_HEAD_FUSED") ? atoi(DBM_TUNE_GETENV("DISC_HEAD_FUSED")) : 1;
-  if (head_fused) {
-    launch_disc_head_fwd(c.h[9].p, P(T_l1W), P(T_l1b), P(T_l2W), P(T_l2b), c.l1.p, logits, N, 512, 100, SLOPE, s);
-  } else {
-    launch_linear_fwd(c.h[9].p, P(T_l1W), P(T_l1b), c.l1.p, N, 512, 100, 1, SLOPE, s);  // :693-695
-    launch_linear_fwd(c.l1.p, P(T_l2W), P(T_l2b), logits, N, 100, 1, 0, SLOPE, s);       // :696
-  }
+  launch_disc_head_fwd(c.h[9].p, P(T_l1W), P(T_l1b), P(T_l2W), P(T_l2b), c.l1.p, logits, N, 512, 100, SLOPE, s);
   }
   c.N = N; c.H = H; c.W = W;
   c.valid = keep && bn_train;
@@ -171,8 +162,8 @@ void Discriminator::forward(int N, int H, int W, const float* img, float* logits
 }
 
 // Weight gradients of one layer group go to the side stream once their inputs are final.  Merged mode (the fused
-// D-step): the pass that is enqueued first only records an event per group; the pass enqueued second
-// (`merge_launcher`) launches the group for both graphs behind both events.
+// D-step): the real batch's pass (slot 0) is enqueued first and only records an event per group; the fake batch's pass
+// (slot 1), enqueued second, launches the group for both graphs behind both events.
 void Discriminator::launch_group(int slot, int g) {
   if (!merge_slots) {
     ctx->fork_to_side(2 + slot);
@@ -181,7 +172,7 @@ void Discriminator::launch_group(int slot, int g) {
   }
   if (!ev_grp[slot][g]) DBM_HIP(hipEventCreateWithFlags(&ev_grp[slot][g], hipEventDisableTiming));
   DBM_HIP(hipEventRecord(ev_grp[slot][g], ctx->stream));
-  if (slot == merge_launcher) {  // the pass that is enqueued second: both events of this step exist now
+  if (slot == 1) {  // the pass that is enqueued second: both events of this step exist now
     DBM_HIP(hipStreamWaitEvent(ctx->side, ev_grp[slot][g], 0));
     if (ev_grp[1 - slot][g]) DBM_HIP(hipStreamWaitEvent(ctx->side, ev_grp[1 - slot][g], 0));
     wbm[g].launch(ctx->side);
@@ -217,8 +208,7 @@ void Discriminator::backward(int slot, const float* glogits, bool join) {
   float* gh = g_h[slot][0].p;
   float* gh_next = g_h[slot][1].p;
   if (!skip_deep) {
-  static const int head_fused = DBM_TUNE_GETENV("DISC_HEAD_FUSED") ? atoi(DBM_TUNE_GETENV("DISC_HEAD_FUSED")) : 1;
-  if (head_fused && disc_head_bwd_fused_ok(N, 100)) {  // both linear layers' backward as ONE launch (round 6: bitwise the two linear_bwd launches)
+  if (disc_head_bwd_fused_ok(N, 100)) {  // both linear layers' backward as ONE launch (round 6: bitwise the two linear_bwd launches)
     launch_disc_head_bwd(c.h[9].p, P(T_l1W), P(T_l2W), glogits, c.l1.p, gh, G(T_l1W), G(T_l1b), G(T_l2W), G(T_l2b), N, 512, 100, SLOPE, s);
   } else {
     launch_linear_bwd(c.l1.p, P(T_l2W), glogits, nullptr, g_l1[slot].p, G(T_l2W), G(T_l2b), N, 100, 1, SLOPE, s);

@@ -74,7 +74,6 @@ Generator::Generator(dbm_ctx* c, int n, float r, int oc) {
 Generator::~Generator() {
   if (twin) delete twin;
   if (ev_prefetch) (void)hipEventDestroy(ev_prefetch);
-  if (ev_trunk) (void)hipEventDestroy(ev_trunk);
   if (ev_csr) (void)hipEventDestroy(ev_csr);
   for (auto& e : ev_off) if (e) (void)hipEventDestroy(e);
   for (auto& e : ev_pack) if (e) (void)hipEventDestroy(e);
@@ -122,8 +121,7 @@ void Generator::pack_extra(hipStream_t s) {
   // the trunk's weight streams only by the persistent kernels behind it, the backward one not before the G-step: they are
   // rebuilt on chain[0] (idle at this point of a step) and the persistent launches wait for their events (~90 us off the
   // critical path of a training step).
-  static const int aside = DBM_TUNE_GETENV("PACK_ASIDE") ? atoi(DBM_TUNE_GETENV("PACK_ASIDE")) : 1;
-  hipStream_t ps = (aside && ctx->chain[0] && ctx->chain[0] != s) ? ctx->chain[0] : s;
+  hipStream_t ps = (ctx->chain[0] && ctx->chain[0] != s) ? ctx->chain[0] : s;
   if (!ev_pack[0]) for (auto& e : ev_pack) DBM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   if (ps != s) {
     DBM_HIP(hipEventRecord(ev_pack[0], s));
@@ -161,20 +159,17 @@ Generator* Generator::get_twin() {
 // number of image ranges the 9x9 stage is cut into (1 or 2): only when a single range would leave the chip
 // mostly idle (few tiles) and the ranges stay equal
 static int trunk_split(int N, long hw) {
-  static const int forced = DBM_TUNE_GETENV("TRUNK_SPLIT") ? atoi(DBM_TUNE_GETENV("TRUNK_SPLIT")) : 0;
   const long tiles = ((long)N * hw + 31) / 32;
   // two ranges: measured +4 % on the training step; more streams than hardware queues (four) serialise: 2.4x slower
   int ns = 1;
   if (tiles <= 1024 && N >= 2 && tiles >= 64) ns = 2;
-  if (forced > 0 && forced <= 2 && N >= forced) ns = forced;
   return ns;
 }
 
 // The backward of the two deformable layers runs on the fused kernels (deform_fused.hip) when the forward did and the
 // planes fit the CSR input-gradient kernel.
 bool Generator::deform_bwd_fused(int H4, int W4) const {
-  static const int fused_env = DBM_TUNE_GETENV("DEFORM_FUSED") ? atoi(DBM_TUNE_GETENV("DEFORM_FUSED")) : 1;
-  return fused_env && out_ch == 1 && deform_conv_fused_ok(64, 64) && deform_input_grad_ok(64, H4, W4);
+  return out_ch == 1 && deform_conv_fused_ok(64, 64) && deform_input_grad_ok(64, H4, W4);
 }
 
 // final_conv_layer1's weight gradient from the channels-last input and the offsets (deform_wgrad64_fused_kernel) instead of from the retained
@@ -276,9 +271,8 @@ void Generator::forward(int N, int H, int W, const float* x, const float* w1, co
   const bool cl16 = !fused && use_bf16 && !(bf16_keep32 & 4) && layers[L_rdb[0]].wcl16 != nullptr &&
                     !(getenv("DBM_CL16") && atoi(getenv("DBM_CL16")) == 0);
   // ... with the post-residual convolution and the full-resolution tail in split-bf16 on NHWC fp32 activations (see below)
-  static const int fused_env_x3 = DBM_TUNE_GETENV("DEFORM_FUSED") ? atoi(DBM_TUNE_GETENV("DEFORM_FUSED")) : 1;
-  const bool x3_tail = use_bf16 && !keep && fused_env_x3 && deform_conv_fused_ok(64, 64) && deform_conv_fused_ok(64, out_ch) &&
-                       layers[L_up1].wx3 != nullptr && !(DBM_TUNE_GETENV("CL16X3") && atoi(DBM_TUNE_GETENV("CL16X3")) == 0);
+  const bool x3_tail = use_bf16 && !keep && deform_conv_fused_ok(64, 64) && deform_conv_fused_ok(64, out_ch) &&
+                       layers[L_up1].wx3 != nullptr;
   // DBM_POST_X3=0 / DBM_PRE_X3=0 (or bits 32 / 64 of DBM_BF16_FP32_LAYERS): the post- / pre-residual convolution in fp32 (igemm)
   // between layout conversions, as before round 5's last changes
   const bool post_x3 = cl16 && x3_tail && layers[L_post].wx3 != nullptr && !(bf16_keep32 & 32) &&
@@ -385,10 +379,6 @@ void Generator::forward(int N, int H, int W, const float* x, const float* w1, co
       launch_trunk_fused(L, s);
       ctx->persist_end(s);
     }
-    if (mark_trunk) {
-      if (!ev_trunk) DBM_HIP(hipEventCreateWithFlags(&ev_trunk, hipEventDisableTiming));
-      DBM_HIP(hipEventRecord(ev_trunk, s));
-    }
   }
   if (cl16) {
     const size_t n = (size_t)N;
@@ -470,12 +460,11 @@ void Generator::forward(int N, int H, int W, const float* x, const float* w1, co
   const long P4 = 16 * hw;
   // The sampler is fused into the GEMM (deform_fused.hip), fed from a channels-last copy of the layer input; the
   // (N, 576, H, W) sample matrices exist only in a retained pass, as a by-product for the two weight gradients.
-  static const int fused_env = DBM_TUNE_GETENV("DEFORM_FUSED") ? atoi(DBM_TUNE_GETENV("DEFORM_FUSED")) : 1;
-  const bool dfused = fused_env && deform_conv_fused_ok(64, 64) && deform_conv_fused_ok(64, out_ch);
+  const bool dfused = deform_conv_fused_ok(64, 64) && deform_conv_fused_ok(64, out_ch);
   // bf16 sweep mode: the upsampling and offset convolutions -- on the signal path, where plain bf16 costs ~100 m rms at the
   // data range -- run in split-bf16 arithmetic (conv_cl16x3_kernel: three bf16 MFMAs per product, 2^-16 operand precision) on
-  // NHWC fp32 activations, which is also what the fused deformable sampler reads.  DBM_CL16X3=0 (read per call): fp32 igemm.
-  const bool x3 = use_bf16 && !keep && dfused && layers[L_up1].wx3 != nullptr && !(DBM_TUNE_GETENV("CL16X3") && atoi(DBM_TUNE_GETENV("CL16X3")) == 0);
+  // NHWC fp32 activations, which is also what the fused deformable sampler reads.
+  const bool x3 = use_bf16 && !keep && dfused && layers[L_up1].wx3 != nullptr;
   auto x3_launch = [&](const IgLayer& L, const float* xin, int ups, int Ho, int Wo, float* y32, float* yp, int act) {
     ClX3Launch q;
     memset(&q, 0, sizeof(q));
@@ -498,9 +487,8 @@ void Generator::forward(int N, int H, int W, const float* x, const float* w1, co
     ConvDesc e = prec(fwd_desc(layers[L_up2], a41.p, 64 * 4 * hw, 2 * h, 2 * w, 1, a42.p, 64 * 16 * hw, N), 8);
     e.act = 1;
     // (the fused deformable sampler reads a channels-last copy of this output: the LDS-tiled form writes it from its epilogue)
-    static const int fused_env0 = DBM_TUNE_GETENV("DEFORM_FUSED") ? atoi(DBM_TUNE_GETENV("DEFORM_FUSED")) : 1;
     a42t_written = false;
-    if (fused_env0 && deform_conv_fused_ok(64, 64) && deform_conv_fused_ok(64, out_ch)) {
+    if (dfused) {
       a42t.ensure((size_t)N * 64 * 16 * hw);
       e.yt = a42t.p;
       a42t_written = conv_tile_writes_yt(e);
@@ -519,8 +507,7 @@ void Generator::forward(int N, int H, int W, const float* x, const float* w1, co
   if (x3) {
     x3_launch(layers[L_off1], a42t.p, 0, H4, W4, nullptr, off1.p, 0);
     // (the split-bf16 tail reads channels-last only: the NCHW copy of this layer's output is not written)
-    static const bool dx3 = !(DBM_TUNE_GETENV("DEFORM_X3") && atoi(DBM_TUNE_GETENV("DEFORM_X3")) == 0);
-    if (dx3 && layers[L_def1].wdx3)
+    if (layers[L_def1].wdx3)
       launch_deform_conv64_x3(a42t.p, off1.p, layers[L_def1].wdx3, P(layers[L_def1].bi), nullptr, a51t.p, N, H4, W4, 32 * P4, 1, SLOPE, s);
     else
       launch_deform_conv_fused(a42t.p, off1.p, layers[L_def1].wf, P(layers[L_def1].bi), nullptr, a51t.p, nullptr, N, 64, H4, W4, 32 * P4, 64,
@@ -723,17 +710,14 @@ void Generator::backward(const float* gy) {
   DBM_MARK(s, "G:backward_tail_layers");
   ctx->fork_to_side(0);
   static const int iter_abl = DBM_MEASURE_ENV("ITER_ABL");  // (libdbm_measure.so only: 2 = no trunk weight gradients, 4 = none of the tail's)
-  const bool inline_wg = wgrad_inline && !ctx->comm_in_step;
-  if (!(iter_abl & 4) && !inline_wg) wbs[0].launch(ctx->side);
+  if (!(iter_abl & 4)) wbs[0].launch(ctx->side);
   if (deform_wgrad_fused(H4, W4) && !(iter_abl & 4)) {   // final_conv_layer1's weight / bias gradient (g_a51 and the offsets are final)
     dw1_partial.ensure(deform_wgrad64_partial_floats(N, H4, W4));
-    launch_deform_wgrad64_fused(a42t.p, off1.p, g_a51.p, G(layers[L_def1].wi), G(layers[L_def1].bi), dw1_partial.p, N, H4, W4, 32 * P4,
-                                inline_wg ? s : ctx->side);
+    launch_deform_wgrad64_fused(a42t.p, off1.p, g_a51.p, G(layers[L_def1].wi), G(layers[L_def1].bi), dw1_partial.p, N, H4, W4, 32 * P4, ctx->side);
   }
   if (col_stale) {  // (fused input block: the im2col images the wide branches' weight gradients read -- wbs[6], launched last)
-    hipStream_t cs = inline_wg ? s : ctx->side;
-    launch_im2col(bw_in[1] ? bw_in[1] : in_w1.p, colW1.p, N, 1, 10 * H, 10 * W, 30, 30, 10, h, w, layers[L_in[1]].CinP, cs);
-    launch_im2col(bw_in[2] ? bw_in[2] : in_w2.p, colW2.p, N, 2, 2 * H, 2 * W, 6, 6, 2, h, w, layers[L_in[2]].CinP, cs);
+    launch_im2col(bw_in[1] ? bw_in[1] : in_w1.p, colW1.p, N, 1, 10 * H, 10 * W, 30, 30, 10, h, w, layers[L_in[1]].CinP, ctx->side);
+    launch_im2col(bw_in[2] ? bw_in[2] : in_w2.p, colW2.p, N, 2, 2 * H, 2 * W, 6, 6, 2, h, w, layers[L_in[2]].CinP, ctx->side);
     col_stale = false;
   }
   // Data-parallel run: the gradient arena is in construction order (input block | pre | trunk | tail), and the backward
@@ -922,11 +906,10 @@ void Generator::backward(const float* gy) {
   //  1008 long workgroups then hold every CU while the eight short dependent launches of this tail and the discriminator's
   //  eval-mode pass each wait for a free slot.  The order below stays.)
   ctx->fork_to_side(6);
-  hipStream_t wgs = inline_wg ? s : ctx->side;
+  hipStream_t wgs = ctx->side;
   DBM_MARK(wgs, "G:side_backlog_done");   // (phase marks on the weight-gradient stream: what stood in front of the trunk's launch is done)
   if (prev_grp >= 0 && !(iter_abl & 2)) wbs[prev_grp].launch(wgs);
   DBM_MARK(wgs, "G:trunk_weight_gradients");
-  if (inline_wg && !(iter_abl & 4)) wbs[0].launch(wgs);
   wbs[6].launch(wgs);
   for (int k = 0; k < nsmall; ++k) {  // the two single-channel 3x3 branches of the input block
     const int i = small_i[k];

@@ -512,7 +512,6 @@ __global__ __launch_bounds__(64 * WAVES) void igemm_conv_kernel(const ConvDesc d
 
   if constexpr (NS) {
     igemm_epilogue_ns(d, acc, kh, pv, n, a, b, cout0, oy0, ox0);
-    if constexpr (NPB == -4) igemm_epilogue_ns(d, acc2, kh, pv, n, a, b, cout0 + 32, oy0, ox0);
   } else if constexpr (NPB == -4) {  // two output tiles: partial-tile slots 2 tile, 2 tile + 1
     if (ks <= 1) {  // (both tiles' operands before the first tile's stores)
       IgemmEpiOps<WAVES> o1, o2;
@@ -723,8 +722,7 @@ std::string KernelProfiler::dump_marks() {
 }
 
 static bool igemm_tap_skip(const ConvDesc& d) {
-  static const int skip_plane = DBM_TUNE_GETENV("IGEMM_SKIP_PLANE") ? atoi(DBM_TUNE_GETENV("IGEMM_SKIP_PLANE")) : 4;
-  return (d.T == 16 || d.T == 4) && d.Hin * d.Win <= skip_plane;
+  return (d.T == 16 || d.T == 4) && d.Hin * d.Win <= 4;
 }
 
 constexpr int IGEMM_NPB = 6;  // channel pairs a wavefront may hold entirely in registers (T = 9 -> 54 VGPRs)
@@ -736,7 +734,7 @@ static void launch_twr(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2) {
   if (d.wp16) {
     if constexpr (!ROW || T == 9) {
       if constexpr (WAVES == 4) {
-        if (d.nosplit) {
+        if (d.nosplit) {  // (decided by the launcher: bf16 on large grids, no cross-workgroup split)
           hipLaunchKernelGGL((igemm_conv_kernel<T, WAVES, -2, ROW, true>), grid, dim3(64 * WAVES), 0, s, d);
           return;
         }
@@ -746,11 +744,6 @@ static void launch_twr(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2) {
     }
   }
   if constexpr (WAVES == 4) {
-    if (d.nosplit) {  // (decided by the launcher: large grids, no cross-workgroup split)
-      if (mt2) hipLaunchKernelGGL((igemm_conv_kernel<T, WAVES, -4, ROW, true>), grid, dim3(64 * WAVES), 0, s, d);
-      else hipLaunchKernelGGL((igemm_conv_kernel<T, WAVES, 0, ROW, true>), grid, dim3(64 * WAVES), 0, s, d);
-      return;
-    }
     if (mt2) {  // two output tiles per wavefront: grid.y counts 64-channel groups
       hipLaunchKernelGGL((igemm_conv_kernel<T, WAVES, -4, ROW>), grid, dim3(64 * WAVES), WAVES * 4096, s, d);
       return;
@@ -780,8 +773,7 @@ static void launch_tw(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2) {
     const bool row = d.sin == 1 && d.ups == 0 && d.dy[0] == d.dy[1] && d.dy[1] == d.dy[2] && d.dx[1] == 0 &&
                      d.dx[0] == -d.dx[2] && (d.dx[0] == 1 || d.dx[0] == -1) && d.dy[3] == d.dy[5] && d.dy[6] == d.dy[8] &&
                      d.dx[3] == d.dx[0] && d.dx[6] == d.dx[0] && d.dx[4] == 0 && d.dx[7] == 0;
-    static const int bf16_row = DBM_TUNE_GETENV("BF16_ROW") ? atoi(DBM_TUNE_GETENV("BF16_ROW")) : 1;
-    if (row && (!d.wp16 || bf16_row)) {
+    if (row) {
       launch_twr<T, WAVES, true>(d, grid, s, mt2);
       return;
     }
@@ -818,32 +810,6 @@ static unsigned igemm_magic(unsigned long long dv) {  // floor(2^32 / dv), satur
   return (unsigned)(m > 0xffffffffULL ? 0xffffffffULL : m);
 }
 
-// Per-shape launch configuration (measured inside the training step, where the neighbours decide what a workgroup count costs):
-// key = (taps, Cin, Cout, positions of the widest phase, phases) -> two tiles per wavefront / wavefronts per tile / K split;
-// -1 = what the rules below say.  DBM_IGEMM_OVERRIDE="T:Cin:Cout:positions:phases=mt2,waves,ks;..." adds entries (tuning aid),
-// DBM_IGEMM_LOG=1 prints every distinct launch once.
-struct IgemmForce { int mt2, waves, ks; };
-typedef std::array<long, 5> IgemmKey;
-static const std::map<IgemmKey, IgemmForce>& igemm_overrides() {
-  static std::map<IgemmKey, IgemmForce> tab = [] {
-    std::map<IgemmKey, IgemmForce> t;
-    if (const char* e = DBM_TUNE_GETENV("IGEMM_OVERRIDE")) {
-      std::string str(e);
-      size_t pos = 0;
-      while (pos < str.size()) {
-        size_t end = str.find(';', pos);
-        if (end == std::string::npos) end = str.size();
-        long k[5]; int f[3];
-        if (sscanf(str.substr(pos, end - pos).c_str(), "%ld:%ld:%ld:%ld:%ld=%d,%d,%d", &k[0], &k[1], &k[2], &k[3], &k[4], &f[0], &f[1], &f[2]) == 8)
-          t[IgemmKey{k[0], k[1], k[2], k[3], k[4]}] = IgemmForce{f[0], f[1], f[2]};
-        pos = end + 1;
-      }
-    }
-    return t;
-  }();
-  return tab;
-}
-
 void launch_igemm_conv(const ConvDesc& d_in, hipStream_t s) {
   if (dbm_abl_skip() & 512) return;  // (libdbm_measure.so only)
   ConvDesc d = d_in;
@@ -870,20 +836,15 @@ void launch_igemm_conv(const ConvDesc& d_in, hipStream_t s) {
   DBM_CHECK(d.CoutP % 32 == 0 && d.Cout <= d.CoutP, "igemm: bad CoutP");
   DBM_CHECK(d.T == 1 || d.T == 4 || d.T == 9 || d.T == 16, "igemm: tap count must be 1, 4, 9 or 16");
   {  // the deep discriminator layers (planes of <= 4 x 4): position-major tiles, live taps only (igemm_pm_kernel)
-    const int pm_enable = DBM_TUNE_GETENV("IGEMM_PM") ? atoi(DBM_TUNE_GETENV("IGEMM_PM")) : 1;          // (read per call: A/B in one process)
-    const int pm_target = DBM_TUNE_GETENV("IGEMM_PM_KSTARGET") ? atoi(DBM_TUNE_GETENV("IGEMM_PM_KSTARGET")) : 512;
-    const int pm_min_n = DBM_TUNE_GETENV("IGEMM_PM_MIN_N") ? atoi(DBM_TUNE_GETENV("IGEMM_PM_MIN_N")) : 16;
-    // (3x3 on 4 x 4 planes -- 6.25 of 9 taps live on average -- stays with the general form: measured 35.5 against 30.7 us;
-    //  DBM_IGEMM_PM_K3_PLANE: largest plane of a 3x3 layer that takes this form)
-    const int pm_k3_plane = DBM_TUNE_GETENV("IGEMM_PM_K3_PLANE") ? atoi(DBM_TUNE_GETENV("IGEMM_PM_K3_PLANE")) : 4;
-    if (pm_enable && !d.wp16 && d.ups == 0 && nph == 1 && (d.T == 9 || d.T == 16) && d.Hin * d.Win <= (d.T == 9 ? pm_k3_plane : 16) && d.OHl * d.OWl <= 16 &&
-        d.N >= pm_min_n && d.Cin % 32 == 0 && 4L * d.T * d.Cin * d.CoutP < (1L << 31) && 4L * (d.N + 32) * d.xsn < (1L << 31)) {  // (32-bit byte offsets)
+    // (3x3 on 4 x 4 planes -- 6.25 of 9 taps live on average -- stays with the general form: measured 35.5 against 30.7 us)
+    if (!d.wp16 && d.ups == 0 && nph == 1 && (d.T == 9 || d.T == 16) && d.Hin * d.Win <= (d.T == 9 ? 4 : 16) && d.OHl * d.OWl <= 16 &&
+        d.N >= 16 && d.Cin % 32 == 0 && 4L * d.T * d.Cin * d.CoutP < (1L << 31) && 4L * (d.N + 32) * d.xsn < (1L << 31)) {  // (32-bit byte offsets)
       d.pm_groups = (d.N + 31) / 32;
       const bool mt2 = d.CoutP % 64 == 0 && d.Cout > 32;
       dim3 grid((unsigned)(d.OHl * d.OWl * d.pm_groups), (unsigned)((d.Cout + (mt2 ? 63 : 31)) / (mt2 ? 64 : 32)), 1u);
       const long tiles = (long)grid.x * grid.y;
       int ks = 1;  // input channels per workgroup stay a multiple of 32 (eight per wavefront)
-      while (ks < 32 && tiles * ks * 2 <= pm_target && (d.Cin / (ks * 2)) % 32 == 0) ks *= 2;
+      while (ks < 32 && tiles * ks * 2 <= 512 && (d.Cin / (ks * 2)) % 32 == 0) ks *= 2;
       const size_t slots = (size_t)tiles * (mt2 ? 2 : 1);
       if (ks > 1 && !(slots * ks * 1024 <= KS_PART_FLOATS && slots <= KS_COUNTERS)) ks = 1;
       if (ks > 1) {
@@ -943,46 +904,30 @@ void launch_igemm_conv(const ConvDesc& d_in, hipStream_t s) {
   long tiles = (long)grid.x * grid.y * nph;
   // Two output-channel tiles per wavefront (the gathered B operand feeds two MFMA chains): layers with >= 64 output
   // channels on large grids -- or, with the cross-workgroup split-K below restoring the workgroup count, any layer
-  // with a long K (DBM_IGEMM_MT2: 0 never, 1 large grids only, 2 also with split-K).
-  static const int mt2_mode = DBM_TUNE_GETENV("IGEMM_MT2") ? atoi(DBM_TUNE_GETENV("IGEMM_MT2")) : 2;
-  static const int ks_enable = DBM_TUNE_GETENV("IGEMM_KSPLIT") ? atoi(DBM_TUNE_GETENV("IGEMM_KSPLIT")) : 1;
-  static const int ks_target = DBM_TUNE_GETENV("IGEMM_KSTARGET") ? atoi(DBM_TUNE_GETENV("IGEMM_KSTARGET")) : 256;
+  // with a long K.
   // (round 3: 1024 -> 256 workgroups per split launch, 512 for the position-major form: inside the step these launches live on
   // the 64 CUs a persistent trunk launch leaves, where the number of workgroups, not the length of a K slice, is what they
   // pay for -- 8.22-8.30 ms per step with 1024 / the general form only, 8.13-8.16 with 256 / 512 and the position-major form)
   // (2048: conv_layer2 of the discriminator -- 1296 two-tile workgroups = 5.06 per CU, a sixth round on sixteen CUs -- stays
   // on one tile per wavefront, the 36 x 36 generator layers (2592) take two: 8.56 -> 8.47 ms per step against 1024)
-  static const int mt2_tiles = DBM_TUNE_GETENV("IGEMM_MT2_TILES") ? atoi(DBM_TUNE_GETENV("IGEMM_MT2_TILES")) : 2048;
-  const bool mt2_ok = mt2_mode && !d.wp16 && d.CoutP % 64 == 0 && grid.y % 2 == 0 && !igemm_tap_skip(d);
-  bool mt2 = mt2_ok && tiles / 2 >= mt2_tiles;
-  if (!mt2 && mt2_ok && mt2_mode >= 2 && ks_enable && (long)d.Cin * d.T >= 1024 && tiles / 2 <= 512 && tiles >= 64) mt2 = true;
-  const IgemmKey key{d.T, d.Cin, d.Cout, total, nph};
-  IgemmForce force{-1, -1, -1};
-  if (!d.wp16) {
-    auto it = igemm_overrides().find(key);
-    if (it != igemm_overrides().end()) force = it->second;
-  }
-  if (force.mt2 >= 0) mt2 = force.mt2 && mt2_ok;
+  const bool mt2_ok = !d.wp16 && d.CoutP % 64 == 0 && grid.y % 2 == 0 && !igemm_tap_skip(d);
+  bool mt2 = mt2_ok && tiles / 2 >= 2048;
+  if (!mt2 && mt2_ok && (long)d.Cin * d.T >= 1024 && tiles / 2 <= 512 && tiles >= 64) mt2 = true;
   if (mt2) { grid.y /= 2; tiles /= 2; }
   // few tiles -> more wavefronts per tile (Cin % 32 == 0 keeps Cin / WAVES even for every choice)
   // (1536 -- eight wavefronts for the 1296-tile layers, 5.06 four-wavefront workgroups per CU -- measured -0.04 ms per step; not
   // taken: the other summation order moves one discriminator gradient of the batch-64 fixture past its bound, a slope flip)
-  static const int w4_tiles = DBM_TUNE_GETENV("IGEMM_W4_TILES") ? atoi(DBM_TUNE_GETENV("IGEMM_W4_TILES")) : 1024;
-  static const int w8_tiles = DBM_TUNE_GETENV("IGEMM_W8_TILES") ? atoi(DBM_TUNE_GETENV("IGEMM_W8_TILES")) : 512;
-  int waves = (tiles >= w4_tiles || mt2) ? 4 : (tiles >= w8_tiles ? 8 : 16);
+  int waves = (tiles >= 1024 || mt2) ? 4 : (tiles >= 512 ? 8 : 16);
   // ... but a wavefront should own a few channel pairs: with a short K (the 32-channel data gradients of the dense
   // blocks) the cross-wavefront reduction and a 1024-thread workgroup cost more than the MFMAs they spread
-  static const int min_pairs = DBM_TUNE_GETENV("IGEMM_MINPAIRS") ? atoi(DBM_TUNE_GETENV("IGEMM_MINPAIRS")) : 4;  // (re-measured at the end of round 2: 6 -> 4, -0.08 ms per step)
-  static const int min_tiles = DBM_TUNE_GETENV("IGEMM_MINTILES") ? atoi(DBM_TUNE_GETENV("IGEMM_MINTILES")) : 96;
-  while (tiles > min_tiles && waves > 4 && d.Cin / (2 * waves) < min_pairs) waves >>= 1;
-  if (force.waves > 0 && !(mt2 && force.waves != 4)) waves = force.waves;
+  // (four channel pairs re-measured at the end of round 2: 6 -> 4, -0.08 ms per step)
+  while (tiles > 96 && waves > 4 && d.Cin / (2 * waves) < 4) waves >>= 1;
   // Few tiles and a long K (the deep discriminator layers: 32..512 tiles, K = 2048..8192): the input channels are also split
   // across workgroups of four wavefronts, about 1024 workgroups per launch; partial tiles are folded deterministically by
   // the last workgroup of each tile (igemm_epilogue).  The bf16 inference images keep the one-workgroup form.
-  if (ks_enable && (force.ks > 1 || (force.ks < 0 && tiles <= 512 && (long)d.Cin * d.T >= 1024)) && !d.wp16) {
+  if (tiles <= 512 && (long)d.Cin * d.T >= 1024 && !d.wp16) {
     int ks = 1;
-    while (ks < 32 && tiles * ks * 2 <= ks_target && (d.Cin / (ks * 2)) % 8 == 0 && d.Cin / (ks * 2) >= 32) ks *= 2;
-    if (force.ks > 1 && (d.Cin / force.ks) % 8 == 0 && d.Cin / force.ks >= 32) ks = force.ks;
+    while (ks < 32 && tiles * ks * 2 <= 256 && (d.Cin / (ks * 2)) % 8 == 0 && d.Cin / (ks * 2) >= 32) ks *= 2;
     const size_t slots = (size_t)tiles * (mt2 ? 2 : 1);
     if (ks > 1 && slots * ks * 1024 <= KS_PART_FLOATS && slots <= KS_COUNTERS) {
       KsWorkspace& w = ks_workspace(s);
@@ -994,26 +939,13 @@ void launch_igemm_conv(const ConvDesc& d_in, hipStream_t s) {
     }
   }
   if (mt2 && waves != 4) { mt2 = false; grid.y *= 2; }
-  {
-    static const bool log = DBM_TUNE_GETENV("IGEMM_LOG") != nullptr;
-    if (log) {
-      static std::map<IgemmKey, int> seen;
-      if (!seen.count(key)) {
-        seen[key] = 1;
-        fprintf(stderr, "igemm %ld:%ld:%ld:%ld:%ld tiles=%ld mt2_ok=%d -> mt2=%d waves=%d ks=%d\n", key[0], key[1], key[2], key[3], key[4],
-                (long)grid.x * grid.y * nph, (int)mt2_ok, (int)mt2, waves, d.ksplit);
-      }
-    }
-  }
   // bf16 inference on large grids (>= 2048 position tiles: the crops of the area sweep): no split-K at all -- each of a
   // workgroup's four wavefronts owns a position tile of its own over the whole K; no LDS reduction, no barrier, the
   // accumulators go out from the registers.  (With sixteen channels per 32-cycle MFMA a K slice is a handful of
   // instructions and the cross-wavefront reduction costs more than it spreads: 14.2 -> 13.2 ms per 288 x 288 crop.  The
-  // fp32 layers keep the split: 88 vs 93-100 us on the 36 x 36 layers, 22.0 vs 25.4 ms per fp32 crop -- DBM_IGEMM_NOSPLIT_F32=1.)
-  static const int ns_tiles = DBM_TUNE_GETENV("IGEMM_NOSPLIT") ? atoi(DBM_TUNE_GETENV("IGEMM_NOSPLIT")) : 2048;
-  static const int ns_f32 = DBM_TUNE_GETENV("IGEMM_NOSPLIT_F32") ? atoi(DBM_TUNE_GETENV("IGEMM_NOSPLIT_F32")) : 0;
+  // fp32 layers keep the split: 88 vs 93-100 us on the 36 x 36 layers, 22.0 vs 25.4 ms per fp32 crop.)
   d.nosplit = 0;
-  if (ns_tiles > 0 && (d.wp16 || ns_f32) && d.ksplit <= 1 && waves == 4 && (long)grid.x >= ns_tiles) {
+  if (d.wp16 && d.ksplit <= 1 && waves == 4 && (long)grid.x >= 2048) {
     d.nosplit = 1;
     grid.x = (grid.x + 3) / 4;
   }

@@ -99,10 +99,7 @@ void launch_bn_eval_coeffs(const BnEvalJobs& jobs, float eps, hipStream_t s);
 void launch_bn_train_bwd(const float* z, const float* gh, const float* gamma, const float* beta, const float* mean,
                          const float* inv_std, float* gz, float* ggamma, float* gbeta, float* scratch, int N, int C,
                          int plane, float slope, hipStream_t s);
-// Linear layers of the discriminator head (tiny): y[n][o] = act(b[o] + sum_k W[o][k] x[n][k])
-void launch_linear_fwd(const float* x, const float* W, const float* b, float* y, int N, int K, int O, int act,
-                       float slope, hipStream_t s);
-// gx[n][k] = sum_o gyz[n][o] W[o][k]; gW[o][k] += sum_n gyz[n][o] x[n][k]; gb[o] += sum_n gyz[n][o]
+// Linear layers of the discriminator head (tiny), backward: gx[n][k] = sum_o gyz[n][o] W[o][k]; gW[o][k] += sum_n gyz[n][o] x[n][k]; gb[o] += sum_n gyz[n][o]
 // where gyz = gy * lrelu'(y) if y_act != null else gy
 void launch_linear_bwd(const float* x, const float* W, const float* gy, const float* y_act, float* gx, float* gW,
                        float* gb, int N, int K, int O, float slope, hipStream_t s);
@@ -179,7 +176,7 @@ struct TrunkFusedBwdLaunch {
   float rs, slope;
 };
 size_t trunk_fused_xcc_offset(int nimg_alloc);  // granules in front of the XCC_ID table at the end of an inbox buffer
-int trunk_local_stores();                       // DBM_TRUNK_LOCAL_ST (default 1): same-XCD exchange stores stay in the L2
+int trunk_local_stores();                       // same-XCD exchange stores stay in the L2 (until the first time-out)
 extern bool g_trunk_local_off;                  // ... until a persistent kernel has timed out once in this process
 size_t trunk_fused_bwd_stream_floats(int nrdb);
 void launch_pack_trunk_fused_bwd(const float* const* d_wsrc, float* wstream, int nrdb, hipStream_t s);

@@ -88,22 +88,6 @@ struct dbm_ctx {
   float* zeros = nullptr;     // 256 B of zeros (igemm out-of-image taps)
   float* ssim_win[2] = {nullptr, nullptr};  // 9-tap 1-D windows: gaussian(1.5), uniform
   DevBuf loss_tmp;            // scratch for the loss entry points
-  // dbm_train_iteration with DBM_ITER_DEFER_EVAL=1 (round 6, opt-in): the G-step's detached eval-mode discriminator pass (srgan_train.py:1228) feeds a LOGGED value only
-  // (the adversarial term of g_loss; its gradient never reaches the generator).  Iteration i therefore only SNAPSHOTS what that pass
-  // reads -- the eval-mode BatchNorm coefficients right behind the discriminator's update (parameters and running statistics as the
-  // reference's call sees them), the generator's fakes, the loss terms' partial sums -- and the pass itself (nine convolutions, two
-  // linear layers, the loss value -> that iteration's metrics row) is enqueued by the NEXT library call: inside iteration i + 1 beside
-  // its generator forwards, or on the main stream at the entry of any other entry point (every DBM_API_BEGIN flushes; dbm_synchronize
-  // and every copy the caller reads metrics with are entry points).  Same kernels, same inputs: the logged numbers are bitwise the same.
-  struct DeferredEval {
-    bool pending = false;
-    struct Discriminator* d = nullptr;
-    int N = 0, H4 = 0, W4 = 0;
-    float w[4] = {0.f, 0.f, 0.f, 0.f};
-    float* out3 = nullptr;          // device: [g_loss, psnr, ssim] of that iteration's metrics row
-    DevBuf fakes, scratch, logits;  // scratch: loss_tmp's layout (16 + 5 N floats)
-    hipEvent_t ev_ready = nullptr;  // the snapshots are complete (recorded on the main stream)
-  } deferred;
   DevBuf stage[8];            // host<->device staging for the non-DEVICE_PTRS entry points
 };
 
@@ -263,13 +247,8 @@ struct Generator : dbm_model {
   Generator* owner = nullptr;  // twin only: the model whose arenas and weight images it aliases
   int chain_base = 0;
   bool use_aux = true;  // backward(): the deformable layers' offset-gradient kernel may run on chain[chain_base]
-  bool wgrad_inline = false;  // backward(): every weight-gradient launch goes to the pass's OWN stream, behind the data-gradient chain
-                              // (dbm_train_iteration, DBM_ITER_EARLY_TWIN=2: the side stream carries the discriminator's weight gradients, and
-                              // a launch queued behind them would wait for the whole D-step)
   int max_split = 2;  // image ranges the 9x9 stage may be cut into (1: everything on the caller's stream)
   hipEvent_t ev_prefetch = nullptr;
-  hipEvent_t ev_trunk = nullptr;   // forward(): recorded behind the 9x9 stage's trunk launch when mark_trunk is set (dbm_train_iteration:
-  bool mark_trunk = false;         // the G-step's own forward may start there instead of behind this forward's full-resolution tail)
   hipEvent_t ev_pack[3] = {nullptr, nullptr, nullptr};  // pack_extra: main stream reached the repack / forward streams built / backward streams built
   // fused 9x9 trunk forward (trunk_fused.hip): per-wavefront weight streams (owner only), per-workspace hand-off granules
   float* tf_wstream = nullptr;
@@ -299,23 +278,22 @@ struct Discriminator : dbm_model {
     bool valid = false;
     DevBuf img, h[10], z[10], mean[10], istd[10], l1, out;
     const float* img_src = nullptr;   // the retained pass's input image: the private copy `img`, or the caller's buffer (borrow_images)
-  } cache[3];         // [2]: the deferred eval-mode pass of dbm_train_iteration (never retained: no backward reads it)
-  DevBuf bn_coef[3];  // eval-mode passes: [scale | shift] of all nine BatchNorm layers (launch_bn_eval_coeffs), one buffer per cache
+  } cache[2];
+  DevBuf bn_coef[2];  // eval-mode passes: [scale | shift] of all nine BatchNorm layers (launch_bn_eval_coeffs), one buffer per cache
                       // slot: two eval-mode passes in flight on different streams never share coefficients
   DevBuf g_h[2][2], g_z[2][10], g_l1[2], g_out, c0_scratch[2];  // per retained graph: the two backward passes overlap
   static const int NWG = 4;
   WgradBatch wbm[NWG];     // the same for BOTH graphs in one launch per group (the fused D-step: twice the work per launch)
   hipEvent_t ev_grp[2][NWG] = {};
   size_t comm_sent_lo = 0, comm_sent_hi = 0;  // gradient range already handed to the exchange by launch_group (this step)
-  int merge_launcher = 0;    // merged mode: the slot whose backward pass is enqueued SECOND (it launches the groups)
-  bool merge_slots = false;  // set by dbm_discriminator_step around its two backward calls (fake first, then real)
+  bool merge_slots = false;  // set by the fused steps around their two backward calls (real first, then fake)
   // set by the fused steps around their retained forwards: conv_layer0's weight gradient reads the caller's image buffer directly (it
   // outlives the call, and the backward pass runs inside it) instead of a private copy -- one 332 KB copy launch less per pass (round 6)
   bool borrow_images = false;
   void launch_group(int slot, int g);
   WgradBatch wb[2][NWG];  // batched weight gradients per retained graph (real / fake batch): layers 9..6, 5..4, 3..2, 1
   Discriminator(dbm_ctx* c);
-  void forward(int N, int H, int W, const float* img, float* logits, bool bn_train, bool keep, int slot, bool coef_ready = false);
+  void forward(int N, int H, int W, const float* img, float* logits, bool bn_train, bool keep, int slot);
   void prepare_eval_coeffs(int slot, hipStream_t s);
   void backward(int slot, const float* glogits, bool join = true);
 };

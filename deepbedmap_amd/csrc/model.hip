@@ -363,9 +363,8 @@ void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_
   } else {
     // the four phases (py, px) of the stride-2 gradient -- output positions (2a + py, 2b + px), 2x2 taps each -- as ONE launch
     // (blockIdx.z = phase); planes that lack a phase (a single row or column) fall back to one launch per phase
-    static const int merge = DBM_TUNE_GETENV("IGEMM_MERGE_PHASES") ? atoi(DBM_TUNE_GETENV("IGEMM_MERGE_PHASES")) : 1;
     base.so = 2; base.T = 4;
-    if (merge && Hin_fwd >= 2 && Win_fwd >= 2) {
+    if (Hin_fwd >= 2 && Win_fwd >= 2) {
       base.nphase = 4;
       for (int ph = 0; ph < 4; ++ph) {
         const int py = ph >> 1, px = ph & 1;

@@ -616,33 +616,6 @@ void launch_bn_sync_bwd_apply(const float* z, const float* gh, const float* gamm
 // ----------------------------------------------------------------------------------------------
 // L.Linear head of the discriminator (srgan_train.py:646-647, 693-696).  51 300 + 101 parameters.
 // ----------------------------------------------------------------------------------------------
-// one wavefront per output element: both rows are read coalesced, then a shuffle reduction
-__global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict__ x, const float* __restrict__ W,
-                                                         const float* __restrict__ b, float* __restrict__ y, int N,
-                                                         int K, int O, int act, float slope) {
-  const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (e >= N * O) return;
-  const int lane = threadIdx.x & 63;
-  const int n = e / O, o = e - n * O;
-  const float* xr = x + (long)n * K;
-  const float* wr = W + (long)o * K;
-  float a = 0.f;
-  for (int k = lane; k < K; k += 64) a = fmaf(xr[k], wr[k], a);
-  for (int s = 32; s > 0; s >>= 1) a += __shfl_down(a, s, 64);
-  if (lane == 0) {
-    float v = a + b[o];
-    if (act) v = v >= 0.f ? v : slope * v;
-    y[e] = v;
-  }
-}
-
-void launch_linear_fwd(const float* x, const float* W, const float* b, float* y, int N, int K, int O, int act,
-                       float slope, hipStream_t s) {
-  if (dbm_abl_skip() & 32) return;  // (libdbm_measure.so only)
-  hipLaunchKernelGGL(linear_fwd_kernel, dim3((N * O + 3) / 4), dim3(256), 0, s, x, W, b, y, N, K, O, act, slope);
-  DBM_HIP(hipGetLastError());
-}
-
 __device__ __forceinline__ float gyz_of(const float* gy, const float* y_act, int idx, float slope) {
   const float g = gy[idx];
   return (y_act == nullptr || y_act[idx] >= 0.f) ? g : slope * g;
@@ -698,10 +671,10 @@ void launch_linear_bwd(const float* x, const float* W, const float* gy, const fl
 }
 
 // ---- the discriminator's head as ONE launch per pass (round 6) ----
-// linear_1 -> LeakyReLU -> linear_2 (:693-696) used to be two launches of linear_fwd_kernel at the end of every discriminator forward
+// linear_1 -> LeakyReLU -> linear_2 (:693-696) used to be two launches of a one-wavefront-per-output kernel at the end of every discriminator forward
 // (three per iteration) and two of linear_bwd_kernel at the head of every backward pass, i.e. of both serial chains the D-step waits for;
 // inside the iteration a launch of that size costs 20-40 us of queueing whatever it computes.  Same arithmetic in the same order as the
-// two-launch form (every sum below is linear_fwd_kernel's / linear_bwd_kernel's own): results are bitwise the same.
+// two-launch form (every sum below is that kernel's / linear_bwd_kernel's own): results are bitwise the same.
 // Forward: one workgroup per image; wavefront w computes outputs w, w + 4, ... of linear_1 (lanes stride the 512 inputs, shuffle tree),
 // the row goes to memory (the backward pass reads it) and to LDS, wavefront 0 then forms the logit.
 template <int K, int NW>
@@ -732,7 +705,7 @@ __global__ __launch_bounds__(64 * NW) void disc_head_fwd_kernel(const float* __r
       const int o = o0 + u * NW;
       float a = 0.f;
 #pragma unroll
-      for (int i = 0; i < KP; ++i) a = fmaf(xv[i], wv[u][i], a);   // (k = lane, lane + 64, ...: linear_fwd_kernel's order)
+      for (int i = 0; i < KP; ++i) a = fmaf(xv[i], wv[u][i], a);   // (k = lane, lane + 64, ...: the two-launch form's order)
       for (int s = 32; s > 0; s >>= 1) a += __shfl_down(a, s, 64);
       if (lane == 0 && o < O) {
         float v = a + b1[o];

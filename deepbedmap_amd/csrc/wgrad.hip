@@ -40,8 +40,8 @@ __device__ unsigned long long g_dbg[4 * 8192];
 
 bool g_wgrad_deterministic = true;  // the reference trains with cudnn_deterministic = True (srgan_train.py:69)
 
-// Deterministic mode: a wavefront's accumulators go out in register order (256-byte stores) to its slot of the partial
-// buffer; wgrad_fold_kernel sums the K slices in order.
+// Deterministic mode: K slices 2k and 2k + 1 add into pair buffer k (WgradPlan::pairW), wgrad_pair_fold_kernel sums the buffers in
+// order.  (The slot-partial epilogue below -- WgradPlan::partial -- is never selected by the planner; see WgradPlan.)
 // gradient targets of K slice bz: gW / gb themselves, or a pair buffer
 __device__ __forceinline__ void pair_targets(const WgradPlan& p, int bz, float*& gW, float*& gb) {
   gW = p.d.gW; gb = p.d.gb;
@@ -1113,50 +1113,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_1x1_kernel(const WgradPlan* __re
 }
 
 
-// Sums the K-slice partials of a weight-gradient launch in slice order and adds them to gW (OIHW) / gb: one workgroup per
-// 256 elements of one wavefront slot's tile.  No fp32 atomics on the K split (the one atomic per element below only
-// serialises the real- and the fake-batch graph of the discriminator: two contributions onto a cleared gradient, and
-// a + b == b + a), hence bitwise reproducible.
-__global__ __launch_bounds__(256) void wgrad_fold_kernel(const WgradPlan* __restrict__ plans, const int* __restrict__ fstarts,
-                                                         int nplans) {
-  int lo = 0, hi = nplans - 1;
-  const int wg = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (fstarts[mid] <= wg) lo = mid; else hi = mid - 1;
-  }
-  const WgradPlan& p = plans[lo];
-  const WgradDesc& d = p.d;
-  const int T = d.KH * d.KW;
-  const int parts = p.fold_tpw * 4;  // 256-element pieces of a slot's fold_tpw * 1024 floats
-  int local = wg - fstarts[lo];
-  const int part = local % parts; local /= parts;
-  const int slot = local % p.fold_slots; local /= p.fold_slots;
-  const int grp = local % p.groups;
-  const int by = local / p.groups;
-  const int ctl = slot % p.fold_cts, tg = slot / p.fold_cts;
-  const int ct = grp * p.fold_ctmul + ctl;
-  const int cout0 = by * 32, cin_w = ct * 32;
-  if (d.gb && grp == 0 && slot == 0 && part == 0 && threadIdx.x < 32 && cout0 + (int)threadIdx.x < d.Cout) {
-    float v = 0.f;
-    for (int z = 0; z < p.S; ++z) v += p.partial_b[((long)z * p.coutTiles + by) * 32 + threadIdx.x];
-    atomicAdd(d.gb + cout0 + threadIdx.x, v);
-  }
-  if (ctl >= p.fold_ctmul || cin_w >= d.Cin) return;
-  const long tsz = (long)p.fold_tpw * 1024;
-  const long tile = (((long)by * p.groups + grp) * p.fold_slots + slot) * tsz;
-  const long sstride = (long)p.coutTiles * p.groups * p.fold_slots * tsz;
-  const int e = part * 256 + threadIdx.x;
-  float v = 0.f;
-#pragma unroll 4
-  for (int z = 0; z < p.S; ++z) v += p.partial[z * sstride + tile + e];
-  const int lane = e & 63, r = (e >> 6) & 15, t = tg * p.fold_tpw + (e >> 10);
-  const int o = cout0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-  const int c = cin_w + (lane & 31);
-  if (o < d.Cout && c < d.Cin) atomicAdd(d.gW + ((long)o * d.Cin + c) * T + t, v);
-}
-
-
 // ---------------------------------------------------------------------------------------------------------------
 // 4x4 / stride 2 / pad 1 layers on tiny output planes (OW <= 4: the discriminator's conv_layer5 / 7 / 9, 9x9 -> 4x4,
 // 4x4 -> 2x2, 2x2 -> 1x1) and, round 3, 3x3 / stride 1 / pad 1 layers on such planes (conv_layer6 / 8: they used to go
@@ -1315,10 +1271,8 @@ __global__ __launch_bounds__(256) void wgrad_s2tiny_kernel(const TinyPlan* __res
 }
 
 static bool s2tiny_eligible(const WgradDesc& d) {
-  static const int on = DBM_TUNE_GETENV("WGRAD_TINY") ? atoi(DBM_TUNE_GETENV("WGRAD_TINY")) : 1;   // bit 0: 4x4 stride 2, bit 1: 3x3 stride 1
-  const bool k4 = (on & 1) && d.KH == 4 && d.KW == 4 && d.stride == 2;
-  static const int on3 = DBM_TUNE_GETENV("WGRAD_TINY3") ? atoi(DBM_TUNE_GETENV("WGRAD_TINY3")) : 1;
-  const bool k3 = on3 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.Hin == d.OH && d.Win == d.OW;
+  const bool k4 = d.KH == 4 && d.KW == 4 && d.stride == 2;
+  const bool k3 = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.Hin == d.OH && d.Win == d.OW;
   return (k4 || k3) && d.pad == 1 && d.ups == 0 && d.OW <= 4 && d.OH <= 4 && d.gb == nullptr &&
          d.Cin % 32 == 0 && d.Cout % 32 == 0 && d.xsc == d.Hin * d.Win && d.dysc == d.OH * d.OW && d.Win >= 2 &&
          (long)d.N * d.OH * d.OW + 4 <= TINY_MAXK && (long)d.N * d.xsn < (1L << 31) && (long)d.N * d.dysn < (1L << 27);
@@ -1577,24 +1531,6 @@ void WgradBatch::reset() {
   }
 }
 
-static int direct_form_enabled() {  // DBM_WGRAD_DIRECT: 1 (default) = wgrad_direct_kernel for the large-plane 3x3 / 4x4 layers
-  static int v = -1;
-  if (v < 0) {
-    const char* e = DBM_TUNE_GETENV("WGRAD_DIRECT");
-    v = e ? atoi(e) : 1;
-  }
-  return v;
-}
-
-static int dma_forms_enabled() {  // DBM_WGRAD_WAVE: 0 = workgroup form only, 1 = + trunk LDS-DMA tasks, 2 (default) = + row-band LDS-DMA
-  static int v = -1;
-  if (v < 0) {
-    const char* e = DBM_TUNE_GETENV("WGRAD_WAVE");
-    v = e ? atoi(e) : 2;
-  }
-  return v;
-}
-
 static const float* device_zeros() {
   static float* z = nullptr;
   if (!z) {
@@ -1612,9 +1548,7 @@ void WgradBatch::build() {
   // 9 = 1x1 on large contiguous planes (LDS-staged GEMM, wgrad_1x1_kernel)
   static const int TT[NCAT] = {1, 9, 16, 9, 9, 16, 9, 9, 16, 1};
   static const int MODE[NCAT] = {0, 0, 0, 2, 3, 3, 4, 4, 4, 5};
-  const bool direct = direct_form_enabled() != 0;
   std::vector<int> cat(descs.size());
-  const int forms = dma_forms_enabled();
   // ---- 4x4 stride-2 layers on tiny planes: their own kernel (wgrad_s2tiny_kernel), outside the category tables.  Two
   // descriptors with the same gradient (the real- and the fake-batch graph of the discriminator) share a plan. ----
   {
@@ -1661,10 +1595,11 @@ void WgradBatch::build() {
     if (tiny_owner[i] >= 0) { cat[i] = -1; continue; }
     const int T = descs[i].KH * descs[i].KW;
     WgradPlan p;
-    const int dm = direct ? direct_mode(descs[i]) : -1;
-    if (T == 1) cat[i] = (direct && gemm1x1_eligible(descs[i])) ? 9 : 0;
-    else if (T == 9) cat[i] = (forms >= 1 && wgrad_plan(descs[i], p, 0, 2) != 0) ? 3 : dm >= 0 ? 6 + dm : (forms >= 2 && wgrad_plan(descs[i], p, 0, 3) != 0) ? 4 : 1;
-    else cat[i] = dm >= 0 ? 6 + dm : (forms >= 2 && wgrad_plan(descs[i], p, 0, 3) != 0) ? 5 : 2;
+    // (the workgroup forms, categories 0 / 1 / 2, serve every layer the other forms refuse)
+    const int dm = direct_mode(descs[i]);
+    if (T == 1) cat[i] = gemm1x1_eligible(descs[i]) ? 9 : 0;
+    else if (T == 9) cat[i] = wgrad_plan(descs[i], p, 0, 2) != 0 ? 3 : dm >= 0 ? 6 + dm : wgrad_plan(descs[i], p, 0, 3) != 0 ? 4 : 1;
+    else cat[i] = dm >= 0 ? 6 + dm : wgrad_plan(descs[i], p, 0, 3) != 0 ? 5 : 2;
   }
   for (int g = 0; g < NCAT; ++g) {
     std::vector<WgradPlan> plans;
@@ -1683,8 +1618,7 @@ void WgradBatch::build() {
         const WgradDesc& d = descs[i];
         work += (long)((d.Cin + 127) / 128) * ((d.Cout + 63) / 64) * d.N * ((d.OH * d.OW + 31) / 32);
       }
-      static const int slots_env = DBM_TUNE_GETENV("WGRAD_1X1_WGS") ? atoi(DBM_TUNE_GETENV("WGRAD_1X1_WGS")) : 512;
-      segs_per_wg = std::max(8L, (work + slots_env - 1) / slots_env);   // bands of 32 positions per workgroup
+      segs_per_wg = std::max(8L, (work + 511) / 512);   // bands of 32 positions per workgroup
     } else if (g >= 6) {
       // direct form: equally long workgroups, about two per CU over the whole launch (a workgroup's K range should stay
       // long enough that its closing atomics are a small fraction: >= 64 segments = 512 positions)
@@ -1694,8 +1628,7 @@ void WgradBatch::build() {
         const WgradDesc& d = descs[i];
         work += (long)((d.Cin + 31) / 32) * ((d.Cout + 31) / 32) * (g == 8 ? 2 : 1) * d.N * d.OH * ((d.OW + 7) / 8);
       }
-      static const int slots_env = DBM_TUNE_GETENV("WGRAD_DIRECT_WGS") ? atoi(DBM_TUNE_GETENV("WGRAD_DIRECT_WGS")) : 512;
-      segs_per_wg = std::max(64L, (work + slots_env - 1) / slots_env);
+      segs_per_wg = std::max(64L, (work + 511) / 512);
     } else if (g >= 3) {
       long units = 0;
       size_t need = 0;
@@ -1705,13 +1638,11 @@ void WgradBatch::build() {
         need = std::max(need, wgrad_plan(descs[i], p, 0, MODE[g], 1));
         units += (long)p.groups * p.coutTiles;
       }
-      static const int slots_env = DBM_TUNE_GETENV("WGRAD_SLOTS") ? atoi(DBM_TUNE_GETENV("WGRAD_SLOTS")) : 0;
       // (few-layer launches -- the discriminator's conv_layer4: 16 units -- take a coarser K split: 256 workgroups of four images
       // instead of 1024 of one, a quarter of the partial tiles to write and fold: 116 -> 90 us standalone, round 3)
-      static const int slots_small = DBM_TUNE_GETENV("WGRAD_SLOTS_SMALL") ? atoi(DBM_TUNE_GETENV("WGRAD_SLOTS_SMALL")) : 256;
-      int slots = slots_env ? slots_env : (need > 40 * 1024 ? 512 : 1024);
+      int slots = need > 40 * 1024 ? 512 : 1024;
       // (<= 32 units: in data-parallel runs the trunk's launches are cut into four groups of 126 units each -- those keep the fine split)
-      if (g == 3 && slots_small && units > 0 && units <= 32) slots = std::min(slots, slots_small);  // (the row-band forms lose: 164 -> 204 us)
+      if (g == 3 && units > 0 && units <= 32) slots = std::min(slots, 256);  // (the row-band forms lose: 164 -> 204 us)
       if (units > 0) S_fixed = (int)std::max(1L, slots / units);
     }
     // workgroup forms: a launch should offer about two workgroups per CU; small batches split their position axis finer
@@ -1738,67 +1669,35 @@ void WgradBatch::build() {
       // but a launch of a few dozen workgroups, e.g. the 4x4 layers of the deep discriminator, is split as well)
       // (256 since round 5 -- the input block's GEMM-shaped launch, 144 workgroups at 128, ends the iteration behind the trunk's launch:
       //  62.6 -> 46 us; 7.61-7.64 against 7.62-7.68 ms per step, 448: 7.64-7.67, 64: 7.68-7.71)
-      static const int det_min = DBM_TUNE_GETENV("WGRAD_DET_MINWG") ? atoi(DBM_TUNE_GETENV("WGRAD_DET_MINWG")) : 256;
-      if (total >= 448 || plans.empty() || g >= 3 || (g_wgrad_deterministic && total >= det_min)) break;
+      if (total >= 448 || plans.empty() || g >= 3 || (g_wgrad_deterministic && total >= 256)) break;
     }
     std::vector<int> fstarts;
     fold_wgs[g] = 0;
     if (g_wgrad_deterministic && !plans.empty()) {
-      static const int SLOTS[NCAT] = {4, 4, 8, 2, 2, 2, 0, 0, 0, 0}, CTS[NCAT] = {4, 4, 4, 2, 2, 1, 0, 0, 0, 0},
-                       TPWS[NCAT] = {1, 9, 8, 9, 9, 8, 0, 0, 0, 0};
-      static const int pairs_env = DBM_TUNE_GETENV("WGRAD_PAIRS") ? atoi(DBM_TUNE_GETENV("WGRAD_PAIRS")) : 1;
-      pair_mode[g] = pairs_env != 0 || g >= 6;  // (the direct form folds through pair buffers only)
-      size_t floats = 0, bfloats = 0;
+      // pair buffers: slices 2k, 2k + 1 -> buffer k (pair 0 straight to the gradient when it is known to be zero)
+      size_t floats = 0;
       int fw = 0;
-      if (pair_mode[g]) {
-        // pair buffers: slices 2k, 2k + 1 -> buffer k (pair 0 straight to the gradient when it is known to be zero)
-        for (auto& pl : plans) {
-          const int npair = (pl.S + 1) / 2, direct = cleared_target ? 1 : 0;
-          const long stride = (((long)pl.d.Cout * pl.d.Cin * pl.d.KH * pl.d.KW + pl.d.Cout) + 3) & ~3L;
-          if (pl.S > 1 && npair - direct > 0) floats += (size_t)(npair - direct) * stride;
-        }
-        if (d_partial[g]) (void)hipFree(d_partial[g]);
-        DBM_HIP(hipMalloc((void**)&d_partial[g], (floats + 4) * sizeof(float)));
-        DBM_HIP(hipMemset(d_partial[g], 0, (floats + 4) * sizeof(float)));
-        float* base = d_partial[g];
-        for (auto& pl : plans) {
-          pl.fold_start = fw;
-          fstarts.push_back(fw);
-          pl.pairW = nullptr; pl.pair_n = 0; pl.pair_direct = 0; pl.pair_stride = 0;
-          if (pl.S <= 1) continue;
-          const int npair = (pl.S + 1) / 2, direct = cleared_target ? 1 : 0;
-          if (npair - direct <= 0) continue;  // two slices onto a cleared gradient: plain atomics commute
-          // (the stride is the exact tensor size + bias; the arena offset is rounded up to four floats)
-          pl.pair_stride = (long)pl.d.Cout * pl.d.Cin * pl.d.KH * pl.d.KW + pl.d.Cout;
-          pl.pairW = base; pl.pair_n = npair - direct; pl.pair_direct = direct;
-          base += (size_t)pl.pair_n * ((pl.pair_stride + 3) & ~3L);
-          fw += (int)((pl.pair_stride + 255) / 256);
-        }
-      } else {
-      // a layer without a K split needs no partials: its single contribution per launch goes out with the atomic
-      // epilogue (at most two launches' worth meet on a cleared gradient: still order-independent)
       for (auto& pl : plans) {
-        pl.pairW = nullptr; pl.pair_n = 0; pl.pair_direct = 0; pl.pair_stride = 0;
-        if (pl.S <= (cleared_target ? 2 : 1)) continue;
-        floats += (size_t)pl.S * pl.coutTiles * pl.groups * SLOTS[g] * TPWS[g] * 1024;
-        bfloats += (size_t)pl.S * pl.coutTiles * 32;
+        const int npair = (pl.S + 1) / 2, direct = cleared_target ? 1 : 0;
+        const long stride = (((long)pl.d.Cout * pl.d.Cin * pl.d.KH * pl.d.KW + pl.d.Cout) + 3) & ~3L;
+        if (pl.S > 1 && npair - direct > 0) floats += (size_t)(npair - direct) * stride;
       }
       if (d_partial[g]) (void)hipFree(d_partial[g]);
-      DBM_HIP(hipMalloc((void**)&d_partial[g], (floats + bfloats + 1) * sizeof(float)));
-      DBM_HIP(hipMemset(d_partial[g], 0, (floats + bfloats + 1) * sizeof(float)));  // (inactive slots are never written)
+      DBM_HIP(hipMalloc((void**)&d_partial[g], (floats + 4) * sizeof(float)));
+      DBM_HIP(hipMemset(d_partial[g], 0, (floats + 4) * sizeof(float)));
       float* base = d_partial[g];
-      float* bbase = base + floats;
       for (auto& pl : plans) {
         pl.fold_start = fw;
         fstarts.push_back(fw);
-        if (pl.S <= (cleared_target ? 2 : 1)) continue;  // (an empty range in the fold table)
-        pl.partial = base; pl.partial_b = bbase;
-        pl.fold_slots = SLOTS[g]; pl.fold_cts = CTS[g]; pl.fold_tpw = TPWS[g];
-        pl.fold_ctmul = (g <= 2) ? pl.G : (g == 5 ? 1 : 2);
-        base += (size_t)pl.S * pl.coutTiles * pl.groups * SLOTS[g] * TPWS[g] * 1024;
-        bbase += (size_t)pl.S * pl.coutTiles * 32;
-        fw += pl.coutTiles * pl.groups * SLOTS[g] * TPWS[g] * 4;
-      }
+        pl.pairW = nullptr; pl.pair_n = 0; pl.pair_direct = 0; pl.pair_stride = 0;
+        if (pl.S <= 1) continue;
+        const int npair = (pl.S + 1) / 2, direct = cleared_target ? 1 : 0;
+        if (npair - direct <= 0) continue;  // two slices onto a cleared gradient: plain atomics commute
+        // (the stride is the exact tensor size + bias; the arena offset is rounded up to four floats)
+        pl.pair_stride = (long)pl.d.Cout * pl.d.Cin * pl.d.KH * pl.d.KW + pl.d.Cout;
+        pl.pairW = base; pl.pair_n = npair - direct; pl.pair_direct = direct;
+        base += (size_t)pl.pair_n * ((pl.pair_stride + 3) & ~3L);
+        fw += (int)((pl.pair_stride + 255) / 256);
       }
       fold_wgs[g] = fw;
       for (int v : fstarts) starts.push_back(v);  // the fold table rides behind the launch table
@@ -1877,11 +1776,8 @@ void WgradBatch::launch(hipStream_t s) {
     else launch_dma(wgrad_1x1_kernel, d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s, 256);
     if (fold_wgs[g]) {
       static const bool abl_fold = (dbm_abl_skip() & 8) != 0;  // (libdbm_measure.so only)
-      if (pair_mode[g]) {
-        if (!abl_fold)
-          hipLaunchKernelGGL(wgrad_pair_fold_kernel, dim3(fold_wgs[g]), dim3(256), 0, s, d_plans[g], d_starts[g] + nplans[g] + 1, nplans[g]);
-      } else
-        hipLaunchKernelGGL(wgrad_fold_kernel, dim3(fold_wgs[g]), dim3(256), 0, s, d_plans[g], d_starts[g] + nplans[g] + 1, nplans[g]);
+      if (!abl_fold)
+        hipLaunchKernelGGL(wgrad_pair_fold_kernel, dim3(fold_wgs[g]), dim3(256), 0, s, d_plans[g], d_starts[g] + nplans[g] + 1, nplans[g]);
       DBM_HIP(hipGetLastError());
     }
     if (g_profiler.enabled) g_profiler.end(s);

@@ -99,16 +99,16 @@ def test_product_library_has_no_work_skipping_switches(built):
 
 
 def test_environment_switches_of_the_product_library_are_few_and_exercised(built):
-    """VERDICT round 5 #8a (knob sprawl: 64 getenv("DBM_*") in libdbm.so).  Round 6: the tuning switches (launch-size rules, kernel-form
-    overrides: DBM_IGEMM_*, DBM_WGRAD_*, ...) exist only in libdbm_measure.so (DBM_TUNE_GETENV, csrc/dbm_internal.h).  What the PRODUCT
-    library still reads -- every DBM_* name in its strings that is not an API flag of include/dbm.h -- must stay at or below 32 names, and
-    every one of them must be set by a parity test under tests/ (a code path the test suite runs) -- not merely mentioned by a tool."""
+    """VERDICT round 5 #8a (knob sprawl: 64 getenv("DBM_*") in libdbm.so).  The tuning switches (launch-size rules, kernel-form
+    overrides: DBM_IGEMM_*, DBM_WGRAD_*, ...) are gone: their defaults are constants of the sources.  What the PRODUCT library still
+    reads -- every DBM_* name in its strings that is not an API flag of include/dbm.h -- must stay at or below 23 names, and every one of them must
+    be set by a parity test under tests/ (a code path the test suite runs) -- not merely mentioned by a tool."""
     blob = open(built.LIB_PATH, "rb").read()
     names = set(m.decode() for m in re.findall(rb"DBM_[A-Z0-9_]+", blob))
     header = open(os.path.join(ROOT, "include", "dbm.h")).read()
     api_names = set(re.findall(r"\b(DBM_[A-Z0-9_]+)\b", header)) | {"DBM_MAX_TAPS", "DBM_HIP", "DBM_CHECK"}
     knobs = sorted(names - api_names)
-    assert len(knobs) <= 32, knobs
+    assert len(knobs) <= 23, knobs
     tests_src = "".join(open(os.path.join(ROOT, "tests", f)).read() for f in os.listdir(os.path.join(ROOT, "tests")) if f.endswith(".py"))
     this = open(__file__).read()
     tests_src = tests_src.replace(this, "")
@@ -117,3 +117,15 @@ def test_environment_switches_of_the_product_library_are_few_and_exercised(built
     # ... and the tuning names are really gone from the product library
     for name in (b"DBM_IGEMM_", b"DBM_WGRAD_", b"DBM_CL16_SLOTS", b"DBM_TRUNK_SPLIT", b"DBM_ITER_AUX", b"DBM_DBWD_ORDER"):
         assert name not in blob, name
+    # ... and so are the product schedules that lost their A/Bs (profiles/r5/ab_twin.txt, ab_conv_tile_classes_late.txt,
+    # profiles/r6/ab_defer_eval.txt)
+    for name in (b"DBM_ITER_DEFER_EVAL", b"DBM_ITER_EARLY_TWIN", b"DBM_CONV_TILE_9"):
+        assert name not in blob, name
+
+
+def test_sources_have_no_tuning_switch_layer():
+    """The tuning layer (DBM_TUNE_GETENV: getenv in libdbm_measure.so, a null pointer in libdbm.so) is gone: every launch rule the
+    product runs is what the sources say."""
+    csrc = os.path.join(ROOT, "deepbedmap_amd", "csrc")
+    offenders = [f for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f)) and "DBM_TUNE_GETENV" in open(os.path.join(csrc, f)).read()]
+    assert not offenders, offenders

@@ -5,5 +5,5 @@
 # bench.py refuses to run with DBM_LIB (or any of the switches) set.
 set -e
 cd "$(dirname "$0")/.."
-make -C deepbedmap_amd/csrc MEASURE=1 -j"$(nproc)"
+make -C deepbedmap_amd/csrc MEASURE=1 -j16
 ls -la deepbedmap_amd/libdbm_measure.so
