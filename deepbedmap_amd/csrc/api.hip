@@ -637,6 +637,10 @@ int dbm_gen_forward(dbm_model* gm, int N, int H, int W, const float* x, const fl
     ~Bf16Scope() { if (g) g->use_bf16 = false; }
   };
   DBM_CHECK(!((flags & DBM_BF16) && keep), "dbm_gen_forward: DBM_BF16 is an inference mode (no DBM_KEEP_GRAPH)");
+  // (the bf16 trunk's conv_cl16 launches write a 192-channel bf16 concat per pixel: refused here, before any buffer is sized for the plane)
+  DBM_CHECK(!(flags & DBM_BF16) || H < 3 || W < 3 || conv_cl16_plane_ok((long)(H - 2) * (W - 2), 192),
+            "dbm_gen_forward: DBM_BF16 needs (H - 2) * (W - 2) <= 5592405 (the bf16 trunk's 32-bit epilogue offsets: 384 bytes per pixel "
+            "< 2^31; the fp32 forward serves larger planes)");
   Bf16Scope bf16(g, (flags & DBM_BF16) != 0);
   if (flags & DBM_DEVICE_PTRS) {
     g->forward(N, H, W, x, w1, w2, w3, y, keep);

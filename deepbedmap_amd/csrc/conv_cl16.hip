@@ -701,12 +701,14 @@ static int cl16_choose_slots(int N, int H, int W, int n_cus, int maxs = CL_MAXSL
   return best;
 }
 
+bool conv_cl16_plane_ok(long plane, int yc16) { return 256L * plane < (1L << 31) && (yc16 == 0 || 2L * yc16 * plane < (1L << 31)); }
+
 void launch_conv_cl16(const ClConvLaunch& L, hipStream_t s) {
   DBM_CHECK(L.Cin % 32 == 0 && L.Cin >= 32 && (L.Cout == 32 || L.Cout == 64), "cl16 conv: Cin % 32 == 0, Cout 32 or 64");
   DBM_CHECK(L.xc % 8 == 0 && (!L.y16 || (L.yc % 4 == 0 && L.y0 % 4 == 0)), "cl16 conv: channel strides must keep 16- / 8-byte alignment");
   // the epilogue addresses r1 / r2 / y32 / y16 through raw buffer accesses with 32-bit byte offsets relative to the image's first
   // pixel (and a 31-bit buffer size): refuse planes those cannot reach instead of dropping their stores
-  DBM_CHECK(256L * L.H * L.W < (1L << 31) && (!L.y16 || 2L * L.yc * L.H * L.W < (1L << 31)),
+  DBM_CHECK(conv_cl16_plane_ok((long)L.H * L.W, L.y16 ? L.yc : 0),
             "cl16 conv: one image plane must stay below 2 GiB per operand (32-bit epilogue offsets)");
   static const int n_cus = [] {
     int dev = 0;

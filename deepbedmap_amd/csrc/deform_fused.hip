@@ -1715,6 +1715,13 @@ __global__ __launch_bounds__(256) void deform1_xw_kernel(const float* __restrict
 
 }  // namespace
 
+// Plane limits of the two LDS-window kernels (deform_conv64_fusedw_kernel, deform_conv64_x3w_kernel): a lane whose sample leaves the
+// window reads its corners at 32-bit byte offsets from the image's first pixel (256 bytes per pixel: H * W < 2^24), and a tap's top-left
+// corner travels packed as (y0 + 2) << 16 | (x0 + 2) with y0 <= H and x0 <= W (H + 2 < 2^15, W + 2 < 2^16).  Past any of them the
+// launchers take the gathering kernels (64-bit offsets, the same bits); a caller that forces a window kernel there is refused.
+static bool deform_window_plane_ok(int H, int W) { return 256L * H * W < (1L << 32) && H <= 32765 && W <= 65533; }
+#define DBM_DEFORM_WINDOW_LIMITS "H <= 32765, W <= 65533, H * W < 2^24"
+
 bool deform_conv_fused_ok(int C, int O) { return C == 64 && (O == 64 || (O >= 1 && O <= 16)); }
 
 void launch_nchw_to_nhwc64(const float* x, float* xt, int N, int plane, hipStream_t s) {
@@ -1733,22 +1740,23 @@ void launch_deform_conv_fused(const float* xt, const float* off, const float* w,
   DBM_CHECK(deform_conv_fused_ok(C, O), "fused deformable convolution: 64 input channels, 64 or <= 16 output channels");
   const long total = (long)N * H * W;
   DBM_CHECK(total < (1L << 31), "fused deformable convolution: more than 2^31 positions");
-  const unsigned blocks = (unsigned)((total + DF_POS - 1) / DF_POS);
-  if (g_profiler.enabled) {
-    // algorithmic bytes: the NHWC input and the 18 offset planes once, the weights once, the output (and its NHWC twin / the
-    // kept sampled columns of a training forward) once
-    const double bytes = 4.0 * ((double)total * (C + 18 + (y ? O : 0) + (yt ? O : 0) + (colout ? 9.0 * C : 0.0)) + 9.0 * C * O);
-    char tag[40];
-    snprintf(tag, sizeof(tag), "deform%d_%dx%d_n%d%s", O, H, W, N, colout ? "_keep" : "");
-    g_profiler.begin(s, 0, 2.0 * (double)total * O * C * 9, bytes, tag, blocks);
-  }
   // (the window form: planes narrow enough that <= 128 consecutive positions + their vertical reach fit the LDS layout, no sample matrix
   //  wanted -- the same bits as the gathering kernel.  119-125 against 111 us standalone on the training tile (one workgroup of four
   //  wavefronts per CU; 704 tiles = three rounds), but 7.56-7.58 against 7.59-7.61 ms per step in three A/B series: it leaves the CUs to
   //  the kernels of the other streams.  DBM_DEFORM_FWD_WINDOW=0: the gathering kernel.  profiles/r6/ab_deform_fwd_fp32_window.txt)
   static const int fwin_env = getenv("DBM_DEFORM_FWD_WINDOW") ? atoi(getenv("DBM_DEFORM_FWD_WINDOW")) : 1;
   const int span_rows = std::min(H, (DWF_POS - 1 + W - 1) / W + 1);   // most rows 128 consecutive positions can span
-  const bool fwin_ok = O == 64 && !colout && fwin_env && (span_rows + 2 * DWF_R + 3) * (W + 2 * DWF_R + 3) <= DWF_MAXPIX;
+  const bool fwin_ok = O == 64 && !colout && fwin_env && (span_rows + 2 * DWF_R + 3) * (W + 2 * DWF_R + 3) <= DWF_MAXPIX &&
+                       deform_window_plane_ok(H, W);
+  const unsigned blocks = (unsigned)((total + DF_POS - 1) / DF_POS);
+  if (g_profiler.enabled) {
+    // algorithmic bytes: the NHWC input and the 18 offset planes once, the weights once, the output (and its NHWC twin / the
+    // kept sampled columns of a training forward) once
+    const double bytes = 4.0 * ((double)total * (C + 18 + (y ? O : 0) + (yt ? O : 0) + (colout ? 9.0 * C : 0.0)) + 9.0 * C * O);
+    char tag[40];
+    snprintf(tag, sizeof(tag), "deform%d%s_%dx%d_n%d%s", O, fwin_ok ? "w" : "", H, W, N, colout ? "_keep" : "");
+    g_profiler.begin(s, 0, 2.0 * (double)total * O * C * 9, bytes, tag, blocks);
+  }
   if (fwin_ok) {
     static bool attr = false;
     if (!attr) {
@@ -1788,9 +1796,12 @@ void launch_deform_conv64_x3(const float* xt, const float* off, const void* wx, 
   DBM_CHECK(total < (1L << 31), "fused deformable convolution: more than 2^31 positions");
   const int tilesX = (W + DW_T - 1) / DW_T, tilesY = (H + DW_T - 1) / DW_T;
   const long tiles = (long)N * tilesX * tilesY;
+  const bool plane_ok = deform_window_plane_ok(H, W);
   if (window < 0) {
     static const int env = getenv("DBM_DEFORM_X3_WINDOW") ? atoi(getenv("DBM_DEFORM_X3_WINDOW")) : 1;
-    window = env && tiles >= 256 ? 1 : 0;
+    window = env && tiles >= 256 && plane_ok ? 1 : 0;
+  } else if (window) {
+    DBM_CHECK(plane_ok, "deformable convolution, LDS-window kernel: the plane exceeds its limits (" DBM_DEFORM_WINDOW_LIMITS ")");
   }
   const unsigned blocks = window ? (unsigned)tiles : (unsigned)((total + DF_POS - 1) / DF_POS);
   if (g_profiler.enabled) {

@@ -215,6 +215,9 @@ struct ClConvLaunch {
 };
 size_t cl16_packed_elems(int Cin, int Cout);   // bf16 elements of a layer's packed image
 void launch_pack_cl16(const float* w_oihw, void* dst, int O, int C, hipStream_t s);
+// conv_cl16's epilogue reaches one image's operands through 32-bit byte offsets: 256 bytes per pixel (fp32 64 channels) and, for a bf16
+// channels-last output of yc16 channels (0: none), 2 * yc16 bytes per pixel must stay below 2^31 per image plane
+bool conv_cl16_plane_ok(long plane, int yc16);
 void launch_conv_cl16(const ClConvLaunch& L, hipStream_t s);
 // (N, 64, plane) fp32 [image stride xsn] -> NHWC fp32 (res, may be null) and NHWC bf16 channels 0..63 of a buffer with `ac`
 // channels per pixel (act, may be null); and back

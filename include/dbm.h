@@ -185,7 +185,17 @@ int dbm_model_params_changed(dbm_model* m);
 
 /* ---- forward / backward ---- */
 /* GeneratorModel.forward(x, w1, w2, w3): srgan_train.py:525-576.  x (N,1,H,W), w1 (N,1,10H,10W), w2 (N,2,2H,2W),
- * w3 (N,1,H,W) -> y (N,1,4(H-2),4(W-2)).  flags: DBM_DEVICE_PTRS, DBM_KEEP_GRAPH, DBM_BF16. */
+ * w3 (N,1,H,W) -> y (N,1,4(H-2),4(W-2)).  flags: DBM_DEVICE_PTRS, DBM_KEEP_GRAPH, DBM_BF16.
+ * Plane limits (input tile H x W, output H4 x W4 = 4(H-2) x 4(W-2)); every other size runs if it fits in memory:
+ *   - refused (DBM_CHECK) when N * H4 * W4 >= 2^31: "fused deformable convolution: more than 2^31 positions" / "igemm: more than
+ *     2^31 output positions" (the launchers index positions in 32 bits);
+ *   - DBM_BF16 only: refused up front when (H-2) * (W-2) > 5592405 ("dbm_gen_forward: DBM_BF16 needs ..."): the bf16 trunk's
+ *     conv_cl16 launches address a 192-channel bf16 concat per image at 32-bit byte offsets (launch_conv_cl16 itself refuses
+ *     "cl16 conv: one image plane must stay below 2 GiB per operand"); the fp32 forward serves those planes;
+ *   - not limits: the deformable layers' LDS-window kernels serve H4 <= 32765, W4 <= 65533, H4 * W4 < 2^24 only, the launchers take
+ *     the gathering kernels (64-bit offsets, the same bits) past them; conv_tile's LDS form hands planes whose 32-bit epilogue
+ *     offsets would overflow to the implicit GEMM (64-bit offsets).
+ * tests/test_gpu_large_planes.py holds a case on each side of each limit. */
 int dbm_gen_forward(dbm_model* g, int N, int H, int W, const float* x, const float* w1, const float* w2,
                     const float* w3, float* y, int flags);
 /* g_loss.backward() through the generator: srgan_train.py:1256.  gy (N,1,4(H-2),4(W-2)) = d loss / d y of the last
@@ -326,7 +336,8 @@ int dbm_op_deform_conv2d(dbm_ctx* ctx, const float* x, const float* off, const f
  * (O <= 16; srgan_train.py:574, the DEM itself) with the multiplication BEFORE the sampler -- nine premultiplied tap planes,
  * scalar gathers --, form 2 = the 64 -> 64 layer (:572) in the sweep's split-bf16 arithmetic (+ LeakyReLU 0.2 if lrelu); forms 3 and 4
  * name form 2's two kernels explicitly -- 3: the sampler reads an LDS window of the input (what the sweep's full-resolution planes take),
- * 4: it gathers every corner from memory (small planes); same arithmetic, same bits */
+ * 4: it gathers every corner from memory (small planes); same arithmetic, same bits.  Form 3 is refused (DBM_CHECK naming the limits)
+ * on planes past its kernel's limits (H <= 32765, W <= 65533, H * W < 2^24); form 2 takes form 4's kernel there */
 int dbm_op_deform_conv2d_form(dbm_ctx* ctx, const float* x, const float* off, const float* w, const float* b, float* y, int N, int H,
                               int W, int O, int form, int lrelu);
 int dbm_op_deform_conv2d_backward(dbm_ctx* ctx, const float* x, const float* off, const float* w, const float* gy,

@@ -92,10 +92,12 @@ def upsample_nearest2_backward(gy):
 #  chainer/functions/connection/deformable_convolution_2d_sampler.py,
 #  chainer/functions/array/spatial_transformer_sampler.py)
 # --------------------------------------------------------------------------------------
-def _deform_geometry(offset, H, W, kh, kw, stride, pad):
+def _deform_geometry(offset, H, W, kh, kw, stride, pad, rows=None, cols=None):
     """Sampling corners / weights exactly as _offset2grid + spatial_transformer_sampler.
 
     offset: (N, 2*kh*kw, OH, OW); channels [0:khkw] are x offsets, [khkw:] y offsets.
+    rows / cols (optional): the output rows / columns offset's OH / OW entries stand for (default: all of
+    them); the normalisation uses the full plane's H and W either way.
     Returns u0,v0 (int, in the doubly padded frame), fractional parts and clip masks,
     each shaped (N, khkw, OH*OW).
     """
@@ -104,8 +106,8 @@ def _deform_geometry(offset, H, W, kh, kw, stride, pad):
     f = offset.dtype.type
     Hp, Wp = H + 2 * pad, W + 2 * pad  # size of the conv-padded image fed to the sampler
     ys, xs = np.meshgrid(
-        np.arange(0, stride * OH, stride, dtype=np.float32),
-        np.arange(0, stride * OW, stride, dtype=np.float32),
+        np.arange(0, stride * OH, stride, dtype=np.float32) if rows is None else (np.asarray(rows) * stride).astype(np.float32),
+        np.arange(0, stride * OW, stride, dtype=np.float32) if cols is None else (np.asarray(cols) * stride).astype(np.float32),
         indexing="ij",
     )
     fx = np.tile(np.arange(kw, dtype=np.float32), kh)
@@ -127,6 +129,56 @@ def _deform_geometry(offset, H, W, kh, kw, stride, pad):
     return u, v, uc, vc, u0, v0, Hp, Wp
 
 
+def _deform_gemm(colm, W, b):
+    """colm (P, C*kh*kw) @ W^T (+ b) in fixed blocks of 256 rows (the last one zero-padded): one BLAS call shape
+    whatever P is, so an output row has the same bits however many rows are computed with it (deform_conv2d_at)."""
+    Wt = np.ascontiguousarray(W.reshape(W.shape[0], -1).T)
+    P = colm.shape[0]
+    y = np.empty((P, Wt.shape[1]), dtype=np.result_type(colm, Wt))
+    for s in range(0, P, _GEMM_ROWS):
+        e = min(s + _GEMM_ROWS, P)
+        if e - s == _GEMM_ROWS:
+            y[s:e] = colm[s:e] @ Wt
+        else:
+            blk = np.zeros((_GEMM_ROWS, colm.shape[1]), dtype=colm.dtype)
+            blk[:e - s] = colm[s:e]
+            y[s:e] = (blk @ Wt)[:e - s]
+    if b is not None:
+        y = y + b
+    return y
+
+
+_GEMM_ROWS = 256
+
+
+def _deform_columns(x, u0, v0, uc, vc, pad):
+    """The bilinear samples (N, C, khkw, P) at _deform_geometry's corners, zero outside x (the sampler's padding), read
+    straight from x without a padded copy."""
+    N, C, H, Wd = x.shape
+    kk, P = u0.shape[1:]
+    u1, v1 = u0 + 1, v0 + 1
+    wu0 = (uc - u0).astype(x.dtype)
+    wu1 = (u1 - uc).astype(x.dtype)
+    wv0 = (vc - v0).astype(x.dtype)
+    wv1 = (v1 - vc).astype(x.dtype)
+    q = pad + 1  # corner (vv, uu) of the doubly padded frame is pixel (vv - q, uu - q) of x
+    zero = x.dtype.type(0)
+
+    def corner(xn, vv, uu):
+        yy, xx = vv - q, uu - q
+        inside = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < Wd)
+        return np.where(inside, xn[:, np.clip(yy, 0, H - 1), np.clip(xx, 0, Wd - 1)], zero)
+
+    col = np.empty((N, C, kk, P), dtype=x.dtype)
+    for n in range(N):
+        x1 = corner(x[n], v0[n], u0[n])  # C,kk,P
+        x2 = corner(x[n], v0[n], u1[n])
+        x3 = corner(x[n], v1[n], u0[n])
+        x4 = corner(x[n], v1[n], u1[n])
+        col[n] = (wu1[n] * wv1[n]) * x1 + (wu0[n] * wv1[n]) * x2 + (wu1[n] * wv0[n]) * x3 + (wu0[n] * wv0[n]) * x4
+    return col
+
+
 def deform_conv2d(x, offset, W, b=None, stride=1, pad=1, return_cache=False):
     """F.deformable_convolution_2d_sampler: bilinear-sample the zero padded input at
     (regular tap position + learned offset), then GEMM with W (O,C,kh,kw)."""
@@ -135,38 +187,47 @@ def deform_conv2d(x, offset, W, b=None, stride=1, pad=1, return_cache=False):
     kk = kh * kw
     OH, OW = offset.shape[2:]
     u, v, uc, vc, u0, v0, Hp, Wp = _deform_geometry(offset, H, Wd, kh, kw, stride, pad)
-    u1, v1 = u0 + 1, v0 + 1
-    xpp = np.pad(x, ((0, 0), (0, 0), (pad + 1, pad + 1), (pad + 1, pad + 1)))
-    wu0 = (uc - u0).astype(x.dtype)
-    wu1 = (u1 - uc).astype(x.dtype)
-    wv0 = (vc - v0).astype(x.dtype)
-    wv1 = (v1 - vc).astype(x.dtype)
-    col = np.empty((N, C, kk, OH * OW), dtype=x.dtype)
-    for n in range(N):
-        x1 = xpp[n][:, v0[n], u0[n]]  # C,kk,P
-        x2 = xpp[n][:, v0[n], u1[n]]
-        x3 = xpp[n][:, v1[n], u0[n]]
-        x4 = xpp[n][:, v1[n], u1[n]]
-        col[n] = (wu1[n] * wv1[n]) * x1 + (wu0[n] * wv1[n]) * x2 + (wu1[n] * wv0[n]) * x3 + (wu0[n] * wv0[n]) * x4
+    col = _deform_columns(x, u0, v0, uc, vc, pad)
     colm = np.ascontiguousarray(col.transpose(0, 3, 1, 2)).reshape(N * OH * OW, C * kk)
-    y = colm @ W.reshape(O, -1).T
-    if b is not None:
-        y = y + b
+    y = _deform_gemm(colm, W, b)
     y = np.ascontiguousarray(y.reshape(N, OH, OW, O).transpose(0, 3, 1, 2))
     if return_cache:
         return y, (colm,)
     return y
 
 
-def deform_conv2d_backward(x, offset, W, gy, stride=1, pad=1):
-    """Returns (gx, goffset, gW, gb).  Gradients of the bilinear sampler follow
-    SpatialTransformerSampler._backward (coordinate gradient masked where clipped)."""
+def deform_conv2d_at(x, offset, W, b=None, rows=None, cols=None, stride=1, pad=1):
+    """deform_conv2d's output at the output rows `rows` (and columns `cols`; default: all) only, without the whole
+    plane's sample matrix: y (N, O, len(rows), len(cols)).  x and offset are the full plane's; the sampling coordinates
+    are _deform_geometry's with the full plane's H and W (the reference normalises by the padded size, so a crop would
+    not give the same fp32 coordinates).  deform_conv2d's sampler and GEMM: the same values."""
     N, C, H, Wd = x.shape
     O, _, kh, kw = W.shape
     kk = kh * kw
     OH, OW = offset.shape[2:]
+    rows = np.arange(OH) if rows is None else np.asarray(rows)
+    cols = np.arange(OW) if cols is None else np.asarray(cols)
+    off = offset[:, :, rows][:, :, :, cols]
+    u, v, uc, vc, u0, v0, Hp, Wp = _deform_geometry(off, H, Wd, kh, kw, stride, pad, rows, cols)
+    col = _deform_columns(x, u0, v0, uc, vc, pad)
+    colm = np.ascontiguousarray(col.transpose(0, 3, 1, 2)).reshape(N * len(rows) * len(cols), C * kk)
+    y = _deform_gemm(colm, W, b)
+    return np.ascontiguousarray(y.reshape(N, len(rows), len(cols), O).transpose(0, 3, 1, 2))
+
+
+def deform_conv2d_backward(x, offset, W, gy, stride=1, pad=1, rows=None):
+    """Returns (gx, goffset, gW, gb).  Gradients of the bilinear sampler follow
+    SpatialTransformerSampler._backward (coordinate gradient masked where clipped).
+    rows (optional): gy holds only these output rows (the full plane's gradient is zero elsewhere);
+    goffset is then returned for these rows only."""
+    N, C, H, Wd = x.shape
+    O, _, kh, kw = W.shape
+    kk = kh * kw
+    if rows is not None:
+        offset = offset[:, :, np.asarray(rows)]
+    OH, OW = offset.shape[2:]
     P = OH * OW
-    u, v, uc, vc, u0, v0, Hp, Wp = _deform_geometry(offset, H, Wd, kh, kw, stride, pad)
+    u, v, uc, vc, u0, v0, Hp, Wp = _deform_geometry(offset, H, Wd, kh, kw, stride, pad, rows)
     u1, v1 = u0 + 1, v0 + 1
     xpp = np.pad(x, ((0, 0), (0, 0), (pad + 1, pad + 1), (pad + 1, pad + 1)))
     wu0 = (uc - u0).astype(x.dtype)

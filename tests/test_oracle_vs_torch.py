@@ -68,6 +68,33 @@ def test_deform_conv_large_offsets_and_border_clipping():
     assert rel(gb, bt.grad.numpy()) < 1e-9
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("shape", [(2, 7, 9, 64), (1, 13, 5, 1), (1, 11, 12, 3), (1, 1, 6, 4)])
+def test_deform_conv_at_chosen_positions_equals_the_whole_plane(dtype, shape):
+    """ops.deform_conv2d_at (the large-plane tests' reference: only the checked rows / columns are evaluated, with the full plane's
+    coordinate normalisation) gives deform_conv2d's values exactly.  Offsets: a random spread plus, per border, taps pushed far past it
+    (clipped to the sampler's zero ring) and just past it (one corner inside)."""
+    N, H, W, O = shape
+    rs = np.random.RandomState(H * W + O)
+    x = rs.normal(size=(N, 64, H, W)).astype(dtype)
+    off = rs.normal(scale=4.0, size=(N, 18, H, W)).astype(dtype)
+    off[:, 0] = -(W + 7)                        # tap 0: far left
+    off[:, 1] = W + 7                           # tap 1: far right
+    off[:, 9 + 2] = -(H + 7)                    # tap 2: far up
+    off[:, 9 + 3] = H + 7                       # tap 3: far down
+    off[:, 4] = rs.uniform(-1.5, -0.5, size=(N, H, W)) - np.arange(W)              # tap 4: straddles the left border ...
+    off[:, 9 + 5] = rs.uniform(0.5, 1.5, size=(N, H, W)) + (H - 1 - np.arange(H))[:, None]   # tap 5: ... and the bottom one
+    w = rs.normal(size=(O, 64, 3, 3)).astype(dtype)
+    b = rs.normal(size=(O,)).astype(dtype)
+    ref = ops.deform_conv2d(x, off, w, b)
+    for rows in ([0], [H - 1], list(range(H)), [H - 1, 0], rs.permutation(H)[: (H + 1) // 2]):
+        y = ops.deform_conv2d_at(x, off, w, b, rows)
+        assert y.dtype == ref.dtype and np.array_equal(y, ref[:, :, rows]), rows
+    rows, cols = [0, H - 1], [W - 1, 0, W // 2]
+    assert np.array_equal(ops.deform_conv2d_at(x, off, w, b, rows, cols), ref[:, :, rows][:, :, :, cols])
+    assert np.array_equal(ops.deform_conv2d_at(x, off, w, None, rows), ops.deform_conv2d(x, off, w)[:, :, rows])
+
+
 def test_deform_conv_zero_offset_is_regular_conv():  # SURVEY A.6 identity
     rs = np.random.RandomState(5)
     x = rs.normal(size=(1, 3, 8, 9)).astype(np.float32)
