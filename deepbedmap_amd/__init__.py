@@ -15,6 +15,7 @@ from .training import (  # noqa: F401
     save_model_weights_and_architecture, split_dataset_random, train_epochs, train_eval_discriminator, train_eval_generator, train_iteration, train_minibatch, trainer,
 )
 from .parallel import DataParallel, shard_batch, shard_slice  # noqa: F401
+from .evaluation import DevicePoints, GridGeometry, TrackStats, get_deepbedmap_test_result, grdtrack, make_test_area_score  # noqa: F401
 from .geotiff import canvas_to_int16, read_geotiff, save_array_to_grid  # noqa: F401
 from .inference import (Shape, clip_inputs, crop_bounds, group_tiles_by_crop_shape, merge_ranks, predict_tiled,  # noqa: F401
                         predict_tiled_resident, tile_steps)

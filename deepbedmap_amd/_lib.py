@@ -100,6 +100,8 @@ SIGNATURES = {
                            C.c_int, c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
     "dbm_psnr": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_int],
     "dbm_ssim": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int],
+    "dbm_grid_track": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                       C.c_double, C.c_void_p, C.c_void_p, C.c_int],
     "dbm_adam_setup": [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double],
     "dbm_adam_update": [C.c_void_p, C.c_double],
     "dbm_discriminator_step": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -230,6 +230,7 @@ int dbm_shutdown(dbm_ctx* ctx) {
   for (auto& e : ctx->comm_ev_pool) (void)hipEventDestroy(e);
   ctx->loss_tmp.release();
   for (auto& b : ctx->stage) b.release();
+  ctx->track_tmp.release();
   (void)hipStreamSynchronize(ctx->side);
   (void)hipStreamDestroy(ctx->side);
   for (auto& st : ctx->chain) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -893,6 +894,65 @@ int dbm_ssim_ex(dbm_ctx* ctx, const float* y_pred, const float* y_true, int N, i
   hipLaunchKernelGGL(ssim_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, sums, N, nwin, dout);
   finish_out(ctx, 2, out, 1, flags);
   finish_sync(ctx, flags);
+  DBM_API_END
+}
+
+int dbm_grid_track(dbm_ctx* ctx, const float* grid_dev, long H, long W, const double geom[5], const double* points, size_t n,
+                   int ncol, int interp, double threshold, double* z_out, double* stats, int flags) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && geom != nullptr, "dbm_grid_track: NULL argument");
+  DBM_CHECK(interp >= 0 && interp <= 2, "dbm_grid_track: interp must be 0 (nearest), 1 (bilinear) or 2 (bicubic)");
+  DBM_CHECK(H >= 1 && W >= 1, "dbm_grid_track: empty grid");
+  DBM_CHECK(interp == 0 || (H >= 2 && W >= 2), "dbm_grid_track: bilinear and bicubic need at least 2 x 2 nodes");
+  DBM_CHECK(threshold > 0.0 && threshold <= 1.0, "dbm_grid_track: threshold must lie in (0, 1]");
+  DBM_CHECK(ncol == 2 || ncol == 3, "dbm_grid_track: points have 2 (x, y) or 3 (x, y, z) columns");
+  DBM_CHECK(std::isfinite(geom[0]) && std::isfinite(geom[1]) && std::isfinite(geom[2]) && std::isfinite(geom[3]) && geom[2] != 0.0 &&
+                geom[3] != 0.0, "dbm_grid_track: x0, y0 finite, dx, dy finite and non-zero");
+  DBM_CHECK(geom[4] == 0.0 || geom[4] == 1.0, "dbm_grid_track: registration must be 0 (gridline) or 1 (pixel)");
+  DBM_CHECK(n == 0 || (grid_dev != nullptr && points != nullptr), "dbm_grid_track: NULL grid or points");
+  const bool reduce = ncol == 3 && stats != nullptr;
+  const double half = geom[4] == 1.0 ? 0.5 : 0.0;
+  TrackLaunch a;
+  a.grid = grid_dev;
+  a.H = H;
+  a.W = W;
+  a.x0 = geom[0]; a.y0 = geom[1]; a.dx = geom[2]; a.dy = geom[3];
+  a.tlo = -half; a.thi = (double)(W - 1) + half;
+  a.slo = -half; a.shi = (double)(H - 1) + half;
+  a.n = (long)n;
+  a.ncol = ncol;
+  a.interp = interp;
+  a.threshold = threshold;
+  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
+  // host forms: points in stage[0], z_interpolated in stage[1] (sizes in floats)
+  if (dev || n == 0) {
+    a.points = points;
+  } else {
+    ctx->stage[0].ensure(2 * n * (size_t)ncol);
+    DBM_HIP(hipMemcpyAsync(ctx->stage[0].p, points, n * ncol * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    a.points = (const double*)ctx->stage[0].p;
+  }
+  a.z_out = nullptr;
+  if (z_out && n > 0) {
+    if (dev) {
+      a.z_out = z_out;
+    } else {
+      ctx->stage[1].ensure(2 * n);
+      a.z_out = (double*)ctx->stage[1].p;
+    }
+  }
+  const int blocks = grid_track_blocks((long)n);
+  ctx->track_tmp.ensure(2 * (8 + 6 * (size_t)blocks));
+  double* dstats = (double*)ctx->track_tmp.p;
+  a.part = reduce ? dstats + 8 : nullptr;
+  launch_grid_track(a, dstats, ctx->stream);
+  if (!dev) {
+    if (a.z_out) DBM_HIP(hipMemcpyAsync(z_out, a.z_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (reduce) DBM_HIP(hipMemcpyAsync(stats, dstats, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));
+  } else if (reduce) {
+    DBM_HIP(hipMemcpyAsync(stats, dstats, 6 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  }
   DBM_API_END
 }
 

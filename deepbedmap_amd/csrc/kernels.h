@@ -242,3 +242,20 @@ struct ClX3Launch {
 size_t cl16x3_packed_elems(int Cin, int Cout);
 void launch_pack_cl16x3(const float* w_oihw, void* dst, int O, int C, hipStream_t s);
 void launch_conv_cl16x3(const ClX3Launch& L, hipStream_t s);
+
+// Grid sampling along survey tracks (track.hip; dbm_grid_track): the float32 grid (H, W) evaluated at n float64 points (x, y[, z])
+// with 64-bit offsets; z_out (n doubles) and part (6 doubles per workgroup: the error moments, folded into stats[6]) may be null
+struct TrackLaunch {
+  const float* grid;
+  long H, W;
+  double x0, y0, dx, dy;
+  double tlo, thi, slo, shi;   // the domain in node units (registration)
+  const double* points;        // (n, ncol), ncol 2 or 3 (part needs 3)
+  long n;
+  int ncol, interp;            // 0 nearest, 1 bilinear, 2 bicubic
+  double threshold;
+  double* z_out;
+  double* part;
+};
+int grid_track_blocks(long n);   // workgroups of the sampling launch (depends on n only): partials needed
+void launch_grid_track(const TrackLaunch& a, double* stats, hipStream_t s);

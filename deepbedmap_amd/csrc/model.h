@@ -89,6 +89,7 @@ struct dbm_ctx {
   float* ssim_win[2] = {nullptr, nullptr};  // 9-tap 1-D windows: gaussian(1.5), uniform
   DevBuf loss_tmp;            // scratch for the loss entry points
   DevBuf stage[8];            // host<->device staging for the non-DEVICE_PTRS entry points
+  DevBuf track_tmp;           // dbm_grid_track: the workgroups' error moments and the folded statistics (doubles)
 };
 
 void dbm_comm_unique_id_impl(void* out128);  // comm.hip: ncclGetUniqueId

@@ -408,8 +408,8 @@ def train_epochs(epochs: int, train_iter, dev_iter, g_model, g_optimizer, d_mode
     (`if rmse_test < best_rmse_test: ... save_model_weights_and_architecture(...)`, :1655-1666; `best_rmse_test` starts
     at 250) and the divergence guard (:1698-1706: PSNR < 0 or NaN losses -> TrialPruned).
 
-    score_fn(g_model) -> float is the reference's `get_deepbedmap_test_result` (RMSE on the test area; lower is better);
-    None uses the epoch's mean validation generator loss.  progress(i, epoch_metrics) is called once per epoch.
+    score_fn(g_model) -> float is the reference's `get_deepbedmap_test_result` (RMSE on the test area; lower is better):
+    `make_test_area_score(...)` builds it; None uses the epoch's mean validation generator loss.  progress(i, epoch_metrics) is called once per epoch.
     Returns (table, best_score, saved_paths): table = {column: np.ndarray[epochs]} of epoch means."""
     columns = list(METRIC_NAMES) + [f"val_{m}" for m in METRIC_NAMES]
     table = {c: np.full(epochs, np.nan, dtype=np.float64) for c in columns}

@@ -246,6 +246,23 @@ int dbm_ssim(dbm_ctx* ctx, const float* y_pred, const float* y_true, int N, int 
 int dbm_ssim_ex(dbm_ctx* ctx, const float* y_pred, const float* y_true, int N, int H, int W, int window_size, int stride,
                 int ssim_window, float* out, int flags);
 
+/* ---- evaluation: `gmt.grdtrack(points, grid)` and the along-track error (srgan_train.py:1458-1464, the test-area RMSE that
+ * get_deepbedmap_test_result returns; deepbedmap.py:530-574, the product grids' elevation error) ----
+ * The float32 grid (H, W) -- ALWAYS a device pointer, row r, column c at (x0 + c dx, y0 + r dy), geom = {x0, y0, dx, dy,
+ * registration (0 gridline: domain [0, W-1] x [0, H-1] in node units; 1 pixel: [-1/2, W-1/2] x [-1/2, H-1/2])} on the host --
+ * is evaluated in float64 at the n points (C-contiguous float64 (n, ncol), ncol 2: x, y; 3: x, y, z) with GMT's interpolant
+ * (`grdtrack -n`): interp 0 nearest, 1 bilinear, 2 bicubic (Keys cubic convolution, a = -1/2).  Outside the domain, or at NaN
+ * coordinates: NaN.  Ghost nodes beyond the edges: linear extrapolation (columns first, then rows).  NaN nodes: the valid nodes'
+ * weighted sum over their weight sum if that sum + 1e-9 >= threshold (GMT's +t, default 0.5), else NaN.
+ * z_out (n doubles, may be NULL) receives z_interpolated; with ncol 3 and stats != NULL the finite errors z_interpolated - z
+ * are reduced to stats = {count, mean, std (ddof 1), min, max, rmse} (count 0: the rest NaN; std NaN below 2), bit for bit the
+ * same from call to call (no float atomics; the launch depends on n only).  flags: DBM_DEVICE_PTRS = points, z_out and stats
+ * are device pointers (asynchronous); otherwise host pointers and the call synchronises.  Refused (status 1, nothing
+ * launched): interp outside 0..2, H or W < 1, H or W < 2 for bilinear / bicubic, threshold outside (0, 1], ncol not 2 or 3,
+ * dx or dy zero or not finite. */
+int dbm_grid_track(dbm_ctx* ctx, const float* grid_dev, long H, long W, const double geom[5], const double* points, size_t n,
+                   int ncol, int interp, double threshold, double* z_out, double* stats, int flags);
+
 /* ---- optimizer ---- */
 /* chainer.optimizers.Adam(alpha, eps=1e-8).setup(model): srgan_train.py:1043-1048 */
 int dbm_adam_setup(dbm_model* m, double alpha, double beta1, double beta2, double eps);
