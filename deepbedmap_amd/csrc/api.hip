@@ -59,6 +59,12 @@ static void mark_grads_cleared(dbm_model* m) {
     if (o->grads == m->grads) { o->grads_void = false; o->grads_touched = false; }
 }
 
+// cleargrads on stream `s` (a view shares its owner's arena: both marks go)
+static void clear_grads(dbm_model* m, hipStream_t s) {
+  DBM_HIP(hipMemsetAsync(m->grads, 0, m->nparam * sizeof(float), s));
+  mark_grads_cleared(m);
+}
+
 // entry of a step entry point: re-arm the persistent kernels when their pause is over, then observe the condition
 static void dbm_step_entry(dbm_ctx* c, bool counts_as_iteration) {
   if (counts_as_iteration) g_step_serial += 1;
@@ -598,8 +604,7 @@ int dbm_model_count_params(dbm_model* m, int64_t* n) {
 }
 int dbm_model_cleargrads(dbm_model* m) {
   DBM_API_BEGIN(m->ctx)
-  DBM_HIP(hipMemsetAsync(m->grads, 0, m->nparam * sizeof(float), m->ctx->stream));
-  mark_grads_cleared(m);  // (a view shares its owner's arena: both marks go)
+  clear_grads(m, m->ctx->stream);
   DBM_API_END
 }
 int dbm_model_param_arena(dbm_model* m, void** dptr, size_t* n) {
@@ -1010,6 +1015,25 @@ int dbm_adam_update(dbm_model* m, double grad_scale) {
 }
 
 // ---- fused steps ----
+namespace {
+// ctx->stream, which every model pass and helper enqueues on, is `on` until the end of the enclosing block
+struct StreamScope {
+  dbm_ctx* c;
+  hipStream_t prev;
+  StreamScope(dbm_ctx* ctx, hipStream_t on) : c(ctx), prev(ctx->stream) { c->stream = on; }
+  ~StreamScope() { c->stream = prev; }
+};
+
+// The gradient exchange of a data-parallel step (comm.hip) for the whole call: with `on`, the backward passes hand finished
+// buckets to comm_bucket, summed over ranks on `stream` (null: chain[1]).  Nothing of it outlives the call, a deferred bucket
+// of a call that throws included.
+struct CommScope {
+  dbm_ctx* c;
+  CommScope(dbm_ctx* ctx, bool on, hipStream_t stream = nullptr) : c(ctx) { c->comm_in_step = on; c->comm_stream = stream; }
+  ~CommScope() { c->comm_in_step = false; c->comm_stream = nullptr; c->comm_defer = false; c->comm_pending.clear(); }
+};
+}  // namespace
+
 int dbm_discriminator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, const float* X, const float* W1,
                            const float* W2, const float* W3, const float* Y, int train, float* metrics) {
   DBM_API_BEGIN(gm->ctx)
@@ -1031,11 +1055,7 @@ int dbm_discriminator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, co
   const bool narrow = (train & 8) != 0 && !g->trunk_fused_ok(H - 2, W - 2);  // (a fused pass is one stream anyway)
   // data-parallel run with a communicator on the context (dbm_comm_init / dbm_comm_set_hook): the gradient buckets are
   // summed over ranks inside this call, overlapped with the backward passes; bit 4 (16) leaves the exchange to the caller
-  struct CommScope {
-    dbm_ctx* c;
-    CommScope(dbm_ctx* ctx, bool on) : c(ctx) { c->comm_in_step = on; }
-    ~CommScope() { c->comm_in_step = false; }
-  } comm_scope(c, (train & 1) && !(train & 16) && c->comm_active());
+  CommScope comm(c, (train & 1) && !(train & 16) && c->comm_active());
   train &= 1;
   // whatever an earlier call retained for a following G-step is void now (n_critic > 1 loops, refilled arrays)
   g->graph_version = -1;
@@ -1055,42 +1075,25 @@ int dbm_discriminator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, co
   const bool sync = c->sync_stats() && train;
   c->fork_to_side(0);
   {
-    hipStream_t main_stream = c->stream;
-    if (!sync) c->stream = c->side;
-    try {
-      d->forward(N, H4, W4, Y, lr, train, train, 0);  // real batch (:1145)
-    } catch (...) {
-      c->stream = main_stream;
-      throw;
-    }
-    c->stream = main_stream;
+    StreamScope on(c, sync ? s : c->side);
+    d->forward(N, H4, W4, Y, lr, train, train, 0);  // real batch (:1145)
   }
   // fake images under enable_backprop=False (:1131-1137)
   g->forward(N, H, W, X, W1, W2, W3, g->yout.p, share && train);
-  g->graph_version = g->param_version;
-  g->graph_epoch = c->data_epoch;
-  g->graph_in[0] = X; g->graph_in[1] = W1; g->graph_in[2] = W2; g->graph_in[3] = W3;
+  g->record_graph(X, W1, W2, W3);
   DBM_MARK(s, "D:generator_forward");
   if (prefetch && train) {
     Generator* t = g->get_twin();
     t->ensure_ws(N, H, W, true);
     if (!g->ev_prefetch) DBM_HIP(hipEventCreateWithFlags(&g->ev_prefetch, hipEventDisableTiming));
-    t->max_split = narrow ? 1 : 2;
     hipStream_t pf = narrow ? c->chain[0] : c->chain[1];
     c->fork(s, pf, 6);  // weights packed, inputs final, and not before this step's own forward is done
-    c->stream = pf;
-    try {
-      t->forward(N, H, W, X, W1, W2, W3, t->yout.p, true);
-    } catch (...) {
-      c->stream = s;
-      throw;
+    {
+      StreamScope on(c, pf);
+      t->forward(N, H, W, X, W1, W2, W3, t->yout.p, true, /*max_split=*/narrow ? 1 : 2);
     }
     DBM_HIP(hipEventRecord(g->ev_prefetch, pf));
-    t->max_split = 2;
-    c->stream = s;
-    t->graph_version = g->param_version;
-    t->graph_epoch = c->data_epoch;
-    t->graph_in[0] = X; t->graph_in[1] = W1; t->graph_in[2] = W2; t->graph_in[3] = W3;
+    t->record_graph(X, W1, W2, W3);
   }
   c->join_side();
   d->forward(N, H4, W4, g->yout.p, lf, train, train, 1);   // fake batch (:1146) -- separate BatchNorm statistics
@@ -1106,8 +1109,7 @@ int dbm_discriminator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, co
   }
   DBM_MARK(s, "D:disc_forward_fake+loss");
   if (train) {
-    DBM_HIP(hipMemsetAsync(d->grads, 0, d->nparam * sizeof(float), s));  // cleargrads (:1162)
-    mark_grads_cleared(d);
+    clear_grads(d, s);  // cleargrads (:1162)
     // d_loss.backward() (:1163): the real- and the fake-batch graphs are independent (gradients are accumulated
     // with atomics), so the fake batch's pass runs on a second stream; both hand their weight gradients to the side stream
     // (while a prefetched generator forward owns chain[0] / chain[1], both passes stay on the main stream)
@@ -1115,41 +1117,23 @@ int dbm_discriminator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, co
     const bool twin_one_stream = g->trunk_fused_ok(H - 2, W - 2);
     const bool two_streams = (!(prefetch && train) || twin_one_stream) && !sync;
     d->ensure_packed_bwd(s);   // (before the fork: both passes read the data-gradient images)
-    if (two_streams) {
-      c->fork(s, c->chain[0], 7);
-      c->stream = c->chain[0];
-    }
-    d->merge_slots = true;  // one weight-gradient launch per layer group for both graphs
+    if (two_streams) c->fork(s, c->chain[0], 7);
     d->comm_sent_lo = d->comm_sent_hi = 0;
-    try {
-      // The pass on the MAIN stream (real batch) is enqueued first: the main stream is the one the step's tail waits
-      // for (measured: D-step 5.72 -> 5.39 ms against enqueueing the fake batch's pass first); the fake batch's pass,
-      // enqueued second, launches the merged weight-gradient groups behind both passes' events.
-      hipStream_t other = c->stream;  // chain[0] when two streams are used, else the main stream
-      c->stream = s;
-      d->backward(0, gr, false);
-      c->stream = other;
-      d->backward(1, gf, false);
-      c->stream = s;
-    } catch (...) {
-      c->stream = s;
-      d->merge_slots = false;
-      throw;
+    // The pass on the MAIN stream (real batch) is enqueued first: the main stream is the one the step's tail waits
+    // for (measured: D-step 5.72 -> 5.39 ms against enqueueing the fake batch's pass first); the fake batch's pass,
+    // enqueued second, launches the merged weight-gradient groups (one launch per layer group for both graphs) behind
+    // both passes' events.
+    d->backward(0, gr, false, /*merge=*/true);
+    {
+      StreamScope on(c, two_streams ? c->chain[0] : s);
+      d->backward(1, gf, false, /*merge=*/true);
     }
-    d->merge_slots = false;
     DBM_MARK(s, "D:disc_backward_real_chain");
     if (two_streams) c->fork(c->chain[0], s, 7);
     DBM_MARK(s, "D:disc_backward_fake_chain_joined");
     c->join_side();
     DBM_MARK(s, "D:weight_gradients_joined");
-    if (c->comm_in_step) {  // what launch_group has not sent yet: [0, lo) and [hi, nparam) in one fused group
-      float* p[2] = {d->grads, d->grads + d->comm_sent_hi};
-      size_t n[2] = {d->comm_sent_lo, d->nparam - d->comm_sent_hi};
-      if (d->comm_sent_hi == 0) { n[0] = d->nparam; n[1] = 0; }
-      c->comm_bucket(p, n, n[1] ? 2 : 1, s);
-      c->comm_join(s);
-      DBM_MARK(s, "D:gradients_exchanged");
-    }
+    if (c->comm_in_step) d->exchange_rest(s);
   }
   DBM_API_END
 }
@@ -1170,24 +1154,15 @@ int dbm_generator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, const 
   // only then may the forward that step prefetched be consumed.  (Pointers, shapes, the parameter version and the
   // library's own record of writes to device memory are checked on top; writes by anybody else are invisible here.)
   const bool use_prefetched = (train & 4) != 0;
-  struct CommScope {
-    dbm_ctx* c;
-    CommScope(dbm_ctx* ctx, bool on) : c(ctx) { c->comm_in_step = on; }
-    ~CommScope() { c->comm_in_step = false; }
-  } comm_scope(c, (train & 1) && !(train & 16) && c->comm_active());
+  CommScope comm(c, (train & 1) && !(train & 16) && c->comm_active());
   train &= 1;
   // Opt-in: the generator and its inputs are unchanged since the D-step of this iteration, so that step's forward
   // (the same numbers: it is the retained form of the pass) is reused instead of recomputed.  Off by default: the
   // reference runs it twice.
-  const bool reuse = share && train && g->have_graph && g->wsTrain && g->graph_version == g->param_version &&
-                     g->graph_epoch == c->data_epoch && g->wsN == N && g->wsH == H && g->wsW == W && g->graph_in[0] == X && g->graph_in[1] == W1 &&
-                     g->graph_in[2] == W2 && g->graph_in[3] == W3;
+  const bool reuse = share && train && g->has_graph_of(N, H, W, X, W1, W2, W3);
   DBM_MARK(s, "G:begin");
   Generator* t = g->twin;
-  const bool prefetched = train && use_prefetched && t && t->have_graph && t->wsTrain && t->graph_version == g->param_version &&
-                          t->graph_epoch == c->data_epoch && t->wsN == N &&
-                          t->wsH == H && t->wsW == W && t->graph_in[0] == X && t->graph_in[1] == W1 && t->graph_in[2] == W2 &&
-                          t->graph_in[3] == W3;
+  const bool prefetched = train && use_prefetched && t && t->has_graph_of(N, H, W, X, W1, W2, W3);
   Generator* gg = prefetched ? t : g;  // the workspace that holds this step's graph
   const bool pack_aside = d->packed_dirty && !reuse && !prefetched && !train;
   if (pack_aside) {  // the discriminator's weight images (stale since its Adam step) are rebuilt under the generator forward
@@ -1213,21 +1188,15 @@ int dbm_generator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, const 
     gen_loss_terms(c, gg->yout.p, Y, X, N, H4, W4, weights, ssim_window, gg->g_y.p);
     hipStream_t aux = c->chain[1];
     c->fork(s, aux, 11);  // fakes, the discriminator's updated weights and the cleared loss scratch are final on `s`
-    c->stream = aux;
-    try {
+    {
+      StreamScope on(c, aux);
       d->forward(N, H4, W4, gg->yout.p, lf, false, false, 1);  // eval-mode BatchNorm, detached (:1228-1229)
       gen_loss_adv(c, nullptr, lf, N, 0, 1);
-    } catch (...) {
-      c->stream = s;
-      throw;
     }
-    c->stream = s;
     DBM_MARK(s, "G:disc_forward+loss");
-    DBM_HIP(hipMemsetAsync(g->grads, 0, g->nparam * sizeof(float), s));  // cleargrads (:1255)
-    mark_grads_cleared(g);
-    gg->grads_cleared = true;  // (the memset above: two-slice weight gradients may fold with atomics, bit for bit)
-    gg->backward(gg->g_y.p);                                             // g_loss.backward() (:1256)
-    gg->grads_cleared = false;
+    clear_grads(g, s);  // cleargrads (:1255)
+    // g_loss.backward() (:1256) into the arena just cleared: two-slice weight gradients may fold with atomics, bit for bit
+    gg->backward(gg->g_y.p, /*cleared=*/true);
     c->fork(aux, s, 12);  // (chain[1] also carried the gradient exchange of a data-parallel run)
     gen_loss_finish(c, N, H4, W4, weights, metrics + 2);
     DBM_MARK(s, "G:generator_backward_joined");
@@ -1237,11 +1206,8 @@ int dbm_generator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, const 
                     train ? gg->g_y.p : nullptr);
     DBM_MARK(s, "G:disc_forward+loss");
     if (train) {
-      DBM_HIP(hipMemsetAsync(g->grads, 0, g->nparam * sizeof(float), s));  // cleargrads (:1255)
-      mark_grads_cleared(g);
-      gg->grads_cleared = true;
-      gg->backward(gg->g_y.p);                                             // g_loss.backward() (:1256)
-      gg->grads_cleared = false;
+      clear_grads(g, s);                             // cleargrads (:1255)
+      gg->backward(gg->g_y.p, /*cleared=*/true);     // g_loss.backward() (:1256)
       c->comm_join(s);
       DBM_MARK(s, "G:generator_backward_joined");
     }
@@ -1295,21 +1261,17 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   // stream priority lost its A/B; moving the tail to chain[0] (DBM_ITER_TAIL) was NEVER validly measured -- DBM_API_BEGIN's
   // join cleared tail_pending, so both arms ran the same schedule -- and the path was deleted without a re-measurement;
   // forking the twin's forward early, measured again in round 5, made the iteration later: profiles/r5/ab_twin.txt.)
-  struct Scope {  // every helper below enqueues on ctx->stream / reads the exchange switches: restore them whatever happens
-    dbm_ctx* c; hipStream_t s; Discriminator* d; Generator* t = nullptr;
-    ~Scope() {
-      c->stream = s; c->comm_in_step = false; c->comm_defer = false; c->comm_stream = nullptr; c->comm_pending.clear();
-      d->merge_slots = false; d->borrow_images = false;
-      if (t) { t->grads_cleared = false; t->use_aux = true; t->max_split = 2; t->csr_early = false; t->csr_prebuilt = false; }
-    }
-  } scope{c, s, d};
-  c->comm_in_step = dp;
-  c->comm_stream = dp ? c->chain[0] : nullptr;
+  CommScope comm(c, dp, dp ? c->chain[0] : nullptr);
   // (profiles/r6/ab_disc_launch_trims.txt, three alternations on one box, medians: all three trims of round 6 on 7.668 ms per step; the
   //  head as two launches per pass 7.695; private image copies 7.681; the D-step's cleargrads at the head of the side stream instead of
   //  between the loss and the backward passes 7.668 against 7.656 WITHOUT it -- that one lost and is gone again: 77 MB of fills in front
   //  of D(real)'s forward cost more than 41 MB behind the loss.)
-  d->borrow_images = true;   // (Y and the generator's output buffers outlive this call; both backward passes run inside it)
+  // The two training-mode discriminator forwards borrow their images (Y and the generator's output buffers outlive this call; both
+  // backward passes run inside it).  None stays borrowed past the call, whether it returns or throws.
+  struct Scope {
+    Discriminator* d;
+    ~Scope() { d->drop_borrowed(); }
+  } scope{d};
   DBM_MARK(s, "D:begin");
   // (libdbm_measure.so only; results are then wrong -- what a part of the iteration costs INSIDE it: 1 = no discriminator work at all
   //  (forwards, backward passes, weight gradients, update, repack, eval-mode pass), 2 = no trunk weight-gradient launch (generator.hip),
@@ -1319,12 +1281,13 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   // ---- D(real) forward on the side stream, underneath the generator forward (:1145) ----
   g->ensure_packed();   // (normally done behind the previous update; never on the side stream: the forward below reads these images)
   c->fork_to_side(0);
-  c->stream = c->side;
   // cleargrads of the G-step (:1255), early: nothing reads or writes the generator's gradient arena between the previous update and this
   // iteration's backward pass, and 35 MB of fill would otherwise sit between the loss and the backward pass on the critical path
   DBM_HIP(hipMemsetAsync(g->grads, 0, g->nparam * sizeof(float), c->side));
-  if (!no_d) d->forward(N, H4, W4, Y, lr, true, true, 0);
-  c->stream = s;
+  if (!no_d) {
+    StreamScope on(c, c->side);
+    d->forward(N, H4, W4, Y, lr, true, true, 0, /*borrow=*/true);
+  }
   // (The G-step's own forward goes to chain[1] behind the first forward; one_fwd: it is the only forward, forked here.
   //  Round 4 measured releasing only its INPUT BLOCK early -- beside the first forward's tail, the trunk launch still behind it:
   //  8.073 against 8.027 ms, two alternations on one box: not kept.)
@@ -1333,7 +1296,6 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
     c->fork(s, pf, 6);
   }
   Generator* t = g->get_twin();
-  scope.t = t;
   t->ensure_ws(N, H, W, true);
   // DBM_ITER_CSR_EARLY (default 1): the deformable layers' sampling lists (they depend on the offsets only) are built on chain[0]
   // behind the discriminator's fake-batch pass -- i.e. beside the generator's loss -- instead of on the backward pass's own path
@@ -1344,14 +1306,13 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   if (!one_fwd) g->forward(N, H, W, X, W1, W2, W3, g->yout.p, false);
   DBM_MARK(s, "D:generator_forward");
   if (!one_fwd) c->fork(s, pf, 6);
-  // ---- the G-step's own forward (:1222-1227), retained graph, second workspace, on chain[1] ----
-  t->max_split = 1;
-  t->csr_early = csr_early_env != 0 && !dp;   // (data-parallel: chain[0] also carries the gradient exchange -- the lists stay on the backward pass's own path)
-  c->stream = pf;
-  t->forward(N, H, W, X, W1, W2, W3, t->yout.p, true);
+  // ---- the G-step's own forward (:1222-1227), retained graph, second workspace, on chain[1] (one image range) ----
+  // (data-parallel: chain[0] also carries the gradient exchange -- the sampling lists stay on the backward pass's own path)
+  {
+    StreamScope on(c, pf);
+    t->forward(N, H, W, X, W1, W2, W3, t->yout.p, true, /*max_split=*/1, /*csr_early=*/csr_early_env != 0 && !dp);
+  }
   DBM_HIP(hipEventRecord(g->ev_prefetch, pf));  // the twin's fakes are final (the G-step's eval-mode discriminator pass reads them)
-  c->stream = s;
-  t->max_split = 2;
   // ---- D(fake) forward, RaGAN loss, cleargrads (:1146-1162) ----
   c->join_side();
   // The data-gradient weight images of both models (stale since their updates; first read by this iteration's backward passes) are rebuilt
@@ -1363,52 +1324,41 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   d->ensure_packed_bwd(c->side);
   DBM_HIP(hipEventRecord(c->ev_iter[3], c->side));   // (what the discriminator's backward passes wait for)
   if (one_fwd) DBM_HIP(hipStreamWaitEvent(s, g->ev_prefetch, 0));  // (the fakes are the retained forward's, written on chain[1])
-  if (!no_d) d->forward(N, H4, W4, one_fwd ? t->yout.p : g->yout.p, lf, true, true, 1);
+  if (!no_d) d->forward(N, H4, W4, one_fwd ? t->yout.p : g->yout.p, lf, true, true, 1, /*borrow=*/true);
   launch_ragan_loss(lr, lf, N, 1, 0, metrics, gr, gf, s);
   DBM_MARK(s, "D:disc_forward_fake+loss");
-  DBM_HIP(hipMemsetAsync(d->grads, 0, d->nparam * sizeof(float), s));
-  mark_grads_cleared(d);
+  clear_grads(d, s);
   // ---- d_loss.backward() (:1163): real batch on the main stream, fake batch on chain[0], weight gradients on side ----
   DBM_HIP(hipStreamWaitEvent(s, c->ev_iter[3], 0));   // (before the fork: both passes read the data-gradient images)
   c->fork(s, c->chain[0], 7);
-  d->merge_slots = true;
   d->comm_sent_lo = d->comm_sent_hi = 0;
   c->comm_defer = dp;  // (chain[0] is the exchange stream AND carries the fake-batch pass: its bucket goes out behind the pass)
-  if (!no_d) d->backward(0, gr, false);
-  c->stream = c->chain[0];
-  if (!no_d) d->backward(1, gf, false);
-  c->stream = s;
-  d->merge_slots = false;
+  if (!no_d) {
+    d->backward(0, gr, false, /*merge=*/true);
+    StreamScope on(c, c->chain[0]);
+    d->backward(1, gf, false, /*merge=*/true);
+  }
   c->comm_defer = false;
   if (dp) c->comm_flush();
   c->fork(c->chain[0], s, 7);
   if (csr_early_env && !dp) t->prebuild_csr(c->chain[0]);   // (behind the fake-batch pass, and behind the mark the main stream waits for)
   c->join_side();  // (the discriminator's weight gradients: everything on the side stream so far)
   DBM_MARK(s, "D:weight_gradients_joined");
-  if (dp) {  // what launch_group has not sent yet: [0, lo) and [hi, nparam) in one fused group; then the optimizer's wait
-    float* p[2] = {d->grads, d->grads + d->comm_sent_hi};
-    size_t n[2] = {d->comm_sent_lo, d->nparam - d->comm_sent_hi};
-    if (d->comm_sent_hi == 0) { n[0] = d->nparam; n[1] = 0; }
-    c->comm_bucket(p, n, n[1] ? 2 : 1, s);
-    c->comm_join(s);
-    DBM_MARK(s, "D:gradients_exchanged");
-  }
+  if (dp) d->exchange_rest(s);
   // ---- the generator's loss terms and backward pass (:1248-1256) on chain[1], behind its forward ----
-  c->stream = pf;
-  DBM_MARK(pf, "G:retained_forward_done");
-  gen_loss_terms(c, t->yout.p, Y, X, N, H4, W4, weights, ssim_window, t->g_y.p);
-  DBM_MARK(pf, "G:loss_terms");
-  DBM_HIP(hipEventRecord(c->ev_iter[0], pf));
-  DBM_HIP(hipStreamWaitEvent(pf, c->ev_iter[2], 0));  // cleargrads (:1255): the fill at the head of the side stream (+ the weight images)
-  mark_grads_cleared(g);
-  t->grads_cleared = true;
-  t->use_aux = false;   // (chain[0] carries the discriminator's fake-batch pass and the gradient exchange)
-  t->backward(t->g_y.p);
-  t->grads_cleared = false;
-  t->use_aux = true;
-  t->graph_version = -1;
-  DBM_HIP(hipEventRecord(c->ev_iter[1], pf));
-  c->stream = s;
+  {
+    StreamScope on(c, pf);
+    DBM_MARK(pf, "G:retained_forward_done");
+    gen_loss_terms(c, t->yout.p, Y, X, N, H4, W4, weights, ssim_window, t->g_y.p);
+    DBM_MARK(pf, "G:loss_terms");
+    DBM_HIP(hipEventRecord(c->ev_iter[0], pf));
+    DBM_HIP(hipStreamWaitEvent(pf, c->ev_iter[2], 0));  // cleargrads (:1255): the fill at the head of the side stream (+ the weight images)
+    mark_grads_cleared(g);
+    // (no aux stream: chain[0] carries the discriminator's fake-batch pass and the gradient exchange)
+    t->backward(t->g_y.p, /*cleared=*/true, /*use_aux=*/false);
+    t->graph_version = -1;
+    DBM_HIP(hipEventRecord(c->ev_iter[1], pf));
+  }
   // ---- discriminator update (:1164), then the G-step's detached eval-mode discriminator pass (:1228-1237) ----
   if (!no_d) adam_update_impl(d, gscale);
   DBM_HIP(hipStreamWaitEvent(s, g->ev_prefetch, 0));  // the twin's fakes (written on chain[1]: nothing else orders this read)

@@ -71,7 +71,7 @@ void Discriminator::prepare_eval_coeffs(int slot, hipStream_t s) {
   launch_bn_eval_coeffs(ej, 1e-5f, s);
 }
 
-void Discriminator::forward(int N, int H, int W, const float* img, float* logits, bool bn_train, bool keep, int slot) {
+void Discriminator::forward(int N, int H, int W, const float* img, float* logits, bool bn_train, bool keep, int slot, bool borrow) {
   DBM_CHECK(slot == 0 || slot == 1, "discriminator cache slot must be 0 or 1");
   int hs[11], ws[11];
   layer_dims(H, W, hs, ws);  // hs[i+1] = spatial size of h_i
@@ -151,7 +151,7 @@ void Discriminator::forward(int N, int H, int W, const float* img, float* logits
   c.N = N; c.H = H; c.W = W;
   c.valid = keep && bn_train;
   if (c.valid) {  // conv_layer0's weight gradient needs the input image: keep a private copy
-    if (borrow_images) {   // (the fused steps: the backward pass runs inside the same call, the images outlive it -- no copy launch)
+    if (borrow) {
       c.img_src = img;
     } else {
       c.img.ensure(n * H * W);
@@ -164,8 +164,8 @@ void Discriminator::forward(int N, int H, int W, const float* img, float* logits
 // Weight gradients of one layer group go to the side stream once their inputs are final.  Merged mode (the fused
 // D-step): the real batch's pass (slot 0) is enqueued first and only records an event per group; the fake batch's pass
 // (slot 1), enqueued second, launches the group for both graphs behind both events.
-void Discriminator::launch_group(int slot, int g) {
-  if (!merge_slots) {
+void Discriminator::launch_group(int slot, int g, bool merge) {
+  if (!merge) {
     ctx->fork_to_side(2 + slot);
     wb[slot][g].launch(ctx->side);
     return;
@@ -186,9 +186,19 @@ void Discriminator::launch_group(int slot, int g) {
   }
 }
 
+// what launch_group has not sent yet: [0, lo) and [hi, nparam) in one fused group
+void Discriminator::exchange_rest(hipStream_t s) {
+  float* p[2] = {grads, grads + comm_sent_hi};
+  size_t n[2] = {comm_sent_lo, nparam - comm_sent_hi};
+  if (comm_sent_hi == 0) { n[0] = nparam; n[1] = 0; }
+  ctx->comm_bucket(p, n, n[1] ? 2 : 1, s);
+  ctx->comm_join(s);
+  DBM_MARK(s, "D:gradients_exchanged");
+}
+
 static inline int wgroup(int layer) { return layer >= 6 ? 0 : layer >= 4 ? 1 : layer >= 2 ? 2 : 3; }
 
-void Discriminator::backward(int slot, const float* glogits, bool join) {
+void Discriminator::backward(int slot, const float* glogits, bool join, bool merge) {
   Cache& c = cache[slot];
   DBM_CHECK(c.valid, "discriminator backward without a retained training-mode forward");
   mark_grads_touched();
@@ -220,8 +230,8 @@ void Discriminator::backward(int slot, const float* glogits, bool join) {
     const int hin = hs[i], win = ws[i], ho = hs[i + 1], wo = ws[i + 1];
     if (skip_deep && i >= 5) {   // (the layers' weight gradients stay: they run on the side stream and are not what a fused deep end replaces)
       run_wgrad(L, c.h[i - 1].p, (long)DC_C[i] * hin * win, hin, win, 0, g_z[slot][i].p, (long)DC_O[i] * ho * wo, ho, wo, N, 1.f,
-                merge_slots ? &wbm[wgroup(i)] : &wb[slot][wgroup(i)]);
-      if (wgroup(i - 1) != wgroup(i)) launch_group(slot, wgroup(i));
+                merge ? &wbm[wgroup(i)] : &wb[slot][wgroup(i)]);
+      if (wgroup(i - 1) != wgroup(i)) launch_group(slot, wgroup(i), merge);
       continue;
     }
     if (ctx->sync_stats()) {
@@ -235,7 +245,7 @@ void Discriminator::backward(int slot, const float* glogits, bool join) {
       launch_bn_train_bwd(c.z[i].p, gh, P(T_bn[i][0]), P(T_bn[i][1]), c.mean[i].p, c.istd[i].p, g_z[slot][i].p, G(T_bn[i][0]),
                           G(T_bn[i][1]), nullptr, N, DC_O[i], ho * wo, SLOPE, s);
     run_wgrad(L, c.h[i - 1].p, (long)DC_C[i] * hin * win, hin, win, 0, g_z[slot][i].p, (long)DC_O[i] * ho * wo, ho, wo, N, 1.f,
-              merge_slots ? &wbm[wgroup(i)] : &wb[slot][wgroup(i)]);
+              merge ? &wbm[wgroup(i)] : &wb[slot][wgroup(i)]);
     ConvDesc d;
     memset(&d, 0, sizeof(d));
     d.x = g_z[slot][i].p; d.xsn = (long)DC_O[i] * ho * wo; d.N = N;
@@ -246,7 +256,7 @@ void Discriminator::backward(int slot, const float* glogits, bool join) {
     // this layer closes its group: the group's weight gradients only need the g_z slabs written so far -- they go out
     // BEFORE this layer's data gradient (conv_layer1's, the largest of the chain, used to stand between the last slab and
     // the last group's launch: that much shorter is the wait for the side stream at the end of the step)
-    if (i == 1 || wgroup(i - 1) != wgroup(i)) launch_group(slot, wgroup(i));
+    if (i == 1 || wgroup(i - 1) != wgroup(i)) launch_group(slot, wgroup(i), merge);
     run_dgrad(L, d, hin, win);
     float* t = gh; gh = gh_next; gh_next = t;
   }
@@ -259,6 +269,6 @@ void Discriminator::backward(int slot, const float* glogits, bool join) {
     launch_smallcin_conv_wgrad(q, gh, 64L * c.H * c.W, G(T_c0W), G(T_c0b), s, c0_scratch[slot].p);
   }
   // (conv_layer1..9 weight gradients: one launch per kernel form and layer group, on the side stream -- see the loop)
-  if (borrow_images) { c.valid = false; c.img_src = nullptr; }   // (a borrowed image is good for ONE backward pass, inside the borrowing call)
+  c.drop_borrowed();   // (a borrowed image is good for ONE backward pass)
   if (join) ctx->join_side();
 }

@@ -156,6 +156,19 @@ Generator* Generator::get_twin() {
   return t;
 }
 
+// A retained forward stands in for the one a later step would run only if it came from the same parameters (the owner's, for a
+// twin) and the same inputs -- pointers and shapes -- with no library write to caller-visible device memory in between.
+void Generator::record_graph(const float* x, const float* w1, const float* w2, const float* w3) {
+  graph_version = (owner ? owner : this)->param_version;
+  graph_epoch = ctx->data_epoch;
+  graph_in[0] = x; graph_in[1] = w1; graph_in[2] = w2; graph_in[3] = w3;
+}
+
+bool Generator::has_graph_of(int N, int H, int W, const float* x, const float* w1, const float* w2, const float* w3) const {
+  return have_graph && wsTrain && graph_version == (owner ? owner : this)->param_version && graph_epoch == ctx->data_epoch &&
+         wsN == N && wsH == H && wsW == W && graph_in[0] == x && graph_in[1] == w1 && graph_in[2] == w2 && graph_in[3] == w3;
+}
+
 // number of image ranges the 9x9 stage is cut into (1 or 2): only when a single range would leave the chip
 // mostly idle (few tiles) and the ranges stay equal
 static int trunk_split(int N, long hw) {
@@ -240,7 +253,7 @@ void Generator::ensure_ws(int N, int H, int W, bool train) {
 }
 
 void Generator::forward(int N, int H, int W, const float* x, const float* w1, const float* w2, const float* w3,
-                        float* y, bool keep) {
+                        float* y, bool keep, int max_split, bool csr_early) {
   ensure_ws(N, H, W, keep);
   ensure_packed();
   // by-products of an EARLIER retained pass (sampling lists built ahead of its backward pass, premultiplied tap planes, the channels-last
@@ -586,7 +599,7 @@ void Generator::prebuild_csr(hipStream_t aux) {
   csr_prebuilt = true;
 }
 
-void Generator::backward(const float* gy) {
+void Generator::backward(const float* gy, bool cleared, bool use_aux) {
   DBM_CHECK(have_graph && wsTrain, "generator backward without a retained forward (DBM_KEEP_GRAPH)");
   mark_grads_touched();
   hipStream_t s = ctx->stream;
@@ -594,7 +607,7 @@ void Generator::backward(const float* gy) {
   const int N = wsN, H = wsH, W = wsW, h = H - 2, w = W - 2;
   const long hw = (long)h * w, P4 = 16 * hw;
   const int H4 = 4 * h, W4 = 4 * w, nrdb = 3 * n_rrdb;
-  for (auto& b : wbs) b.cleared_target = grads_cleared;
+  for (auto& b : wbs) b.cleared_target = cleared;
   // ---- final_conv_layer2 (deformable, 64 -> 1) ----
   const bool bfused = deform_bwd_fused(H4, W4);
   const bool pre_csr = csr_prebuilt && bfused;   // (prebuild_csr: both layers' sampling lists are already being built on another stream)
@@ -801,7 +814,7 @@ void Generator::backward(const float* gy) {
     }
   }
   if (!fused) (owner ? owner : this)->ensure_packed_lazy();
-  const int nsplit = fused ? 1 : std::min(trunk_split(N, hw), max_split);
+  const int nsplit = fused ? 1 : trunk_split(N, hw);
   auto cstream = [&](int c) { return c == 0 ? s : ctx->chain[chain_base + c - 1]; };
   auto chunk = [&](ConvDesc d, int c) {  // descriptor restricted to image range c
     const long n0 = ((long)c * N) / nsplit;

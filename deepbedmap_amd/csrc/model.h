@@ -207,20 +207,21 @@ struct Generator : dbm_model {
   long graph_version = -1;
   long graph_epoch = -1;   // dbm_ctx::data_epoch at the time of that forward
   const float* graph_in[4] = {nullptr, nullptr, nullptr, nullptr};
+  void record_graph(const float* x, const float* w1, const float* w2, const float* w3);  // (behind the forward)
+  bool has_graph_of(int N, int H, int W, const float* x, const float* w1, const float* w2, const float* w3) const;
   bool col_stale = false;   // the retained forward ran the fused input block: colW1 / colW2 are rebuilt by backward()
   const float* bw_in[4] = {nullptr, nullptr, nullptr, nullptr};  // forward inputs, needed by the input-block wgrad
   static const int NWB = 7;
-  bool grads_cleared = false;  // set by dbm_generator_step around backward(): cleargrads has just run (WgradBatch::cleared_target)
   int wbs_groups = -1;  // trunk groups the batches below were planned for
   WgradBatch wbs[NWB];  // batched weight gradients: tail, 5 trunk groups, pre-residual + input block (launched on the side stream)
   std::vector<DevBuf> cat, dA;
   DevBuf in_x, in_w1, in_w2, in_w3, a0, a3, a41, a42, off1, off2, col1, col2, a51, yout;
   DevBuf csr_ws;       // sampling lists of the deformable layers' input-gradient gather (deform_csr_build_kernel)
-  // The lists depend on the layers' offsets only.  csr_early (set by dbm_train_iteration around the retained forward): forward() marks
-  // the two offset tensors (ev_off), prebuild_csr(aux) builds both lists on `aux` beside the generator's loss (the 64 -> 64 layer's in
-  // csr_ws, the 64 -> 1 layer's in csr_ws2) and backward() only waits for them (ev_csr) instead of building them on its own path.
+  // The lists depend on the layers' offsets only.  forward(..., csr_early) marks the two offset tensors (ev_off), prebuild_csr(aux)
+  // builds both lists on `aux` beside the generator's loss (the 64 -> 64 layer's in csr_ws, the 64 -> 1 layer's in csr_ws2) and
+  // backward() only waits for them (ev_csr) instead of building them on its own path.
   DevBuf csr_ws2;
-  bool csr_early = false, csr_marked = false, csr_prebuilt = false;
+  bool csr_marked = false, csr_prebuilt = false;
   hipEvent_t ev_off[2] = {nullptr, nullptr}, ev_csr = nullptr;
   void prebuild_csr(hipStream_t aux);
   DevBuf dw2_partial;  // per-workgroup partial sums of final_conv_layer2's weight gradient (deform_bwd1_fused_kernel)
@@ -247,8 +248,6 @@ struct Generator : dbm_model {
   Generator* twin = nullptr;
   Generator* owner = nullptr;  // twin only: the model whose arenas and weight images it aliases
   int chain_base = 0;
-  bool use_aux = true;  // backward(): the deformable layers' offset-gradient kernel may run on chain[chain_base]
-  int max_split = 2;  // image ranges the 9x9 stage may be cut into (1: everything on the caller's stream)
   hipEvent_t ev_prefetch = nullptr;
   hipEvent_t ev_pack[3] = {nullptr, nullptr, nullptr};  // pack_extra: main stream reached the repack / forward streams built / backward streams built
   // fused 9x9 trunk forward (trunk_fused.hip): per-wavefront weight streams (owner only), per-workspace hand-off granules
@@ -266,8 +265,13 @@ struct Generator : dbm_model {
   Generator(dbm_ctx* c, int n, float r, int oc);
   void ensure_ws(int N, int H, int W, bool train);
   int slot(int j) const { return wsTrain ? j : (j == 0 ? 0 : 1 + ((j - 1) & 3)); }
-  void forward(int N, int H, int W, const float* x, const float* w1, const float* w2, const float* w3, float* y, bool keep);
-  void backward(const float* gy);
+  // max_split: image ranges the 9x9 stage may be cut into (1: everything on the caller's stream); csr_early: mark the offsets for
+  // prebuild_csr
+  void forward(int N, int H, int W, const float* x, const float* w1, const float* w2, const float* w3, float* y, bool keep,
+               int max_split = 2, bool csr_early = false);
+  // cleared: the gradient arena has just been zeroed on this stream (WgradBatch::cleared_target); use_aux: the deformable layers'
+  // offset-gradient kernels may run on chain[chain_base]
+  void backward(const float* gy, bool cleared = false, bool use_aux = true);
 };
 
 struct Discriminator : dbm_model {
@@ -278,7 +282,8 @@ struct Discriminator : dbm_model {
     int N = 0, H = 0, W = 0;
     bool valid = false;
     DevBuf img, h[10], z[10], mean[10], istd[10], l1, out;
-    const float* img_src = nullptr;   // the retained pass's input image: the private copy `img`, or the caller's buffer (borrow_images)
+    const float* img_src = nullptr;   // the retained pass's input image: the private copy `img`, or the caller's buffer (forward's `borrow`)
+    void drop_borrowed() { if (img_src && img_src != img.p) { valid = false; img_src = nullptr; } }
   } cache[2];
   DevBuf bn_coef[2];  // eval-mode passes: [scale | shift] of all nine BatchNorm layers (launch_bn_eval_coeffs), one buffer per cache
                       // slot: two eval-mode passes in flight on different streams never share coefficients
@@ -287,14 +292,16 @@ struct Discriminator : dbm_model {
   WgradBatch wbm[NWG];     // the same for BOTH graphs in one launch per group (the fused D-step: twice the work per launch)
   hipEvent_t ev_grp[2][NWG] = {};
   size_t comm_sent_lo = 0, comm_sent_hi = 0;  // gradient range already handed to the exchange by launch_group (this step)
-  bool merge_slots = false;  // set by the fused steps around their two backward calls (real first, then fake)
-  // set by the fused steps around their retained forwards: conv_layer0's weight gradient reads the caller's image buffer directly (it
-  // outlives the call, and the backward pass runs inside it) instead of a private copy -- one 332 KB copy launch less per pass (round 6)
-  bool borrow_images = false;
-  void launch_group(int slot, int g);
+  void exchange_rest(hipStream_t s);  // the rest of the arena to the exchange, then `s` waits for all of it
+  void launch_group(int slot, int g, bool merge);
   WgradBatch wb[2][NWG];  // batched weight gradients per retained graph (real / fake batch): layers 9..6, 5..4, 3..2, 1
   Discriminator(dbm_ctx* c);
-  void forward(int N, int H, int W, const float* img, float* logits, bool bn_train, bool keep, int slot);
+  // borrow: conv_layer0's weight gradient reads the caller's image buffer directly instead of a private copy -- one 332 KB copy
+  // launch less per pass (round 6).  A borrowed image is good for ONE backward pass, which the borrowing call runs itself: the
+  // pass drops it, and so does the call's exit (drop_borrowed), whether it returns or throws.
+  void forward(int N, int H, int W, const float* img, float* logits, bool bn_train, bool keep, int slot, bool borrow = false);
+  void drop_borrowed() { for (Cache& c : cache) c.drop_borrowed(); }
   void prepare_eval_coeffs(int slot, hipStream_t s);
-  void backward(int slot, const float* glogits, bool join = true);
+  // merge: the fused steps' two passes (real first, then fake) share one weight-gradient launch per layer group
+  void backward(int slot, const float* glogits, bool join = true, bool merge = false);
 };

@@ -1196,6 +1196,28 @@ def test_fused_iteration_random_batch_sizes(dbm, n, n_blocks):
         assert np.allclose(got[2:], ref_g, rtol=2e-4, atol=1e-5), (got, ref_g)
 
 
+def test_fused_iteration_that_throws_leaves_no_borrowed_image(dbm):
+    """The single-call iteration's retained discriminator passes read the caller's images (no private copy) and are good for
+    the backward passes inside that call only.  A call that throws between the real batch's forward and its backward pass
+    (a two-channel generator fails its retained forward's check) must not leave that pass behind: a later backward pass on
+    slot 0 is refused instead of reading a caller's buffer that may be gone.  The discriminator and the context then still
+    run a normal iteration."""
+    arrays = dbm.device_batch(fixture_arrays(n=2))
+    od = omodel.DiscriminatorModel(seed=5)
+    d = copy_params(dbm.DiscriminatorModel(initialize=False), od.params, od.persistent)
+    d_opt = dbm.optimizers.Adam(alpha=1e-3, eps=1e-7).setup(d)
+    g2 = dbm.GeneratorModel(num_residual_blocks=2, out_channels=2)
+    g2_opt = dbm.optimizers.Adam(alpha=1e-3, eps=1e-7).setup(g2)
+    with pytest.raises(dbm.DbmError, match="out_channels"):
+        dbm.train_minibatch(arrays, g2, g2_opt, d, d_opt, fused=True)
+    with pytest.raises(dbm.DbmError, match="without a retained training-mode forward"):
+        d.backward(0, dbm.to_device(np.ones((2, 1), np.float32)))
+    g = copy_params(dbm.GeneratorModel(num_residual_blocks=2, initialize=False), scaled_oracle_generator(2, 3.0).params)
+    g_opt = dbm.optimizers.Adam(alpha=1e-3, eps=1e-7).setup(g)
+    out = dbm.train_minibatch(arrays, g, g_opt, d, d_opt, fused=True)
+    assert len(out) == 5 and np.all(np.isfinite(out)), out
+
+
 def test_profiler_brackets_in_step_and_standalone(dbm):
     """bench.py's roofline leg: hipEvent brackets around the launches of the MFMA kernel families, in the running step
     (dbm_profile_begin) and with the device synchronised around every launch (dbm_profile_begin_serial: standalone
