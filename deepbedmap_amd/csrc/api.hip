@@ -237,6 +237,7 @@ int dbm_shutdown(dbm_ctx* ctx) {
   ctx->loss_tmp.release();
   for (auto& b : ctx->stage) b.release();
   ctx->track_tmp.release();
+  ctx->tile_tmp.release();
   (void)hipStreamSynchronize(ctx->side);
   (void)hipStreamDestroy(ctx->side);
   for (auto& st : ctx->chain) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -958,6 +959,80 @@ int dbm_grid_track(dbm_ctx* ctx, const float* grid_dev, long H, long W, const do
   } else if (reduce) {
     DBM_HIP(hipMemcpyAsync(stats, dstats, 6 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   }
+  DBM_API_END
+}
+
+int dbm_grid_tile(dbm_ctx* ctx, const float* grid_dev, long H, long W, const double geom[4], const void* windows_host, long n, int mode,
+                  double resolution, int out_h, int out_w, const double* nodata, const float* gapfiller, int fill_nan, float* out_dev,
+                  size_t window_stride, int* counts_dev) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && geom != nullptr, "dbm_grid_tile: NULL argument");
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  DBM_CHECK(mode == 0 || mode == 1, "dbm_grid_tile: mode must be 0 (slicing) or 1 (bilinear)");
+  DBM_CHECK(n >= 0, "dbm_grid_tile: negative number of windows");
+  DBM_CHECK(out_h >= 1 && out_w >= 1, "dbm_grid_tile: empty tiles");
+  DBM_CHECK((long)out_h * out_w < (1L << 31), "dbm_grid_tile: one tile must stay below 2^31 values");
+  DBM_CHECK(H >= 1 && W >= 1, "dbm_grid_tile: empty raster");
+  DBM_CHECK(mode == 0 || (H >= 2 && W >= 2), "dbm_grid_tile: bilinear needs at least 2 x 2 nodes");
+  DBM_CHECK(std::isfinite(geom[0]) && std::isfinite(geom[1]) && std::isfinite(geom[2]) && std::isfinite(geom[3]) && geom[2] != 0.0 &&
+                geom[3] != 0.0, "dbm_grid_tile: x0, y0 finite, dx, dy finite and non-zero");
+  DBM_CHECK(mode == 0 || (std::isfinite(resolution) && resolution > 0.0), "dbm_grid_tile: the resolution must be positive");
+  DBM_CHECK(window_stride >= (size_t)out_h * (size_t)out_w, "dbm_grid_tile: the window stride is smaller than one tile");
+  DBM_CHECK(n == 0 || (grid_dev != nullptr && out_dev != nullptr && windows_host != nullptr), "dbm_grid_tile: NULL raster, windows or output");
+  DBM_CHECK(nodata == nullptr || std::isnan(*nodata) || std::isfinite(*nodata), "dbm_grid_tile: nodata must be finite or NaN");
+  if (mode == 0) {  // a pure copy: every window must lie inside the raster
+    const long* w = (const long*)windows_host;
+    for (long k = 0; k < n; ++k, w += 4) {
+      const long r1 = w[0] + (long)(out_h - 1) * w[2], c1 = w[1] + (long)(out_w - 1) * w[3];
+      DBM_CHECK((w[2] == 1 || w[2] == -1) && (w[3] == 1 || w[3] == -1) && w[0] >= 0 && w[0] < H && r1 >= 0 && r1 < H && w[1] >= 0 &&
+                    w[1] < W && c1 >= 0 && c1 < W, "dbm_grid_tile: window " + std::to_string(k) + " does not lie inside the raster");
+    }
+  }
+  if (n > 0) {
+    TileLaunch a;
+    a.grid = grid_dev;
+    a.H = H; a.W = W;
+    a.x0 = geom[0]; a.y0 = geom[1]; a.dx = geom[2]; a.dy = geom[3];
+    a.n = n;
+    a.out_h = out_h; a.out_w = out_w; a.mode = mode;
+    a.res = resolution;
+    a.has_nodata = nodata != nullptr && !std::isnan(*nodata);   // (a NaN nodata masks nothing: data_prep.py:702)
+    a.nodata = a.has_nodata ? *nodata : 0.0;
+    a.nodata_band = 1e-8 + 1e-5 * std::fabs(a.nodata);
+    a.has_fill = gapfiller != nullptr;
+    a.fill = gapfiller ? *gapfiller : 0.0f;
+    a.fill_nan = fill_nan != 0;
+    a.out = out_dev;
+    a.out_stride = (long)window_stride;
+    a.counts = counts_dev;
+    ctx->stage[7].ensure(8 * (size_t)n);  // (floats: 4 x 8 bytes per window)
+    DBM_HIP(hipMemcpyAsync(ctx->stage[7].p, windows_host, 32 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    a.windows = ctx->stage[7].p;
+    if (counts_dev) DBM_HIP(hipMemsetAsync(counts_dev, 0, sizeof(int) * (size_t)n, ctx->stream));
+    launch_grid_tile(a, ctx->stream);
+  }
+  DBM_API_END
+}
+
+int dbm_grid_filled_windows(dbm_ctx* ctx, const float* grid_dev, long H, long W, int size, int step, int flip_rows, int flip_cols,
+                            unsigned char* flags_dev) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_grid_filled_windows: NULL context");
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  DBM_CHECK(size >= 2 && size % 2 == 0 && size <= FILLED_LDS_BYTES, "dbm_grid_filled_windows: the window size must be even, 2..8192");
+  DBM_CHECK(step >= 1, "dbm_grid_filled_windows: the step must be positive");
+  DBM_CHECK(H >= size && W >= size, "dbm_grid_filled_windows: the raster is smaller than one window");
+  DBM_CHECK(grid_dev != nullptr && flags_dev != nullptr, "dbm_grid_filled_windows: NULL raster or flags");
+  FilledLaunch a;
+  a.grid = grid_dev;
+  a.H = H; a.W = W;
+  a.size = size; a.step = step;
+  a.flip_rows = flip_rows != 0; a.flip_cols = flip_cols != 0;
+  filled_windows_geometry(a);
+  ctx->tile_tmp.ensure(((size_t)a.rows * (size_t)a.nx + 3) / 4);
+  a.rowany = (unsigned char*)ctx->tile_tmp.p;
+  a.flags = flags_dev;
+  launch_filled_windows(a, ctx->stream);
   DBM_API_END
 }
 

@@ -259,3 +259,41 @@ struct TrackLaunch {
 };
 int grid_track_blocks(long n);   // workgroups of the sampling launch (depends on n only): partials needed
 void launch_grid_track(const TrackLaunch& a, double* stats, hipStream_t s);
+
+// Cutting tiles from a resident raster (tile.hip; dbm_grid_tile): out[k * out_stride + r * out_w + c] for n windows of (out_h, out_w).
+// mode 1: windows = n x (left, bottom, right, top) doubles, bilinear at np.linspace coordinates of resolution res; mode 0: windows =
+// n x (row0, col0, row step, column step) int64, a copy (every node inside the raster: checked by the caller).  counts (n ints,
+// zeroed by the caller) may be null.
+struct TileLaunch {
+  const float* grid;
+  long H, W;
+  double x0, y0, dx, dy;
+  const void* windows;         // device
+  long n;
+  int out_h, out_w, mode;
+  double res;
+  int has_nodata, has_fill, fill_nan;
+  double nodata, nodata_band;  // masked iff |v - nodata| <= nodata_band = 1e-8 + 1e-5 |nodata|
+  float fill;
+  float* out;
+  long out_stride;             // floats between windows, >= out_h * out_w
+  int* counts;
+};
+void launch_grid_tile(const TileLaunch& a, hipStream_t s);
+
+// Fully filled windows of a raster (tile.hip; dbm_grid_filled_windows): flags[uly * nx + ulx] = 1 iff no node of rows [uly step, uly step
+// + size) x columns [ulx step, ulx step + size) is NaN, rows counted from the north (flip_rows: raster row 0 is the south edge), columns
+// from the west (flip_cols).  rowany: rows * nx bytes of scratch.  filled_windows_geometry fills ny, nx, rows, nw, nseg from H, W,
+// size, step (size <= FILLED_LDS_BYTES).
+constexpr long FILLED_LDS_BYTES = 8192;
+struct FilledLaunch {
+  const float* grid;
+  long H, W;
+  int size, step, flip_rows, flip_cols;
+  long ny, nx, rows;           // candidate windows; raster rows they cover
+  long nw, nseg;               // window columns per workgroup of the row pass, workgroups per row
+  unsigned char* rowany;
+  unsigned char* flags;
+};
+void filled_windows_geometry(FilledLaunch& a);
+void launch_filled_windows(const FilledLaunch& a, hipStream_t s);

@@ -90,6 +90,7 @@ struct dbm_ctx {
   DevBuf loss_tmp;            // scratch for the loss entry points
   DevBuf stage[8];            // host<->device staging for the non-DEVICE_PTRS entry points
   DevBuf track_tmp;           // dbm_grid_track: the workgroups' error moments and the folded statistics (doubles)
+  DevBuf tile_tmp;            // dbm_grid_filled_windows: the row pass's byte plane
 };
 
 void dbm_comm_unique_id_impl(void* out128);  // comm.hip: ncclGetUniqueId

@@ -263,6 +263,38 @@ int dbm_ssim_ex(dbm_ctx* ctx, const float* y_pred, const float* y_true, int N, i
 int dbm_grid_track(dbm_ctx* ctx, const float* grid_dev, long H, long W, const double geom[5], const double* points, size_t n,
                    int ncol, int interp, double threshold, double* z_out, double* stats, int flags);
 
+/* ---- tiling: `selective_tile` (data_prep.py:622-741: every raster cut and bilinearly geo-registered to a list of windows; the
+ * training set data_prep.py:757-771, 880-911 and the inputs of an area deepbedmap.py:132-213 are built from it) ----
+ * The float32 raster (H, W) -- ALWAYS a device pointer, node (r, c) at (x0 + c dx, y0 + r dy), geom = {x0, y0, dx, dy}, either sign --
+ * is cut into n tiles of (out_h, out_w): out_dev[k * window_stride + r * out_w + c] (device, window_stride in floats: with
+ * window_stride = 2 * out_h * out_w two calls fill the two channels of an (n, 2, h, w) array).  windows_host is a HOST array of
+ * 32 bytes per window, staged like dbm_gather_rows' indices; the call is asynchronous on the context's stream.
+ * mode 1 (interpolate=True): windows = (left, bottom, right, top) doubles, already padded.  Tile row r, column c is the raster at
+ * y = np.linspace(top - res/2, bottom + res/2, out_h)[r], x = np.linspace(left + res/2, right - res/2, out_w)[c] (float64, NumPy's
+ * bits: multiply, then add, the end point exact), interpolated as scipy.interpolate.interpn(method="linear") does it: axes sorted
+ * ascending, node coordinates x0 + j dx, cell i with g[i] <= c < g[i+1] (last node: i = n - 2, t = 1), NaN outside [g[0], g[n-1]]
+ * or at a NaN coordinate, the float64 sum of z * (wy * wx) over all four nodes with zero weights included (a NaN node makes its
+ * whole closed cell NaN), no fused multiply-add.
+ * mode 0 (interpolate=False, `sel(method="nearest", tolerance=0)`): windows = (row0, col0, row step, column step) int64, steps +-1,
+ * a pure copy; the caller has checked that the tile's coordinates ARE node coordinates.
+ * Masking (data_prep.py:699-730, numpy.ma.masked_values applied after the interpolation): with nodata != NULL and *nodata not NaN a
+ * value v is masked iff |v - nodata| <= 1e-8 + 1e-5 |nodata| (v in float64, before rounding); NaN values are not masked unless
+ * fill_nan (an extension); masked values become *gapfiller if gapfiller != NULL; counts_dev (n ints, device, may be NULL) receives
+ * the number of masked values per window.  Values are rounded to float32 once, at the end.
+ * Refused (status 1, nothing launched): mode outside 0..1, n < 0, out_h or out_w < 1, H or W < 2 for mode 1, dx or dy zero or not
+ * finite, a resolution that is not positive (mode 1), window_stride < out_h * out_w, a NULL raster, window list or output with
+ * n > 0, a nodata that is infinite, a mode 0 window that leaves the raster.  n = 0 succeeds and does nothing. */
+int dbm_grid_tile(dbm_ctx* ctx, const float* grid_dev, long H, long W, const double geom[4], const void* windows_host, long n, int mode,
+                  double resolution, int out_h, int out_w, const double* nodata, const float* gapfiller, int fill_nan, float* out_dev,
+                  size_t window_stride, int* counts_dev);
+/* `get_window_bounds` (data_prep.py:501-572: `view_as_windows(mask, (height, width), step)` and `~any`): flags_dev[uly * nx + ulx]
+ * (device bytes, ny = (H - size) / step + 1 rows of nx = (W - size) / step + 1) = 1 iff no node of rows [uly step, uly step + size)
+ * x columns [ulx step, ulx step + size) is NaN.  Rows are counted from the NORTH edge (flip_rows != 0: raster row 0 is the south
+ * edge), columns from the west (flip_cols != 0: raster column 0 is the east edge).  Asynchronous.  `argwhere` and the bounds stay
+ * with the caller.  Refused (status 1): size odd, < 2 or > 8192, step < 1, H or W < size, NULL pointers. */
+int dbm_grid_filled_windows(dbm_ctx* ctx, const float* grid_dev, long H, long W, int size, int step, int flip_rows, int flip_cols,
+                            unsigned char* flags_dev);
+
 /* ---- optimizer ---- */
 /* chainer.optimizers.Adam(alpha, eps=1e-8).setup(model): srgan_train.py:1043-1048 */
 int dbm_adam_setup(dbm_model* m, double alpha, double beta1, double beta2, double eps);
@@ -293,7 +325,7 @@ int dbm_discriminator_step(dbm_model* g, dbm_model* d, int N, int H, int W, cons
  * (its bit 1); bit 2 (4) = consume the forward that step prefetched (its bit 2): the caller asserts that the five
  * arrays are the same, UNCHANGED, device arrays.  The library additionally checks pointers, shapes, the parameter
  * version and its own record of writes to device memory (dbm_memcpy_h2d, dbm_gather_rows, dbm_fill_f32,
- * dbm_memcpy2d_d2d, dbm_malloc, dbm_free); writes by anybody else (another library filling the same buffer in
+ * dbm_memcpy2d_d2d, dbm_grid_tile, dbm_grid_filled_windows, dbm_malloc, dbm_free); writes by anybody else (another library filling the same buffer in
  * place) are invisible to it, hence the explicit bit.  Without it the prefetched pass is discarded and the forward is
  * recomputed.  bit 4 (16) = see dbm_discriminator_step. */
 int dbm_generator_step(dbm_model* g, dbm_model* d, int N, int H, int W, const float* X, const float* W1,
