@@ -30,11 +30,12 @@ static void dbm_handle_persistent_timeout(dbm_ctx* c) {
   c->timeout_skipped[0] = c->timeout_skipped[1] = 0;
   for (dbm_model* m : c->models) {  // optimizer launches that found the condition up did nothing: take their step counts back
     int n = 0;
-    if (m->type == 0) static_cast<Generator*>(m)->graph_version = -1;  // retained / prefetched passes are void
+    if (m->type == 0)
+      for (GenWorkspace& w : static_cast<Generator*>(m)->ws) w.graph_version = -1;  // retained / prefetched passes are void
     // ... and so is whatever a backward pass has summed into the gradient arenas since the event (the observing call may be a
     // host-synchronising forward, long before the update that would apply them): marked until the next cleargrads
     if (m->grads_touched) m->grads_void = true;
-    if (m->is_view || !m->d_adam_skipped) continue;
+    if (!m->d_adam_skipped) continue;
     if (hipMemcpy(&n, m->d_adam_skipped, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess && n > 0) {
       m->adam_t -= n;
       c->timeout_skipped[m->type == 1 ? 0 : 1] += n;
@@ -53,13 +54,10 @@ static void dbm_handle_persistent_timeout(dbm_ctx* c) {
           c->timeout_events, c->timeout_skipped[0], c->timeout_skipped[1], pause);
 }
 
-// the gradient arena of `m` (shared with its views) has just been cleared on the stream: whatever a void pass left there is gone
-static void mark_grads_cleared(dbm_model* m) {
-  for (dbm_model* o : m->ctx->models)
-    if (o->grads == m->grads) { o->grads_void = false; o->grads_touched = false; }
-}
+// the gradient arena of `m` has just been cleared on the stream: whatever a void pass left there is gone
+static void mark_grads_cleared(dbm_model* m) { m->grads_void = false; m->grads_touched = false; }
 
-// cleargrads on stream `s` (a view shares its owner's arena: both marks go)
+// cleargrads on stream `s`
 static void clear_grads(dbm_model* m, hipStream_t s) {
   DBM_HIP(hipMemsetAsync(m->grads, 0, m->nparam * sizeof(float), s));
   mark_grads_cleared(m);
@@ -71,7 +69,7 @@ static void dbm_step_entry(dbm_ctx* c, bool counts_as_iteration) {
   if (g_trunk_fused_off && g_trunk_rearm_at >= 0 && g_step_serial >= g_trunk_rearm_at) {
     g_trunk_fused_off = false;
     for (dbm_model* m : c->models)
-      if (m->type == 0 && !m->is_view) m->packed_dirty = true;  // the trunk's weight streams were not maintained meanwhile
+      if (m->type == 0) m->packed_dirty = true;  // the trunk's weight streams were not maintained meanwhile
     fprintf(stderr, "libdbm: persistent trunk kernels re-armed (iteration %ld)\n", g_step_serial);
   }
   if (c->dev_err && *(volatile int*)c->dev_err) {
@@ -634,6 +632,7 @@ int dbm_gen_forward(dbm_model* gm, int N, int H, int W, const float* x, const fl
   DBM_CHECK(gm->type == 0, "dbm_gen_forward: not a generator");
   DBM_CHECK(N >= 1 && x && w1 && w2 && w3 && y, "dbm_gen_forward: bad arguments");
   Generator* g = static_cast<Generator*>(gm);
+  GenWorkspace& ws = g->ws[0];
   const bool keep = flags & DBM_KEEP_GRAPH;
   const size_t n = (size_t)N, hw = (size_t)H * W, P4 = 16 * (size_t)(H - 2) * (W - 2) * (size_t)g->out_ch;
   struct Bf16Scope {  // DBM_BF16: the convolution descriptors of this call point at the bf16 weight images
@@ -650,16 +649,16 @@ int dbm_gen_forward(dbm_model* gm, int N, int H, int W, const float* x, const fl
             "< 2^31; the fp32 forward serves larger planes)");
   Bf16Scope bf16(g, (flags & DBM_BF16) != 0);
   if (flags & DBM_DEVICE_PTRS) {
-    g->forward(N, H, W, x, w1, w2, w3, y, keep);
+    g->forward(ws, N, H, W, x, w1, w2, w3, y, keep);
   } else {
-    g->ensure_ws(N, H, W, keep);
+    g->ensure_ws(ws, N, H, W, keep);
     hipStream_t s = g->ctx->stream;
-    DBM_HIP(hipMemcpyAsync(g->in_x.p, x, n * hw * 4, hipMemcpyHostToDevice, s));
-    DBM_HIP(hipMemcpyAsync(g->in_w1.p, w1, n * 100 * hw * 4, hipMemcpyHostToDevice, s));
-    DBM_HIP(hipMemcpyAsync(g->in_w2.p, w2, n * 8 * hw * 4, hipMemcpyHostToDevice, s));
-    DBM_HIP(hipMemcpyAsync(g->in_w3.p, w3, n * hw * 4, hipMemcpyHostToDevice, s));
-    g->forward(N, H, W, g->in_x.p, g->in_w1.p, g->in_w2.p, g->in_w3.p, g->yout.p, keep);
-    DBM_HIP(hipMemcpyAsync(y, g->yout.p, n * P4 * 4, hipMemcpyDeviceToHost, s));
+    DBM_HIP(hipMemcpyAsync(ws.in_x.p, x, n * hw * 4, hipMemcpyHostToDevice, s));
+    DBM_HIP(hipMemcpyAsync(ws.in_w1.p, w1, n * 100 * hw * 4, hipMemcpyHostToDevice, s));
+    DBM_HIP(hipMemcpyAsync(ws.in_w2.p, w2, n * 8 * hw * 4, hipMemcpyHostToDevice, s));
+    DBM_HIP(hipMemcpyAsync(ws.in_w3.p, w3, n * hw * 4, hipMemcpyHostToDevice, s));
+    g->forward(ws, N, H, W, ws.in_x.p, ws.in_w1.p, ws.in_w2.p, ws.in_w3.p, ws.yout.p, keep);
+    DBM_HIP(hipMemcpyAsync(y, ws.yout.p, n * P4 * 4, hipMemcpyDeviceToHost, s));
     finish_sync(g->ctx, flags);   // (observes a persistent-kernel time-out: status 7, the results are void)
   }
   DBM_API_END
@@ -669,13 +668,14 @@ int dbm_gen_backward(dbm_model* gm, const float* gy, int flags) {
   DBM_API_BEGIN(gm->ctx)
   DBM_CHECK(gm->type == 0, "dbm_gen_backward: not a generator");
   Generator* g = static_cast<Generator*>(gm);
+  GenWorkspace& ws = g->ws[0];
   if (flags & DBM_DEVICE_PTRS) {
-    g->backward(gy);
+    g->backward(ws, gy);
   } else {
-    DBM_CHECK(g->have_graph, "generator backward without a retained forward (DBM_KEEP_GRAPH)");
-    const size_t cnt = (size_t)g->wsN * 16 * (g->wsH - 2) * (g->wsW - 2);
-    DBM_HIP(hipMemcpyAsync(g->g_y.p, gy, cnt * 4, hipMemcpyHostToDevice, g->ctx->stream));
-    g->backward(g->g_y.p);
+    DBM_CHECK(ws.have_graph, "generator backward without a retained forward (DBM_KEEP_GRAPH)");
+    const size_t cnt = (size_t)ws.N * 16 * (ws.H - 2) * (ws.W - 2);
+    DBM_HIP(hipMemcpyAsync(ws.g_y.p, gy, cnt * 4, hipMemcpyHostToDevice, g->ctx->stream));
+    g->backward(ws, ws.g_y.p);
     finish_sync(g->ctx, flags);
   }
   DBM_API_END
@@ -1126,16 +1126,15 @@ int dbm_discriminator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, co
   // work changes.
   const bool prefetch = (train & 4) != 0 && !share;
   // bit 8: the caller runs collectives on a stream of its own (RCCL): the prefetched forward then stays on ONE library
-  // stream so that, with the caller's two, no more than four are ever busy (see Generator::twin)
+  // stream so that, with the caller's two, no more than four are ever busy (see Generator::ws)
   const bool narrow = (train & 8) != 0 && !g->trunk_fused_ok(H - 2, W - 2);  // (a fused pass is one stream anyway)
   // data-parallel run with a communicator on the context (dbm_comm_init / dbm_comm_set_hook): the gradient buckets are
   // summed over ranks inside this call, overlapped with the backward passes; bit 4 (16) leaves the exchange to the caller
   CommScope comm(c, (train & 1) && !(train & 16) && c->comm_active());
   train &= 1;
   // whatever an earlier call retained for a following G-step is void now (n_critic > 1 loops, refilled arrays)
-  g->graph_version = -1;
-  if (g->twin) g->twin->graph_version = -1;
-  g->ensure_ws(N, H, W, share && train);
+  for (GenWorkspace& w : g->ws) w.graph_version = -1;
+  g->ensure_ws(g->ws[0], N, H, W, share && train);
   d->g_out.ensure(4 * (size_t)N);
   float* lr = d->g_out.p;
   float* lf = lr + N;
@@ -1154,24 +1153,24 @@ int dbm_discriminator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, co
     d->forward(N, H4, W4, Y, lr, train, train, 0);  // real batch (:1145)
   }
   // fake images under enable_backprop=False (:1131-1137)
-  g->forward(N, H, W, X, W1, W2, W3, g->yout.p, share && train);
-  g->record_graph(X, W1, W2, W3);
+  g->forward(g->ws[0], N, H, W, X, W1, W2, W3, g->ws[0].yout.p, share && train);
+  g->record_graph(g->ws[0], X, W1, W2, W3);
   DBM_MARK(s, "D:generator_forward");
   if (prefetch && train) {
-    Generator* t = g->get_twin();
-    t->ensure_ws(N, H, W, true);
+    GenWorkspace& t = g->ws[1];
+    g->ensure_ws(t, N, H, W, true);
     if (!g->ev_prefetch) DBM_HIP(hipEventCreateWithFlags(&g->ev_prefetch, hipEventDisableTiming));
     hipStream_t pf = narrow ? c->chain[0] : c->chain[1];
     c->fork(s, pf, 6);  // weights packed, inputs final, and not before this step's own forward is done
     {
       StreamScope on(c, pf);
-      t->forward(N, H, W, X, W1, W2, W3, t->yout.p, true, /*max_split=*/narrow ? 1 : 2);
+      g->forward(t, N, H, W, X, W1, W2, W3, t.yout.p, true, /*max_split=*/narrow ? 1 : 2);
     }
     DBM_HIP(hipEventRecord(g->ev_prefetch, pf));
-    t->record_graph(X, W1, W2, W3);
+    g->record_graph(t, X, W1, W2, W3);
   }
   c->join_side();
-  d->forward(N, H4, W4, g->yout.p, lf, train, train, 1);   // fake batch (:1146) -- separate BatchNorm statistics
+  d->forward(N, H4, W4, g->ws[0].yout.p, lf, train, train, 1);   // fake batch (:1146) -- separate BatchNorm statistics
   if (sync) {  // relativistic means over the global batch (:995-1004)
     float* sb = c->sync_buf.p + 3 * 512;
     launch_ragan_sync_sums(lr, lf, N, sb, s);
@@ -1189,8 +1188,8 @@ int dbm_discriminator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, co
     // with atomics), so the fake batch's pass runs on a second stream; both hand their weight gradients to the side stream
     // (while a prefetched generator forward owns chain[0] / chain[1], both passes stay on the main stream)
     // (with the persistent trunk kernel the prefetched forward occupies ONE stream, chain[1]: chain[0] is free again)
-    const bool twin_one_stream = g->trunk_fused_ok(H - 2, W - 2);
-    const bool two_streams = (!(prefetch && train) || twin_one_stream) && !sync;
+    const bool prefetch_one_stream = g->trunk_fused_ok(H - 2, W - 2);
+    const bool two_streams = (!(prefetch && train) || prefetch_one_stream) && !sync;
     d->ensure_packed_bwd(s);   // (before the fork: both passes read the data-gradient images)
     if (two_streams) c->fork(s, c->chain[0], 7);
     d->comm_sent_lo = d->comm_sent_hi = 0;
@@ -1234,11 +1233,10 @@ int dbm_generator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, const 
   // Opt-in: the generator and its inputs are unchanged since the D-step of this iteration, so that step's forward
   // (the same numbers: it is the retained form of the pass) is reused instead of recomputed.  Off by default: the
   // reference runs it twice.
-  const bool reuse = share && train && g->has_graph_of(N, H, W, X, W1, W2, W3);
+  const bool reuse = share && train && g->has_graph_of(g->ws[0], N, H, W, X, W1, W2, W3);
   DBM_MARK(s, "G:begin");
-  Generator* t = g->twin;
-  const bool prefetched = train && use_prefetched && t && t->has_graph_of(N, H, W, X, W1, W2, W3);
-  Generator* gg = prefetched ? t : g;  // the workspace that holds this step's graph
+  const bool prefetched = train && use_prefetched && g->has_graph_of(g->ws[1], N, H, W, X, W1, W2, W3);
+  GenWorkspace& gg = g->ws[prefetched];  // the workspace that holds this step's graph
   const bool pack_aside = d->packed_dirty && !reuse && !prefetched && !train;
   if (pack_aside) {  // the discriminator's weight images (stale since its Adam step) are rebuilt under the generator forward
     c->fork_to_side(5);
@@ -1250,39 +1248,39 @@ int dbm_generator_step(dbm_model* gm, dbm_model* dm, int N, int H, int W, const 
   if (prefetched) {
     if (!overlap_d) d->ensure_packed();
     DBM_HIP(hipStreamWaitEvent(s, g->ev_prefetch, 0));
-    t->graph_version = -1;  // consumed
+    gg.graph_version = -1;  // consumed
   } else if (!reuse) {
-    g->ensure_ws(N, H, W, train != 0);
-    g->forward(N, H, W, X, W1, W2, W3, g->yout.p, train != 0);  // (:1222-1227)
+    g->ensure_ws(gg, N, H, W, train != 0);
+    g->forward(gg, N, H, W, X, W1, W2, W3, gg.yout.p, train != 0);  // (:1222-1227)
   }
   DBM_MARK(s, "G:generator_forward");
   if (pack_aside) c->join_side();
   d->g_out.ensure(4 * (size_t)N);
   float* lf = d->g_out.p;
   if (overlap_d) {
-    gen_loss_terms(c, gg->yout.p, Y, X, N, H4, W4, weights, ssim_window, gg->g_y.p);
+    gen_loss_terms(c, gg.yout.p, Y, X, N, H4, W4, weights, ssim_window, gg.g_y.p);
     hipStream_t aux = c->chain[1];
     c->fork(s, aux, 11);  // fakes, the discriminator's updated weights and the cleared loss scratch are final on `s`
     {
       StreamScope on(c, aux);
-      d->forward(N, H4, W4, gg->yout.p, lf, false, false, 1);  // eval-mode BatchNorm, detached (:1228-1229)
+      d->forward(N, H4, W4, gg.yout.p, lf, false, false, 1);  // eval-mode BatchNorm, detached (:1228-1229)
       gen_loss_adv(c, nullptr, lf, N, 0, 1);
     }
     DBM_MARK(s, "G:disc_forward+loss");
     clear_grads(g, s);  // cleargrads (:1255)
     // g_loss.backward() (:1256) into the arena just cleared: two-slice weight gradients may fold with atomics, bit for bit
-    gg->backward(gg->g_y.p, /*cleared=*/true);
+    g->backward(gg, gg.g_y.p, /*cleared=*/true);
     c->fork(aux, s, 12);  // (chain[1] also carried the gradient exchange of a data-parallel run)
     gen_loss_finish(c, N, H4, W4, weights, metrics + 2);
     DBM_MARK(s, "G:generator_backward_joined");
   } else {
-    d->forward(N, H4, W4, gg->yout.p, lf, false, false, 1);  // eval-mode BatchNorm, detached (:1228-1229)
-    gen_loss_device(c, gg->yout.p, Y, X, nullptr, lf, N, H4, W4, weights, 0, 1, ssim_window, metrics + 2,
-                    train ? gg->g_y.p : nullptr);
+    d->forward(N, H4, W4, gg.yout.p, lf, false, false, 1);  // eval-mode BatchNorm, detached (:1228-1229)
+    gen_loss_device(c, gg.yout.p, Y, X, nullptr, lf, N, H4, W4, weights, 0, 1, ssim_window, metrics + 2,
+                    train ? gg.g_y.p : nullptr);
     DBM_MARK(s, "G:disc_forward+loss");
     if (train) {
       clear_grads(g, s);                             // cleargrads (:1255)
-      gg->backward(gg->g_y.p, /*cleared=*/true);     // g_loss.backward() (:1256)
+      g->backward(gg, gg.g_y.p, /*cleared=*/true);  // g_loss.backward() (:1256)
       c->comm_join(s);
       DBM_MARK(s, "G:generator_backward_joined");
     }
@@ -1320,9 +1318,8 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   const int H4 = 4 * (H - 2), W4 = 4 * (W - 2);
   const bool dp = c->comm_active();
   const double gscale = dp ? 1.0 / c->comm_world : 1.0;
-  g->graph_version = -1;
-  if (g->twin) g->twin->graph_version = -1;
-  g->ensure_ws(N, H, W, false);
+  for (GenWorkspace& w : g->ws) w.graph_version = -1;
+  g->ensure_ws(g->ws[0], N, H, W, false);
   d->g_out.ensure(5 * (size_t)N);
   float* lr = d->g_out.p;
   float* lf = lr + N;
@@ -1335,7 +1332,7 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   // metrics -- runs on the main stream.  Round 3 tried three alternatives (profiles/design_history_r1-r3.md): raising chain[1]'s
   // stream priority lost its A/B; moving the tail to chain[0] (DBM_ITER_TAIL) was NEVER validly measured -- DBM_API_BEGIN's
   // join cleared tail_pending, so both arms ran the same schedule -- and the path was deleted without a re-measurement;
-  // forking the twin's forward early, measured again in round 5, made the iteration later: profiles/r5/ab_twin.txt.)
+  // forking the second workspace's forward early, measured again in round 5, made the iteration later: profiles/r5/ab_twin.txt.)
   CommScope comm(c, dp, dp ? c->chain[0] : nullptr);
   // (profiles/r6/ab_disc_launch_trims.txt, three alternations on one box, medians: all three trims of round 6 on 7.668 ms per step; the
   //  head as two launches per pass 7.695; private image copies 7.681; the D-step's cleargrads at the head of the side stream instead of
@@ -1370,24 +1367,24 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
     g->ensure_packed();
     c->fork(s, pf, 6);
   }
-  Generator* t = g->get_twin();
-  t->ensure_ws(N, H, W, true);
+  GenWorkspace& t = g->ws[1];
+  g->ensure_ws(t, N, H, W, true);
   // DBM_ITER_CSR_EARLY (default 1): the deformable layers' sampling lists (they depend on the offsets only) are built on chain[0]
   // behind the discriminator's fake-batch pass -- i.e. beside the generator's loss -- instead of on the backward pass's own path
   // (Generator::prebuild_csr; 7.69-7.70 against 7.77-7.78 ms.  On the side stream, which must then wait for the retained forward's
   // tail, the discriminator's weight gradients start late: 8.07)
   static const int csr_early_env = getenv("DBM_ITER_CSR_EARLY") ? atoi(getenv("DBM_ITER_CSR_EARLY")) : 1;
   // ---- fakes under enable_backprop=False (:1131-1137) ----
-  if (!one_fwd) g->forward(N, H, W, X, W1, W2, W3, g->yout.p, false);
+  if (!one_fwd) g->forward(g->ws[0], N, H, W, X, W1, W2, W3, g->ws[0].yout.p, false);
   DBM_MARK(s, "D:generator_forward");
   if (!one_fwd) c->fork(s, pf, 6);
   // ---- the G-step's own forward (:1222-1227), retained graph, second workspace, on chain[1] (one image range) ----
   // (data-parallel: chain[0] also carries the gradient exchange -- the sampling lists stay on the backward pass's own path)
   {
     StreamScope on(c, pf);
-    t->forward(N, H, W, X, W1, W2, W3, t->yout.p, true, /*max_split=*/1, /*csr_early=*/csr_early_env != 0 && !dp);
+    g->forward(t, N, H, W, X, W1, W2, W3, t.yout.p, true, /*max_split=*/1, /*csr_early=*/csr_early_env != 0 && !dp);
   }
-  DBM_HIP(hipEventRecord(g->ev_prefetch, pf));  // the twin's fakes are final (the G-step's eval-mode discriminator pass reads them)
+  DBM_HIP(hipEventRecord(g->ev_prefetch, pf));  // the second workspace's fakes are final (the G-step's eval-mode discriminator pass reads them)
   // ---- D(fake) forward, RaGAN loss, cleargrads (:1146-1162) ----
   c->join_side();
   // The data-gradient weight images of both models (stale since their updates; first read by this iteration's backward passes) are rebuilt
@@ -1399,7 +1396,7 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   d->ensure_packed_bwd(c->side);
   DBM_HIP(hipEventRecord(c->ev_iter[3], c->side));   // (what the discriminator's backward passes wait for)
   if (one_fwd) DBM_HIP(hipStreamWaitEvent(s, g->ev_prefetch, 0));  // (the fakes are the retained forward's, written on chain[1])
-  if (!no_d) d->forward(N, H4, W4, one_fwd ? t->yout.p : g->yout.p, lf, true, true, 1, /*borrow=*/true);
+  if (!no_d) d->forward(N, H4, W4, one_fwd ? t.yout.p : g->ws[0].yout.p, lf, true, true, 1, /*borrow=*/true);
   launch_ragan_loss(lr, lf, N, 1, 0, metrics, gr, gf, s);
   DBM_MARK(s, "D:disc_forward_fake+loss");
   clear_grads(d, s);
@@ -1416,7 +1413,7 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   c->comm_defer = false;
   if (dp) c->comm_flush();
   c->fork(c->chain[0], s, 7);
-  if (csr_early_env && !dp) t->prebuild_csr(c->chain[0]);   // (behind the fake-batch pass, and behind the mark the main stream waits for)
+  if (csr_early_env && !dp) g->prebuild_csr(t, c->chain[0]);   // (behind the fake-batch pass, and behind the mark the main stream waits for)
   c->join_side();  // (the discriminator's weight gradients: everything on the side stream so far)
   DBM_MARK(s, "D:weight_gradients_joined");
   if (dp) d->exchange_rest(s);
@@ -1424,21 +1421,21 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
   {
     StreamScope on(c, pf);
     DBM_MARK(pf, "G:retained_forward_done");
-    gen_loss_terms(c, t->yout.p, Y, X, N, H4, W4, weights, ssim_window, t->g_y.p);
+    gen_loss_terms(c, t.yout.p, Y, X, N, H4, W4, weights, ssim_window, t.g_y.p);
     DBM_MARK(pf, "G:loss_terms");
     DBM_HIP(hipEventRecord(c->ev_iter[0], pf));
     DBM_HIP(hipStreamWaitEvent(pf, c->ev_iter[2], 0));  // cleargrads (:1255): the fill at the head of the side stream (+ the weight images)
     mark_grads_cleared(g);
     // (no aux stream: chain[0] carries the discriminator's fake-batch pass and the gradient exchange)
-    t->backward(t->g_y.p, /*cleared=*/true, /*use_aux=*/false);
-    t->graph_version = -1;
+    g->backward(t, t.g_y.p, /*cleared=*/true, /*use_aux=*/false);
+    t.graph_version = -1;
     DBM_HIP(hipEventRecord(c->ev_iter[1], pf));
   }
   // ---- discriminator update (:1164), then the G-step's detached eval-mode discriminator pass (:1228-1237) ----
   if (!no_d) adam_update_impl(d, gscale);
-  DBM_HIP(hipStreamWaitEvent(s, g->ev_prefetch, 0));  // the twin's fakes (written on chain[1]: nothing else orders this read)
+  DBM_HIP(hipStreamWaitEvent(s, g->ev_prefetch, 0));  // the second workspace's fakes (written on chain[1]: nothing else orders this read)
   // (Deferring this pass to the next library call, round 6, measured slower wherever it went: profiles/r6/ab_defer_eval.txt.)
-  if (!no_d && !(iter_abl & 8)) d->forward(N, H4, W4, t->yout.p, lf_eval, false, false, 1);  // (repacks the updated weights first)
+  if (!no_d && !(iter_abl & 8)) d->forward(N, H4, W4, t.yout.p, lf_eval, false, false, 1);  // (repacks the updated weights first)
   DBM_HIP(hipStreamWaitEvent(s, c->ev_iter[0], 0));  // the loss scratch was cleared on chain[1]
   gen_loss_adv(c, nullptr, lf_eval, N, 0, 1);
   gen_loss_finish(c, N, H4, W4, weights, metrics + 2);   // (the loss terms are final: not behind the backward pass's join -- it sat between the

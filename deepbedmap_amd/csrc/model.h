@@ -146,16 +146,14 @@ struct dbm_model {
   // backward pass: dbm_adam_update answers status 9 until the arena has been cleared (dbm_model_cleargrads, or the cleargrads
   // inside the step entry points) -- whichever call observed the event, and however many host-synchronising calls lie between
   bool grads_void = false;
-  // a backward pass has been enqueued into this model's gradient arena since it was last cleared (set by Generator / Discriminator::backward
-  // for every model sharing the arena, reset by mark_grads_cleared): a time-out observed while the arena is still clean voids nothing
+  // a backward pass has been enqueued into this model's gradient arena since it was last cleared (set by Generator / Discriminator::backward,
+  // reset by mark_grads_cleared): a time-out observed while the arena is still clean voids nothing
   bool grads_touched = false;
-  void mark_grads_touched();
   bool packed_dirty = true;
   long param_version = 0;  // bumped by every write to the parameter arena
   long packed16_version = -1;  // param_version the bf16 forward images were built from
   bool use_bf16 = false;       // fwd_desc hands out the bf16 images (set around a DBM_BF16 forward)
   void ensure_packed_bf16();
-  bool is_view = false;    // arenas and packed weight images belong to another model (Generator::twin)
   std::vector<IgLayer> layers;
   PackJob* d_pack_jobs = nullptr;  // device job table of the one-launch weight repack: the FORWARD images (IgLayer::wf)
   int n_pack_jobs = 0, n_pack_blocks = 0;
@@ -190,31 +188,22 @@ struct dbm_model {
                  int OH, int OW, int N, float scale, WgradBatch* batch = nullptr) const;
 };
 
-struct Generator : dbm_model {
-  int n_rrdb = 12, out_ch = 1;
-  float rs = 0.1f;
-  // layer indices into `layers`
-  int L_pre, L_post, L_up1, L_up2, L_off1, L_def1, L_off2;
-  std::vector<int> L_rdb;  // nrdb*5
-  int T_in[4][2];          // input block (W, b) tensor ids
-  int L_in[4] = {-1, -1, -1, -1};  // W1 / W2 branches run as im2col + GEMM on the MFMA kernels
-  DevBuf colW1, colW2;
-  int T_def2W, T_def2b;
-  // workspace
-  int wsN = 0, wsH = 0, wsW = 0;
-  bool wsTrain = false;
+// Everything one forward / backward pass of the generator leaves behind or works in: activations, gradients, scratch, the record of
+// the retained graph and the batches planned over these buffers.  Allocates nothing until a pass sizes it (Generator::ensure_ws).
+struct GenWorkspace {
+  int N = 0, H = 0, W = 0;
+  bool train = false;
   bool have_graph = false;
   // what the retained graph was computed from (opt-in reuse of the D-step's generator forward by the G-step)
   long graph_version = -1;
   long graph_epoch = -1;   // dbm_ctx::data_epoch at the time of that forward
   const float* graph_in[4] = {nullptr, nullptr, nullptr, nullptr};
-  void record_graph(const float* x, const float* w1, const float* w2, const float* w3);  // (behind the forward)
-  bool has_graph_of(int N, int H, int W, const float* x, const float* w1, const float* w2, const float* w3) const;
   bool col_stale = false;   // the retained forward ran the fused input block: colW1 / colW2 are rebuilt by backward()
   const float* bw_in[4] = {nullptr, nullptr, nullptr, nullptr};  // forward inputs, needed by the input-block wgrad
   static const int NWB = 7;
   int wbs_groups = -1;  // trunk groups the batches below were planned for
   WgradBatch wbs[NWB];  // batched weight gradients: tail, 5 trunk groups, pre-residual + input block (launched on the side stream)
+  DevBuf colW1, colW2;  // im2col images of the input block's W1 / W2 branches
   std::vector<DevBuf> cat, dA;
   DevBuf in_x, in_w1, in_w2, in_w3, a0, a3, a41, a42, off1, off2, col1, col2, a51, yout;
   DevBuf csr_ws;       // sampling lists of the deformable layers' input-gradient gather (deform_csr_build_kernel)
@@ -224,10 +213,7 @@ struct Generator : dbm_model {
   DevBuf csr_ws2;
   bool csr_marked = false, csr_prebuilt = false;
   hipEvent_t ev_off[2] = {nullptr, nullptr}, ev_csr = nullptr;
-  void prebuild_csr(hipStream_t aux);
   DevBuf dw2_partial;  // per-workgroup partial sums of final_conv_layer2's weight gradient (deform_bwd1_fused_kernel)
-  bool deform_bwd_fused(int H4, int W4) const;
-  bool deform_wgrad_fused(int H4, int W4) const;
   DevBuf dw1_partial;  // per-workgroup partial tiles of final_conv_layer1's weight gradient (deform_wgrad64_fused_kernel)
   DevBuf zdef;        // the last layer's premultiplied tap planes (N, 9 * out_ch, 4H, 4W): deform1_premul_kernel
   bool a42t_written = false;  // forward(): post_upsample_conv_layer_2 wrote the channels-last twin of its output itself
@@ -241,38 +227,55 @@ struct Generator : dbm_model {
   DevBuf a0t;        // the input block's 128-channel concat channels-last (the split-bf16 pre-residual convolution of the sweep)
   DevBuf a1t;        // NHWC fp32 copy of the trunk's input (the post-residual convolution's skip operand in that tail)
   DevBuf g_a0, g_a3, g_u1, g_z41, g_u2, g_a42, goff1, goff2, gcol, g_a51, g_y;
-  // A second workspace on the same parameters: the G-step's generator forward can be enqueued while the D-step's
-  // discriminator passes are still running (dbm_discriminator_step, prefetch flag).  The twin aliases this model's
-  // arenas and packed weight images.  NOTE the library never has more than FOUR streams busy at once (main, side,
-  // chain[0], chain[1]): with a fifth, streams share a hardware queue and independent chains serialise (measured:
-  // every phase of the step 2x slower).
-  Generator* twin = nullptr;
-  Generator* owner = nullptr;  // twin only: the model whose arenas and weight images it aliases
-  int chain_base = 0;
-  hipEvent_t ev_prefetch = nullptr;
+  // hand-off granules of the persistent trunk kernels and the launch counter they are stamped with: one set per workspace
+  unsigned long long* tf_inbox = nullptr;
+  int tf_epoch = 0;
+  int slot(int j) const { return train ? j : (j == 0 ? 0 : 1 + ((j - 1) & 3)); }
+  GenWorkspace() = default;
+  GenWorkspace(const GenWorkspace&) = delete;
+  ~GenWorkspace();
+};
+
+struct Generator : dbm_model {
+  int n_rrdb = 12, out_ch = 1;
+  float rs = 0.1f;
+  // layer indices into `layers`
+  int L_pre, L_post, L_up1, L_up2, L_off1, L_def1, L_off2;
+  std::vector<int> L_rdb;  // nrdb*5
+  int T_in[4][2];          // input block (W, b) tensor ids
+  int L_in[4] = {-1, -1, -1, -1};  // W1 / W2 branches run as im2col + GEMM on the MFMA kernels
+  int T_def2W, T_def2b;
+  // Two workspaces on the one set of parameters and weight images.  ws[0] serves every single pass; ws[1] holds the G-step's own
+  // retained forward, enqueued while the D-step's discriminator passes are still running (dbm_discriminator_step's prefetch flag,
+  // dbm_train_iteration).  NOTE the library never has more than FOUR streams busy at once (main, side, chain[0], chain[1]): with
+  // a fifth, streams share a hardware queue and independent chains serialise (measured: every phase of the step 2x slower).
+  GenWorkspace ws[2];
+  hipEvent_t ev_prefetch = nullptr;  // ws[1]'s fakes are final
   hipEvent_t ev_pack[3] = {nullptr, nullptr, nullptr};  // pack_extra: main stream reached the repack / forward streams built / backward streams built
-  // fused 9x9 trunk forward (trunk_fused.hip): per-wavefront weight streams (owner only), per-workspace hand-off granules
+  // fused 9x9 trunk (trunk_fused.hip, trunk_fused_bwd.hip): per-wavefront weight streams
   float* tf_wstream = nullptr;
   float* tf_bstream = nullptr;
   float* tf_bwd_wstream = nullptr;   // transposed / tap-flipped streams of the fused data-gradient chain
   const float** tf_wsrc = nullptr;   // device tables of the trunk layers' W / b
   const float** tf_bsrc = nullptr;
-  unsigned long long* tf_inbox = nullptr;
-  int tf_epoch = 0;
   void pack_extra(hipStream_t s) override;
   bool trunk_fused_ok(int h, int w) const;
-  Generator* get_twin();
+  bool deform_bwd_fused(int H4, int W4) const;
+  bool deform_wgrad_fused(int H4, int W4) const;
   ~Generator() override;
   Generator(dbm_ctx* c, int n, float r, int oc);
-  void ensure_ws(int N, int H, int W, bool train);
-  int slot(int j) const { return wsTrain ? j : (j == 0 ? 0 : 1 + ((j - 1) & 3)); }
+  // The passes below run in the workspace they are given, on ctx->stream.
+  void ensure_ws(GenWorkspace& ws, int N, int H, int W, bool train);
+  void record_graph(GenWorkspace& ws, const float* x, const float* w1, const float* w2, const float* w3) const;  // (behind the forward)
+  bool has_graph_of(const GenWorkspace& ws, int N, int H, int W, const float* x, const float* w1, const float* w2, const float* w3) const;
   // max_split: image ranges the 9x9 stage may be cut into (1: everything on the caller's stream); csr_early: mark the offsets for
   // prebuild_csr
-  void forward(int N, int H, int W, const float* x, const float* w1, const float* w2, const float* w3, float* y, bool keep,
-               int max_split = 2, bool csr_early = false);
+  void forward(GenWorkspace& ws, int N, int H, int W, const float* x, const float* w1, const float* w2, const float* w3, float* y,
+               bool keep, int max_split = 2, bool csr_early = false);
+  void prebuild_csr(GenWorkspace& ws, hipStream_t aux);
   // cleared: the gradient arena has just been zeroed on this stream (WgradBatch::cleared_target); use_aux: the deformable layers'
-  // offset-gradient kernels may run on chain[chain_base]
-  void backward(const float* gy, bool cleared = false, bool use_aux = true);
+  // offset-gradient kernels may run on chain[0]
+  void backward(GenWorkspace& ws, const float* gy, bool cleared = false, bool use_aux = true);
 };
 
 struct Discriminator : dbm_model {

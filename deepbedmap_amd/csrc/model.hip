@@ -54,7 +54,6 @@ dbm_model::~dbm_model() {
   if (ctx)
     for (size_t i = 0; i < ctx->models.size(); ++i)
       if (ctx->models[i] == this) { ctx->models.erase(ctx->models.begin() + i); break; }
-  if (is_view) return;  // nothing here is owned
   if (d_adam_skipped) (void)hipFree(d_adam_skipped);
   for (auto& L : layers) {
     if (L.wf) (void)hipFree(L.wf);
@@ -73,12 +72,6 @@ dbm_model::~dbm_model() {
   if (d_pack_jobs) (void)hipFree(d_pack_jobs);
   if (d_bwd_jobs) (void)hipFree(d_bwd_jobs);
   if (d_lazy_jobs) (void)hipFree(d_lazy_jobs);
-}
-
-void dbm_model::mark_grads_touched() {
-  for (dbm_model* o : ctx->models)
-    if (o->grads == grads) o->grads_touched = true;
-  grads_touched = true;
 }
 
 int dbm_model::add_tensor(const std::string& key, std::vector<int64_t> shape, int kind) {
@@ -253,7 +246,6 @@ void dbm_model::ensure_packed(hipStream_t on) {
 }
 
 void dbm_model::ensure_packed_bwd(hipStream_t on) {
-  if (is_view) return;
   if (packed_dirty) ensure_packed(on);
   if (!bwd_dirty) return;
   if (n_bwd_jobs) launch_pack_jobs(d_bwd_jobs, n_bwd_jobs, n_bwd_blocks, on ? on : ctx->stream);
@@ -343,7 +335,7 @@ ConvDesc dbm_model::fwd_desc(const IgLayer& L, const float* x, long xsn, int Hin
 // (after upsample), i.e. the dims of the gradient being produced.
 void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_fwd, hipStream_t s) const {
   if (!s) s = ctx->stream;
-  DBM_CHECK(is_view || !bwd_dirty, "run_dgrad: the data-gradient weight images are stale (ensure_packed_bwd was not called)");
+  DBM_CHECK(!bwd_dirty, "run_dgrad: the data-gradient weight images are stale (ensure_packed_bwd was not called)");
   const int OH = (Hin_fwd + 2 * L.pad - L.Kview) / L.stride + 1, OW = (Win_fwd + 2 * L.pad - L.Kview) / L.stride + 1;
   base.xsc = OH * OW; base.Cin = L.OP; base.Hin = OH; base.Win = OW; base.ups = 0;
   static const int cin_live_env = getenv("DBM_CIN_LIVE") ? atoi(getenv("DBM_CIN_LIVE")) : 1;   // (A/B switch)
