@@ -236,6 +236,7 @@ int dbm_shutdown(dbm_ctx* ctx) {
   for (auto& b : ctx->stage) b.release();
   ctx->track_tmp.release();
   ctx->tile_tmp.release();
+  ctx->resample_tmp.release();
   (void)hipStreamSynchronize(ctx->side);
   (void)hipStreamDestroy(ctx->side);
   for (auto& st : ctx->chain) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -1033,6 +1034,40 @@ int dbm_grid_filled_windows(dbm_ctx* ctx, const float* grid_dev, long H, long W,
   a.rowany = (unsigned char*)ctx->tile_tmp.p;
   a.flags = flags_dev;
   launch_filled_windows(a, ctx->stream);
+  DBM_API_END
+}
+
+int dbm_grid_rescale(dbm_ctx* ctx, const float* in_dev, long H, long W, long out_h, long out_w, int order, int anti_aliasing, int clip,
+                     int input_cast, float* out_dev) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_grid_rescale: NULL context");
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  DBM_CHECK(order == 1 || order == 3, "dbm_grid_rescale: order must be 1 (linear) or 3 (cubic B-spline)");
+  DBM_CHECK(H >= 2 && W >= 2, "dbm_grid_rescale: the input needs at least 2 x 2 nodes");
+  DBM_CHECK(out_h >= 1 && out_w >= 1, "dbm_grid_rescale: empty output");
+  DBM_CHECK(in_dev != nullptr && out_dev != nullptr, "dbm_grid_rescale: NULL input or output");
+  DBM_CHECK((const void*)in_dev != (const void*)out_dev, "dbm_grid_rescale: the output must not be the input");
+  RescaleLaunch a;
+  a.in = in_dev;
+  a.H = H; a.W = W; a.out_h = out_h; a.out_w = out_w;
+  a.order = order;
+  a.anti_aliasing = anti_aliasing != 0; a.clip = clip != 0; a.input_cast = input_cast != 0;
+  a.out = out_dev;
+  ctx->resample_tmp.ensure(2 * grid_rescale_workspace(a));   // (DevBuf counts floats)
+  a.ws = (double*)ctx->resample_tmp.p;
+  launch_grid_rescale(a, ctx->stream);
+  DBM_API_END
+}
+
+int dbm_grid_rolling_std(dbm_ctx* ctx, const float* in_dev, long H, long W, int window, float* out_dev) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_grid_rolling_std: NULL context");
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  DBM_CHECK(window >= 1 && window <= 63 && window % 2 == 1, "dbm_grid_rolling_std: the window must be odd, 1..63");
+  DBM_CHECK(H >= 1 && W >= 1, "dbm_grid_rolling_std: empty grid");
+  DBM_CHECK(in_dev != nullptr && out_dev != nullptr, "dbm_grid_rolling_std: NULL input or output");
+  DBM_CHECK((const void*)in_dev != (const void*)out_dev, "dbm_grid_rolling_std: the output must not be the input");
+  launch_rolling_std(in_dev, H, W, window, out_dev, ctx->stream);
   DBM_API_END
 }
 

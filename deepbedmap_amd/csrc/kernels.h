@@ -297,3 +297,21 @@ struct FilledLaunch {
 };
 void filled_windows_geometry(FilledLaunch& a);
 void launch_filled_windows(const FilledLaunch& a, hipStream_t s);
+
+// Rescaling a resident grid (resample.hip; dbm_grid_rescale): the float32 grid (H, W) -> out (out_h, out_w), the scipy.ndimage chain of
+// scikit-image's `rescale`: optional int32 cast, min / max for the clip, Gaussian per downscaled axis, cubic B-spline prefilter (order 3),
+// linear or cubic evaluation at (o + 0.5) in / out - 0.5, everything mirrored at the edges, float64 until the one final rounding.
+// ws: grid_rescale_workspace(a) doubles of scratch (two float64 planes unless order 1 runs unfiltered).
+struct RescaleLaunch {
+  const float* in;
+  long H, W, out_h, out_w;
+  int order, anti_aliasing, clip, input_cast;
+  float* out;
+  double* ws;
+};
+size_t grid_rescale_workspace(const RescaleLaunch& a);
+void launch_grid_rescale(const RescaleLaunch& a, hipStream_t s);
+
+// Rolling-window standard deviation (resample.hip; dbm_grid_rolling_std): population standard deviation of the non-NaN nodes of the
+// centred window x window neighbourhood cut at the edges (window odd, 1..63), NaN where there is none
+void launch_rolling_std(const float* in, long H, long W, int window, float* out, hipStream_t s);

@@ -91,6 +91,7 @@ struct dbm_ctx {
   DevBuf stage[8];            // host<->device staging for the non-DEVICE_PTRS entry points
   DevBuf track_tmp;           // dbm_grid_track: the workgroups' error moments and the folded statistics (doubles)
   DevBuf tile_tmp;            // dbm_grid_filled_windows: the row pass's byte plane
+  DevBuf resample_tmp;        // dbm_grid_rescale: min / max, Gaussian weights and the float64 planes (doubles)
 };
 
 void dbm_comm_unique_id_impl(void* out128);  // comm.hip: ncclGetUniqueId

@@ -295,6 +295,28 @@ int dbm_grid_tile(dbm_ctx* ctx, const float* grid_dev, long H, long W, const dou
 int dbm_grid_filled_windows(dbm_ctx* ctx, const float* grid_dev, long H, long W, int size, int step, int flip_rows, int flip_cols,
                             unsigned char* flags_dev);
 
+/* ---- comparison grids: the bicubic BEDMAP2 baseline and the synthetic grid at 250 m (deepbedmap.py:323-331, 348-356:
+ * `skimage.transform.rescale(image.astype(np.int32), scale, order, mode="reflect", anti_aliasing=True, preserve_range=True)`; again at
+ * paper_figures.py:893-917), whose track error is set against DeepBedMap's (deepbedmap.py:550-574, 622-626) ----
+ * The float32 grid (H, W) -> out_dev (out_h, out_w), both DEVICE pointers, asynchronous on the context's stream, by the scipy.ndimage
+ * chain that current scikit-image releases run for `rescale` (the caller computes out = round(scale * in)): with input_cast the values
+ * are truncated toward zero first (`.astype(np.int32)`); with anti_aliasing each axis with factor = in / out > 1 is filtered by
+ * gaussian_filter(sigma = (factor - 1) / 2, mode="mirror", truncate 4: radius int(4 sigma + 0.5)), axis 0 first; order 3 prefilters both
+ * axes (pole sqrt(3) - 2, gain 6, mirror start values); output node o samples the input coordinate (o + 0.5) in / out - 0.5 (zoom with
+ * grid_mode=True, mode="mirror") with linear (order 1) or cubic B-spline (order 3) weights; with clip the result is clamped to [min, max]
+ * of the (cast) input.  Float64 throughout, rounded to float32 once; the same bits from call to call.  NaN or infinite nodes are outside
+ * the contract (the recursive filter spreads them over rows and columns, as scipy's does).  The pinned scikit-image 0.15 of the reference
+ * interpolates differently.  Refused (status 1, nothing launched): order not 1 or 3, H or W < 2, out_h or out_w < 1, NULL
+ * pointers, out_dev == in_dev. */
+int dbm_grid_rescale(dbm_ctx* ctx, const float* in_dev, long H, long W, long out_h, long out_w, int order, int anti_aliasing, int clip,
+                     int input_cast, float* out_dev);
+/* `standard_deviation_2d(grid, window_length)` (paper_figures.py:847-867, used at :928-931 and sampled along a transect at :989-998):
+ * out_dev[r, c] (device) = the population standard deviation (ddof 0) of the non-NaN nodes of rows r - h .. r + h, columns c - h .. c + h
+ * (h = window / 2) that lie inside the grid, NaN where there is none; float64 sums of values shifted by one valid node of the window
+ * (a constant window gives exactly 0), rounded to float32 once.  Asynchronous.  Refused (status 1): window even or outside 1..63, H or
+ * W < 1, NULL pointers, out_dev == in_dev. */
+int dbm_grid_rolling_std(dbm_ctx* ctx, const float* in_dev, long H, long W, int window, float* out_dev);
+
 /* ---- optimizer ---- */
 /* chainer.optimizers.Adam(alpha, eps=1e-8).setup(model): srgan_train.py:1043-1048 */
 int dbm_adam_setup(dbm_model* m, double alpha, double beta1, double beta2, double eps);
@@ -325,7 +347,7 @@ int dbm_discriminator_step(dbm_model* g, dbm_model* d, int N, int H, int W, cons
  * (its bit 1); bit 2 (4) = consume the forward that step prefetched (its bit 2): the caller asserts that the five
  * arrays are the same, UNCHANGED, device arrays.  The library additionally checks pointers, shapes, the parameter
  * version and its own record of writes to device memory (dbm_memcpy_h2d, dbm_gather_rows, dbm_fill_f32,
- * dbm_memcpy2d_d2d, dbm_grid_tile, dbm_grid_filled_windows, dbm_malloc, dbm_free); writes by anybody else (another library filling the same buffer in
+ * dbm_memcpy2d_d2d, dbm_grid_tile, dbm_grid_filled_windows, dbm_grid_rescale, dbm_grid_rolling_std, dbm_malloc, dbm_free); writes by anybody else (another library filling the same buffer in
  * place) are invisible to it, hence the explicit bit.  Without it the prefetched pass is discarded and the forward is
  * recomputed.  bit 4 (16) = see dbm_discriminator_step. */
 int dbm_generator_step(dbm_model* g, dbm_model* d, int N, int H, int W, const float* X, const float* W1,
