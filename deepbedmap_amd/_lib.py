@@ -107,6 +107,10 @@ SIGNATURES = {
     "dbm_grid_filled_windows": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "dbm_grid_rescale": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "dbm_grid_rolling_std": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_void_p],
+    "dbm_points_polar_stereographic": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int],
+    "dbm_points_region": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int],
+    "dbm_points_blockmedian": [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_size_t,
+                               C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int],
     "dbm_adam_setup": [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double],
     "dbm_adam_update": [C.c_void_p, C.c_double],
     "dbm_discriminator_step": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -235,6 +235,7 @@ int dbm_shutdown(dbm_ctx* ctx) {
   ctx->loss_tmp.release();
   for (auto& b : ctx->stage) b.release();
   ctx->track_tmp.release();
+  ctx->points_tmp.release();
   ctx->tile_tmp.release();
   ctx->resample_tmp.release();
   (void)hipStreamSynchronize(ctx->side);
@@ -1068,6 +1069,143 @@ int dbm_grid_rolling_std(dbm_ctx* ctx, const float* in_dev, long H, long W, int 
   DBM_CHECK(in_dev != nullptr && out_dev != nullptr, "dbm_grid_rolling_std: NULL input or output");
   DBM_CHECK((const void*)in_dev != (const void*)out_dev, "dbm_grid_rolling_std: the output must not be the input");
   launch_rolling_std(in_dev, H, W, window, out_dev, ctx->stream);
+  DBM_API_END
+}
+
+// ---- gridding point clouds (points.hip) ----
+// table arguments of the dbm_points_* entry points without DBM_DEVICE_PTRS: staged in ctx->stage[k] (DevBuf counts floats)
+static double* points_stage(dbm_ctx* ctx, int k, size_t doubles) {
+  ctx->stage[k].ensure(2 * (doubles > 0 ? doubles : 1));
+  return (double*)ctx->stage[k].p;
+}
+
+int dbm_points_polar_stereographic(dbm_ctx* ctx, const double* points_in, size_t n, int ncol, const double proj[6], double* points_out,
+                                   int flags) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && proj != nullptr, "dbm_points_polar_stereographic: NULL argument");
+  DBM_CHECK(ncol >= 2, "dbm_points_polar_stereographic: a table has at least 2 columns (longitude, latitude)");
+  DBM_CHECK(n < ((size_t)1 << 31), "dbm_points_polar_stereographic: n must stay below 2^31");
+  DBM_CHECK(std::isfinite(proj[0]) && proj[0] > 0.0 && std::isfinite(proj[1]) && proj[1] > 1.0,
+            "dbm_points_polar_stereographic: the semi-major axis must be positive and the inverse flattening above 1");
+  DBM_CHECK(proj[2] >= -90.0 && proj[2] < 0.0, "dbm_points_polar_stereographic: the latitude of true scale must lie in [-90, 0) (south-pole case)");
+  DBM_CHECK(std::isfinite(proj[3]) && std::isfinite(proj[4]) && std::isfinite(proj[5]),
+            "dbm_points_polar_stereographic: longitude of origin, false easting and false northing must be finite");
+  DBM_CHECK(n == 0 || (points_in != nullptr && points_out != nullptr), "dbm_points_polar_stereographic: NULL table");
+  if (n == 0) return 0;
+  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
+  const double rad = 3.14159265358979323846 / 180.0;
+  const double f = 1.0 / proj[1], e = std::sqrt(2.0 * f - f * f);
+  const double cc = std::sqrt(std::pow(1.0 + e, 1.0 + e) * std::pow(1.0 - e, 1.0 - e));
+  const double sf = std::sin(proj[2] * rad), esf = e * sf;
+  const double tf = std::tan((45.0 + 0.5 * proj[2]) * rad) / std::pow((1.0 + esf) / (1.0 - esf), 0.5 * e);
+  const double mf = std::cos(proj[2] * rad) / std::sqrt(1.0 - e * e * sf * sf);
+  // phi_F = -90: m_F = t_F = 0 and the scale at the pole is taken as 1 (variant A with k0 = 1)
+  const double k0 = proj[2] == -90.0 ? 1.0 : mf * cc / (2.0 * tf);
+  ProjLaunch a;
+  a.n = (long)n;
+  a.ncol = ncol;
+  a.e = e;
+  a.half_e = 0.5 * e;
+  a.scale = 2.0 * proj[0] * k0 / cc;
+  a.lon0 = proj[3] * rad;
+  a.fe = proj[4];
+  a.fn = proj[5];
+  if (dev) {
+    ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+    a.in = points_in;
+    a.out = points_out;
+  } else {
+    double* st = points_stage(ctx, 0, n * (size_t)ncol);
+    DBM_HIP(hipMemcpyAsync(st, points_in, n * ncol * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    a.in = a.out = st;
+  }
+  launch_points_project(a, ctx->stream);
+  if (!dev) {
+    DBM_HIP(hipMemcpyAsync(points_out, a.out, n * ncol * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  DBM_API_END
+}
+
+int dbm_points_region(dbm_ctx* ctx, const double* points, size_t n, int ncol, double increment, double* region_out, int64_t* count_out,
+                      int flags) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && region_out != nullptr && count_out != nullptr, "dbm_points_region: NULL argument");
+  DBM_CHECK(ncol >= 2, "dbm_points_region: a table has at least 2 columns (x, y)");
+  DBM_CHECK(n < ((size_t)1 << 31), "dbm_points_region: n must stay below 2^31");
+  DBM_CHECK(std::isfinite(increment) && increment > 0.0, "dbm_points_region: the increment must be positive and finite");
+  DBM_CHECK(n == 0 || points != nullptr, "dbm_points_region: NULL table");
+  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
+  const size_t ws = points_region_workspace((long)n);
+  ctx->points_tmp.ensure((ws + 64) / 4);
+  char* scratch = (char*)ctx->points_tmp.p;
+  double* dregion = dev ? region_out : (double*)(scratch + ws);
+  long long* dcount = dev ? (long long*)count_out : (long long*)(scratch + ws + 32);
+  const double* dpts = points;
+  if (!dev && n > 0) {
+    double* st = points_stage(ctx, 0, n * (size_t)ncol);
+    DBM_HIP(hipMemcpyAsync(st, points, n * ncol * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    dpts = st;
+  }
+  if (dev) ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  launch_points_region(dpts, (long)n, ncol, increment, scratch, dregion, dcount, ctx->stream);
+  if (!dev) {
+    DBM_HIP(hipMemcpyAsync(region_out, dregion, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipMemcpyAsync(count_out, dcount, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  DBM_API_END
+}
+
+int dbm_points_blockmedian(dbm_ctx* ctx, const double* points, size_t n, const double region[4], double spacing, double* table_out,
+                           size_t table_capacity, int64_t* n_blocks_out, float* grid_dev, int* counts_dev, int flags) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && region != nullptr && n_blocks_out != nullptr, "dbm_points_blockmedian: NULL argument");
+  DBM_CHECK(n < ((size_t)1 << 31), "dbm_points_blockmedian: n must stay below 2^31");
+  DBM_CHECK(std::isfinite(spacing) && spacing > 0.0, "dbm_points_blockmedian: the spacing must be positive and finite");
+  DBM_CHECK(std::isfinite(region[0]) && std::isfinite(region[1]) && std::isfinite(region[2]) && std::isfinite(region[3]) &&
+                region[1] >= region[0] && region[3] >= region[2], "dbm_points_blockmedian: the region must be finite with max >= min");
+  const double wd = (region[1] - region[0]) / spacing, hd = (region[3] - region[2]) / spacing;
+  DBM_CHECK(wd < 2147483647.0 && hd < 2147483647.0, "dbm_points_blockmedian: H W must stay below 2^31 blocks");
+  const long W = (long)std::llrint(wd) + 1, H = (long)std::llrint(hd) + 1;
+  DBM_CHECK(H * W < (1L << 31), "dbm_points_blockmedian: H W must stay below 2^31 blocks");
+  DBM_CHECK(n == 0 || points != nullptr, "dbm_points_blockmedian: NULL table");
+  DBM_CHECK(table_capacity == 0 || table_out != nullptr, "dbm_points_blockmedian: NULL table_out");
+  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
+  BlockMedianLaunch a;
+  a.n = (long)n;
+  a.H = H;
+  a.W = W;
+  a.xmin = region[0];
+  // the north edge fitted to the increment (+e): the region's own ymax when the spacing divides the region, else ymin + (H - 1) inc
+  const double span = (double)(H - 1) * spacing;
+  a.ymax = span == region[3] - region[2] ? region[3] : region[2] + span;
+  a.inc = spacing;
+  ctx->points_tmp.ensure((blockmedian_workspace(a.n, H * W) + 3) / 4);
+  blockmedian_carve(a, ctx->points_tmp.p);
+  a.points = points;
+  if (!dev && n > 0) {
+    double* st = points_stage(ctx, 0, 3 * n);
+    DBM_HIP(hipMemcpyAsync(st, points, 3 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    a.points = st;
+  }
+  launch_blockmedian_count(a, ctx->stream);
+  unsigned totals[1 + DBM_BLOCKMEDIAN_CLASSES];
+  DBM_HIP(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  const size_t m = totals[0];
+  DBM_CHECK(m <= table_capacity, "dbm_points_blockmedian: the table holds " + std::to_string(table_capacity) + " rows, " +
+                                     std::to_string(m) + " blocks are not empty; nothing was written");
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  a.table = dev ? table_out : points_stage(ctx, 1, 3 * m);
+  a.grid = grid_dev;
+  a.counts = counts_dev;
+  launch_blockmedian_select(a, totals, ctx->stream);
+  *n_blocks_out = (int64_t)m;
+  if (!dev) {
+    if (m > 0) DBM_HIP(hipMemcpyAsync(table_out, a.table, 3 * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));
+  }
   DBM_API_END
 }
 

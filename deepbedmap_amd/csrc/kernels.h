@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdlib>
 #include "dbm_internal.h"
+#include "../../include/dbm.h"   // the block-median size classes are part of the ABI
 
 struct SmallConvDesc {
   const float* x; long xsn; int Cin, Hin, Win;
@@ -315,3 +316,42 @@ void launch_grid_rescale(const RescaleLaunch& a, hipStream_t s);
 // Rolling-window standard deviation (resample.hip; dbm_grid_rolling_std): population standard deviation of the non-NaN nodes of the
 // centred window x window neighbourhood cut at the edges (window odd, 1..63), NaN where there is none
 void launch_rolling_std(const float* in, long H, long W, int window, float* out, hipStream_t s);
+
+// Survey point clouds (points.hip; dbm_points_polar_stereographic, dbm_points_region, dbm_points_blockmedian): float64 tables (n, ncol)
+// Polar stereographic, variant B, south-pole case: columns 0, 1 (longitude, latitude in degrees) -> (easting, northing), the rest copied;
+// e = eccentricity, half_e = e / 2, scale = 2 a k0 / sqrt((1+e)^(1+e) (1-e)^(1-e)), lon0 in radians (host, float64); out may be in
+struct ProjLaunch {
+  const double* in;
+  double* out;
+  long n;
+  int ncol;
+  double e, half_e, scale, lon0, fe, fn;
+};
+void launch_points_project(const ProjLaunch& a, hipStream_t s);
+// region[4] = {floor(xmin / inc) inc, ceil(xmax / inc) inc, floor(ymin / inc) inc, ceil(ymax / inc) inc} over the rows whose x, y[, z] are
+// finite, *count = their number (none: four NaNs, 0); ws: points_region_workspace(n) bytes
+size_t points_region_workspace(long n);
+void launch_points_region(const double* pts, long n, int ncol, double inc, void* ws, double* region, long long* count, hipStream_t s);
+// Block medians of (n, 3) rows on the H x W gridline-registered blocks of spacing inc whose north-west node is (xmin, ymax).  Two phases
+// with a host read of totals between them: _count fills blk, cnt, off, rowof, the size classes' lists and totals = {non-empty blocks,
+// blocks per class}; _select writes table (3 doubles per non-empty block, block-index order), grid and counts (H W each, may be null).
+struct BlockMedianLaunch {
+  const double* points;
+  long n, H, W;
+  double xmin, ymax, inc;
+  int* blk;            // n: block of each row or -1
+  unsigned* perm;      // n: rows, block-contiguous
+  unsigned* cnt;       // H W: histogram (counted down to zero by the scatter)
+  unsigned* rowof;     // H W: table row of a non-empty block
+  unsigned* off;       // H W + 1: first place of each block in perm
+  uint2* part;         // per scan tile: (points, non-empty blocks) before it
+  unsigned* totals;    // 1 + DBM_BLOCKMEDIAN_CLASSES
+  unsigned* lists[DBM_BLOCKMEDIAN_CLASSES];
+  double* table;
+  float* grid;
+  int* counts;
+};
+size_t blockmedian_workspace(long n, long hw);   // bytes
+void blockmedian_carve(BlockMedianLaunch& a, void* ws);
+void launch_blockmedian_count(const BlockMedianLaunch& a, hipStream_t s);
+void launch_blockmedian_select(const BlockMedianLaunch& a, const unsigned* totals, hipStream_t s);

@@ -92,6 +92,7 @@ struct dbm_ctx {
   DevBuf track_tmp;           // dbm_grid_track: the workgroups' error moments and the folded statistics (doubles)
   DevBuf tile_tmp;            // dbm_grid_filled_windows: the row pass's byte plane
   DevBuf resample_tmp;        // dbm_grid_rescale: min / max, Gaussian weights and the float64 planes (doubles)
+  DevBuf points_tmp;          // dbm_points_region: the workgroups' boxes; dbm_points_blockmedian: block indices, histogram, scan, lists
 };
 
 void dbm_comm_unique_id_impl(void* out128);  // comm.hip: ncclGetUniqueId

@@ -1,0 +1,245 @@
+"""From a survey's point cloud to the `points` table and the 250 m ground-truth raster (reference data_prep.py:322-334, 353-378,
+406-407).
+
+The reference reprojects longitude / latitude with pyproj (`filters.reprojection` of ascii_to_xyz), takes the cloud's bounding box
+with `gmt info -I` (get_region) and thins the cloud with `gmt.blockmedian` before gridding it (xyz_to_grid).  Those three passes over
+the largest tables of the workflow -- tens of millions of float64 rows per survey -- run here on the GPU (dbm_points_polar_stereographic,
+dbm_points_region, dbm_points_blockmedian, include/dbm.h); what they produce is what `grdtrack`, `DevicePoints`, `make_test_area_score`
+(the table) and `Raster`, `tile_training_set` (the raster) take.  Semantics, the tie rule and what is unverified against GMT: DESIGN.md
+"Gridding point clouds".  NOT built: GMT `surface`, `gmt info -Is<inc>`, the CSV reading of ascii_to_xyz, `grdsample -T`.  No CPU
+fallback: without a GPU every call that computes raises DbmError.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .evaluation import DevicePoints, GridGeometry
+from .srgan import DeviceArray
+
+# EPSG method 9829 parameters {a, 1/f, latitude of true scale, longitude of origin, false easting, false northing}
+EPSG3031 = (6378137.0, 298.257223563, -71.0, 0.0, 0.0, 0.0)
+_SRS_PAIRS = {("EPSG:4326", "EPSG:3031"): EPSG3031}
+
+# include/dbm.h: threads per workgroup of the point passes; the largest block population of each size class of the block medians'
+# selection, in ascending order (8 lanes, 32 lanes, a wavefront, a workgroup sorting in LDS; larger blocks: selection out of global
+# memory).  tests/test_gridding_host.py holds them to the header.
+POINTS_THREADS = 256
+BLOCKMEDIAN_SUB8 = 8
+BLOCKMEDIAN_SUB32 = 32
+BLOCKMEDIAN_WAVE = 64
+BLOCKMEDIAN_LDS = 2048
+BLOCKMEDIAN_CLASS_BOUNDARIES = (BLOCKMEDIAN_SUB8, BLOCKMEDIAN_SUB32, BLOCKMEDIAN_WAVE, BLOCKMEDIAN_LDS)
+
+
+def _table(points, ncols, what):
+    """float64 C-contiguous (n, ncol) from an array or a DataFrame with columns x, y[, z] (no pandas import)"""
+    if hasattr(points, "columns"):
+        cols = ["x", "y", "z"] if "z" in points.columns else ["x", "y"]
+        points = points[cols].to_numpy()
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 2 or not ncols(pts.shape[1]):
+        raise ValueError(f"{what}; got shape {pts.shape}")
+    return pts
+
+
+def _like(points, values):
+    """`values` (n, ncol) as the kind of object `points` is: a DataFrame keeps its index and its other columns"""
+    if hasattr(points, "columns"):
+        out = points.copy()
+        for k, name in enumerate(["x", "y", "z"][:values.shape[1]]):
+            out[name] = values[:, k]
+        return out
+    return values
+
+
+def _fmt(v):
+    """a coordinate as GMT prints it (%.16g, negative zero as 0)"""
+    return format(float(v) + 0.0, ".16g")
+
+
+def parse_region(region):
+    """'xmin/xmax/ymin/ymax' or a 4-sequence -> (xmin, xmax, ymin, ymax) floats; finite, max >= min"""
+    if isinstance(region, str):
+        parts = region.strip().split("/")
+        if len(parts) != 4:
+            raise ValueError(f"region must be 'xmin/xmax/ymin/ymax', got {region!r}")
+        try:
+            vals = tuple(float(p) for p in parts)
+        except ValueError:
+            raise ValueError(f"region must be 'xmin/xmax/ymin/ymax' with four numbers, got {region!r}") from None
+    else:
+        try:
+            vals = tuple(float(v) for v in region)
+        except (TypeError, ValueError):
+            raise ValueError(f"region must be a string or four numbers, got {region!r}") from None
+        if len(vals) != 4:
+            raise ValueError(f"region must hold four numbers, got {len(vals)}")
+    if not all(np.isfinite(v) for v in vals):
+        raise ValueError(f"region must be finite, got {region!r}")
+    if vals[1] < vals[0] or vals[3] < vals[2]:
+        raise ValueError(f"region must have xmax >= xmin and ymax >= ymin, got {region!r}")
+    return vals
+
+
+def _spacing(spacing):
+    try:
+        s = float(spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"the spacing must be a positive number, got {spacing!r}") from None
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError(f"the spacing must be positive and finite, got {spacing!r}")
+    return s
+
+
+def block_shape(region, spacing):
+    """(H, W) of the gridline-registered blocks of `spacing` over `region`, the north / east edge fitted to the spacing (GMT's `+e`):
+    round((max - min) / spacing) + 1 per axis"""
+    xmin, xmax, ymin, ymax = parse_region(region)
+    s = _spacing(spacing)
+    H, W = int(np.rint((ymax - ymin) / s)) + 1, int(np.rint((xmax - xmin) / s)) + 1
+    if H * W >= 2 ** 31:
+        raise ValueError(f"{H} x {W} blocks: the grid must stay below 2^31 blocks")
+    return H, W
+
+
+def block_geometry(region, spacing):
+    """GridGeometry of the block raster: node (0, 0) is the north-west node (xmin, ymax), rows run south"""
+    xmin, _, ymin, ymax = parse_region(region)
+    s = _spacing(spacing)
+    H, _ = block_shape(region, spacing)
+    span = float(H - 1) * s
+    return GridGeometry(x0=xmin, y0=ymax if span == ymax - ymin else ymin + span, dx=s, dy=-s, registration="gridline")
+
+
+def reproject(points, in_srs="EPSG:4326", out_srs="EPSG:3031", ctx=None):
+    """The `filters.reprojection` step of ascii_to_xyz (data_prep.py:322-334): columns x, y = longitude, latitude in degrees become
+    easting, northing in metres (polar stereographic, EPSG method 9829 variant B, south-pole case); further columns are kept.  Only
+    EPSG:4326 -> EPSG:3031 is supported.  Returns the kind of object it was given: array -> array, DataFrame -> DataFrame; a DevicePoints
+    is converted IN PLACE and returned.  A latitude outside [-90, 0] is refused with ValueError before anything is converted (a resident
+    table is inspected on the device, over its rows whose x, y[, z] are all finite: the rows every later stage keeps)."""
+    key = (str(in_srs).upper(), str(out_srs).upper())
+    if key not in _SRS_PAIRS:
+        raise ValueError(f"reproject: only {sorted(_SRS_PAIRS)} are supported, got {in_srs!r} -> {out_srs!r}")
+    proj = np.array(_SRS_PAIRS[key], dtype=np.float64)
+    lib_args = (proj.ctypes.data_as(C.POINTER(C.c_double)),)
+    if isinstance(points, DevicePoints):
+        # the latitudes' range, on the device: with an increment of 2^-20 degrees (-90 is a multiple) the outward rounding of
+        # dbm_points_region moves ymin below -90 iff a latitude lies below it and ymax above 0 iff a latitude lies above it
+        (_, _, lat_lo, lat_hi), count = region_of(points, 2.0 ** -20)
+        if count and (lat_lo < -90.0 or lat_hi > 0.0):
+            raise ValueError("reproject: latitudes must lie in [-90, 0] (the south-pole case of the polar stereographic projection)")
+        _lib.check(_lib.lib().dbm_points_polar_stereographic(points.ctx.handle, C.c_void_p(points.ptr), points.n, points.ncol, *lib_args,
+                                                             C.c_void_p(points.ptr), _lib.DEVICE_PTRS), points.ctx.handle)
+        return points
+    pts = _table(points, lambda c: c >= 2, "reproject: points must be (n, >= 2) longitude, latitude[, ...]")
+    lat = pts[:, 1]
+    if np.any(lat[np.isfinite(lat)] > 0.0) or np.any(lat[np.isfinite(lat)] < -90.0):
+        raise ValueError("reproject: latitudes must lie in [-90, 0] (the south-pole case of the polar stereographic projection)")
+    ctx = ctx or _lib.default_context()
+    out = np.empty_like(pts)
+    _lib.check(_lib.lib().dbm_points_polar_stereographic(ctx.handle, pts.ctypes.data_as(C.c_void_p), pts.shape[0], pts.shape[1], *lib_args,
+                                                         out.ctypes.data_as(C.c_void_p), 0), ctx.handle)
+    return _like(points, out)
+
+
+def region_of(xyz_data, round_increment=250, ctx=None):
+    """((xmin, xmax, ymin, ymax) moved outward to multiples of round_increment, number of rows with finite x, y[, z]); four NaNs and 0
+    without such a row"""
+    inc = _spacing(round_increment)
+    region, count = np.empty(4, dtype=np.float64), C.c_int64(0)
+    if isinstance(xyz_data, DevicePoints):
+        ctx = xyz_data.ctx
+        out = ctx.malloc(64)
+        try:
+            _lib.check(_lib.lib().dbm_points_region(ctx.handle, C.c_void_p(xyz_data.ptr), xyz_data.n, xyz_data.ncol, inc, C.c_void_p(out),
+                                                    C.c_void_p(out + 32), _lib.DEVICE_PTRS), ctx.handle)
+            host = np.empty(5, dtype=np.float64)
+            _lib.check(_lib.lib().dbm_memcpy_d2h(ctx.handle, host.ctypes.data_as(C.c_void_p), C.c_void_p(out), 40), ctx.handle)
+        finally:
+            ctx.free(out)
+        return tuple(float(v) for v in host[:4]), int(host[4:].view(np.int64)[0])
+    pts = _table(xyz_data, lambda c: c >= 2, "get_region: the table must be (n, >= 2) x, y[, z]")
+    ctx = ctx or _lib.default_context()
+    _lib.check(_lib.lib().dbm_points_region(ctx.handle, pts.ctypes.data_as(C.c_void_p), pts.shape[0], pts.shape[1], inc,
+                                            region.ctypes.data_as(C.c_void_p), C.byref(count), 0), ctx.handle)
+    return tuple(float(v) for v in region), int(count.value)
+
+
+def get_region(xyz_data, round_increment=250, ctx=None):
+    """get_region (data_prep.py:353-378) as `gmt info -I<inc>` answers it -- NOT `-Is<inc>`, the variant the reference calls, which
+    widens the box further to dimensions that suit GMT surface (not built; it only ever widens): the bounding box of the rows with
+    finite x, y and z moved outward to multiples of round_increment, as the string 'xmin/xmax/ymin/ymax' that GMT prints and -R takes.
+    xyz_data: array, DataFrame with columns x, y, z, or DevicePoints."""
+    region, count = region_of(xyz_data, round_increment, ctx)
+    if count == 0:
+        raise ValueError("get_region: the table has no row with finite coordinates")
+    return "/".join(_fmt(v) for v in region)
+
+
+def _blockmedian(table, region, spacing, want_grid, want_counts, ctx):
+    """(table (m, 3), grid DeviceArray or None, counts int32 (H, W) or None, geometry)"""
+    r4 = np.array(parse_region(region), dtype=np.float64)
+    s = _spacing(spacing)
+    H, W = block_shape(r4, s)
+    geometry = block_geometry(r4, s)
+    if isinstance(table, DevicePoints):
+        if table.ncol != 3:
+            raise ValueError(f"blockmedian: the table must be (n, 3) x, y, z; got {table.ncol} columns")
+        ctx, n, pts = table.ctx, table.n, None
+    else:
+        pts = _table(table, lambda c: c == 3, "blockmedian: the table must be (n, 3) x, y, z")
+        ctx, n = ctx or _lib.default_context(), pts.shape[0]
+    lib = _lib.lib()
+    grid = DeviceArray((H, W), ctx) if want_grid else None
+    cdev = ctx.malloc(4 * H * W) if want_counts else None
+    cap = max(min(n, H * W), 1)
+    m = C.c_int64(0)
+    try:
+        args = (r4.ctypes.data_as(C.POINTER(C.c_double)), s)
+        tail = (cap, C.byref(m), C.c_void_p(grid.ptr) if grid is not None else None, C.c_void_p(cdev) if cdev else None)
+        if pts is None:
+            tdev = ctx.malloc(24 * cap)
+            try:
+                _lib.check(lib.dbm_points_blockmedian(ctx.handle, C.c_void_p(table.ptr), n, *args, C.c_void_p(tdev), *tail, _lib.DEVICE_PTRS),
+                           ctx.handle)
+                out = np.empty((int(m.value), 3), dtype=np.float64)
+                if out.size:
+                    _lib.check(lib.dbm_memcpy_d2h(ctx.handle, out.ctypes.data_as(C.c_void_p), C.c_void_p(tdev), out.nbytes), ctx.handle)
+            finally:
+                ctx.free(tdev)
+        else:
+            out = np.empty((cap, 3), dtype=np.float64)
+            _lib.check(lib.dbm_points_blockmedian(ctx.handle, pts.ctypes.data_as(C.c_void_p), n, *args, out.ctypes.data_as(C.c_void_p), *tail, 0),
+                       ctx.handle)
+            out = out[:int(m.value)].copy()
+        counts = None
+        if cdev:
+            counts = np.empty((H, W), dtype=np.int32)
+            _lib.check(lib.dbm_memcpy_d2h(ctx.handle, counts.ctypes.data_as(C.c_void_p), C.c_void_p(cdev), counts.nbytes), ctx.handle)
+    finally:
+        if cdev:
+            ctx.free(cdev)
+    if grid is not None:
+        grid._gen += 1
+    return out, grid, counts, geometry
+
+
+def blockmedian(table, region, spacing=250, ctx=None):
+    """`gmt.blockmedian(table=table, region=region, spacing=f"{spacing}+e")` (data_prep.py:406-407): per non-empty block of the
+    gridline-registered grid over `region` the medians of x, of y and of z, in the order blockmedian prints (north row first, west to
+    east).  table: (n, 3) array, DataFrame with columns x, y, z, or DevicePoints; region: 'xmin/xmax/ymin/ymax' or four numbers.
+    Returns (m, 3) float64, or a DataFrame with columns x, y, z if given one."""
+    out, _, _, _ = _blockmedian(table, region, spacing, False, False, ctx)
+    if hasattr(table, "columns"):
+        return type(table)({"x": out[:, 0], "y": out[:, 1], "z": out[:, 2]})
+    return out
+
+
+def blockmedian_grid(points, region, spacing=250, counts=False, download=True, ctx=None):
+    """The block medians of z as a raster: (grid (H, W) float32 with NaN in empty blocks, GridGeometry[, counts (H, W) int32]).  With
+    download=False the grid is a DeviceArray, used in place by `Raster`, `grdtrack` and `standard_deviation_2d`.  This is the cloud
+    binned, NOT interpolated: GMT `surface` is not built."""
+    _, grid, cnt, geometry = _blockmedian(points, region, spacing, True, bool(counts), ctx)
+    g = grid.get() if download else grid
+    return (g, geometry, cnt) if counts else (g, geometry)

@@ -54,6 +54,17 @@ enum {
                           conv_layer5 of the trunk in another order) */
 };
 enum { DBM_KIND_PARAM = 0, DBM_KIND_PERSISTENT = 1 };
+/* dbm_points_*: threads per workgroup of the point passes, and the largest block population of each size class of the block
+ * medians' selection (points.hip: 8 lanes, 32 lanes, one wavefront, one workgroup sorting in LDS; anything larger is selected
+ * out of global memory).  Constants of the sources, listed here so that tests can build clouds on both sides of every boundary. */
+enum {
+  DBM_POINTS_THREADS = 256,
+  DBM_BLOCKMEDIAN_SUB8 = 8,
+  DBM_BLOCKMEDIAN_SUB32 = 32,
+  DBM_BLOCKMEDIAN_WAVE = 64,
+  DBM_BLOCKMEDIAN_LDS = 2048,
+  DBM_BLOCKMEDIAN_CLASSES = 5
+};
 
 /* ---- context ---- */
 int dbm_init(int hip_device, dbm_ctx** out);      /* replaces model.to_gpu(): srgan_train.py:1038-1040, deepbedmap.py:659 */
@@ -316,6 +327,53 @@ int dbm_grid_rescale(dbm_ctx* ctx, const float* in_dev, long H, long W, long out
  * (a constant window gives exactly 0), rounded to float32 once.  Asynchronous.  Refused (status 1): window even or outside 1..63, H or
  * W < 1, NULL pointers, out_dev == in_dev. */
 int dbm_grid_rolling_std(dbm_ctx* ctx, const float* in_dev, long H, long W, int window, float* out_dev);
+
+/* ---- gridding: survey point clouds -> the `points` table and the 250 m ground-truth raster (data_prep.py:322-334 the
+ * `filters.reprojection` step of ascii_to_xyz; :353-378 get_region; :406-407 the `gmt.blockmedian` preprocessing of xyz_to_grid) ----
+ * Point tables are C-contiguous float64 (n, ncol), as dbm_grid_track takes them; all arithmetic is float64.  flags: DBM_DEVICE_PTRS =
+ * the table arguments are device pointers; otherwise host pointers, staged, and the call synchronises.  NOT built: GMT
+ * `surface`, `gmt info -Is<inc>` (the surface-friendly widening), the CSV reading of ascii_to_xyz, `grdsample -T`.
+ *
+ * dbm_points_polar_stereographic (data_prep.py:322-334, what pyproj's EPSG:4326 -> EPSG:3031 transformer computes): EPSG method 9829
+ * (Polar Stereographic, variant B), south-pole case, Guidance Note 7-2.  Columns 0 and 1 -- longitude, latitude in degrees -- become
+ * easting, northing in metres; columns 2.. are copied unchanged.  proj = {a, 1/f, latitude of true scale (degrees, < 0), longitude of
+ * origin (degrees), false easting, false northing}; EPSG:3031 is {6378137, 298.257223563, -71, 0, 0, 0}.  With e^2 = 2f - f^2,
+ * C = sqrt((1+e)^(1+e) (1-e)^(1-e)): t = tan(pi/4 + phi/2) / ((1 + e sin phi) / (1 - e sin phi))^(e/2), m_F = cos phi_F /
+ * sqrt(1 - e^2 sin^2 phi_F), k0 = m_F C / (2 t_F), rho = 2 a k0 t / C, E = FE + rho sin(lambda - lambda0), N = FN + rho cos(lambda -
+ * lambda0); the constants are computed once on the host.  A non-finite longitude or latitude gives NaN for both outputs.  Latitudes are
+ * NOT range-checked here (the southern variant holds for [-90, 0]; the Python layer refuses anything else).  points_out may be points_in
+ * (in place).  Asynchronous with DBM_DEVICE_PTRS.  Refused (status 1, nothing launched or written): ncol < 2, n >= 2^31, a, 1/f not
+ * finite or a <= 0 or 1/f <= 1, a latitude of true scale outside [-90, 0), other parameters not finite, NULL tables with n > 0.
+ *
+ * dbm_points_region (data_prep.py:353-378 with `gmt info -I<inc>`, NOT `-Is<inc>`): over the rows whose x, y (and z, if ncol >= 3) are
+ * all finite, region_out = {floor(xmin / inc) inc, ceil(xmax / inc) inc, floor(ymin / inc) inc, ceil(ymax / inc) inc} and *count_out =
+ * the number of such rows (int64); none: four NaNs and 0.  No float atomics, the launch depends on n only: the same bits from call to
+ * call.  With DBM_DEVICE_PTRS points, region_out and count_out are device pointers (asynchronous).  Refused (status 1, nothing
+ * written): ncol < 2, n >= 2^31, an increment that is not positive and finite, NULL outputs, a NULL table with n > 0.
+ *
+ * dbm_points_blockmedian (data_prep.py:406-407, `gmt.blockmedian(table, region, spacing="<inc>+e")`, GMT's defaults: gridline
+ * registration, no -Q): points is (n, 3) x, y, z.  Grid: region = {xmin, xmax, ymin, ymax}, W = llrint((xmax - xmin) / inc) + 1,
+ * H = llrint((ymax - ymin) / inc) + 1 blocks centred on nodes (the north / east edge fitted to the increment, `+e`), row 0 the NORTH
+ * row: GridGeometry(x0 = xmin, y0 = ymax, dx = inc, dy = -inc, gridline).  A row with a non-finite x, y or z is dropped
+ * (data_prep.py:304); col = floor((x - xmin) / inc + 0.5), row = floor((ymax - y) / inc + 0.5) in float64, IEEE division, no fused
+ * multiply-add; the point is used iff 0 <= col < W and 0 <= row < H (so points up to half a block outside the region count); a
+ * coordinate exactly on a block boundary goes to the eastern / southern block (this project's choice).  Per non-empty block: the medians
+ * of x, of y and of z, each on its own; k values: the middle one, or 0.5 (lo + hi) of the two middle ones, in the total order that puts
+ * -0.0 before +0.0.  table_out (table_capacity rows of 3 doubles; host or, with DBM_DEVICE_PTRS, device) receives the m non-empty
+ * blocks in block-index order (north row first, west to east: the order blockmedian prints); *n_blocks_out (ALWAYS a host pointer)
+ * = m.  grid_dev (H W float32, ALWAYS device, may be NULL): median z rounded to float32 once, NaN in empty blocks; counts_dev (H W
+ * int32, ALWAYS device, may be NULL): points per block.  Every output is a function of the multiset of rows: the same bytes from call to
+ * call and under any permutation of the rows (integer atomics for the histogram and the placement only, no float atomics).  The call
+ * reads m back before it writes anything, so it synchronises the context's stream once even with DBM_DEVICE_PTRS.  min(n, H W) rows
+ * of capacity always suffice.  Refused (status 1, no output written): n >= 2^31, H W >= 2^31, a spacing that is not positive and
+ * finite, a region that is not finite or has max < min, NULL region / n_blocks_out / table_out (with capacity > 0) / points (n > 0),
+ * table_capacity < m. */
+int dbm_points_polar_stereographic(dbm_ctx* ctx, const double* points_in, size_t n, int ncol, const double proj[6], double* points_out,
+                                   int flags);
+int dbm_points_region(dbm_ctx* ctx, const double* points, size_t n, int ncol, double increment, double* region_out, int64_t* count_out,
+                      int flags);
+int dbm_points_blockmedian(dbm_ctx* ctx, const double* points, size_t n, const double region[4], double spacing, double* table_out,
+                           size_t table_capacity, int64_t* n_blocks_out, float* grid_dev, int* counts_dev, int flags);
 
 /* ---- optimizer ---- */
 /* chainer.optimizers.Adam(alpha, eps=1e-8).setup(model): srgan_train.py:1043-1048 */
