@@ -1624,14 +1624,15 @@ int dbm_train_iteration(dbm_model* gm, dbm_model* dm, int N, int H, int W, const
 }
 
 // ---- op-level entry points ----
-static IgLayer make_temp_layer(dbm_ctx* ctx, const float* w, int O, int C, int k, int stride, int pad, dbm_model& holder) {
-  // a throw-away single-layer "model" whose param arena aliases the caller's weights
+static IgLayer make_temp_layer(dbm_ctx* ctx, const float* w, int O, int C, int k, int stride, int pad, dbm_model& holder, bool bias = true,
+                               bool as_1x1 = false) {
+  // a throw-away single-layer "model" whose param arena holds a copy of the caller's weights
   holder.ctx = ctx;
   holder.add_tensor("op/W", {O, C, k, k}, DBM_KIND_PARAM);
   holder.add_tensor("op/b", {O}, DBM_KIND_PARAM);
   holder.alloc_arenas();
   DBM_HIP(hipMemcpyAsync(holder.params, w, sizeof(float) * (size_t)O * C * k * k, hipMemcpyDeviceToDevice, ctx->stream));
-  holder.add_iglayer("op", O, C, k, stride, pad, true);
+  holder.add_iglayer("op", O, C, k, stride, pad, bias, as_1x1);
   holder.ensure_packed();
   return holder.layers[0];
 }
@@ -1687,12 +1688,8 @@ int dbm_op_conv2d_backward(dbm_ctx* ctx, const float* x, const float* w, const f
       launch_wgrad(wd, ctx->stream);
     }
     if (gx) {
-      ConvDesc d;
-      memset(&d, 0, sizeof(d));
-      d.x = gy; d.xsn = (long)O * OH * OW; d.N = N;
-      d.y = gx; d.ysn = (long)C * Hl * Wl; d.s1 = 1.f; d.s2 = 1.f;
       holder.ensure_packed_bwd();
-      holder.run_dgrad(L, d, Hl, Wl);  // gradient w.r.t. the (upsampled) conv input
+      holder.run_dgrad(L, dbm_model::dgrad_desc(gy, (long)O * OH * OW, gx, (long)C * Hl * Wl, N), Hl, Wl);  // gradient w.r.t. the (upsampled) conv input
     }
     DBM_HIP(hipStreamSynchronize(ctx->stream));
   }
@@ -1709,7 +1706,7 @@ int dbm_op_conv2d_cl16(dbm_ctx* ctx, const float* x, const float* w, const float
   hipStream_t s = ctx->stream;
   const int plane = H * W;
   const size_t P = (size_t)N * plane;
-  DevBuf act, res, out, wimg, bias;
+  ScopedBuf act, res, out, wimg, bias;
   act.ensure(P * C / 2 + 8);
   out.ensure(P * 64);
   wimg.ensure(cl16_packed_elems(C, O) / 2 + 8);
@@ -1730,7 +1727,6 @@ int dbm_op_conv2d_cl16(dbm_ctx* ctx, const float* x, const float* w, const float
   launch_conv_cl16(q, s);
   launch_cl_to_nchw(out.p, y, (long)O * plane, N, plane, s, O);
   DBM_HIP(hipStreamSynchronize(s));
-  act.release(); res.release(); out.release(); wimg.release(); bias.release();
   DBM_API_END
 }
 
@@ -1743,7 +1739,7 @@ int dbm_op_conv2d_cl16x3(dbm_ctx* ctx, const float* x, const float* w, const flo
   DBM_CHECK(O >= 1 && O <= 64 && (ups == 0 || ups == 1), "cl16x3 conv op: O <= 64, ups 0 / 1");
   hipStream_t s = ctx->stream;
   const int Hs = H >> ups, Ws = W >> ups, plane = H * W, splane = Hs * Ws;
-  DevBuf xin, out, wimg, bias;
+  ScopedBuf xin, out, wimg, bias;
   xin.ensure((size_t)N * splane * 64);
   out.ensure((size_t)N * plane * 64);
   wimg.ensure(cl16x3_packed_elems(64, O) / 2 + 8);
@@ -1764,10 +1760,10 @@ int dbm_op_conv2d_cl16x3(dbm_ctx* ctx, const float* x, const float* w, const flo
   launch_conv_cl16x3(q, s);
   if (!planar) launch_cl_to_nchw(out.p, y, (long)O * plane, N, plane, s, O);
   DBM_HIP(hipStreamSynchronize(s));
-  xin.release(); out.release(); wimg.release(); bias.release();
   DBM_API_END
 }
 
+// One named forward form of a deformable layer, whatever the switches say (the parity tests of the forms against each other).
 int dbm_op_deform_conv2d_form(dbm_ctx* ctx, const float* x, const float* off, const float* w, const float* b, float* y, int N, int H,
                               int W, int O, int form, int lrelu) {
   DBM_API_BEGIN(ctx)
@@ -1775,7 +1771,7 @@ int dbm_op_deform_conv2d_form(dbm_ctx* ctx, const float* x, const float* off, co
             "deform conv op: form 1 (O <= 16, premultiplied) or 2 (O = 64, split-bf16; 3: its LDS-window kernel, 4: its gathering kernel)");
   hipStream_t s = ctx->stream;
   const long plane = (long)H * W;
-  DevBuf xt, z, wx;
+  ScopedBuf xt, z, wx;
   xt.ensure((size_t)N * 64 * plane);
   launch_nchw_to_nhwc64(x, xt.p, N, (int)plane, s);
   if (form == 1) {
@@ -1787,51 +1783,38 @@ int dbm_op_deform_conv2d_form(dbm_ctx* ctx, const float* x, const float* off, co
     launch_deform_conv64_x3(xt.p, off, wx.p, b, y, nullptr, N, H, W, 18L * plane, lrelu, 0.2f, s, form == 3 ? 1 : form == 4 ? 0 : -1);
   }
   DBM_HIP(hipStreamSynchronize(s));
-  xt.release(); z.release(); wx.release();
   DBM_API_END
 }
 
+// The two entry points below run the generator's own launch sequences (deform_layer.hip) on scoped temporaries: they size buffers,
+// transpose, build the temporary layer and call; which kernel form runs is decided there.
 int dbm_op_deform_conv2d(dbm_ctx* ctx, const float* x, const float* off, const float* w, const float* b, float* y,
                          int N, int C, int H, int W, int O) {
   DBM_API_BEGIN(ctx)
   DBM_CHECK(C % 32 == 0, "deform conv op: C % 32 == 0");
-  const bool fused = deform_conv_fused_ok(C, O);
-  DevBuf col;
-  if (!fused) {
-    col.ensure((size_t)N * C * 9 * H * W);
-    launch_deform_sample(x, off, col.p, N, C, H, W, 18L * H * W, ctx->stream);
-  }
-  DevBuf xt;
-  if (fused) {
-    xt.ensure((size_t)N * C * H * W);
-    launch_nchw_to_nhwc64(x, xt.p, N, H * W, ctx->stream);
-  }
-  if (fused && O <= 16) {  // (the few-output-channel form reads the OIHW weights directly, one launch per output channel)
-    launch_deform_conv_fused(xt.p, off, w, b, y, nullptr, nullptr, N, C, H, W, 18L * H * W, O, 0, 0.2f, ctx->stream);
-  } else if (O == 1) {
-    launch_gemv_cols(col.p, w, b, y, N, C * 9, H * W, ctx->stream);
+  hipStream_t s = ctx->stream;
+  const long P = (long)H * W;
+  const DeformForms f = deform_layer_forms(C, O, H, W);
+  ScopedBuf col, xt;
+  dbm_model holder;   // (stays empty where the form reads the OIHW tensor itself)
+  if (f.fwd_fused) {
+    xt.ensure((size_t)N * C * P);
+    launch_nchw_to_nhwc64(x, xt.p, N, (int)P, s);
   } else {
-    dbm_model holder;
-    holder.ctx = ctx;
-    holder.add_tensor("op/W", {O, C, 3, 3}, DBM_KIND_PARAM);
-    holder.add_tensor("op/b", {O}, DBM_KIND_PARAM);
-    holder.alloc_arenas();
-    DBM_HIP(hipMemcpyAsync(holder.params, w, sizeof(float) * (size_t)O * C * 9, hipMemcpyDeviceToDevice, ctx->stream));
-    if (b) DBM_HIP(hipMemcpyAsync(holder.params + (size_t)O * C * 9, b, sizeof(float) * O, hipMemcpyDeviceToDevice, ctx->stream));
-    holder.add_iglayer("op", O, C, 3, 1, 0, true, true);
-    holder.ensure_packed();
-    if (fused) {
-      launch_deform_conv_fused(xt.p, off, holder.layers[0].wf, b ? holder.P(holder.layers[0].bi) : nullptr, y, nullptr, nullptr, N, C, H, W,
-                               18L * H * W, O, 0, 0.2f, ctx->stream);
-    } else {
-      ConvDesc d = holder.fwd_desc(holder.layers[0], col.p, (long)C * 9 * H * W, H, W, 0, y, (long)O * H * W, N);
-      launch_igemm_conv(d, ctx->stream);
-    }
-    DBM_HIP(hipStreamSynchronize(ctx->stream));
+    col.ensure((size_t)N * C * 9 * P);
   }
-  DBM_HIP(hipStreamSynchronize(ctx->stream));
-  col.release();
-  xt.release();
+  const float* bias = b;
+  if (f.fwd_packed) {
+    const IgLayer L = make_temp_layer(ctx, w, O, C, 3, 1, 0, holder, true, /*as_1x1=*/true);
+    if (b) {
+      DBM_HIP(hipMemcpyAsync(holder.P(L.bi), b, sizeof(float) * O, hipMemcpyDeviceToDevice, s));
+      bias = holder.P(L.bi);
+    }
+  }
+  // (the few-output-channel form reads the OIHW weights directly; without the z scratch: the gather-then-multiply kernel)
+  deform_layer_forward(holder, f.fwd_packed ? &holder.layers[0] : nullptr, f, x, xt.p, off, 18 * P, w, bias, y, nullptr, col.p, nullptr, N, C, H, W,
+                       O, 0, s);
+  DBM_HIP(hipStreamSynchronize(s));
   DBM_API_END
 }
 
@@ -1839,85 +1822,38 @@ int dbm_op_deform_conv2d_backward(dbm_ctx* ctx, const float* x, const float* off
                                   float* gx, float* goff, float* gw, float* gb, int N, int C, int H, int W, int O) {
   DBM_API_BEGIN(ctx)
   DBM_CHECK(C % 32 == 0, "deform conv op: C % 32 == 0");
+  DBM_CHECK(O == 1 || O % 32 == 0, "deform conv op backward: O == 1 or O % 32 == 0");
   hipStream_t s = ctx->stream;
   const long P = (long)H * W;
-  const bool fused = deform_conv_fused_ok(C, O) && deform_input_grad_ok(C, H, W);
-  DevBuf col, gcol, xt, part, cws;
-  if (fused) {
+  const DeformForms f = deform_layer_forms(C, O, H, W);
+  ScopedBuf col, gcol, xt, part, cws, z, gt;
+  if (f.bwd_fused) {
     cws.ensure(deform_csr_workspace_floats(N, H, W));
     xt.ensure((size_t)N * C * P);
     launch_nchw_to_nhwc64(x, xt.p, N, (int)P, s);
   }
-  if (!(fused && O == 1)) {
+  if (!(f.bwd_fused && O == 1)) {   // (what a retained forward leaves for the forms that read the sample matrix)
     col.ensure((size_t)N * C * 9 * P);
     launch_deform_sample(x, off, col.p, N, C, H, W, 18 * P, s);
   }
   if (O == 1) {
-    if (fused) {
-      part.ensure(deform_bwd1_partial_floats(N, H, W));
-      // (the premultiplied form the generator's backward pass uses -- round 5 --; DBM_DEFORM1_PREMUL_BWD=0: the gathering kernels)
-      static const bool premul_bwd = !(getenv("DBM_DEFORM1_PREMUL_BWD") && atoi(getenv("DBM_DEFORM1_PREMUL_BWD")) == 0);
-      if (premul_bwd && C == 64) {
-        DevBuf z, gt;
-        z.ensure((size_t)N * 9 * P);
-        gt.ensure((size_t)N * 9 * P);
-        launch_deform1_premul(xt.p, w, z.p, N, H, W, 1, s);
-        launch_deform_bwd1_premul(xt.p, off, w, gy, z.p, goff, gx, gw, gb, part.p, cws.p, gt.p, N, H, W, 18 * P, s);
-        DBM_HIP(hipStreamSynchronize(s));
-        z.release();
-        gt.release();
-      } else {
-        launch_deform_bwd1_fused(xt.p, off, w, gy, goff, gw, gb, part.p, N, H, W, 18 * P, s);
-        launch_deform_input_grad(x, off, nullptr, w, gy, gx, N, C, H, W, 18 * P, s, cws.p);
-      }
-    } else {
-      launch_deform_backward(x, off, nullptr, w, gy, gx, goff, N, C, H, W, 18 * P, s);
-      launch_gemv_cols_wgrad(col.p, gy, gw, gb, N, C * 9, (int)P, s);
+    if (f.bwd_fused) part.ensure(deform_bwd1_partial_floats(N, H, W));
+    if (f.premul_bwd) {   // (... and its premultiplied planes)
+      z.ensure((size_t)N * 9 * P);
+      gt.ensure((size_t)N * 9 * P);
+      launch_deform1_premul(xt.p, w, z.p, N, H, W, 1, s);
     }
+    deform1_backward(f, x, xt.p, off, 18 * P, w, gy, z.p, col.p, gx, goff, gw, gb, part.p, cws.p, gt.p, false, N, C, H, W, s, s, s);
   } else {
-    DBM_CHECK(O % 32 == 0, "deform conv op backward: O == 1 or O % 32 == 0");
     dbm_model holder;
-    holder.ctx = ctx;
-    holder.add_tensor("op/W", {O, C, 3, 3}, DBM_KIND_PARAM);
-    holder.add_tensor("op/b", {O}, DBM_KIND_PARAM);
-    holder.alloc_arenas();
-    DBM_HIP(hipMemcpyAsync(holder.params, w, sizeof(float) * (size_t)O * C * 9, hipMemcpyDeviceToDevice, s));
-    holder.add_iglayer("op", O, C, 3, 1, 0, true, true);
-    holder.ensure_packed();
+    const IgLayer L = make_temp_layer(ctx, w, O, C, 3, 1, 0, holder, true, /*as_1x1=*/true);
     holder.ensure_packed_bwd();
-    const IgLayer& L = holder.layers[0];
     gcol.ensure((size_t)N * C * 9 * P);
-    if (fused) {
-      launch_deform_bwd64_fused(xt.p, off, L.wb[1], gy, gcol.p, goff, N, H, W, 18 * P, s);
-      launch_deform_input_grad(x, off, gcol.p, nullptr, nullptr, gx, N, C, H, W, 18 * P, s, cws.p);
-    } else {
-      ConvDesc d;
-      memset(&d, 0, sizeof(d));
-      d.x = gy; d.xsn = O * P; d.N = N; d.y = gcol.p; d.ysn = C * 9 * P; d.s1 = 1.f; d.s2 = 1.f;
-      holder.run_dgrad(L, d, H, W);
-      launch_deform_backward(x, off, gcol.p, nullptr, nullptr, gx, goff, N, C, H, W, 18 * P, s);
-    }
-    // (the generator's own form since round 6: the sampler-fused weight gradient, no sample matrix; DBM_DEFORM_WGRAD_FUSED=0: the 1x1 form)
-    static const int wg_fused_env = getenv("DBM_DEFORM_WGRAD_FUSED") ? atoi(getenv("DBM_DEFORM_WGRAD_FUSED")) : 1;
-    if (fused && wg_fused_env && C == 64 && O == 64) {
-      part.ensure(deform_wgrad64_partial_floats(N, H, W));
-      launch_deform_wgrad64_fused(xt.p, off, gy, gw, gb, part.p, N, H, W, 18 * P, s);
-    } else {
-      WgradDesc wd;
-      memset(&wd, 0, sizeof(wd));
-      wd.x = col.p; wd.xsn = C * 9 * P; wd.xsc = (int)P; wd.Cin = C * 9; wd.Hin = H; wd.Win = W;
-      wd.dy = gy; wd.dysn = O * P; wd.dysc = (int)P; wd.Cout = O; wd.OH = H; wd.OW = W;
-      wd.KH = wd.KW = 1; wd.stride = 1; wd.pad = 0; wd.N = N; wd.scale = 1.f; wd.gW = gw; wd.gb = gb;
-      launch_wgrad(wd, s);
-    }
-    DBM_HIP(hipStreamSynchronize(s));
+    deform64_backward_data(holder, L, f, x, xt.p, off, 18 * P, gy, gcol.p, gx, goff, cws.p, false, N, H, W, s);
+    if (f.wgrad_fused) part.ensure(deform_wgrad64_partial_floats(N, H, W));
+    deform64_wgrad(holder, L, f, xt.p, col.p, off, 18 * P, gy, gw, gb, part.p, N, H, W, s, nullptr);
   }
   DBM_HIP(hipStreamSynchronize(s));
-  col.release();
-  gcol.release();
-  xt.release();
-  part.release();
-  cws.release();
   DBM_API_END
 }
 

@@ -246,10 +246,7 @@ void Discriminator::backward(int slot, const float* glogits, bool join, bool mer
                           G(T_bn[i][1]), nullptr, N, DC_O[i], ho * wo, SLOPE, s);
     run_wgrad(L, c.h[i - 1].p, (long)DC_C[i] * hin * win, hin, win, 0, g_z[slot][i].p, (long)DC_O[i] * ho * wo, ho, wo, N, 1.f,
               merge ? &wbm[wgroup(i)] : &wb[slot][wgroup(i)]);
-    ConvDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x = g_z[slot][i].p; d.xsn = (long)DC_O[i] * ho * wo; d.N = N;
-    d.y = gh_next; d.ysn = (long)DC_C[i] * hin * win; d.s1 = 1.f; d.s2 = 1.f;
+    ConvDesc d = dgrad_desc(g_z[slot][i].p, (long)DC_O[i] * ho * wo, gh_next, (long)DC_C[i] * hin * win, N);
     if (i == 1) {  // through conv_layer0's LeakyReLU
       d.mask = c.h[0].p; d.masksn = 64L * c.H * c.W; d.mask_c0 = 0;
     }

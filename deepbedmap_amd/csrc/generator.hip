@@ -157,19 +157,6 @@ static int trunk_split(int N, long hw) {
   return ns;
 }
 
-// The backward of the two deformable layers runs on the fused kernels (deform_fused.hip) when the forward did and the
-// planes fit the CSR input-gradient kernel.
-bool Generator::deform_bwd_fused(int H4, int W4) const {
-  return out_ch == 1 && deform_conv_fused_ok(64, 64) && deform_input_grad_ok(64, H4, W4);
-}
-
-// final_conv_layer1's weight gradient from the channels-last input and the offsets (deform_wgrad64_fused_kernel) instead of from the retained
-// sample matrix.  DBM_DEFORM_WGRAD_FUSED=0: the sample matrix + the 1x1 form (A/B; both are parity-tested).
-bool Generator::deform_wgrad_fused(int H4, int W4) const {
-  static const int env = getenv("DBM_DEFORM_WGRAD_FUSED") ? atoi(getenv("DBM_DEFORM_WGRAD_FUSED")) : 1;
-  return env != 0 && deform_bwd_fused(H4, W4) && deform_conv_fused_ok(64, 64) && deform_conv_fused_ok(64, out_ch);
-}
-
 void Generator::ensure_ws(GenWorkspace& ws, int N, int H, int W, bool train) {
   const bool same = (N == ws.N && H == ws.H && W == ws.W);
   if (same && (ws.train || !train)) return;
@@ -261,8 +248,7 @@ void Generator::forward(GenWorkspace& ws, int N, int H, int W, const float* x, c
   const bool cl16 = !fused && use_bf16 && !(bf16_keep32 & 4) && layers[L_rdb[0]].wcl16 != nullptr &&
                     !(getenv("DBM_CL16") && atoi(getenv("DBM_CL16")) == 0);
   // ... with the post-residual convolution and the full-resolution tail in split-bf16 on NHWC fp32 activations (see below)
-  const bool x3_tail = use_bf16 && !keep && deform_conv_fused_ok(64, 64) && deform_conv_fused_ok(64, out_ch) &&
-                       layers[L_up1].wx3 != nullptr;
+  const bool x3_tail = use_bf16 && !keep && layers[L_up1].wx3 != nullptr;
   // DBM_POST_X3=0 / DBM_PRE_X3=0 (or bits 32 / 64 of DBM_BF16_FP32_LAYERS): the post- / pre-residual convolution in fp32 (igemm)
   // between layout conversions, as before round 5's last changes
   const bool post_x3 = cl16 && x3_tail && layers[L_post].wx3 != nullptr && !(bf16_keep32 & 32) &&
@@ -448,12 +434,11 @@ void Generator::forward(GenWorkspace& ws, int N, int H, int W, const float* x, c
   const int H4 = 4 * h, W4 = 4 * w;
   const long P4 = 16 * hw;
   // The sampler is fused into the GEMM (deform_fused.hip), fed from a channels-last copy of the layer input; the
-  // (N, 576, H, W) sample matrices exist only in a retained pass, as a by-product for the two weight gradients.
-  const bool dfused = deform_conv_fused_ok(64, 64) && deform_conv_fused_ok(64, out_ch);
-  // bf16 sweep mode: the upsampling and offset convolutions -- on the signal path, where plain bf16 costs ~100 m rms at the
+  // (N, 576, H, W) sample matrices exist only in a retained pass whose backward reads them (deform_layer.hip has the forms).
+  const DeformForms f1 = deform_layer_forms(64, 64, H4, W4), f2 = deform_layer_forms(64, out_ch, H4, W4);
+  // bf16 sweep mode (x3_tail): the upsampling and offset convolutions -- on the signal path, where plain bf16 costs ~100 m rms at the
   // data range -- run in split-bf16 arithmetic (conv_cl16x3_kernel: three bf16 MFMAs per product, 2^-16 operand precision) on
   // NHWC fp32 activations, which is also what the fused deformable sampler reads.
-  const bool x3 = use_bf16 && !keep && dfused && layers[L_up1].wx3 != nullptr;
   auto x3_launch = [&](const IgLayer& L, const float* xin, int ups, int Ho, int Wo, float* y32, float* yp, int act) {
     ClX3Launch q;
     memset(&q, 0, sizeof(q));
@@ -461,7 +446,7 @@ void Generator::forward(GenWorkspace& ws, int N, int H, int W, const float* x, c
     q.y32 = y32; q.yc = 64; q.yp = yp; q.ysn = 32L * Ho * Wo; q.ypc = L.O; q.act = act; q.slope = SLOPE; q.N = N; q.H = Ho; q.W = Wo;
     launch_conv_cl16x3(q, s);
   };
-  if (x3) {
+  if (x3_tail) {
     ws.a3t.ensure((size_t)N * 64 * hw);
     ws.a41t.ensure((size_t)N * 64 * 4 * hw);
     ws.a42t.ensure((size_t)N * 64 * P4);
@@ -476,31 +461,23 @@ void Generator::forward(GenWorkspace& ws, int N, int H, int W, const float* x, c
     ConvDesc e = prec(fwd_desc(layers[L_up2], ws.a41.p, 64 * 4 * hw, 2 * h, 2 * w, 1, ws.a42.p, 64 * 16 * hw, N), 8);
     e.act = 1;
     // (the fused deformable sampler reads a channels-last copy of this output: the LDS-tiled form writes it from its epilogue)
-    ws.a42t_written = false;
-    if (dfused) {
-      ws.a42t.ensure((size_t)N * 64 * 16 * hw);
-      e.yt = ws.a42t.p;
-      ws.a42t_written = conv_tile_writes_yt(e);
-      if (!ws.a42t_written) e.yt = nullptr;
-    }
+    ws.a42t.ensure((size_t)N * 64 * 16 * hw);
+    e.yt = ws.a42t.p;
+    ws.a42t_written = conv_tile_writes_yt(e);
+    if (!ws.a42t_written) e.yt = nullptr;
     launch_igemm_conv(e, s);
   }
-  // ---- deformable conv 1 + LeakyReLU (:572-573): offset conv, sampler -> col, GEMM over 576 columns ----
-  if (dfused) {
-    ws.a42t.ensure((size_t)N * 64 * P4);
-    ws.a51t.ensure((size_t)N * 64 * P4);
-  } else {
-    ws.col1.ensure((size_t)N * 576 * P4);
-    if (keep) ws.col2.ensure((size_t)N * 576 * P4);
-  }
-  if (x3) {
+  // ---- deformable conv 1 + LeakyReLU (:572-573): offset conv, then the layer (deform_layer_forward) ----
+  ws.a42t.ensure((size_t)N * 64 * P4);
+  ws.a51t.ensure((size_t)N * 64 * P4);
+  if (x3_tail) {
     x3_launch(layers[L_off1], ws.a42t.p, 0, H4, W4, nullptr, ws.off1.p, 0);
     // (the split-bf16 tail reads channels-last only: the NCHW copy of this layer's output is not written)
     if (layers[L_def1].wdx3)
       launch_deform_conv64_x3(ws.a42t.p, ws.off1.p, layers[L_def1].wdx3, P(layers[L_def1].bi), nullptr, ws.a51t.p, N, H4, W4, 32 * P4, 1, SLOPE, s);
     else
-      launch_deform_conv_fused(ws.a42t.p, ws.off1.p, layers[L_def1].wf, P(layers[L_def1].bi), nullptr, ws.a51t.p, nullptr, N, 64, H4, W4, 32 * P4, 64,
-                               1, SLOPE, s);
+      deform_layer_forward(*this, &layers[L_def1], f1, nullptr, ws.a42t.p, ws.off1.p, 32 * P4, nullptr, P(layers[L_def1].bi), nullptr, ws.a51t.p,
+                           nullptr, nullptr, N, 64, H4, W4, 64, 1, s);
   } else {
     ConvDesc d = prec(fwd_desc(layers[L_off1], ws.a42.p, 64 * P4, H4, W4, 0, ws.off1.p, 32 * P4, N), 16);
     launch_igemm_conv(d, s);
@@ -510,53 +487,36 @@ void Generator::forward(GenWorkspace& ws, int N, int H, int W, const float* x, c
         if (!e) DBM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
       DBM_HIP(hipEventRecord(ws.ev_off[0], s));
     }
-    if (dfused) {
-      if (!ws.a42t_written) launch_nchw_to_nhwc64(ws.a42.p, ws.a42t.p, N, (int)P4, s);
-      // (round 6: the layer's weight gradient re-samples -- deform_wgrad64_fused_kernel -- so a retained pass no longer writes the
-      //  191 MB sample matrix from this kernel's tap loop; only the unfused backward path still reads it)
-      float* colout = nullptr;
-      if (keep && !deform_wgrad_fused(H4, W4)) {
-        ws.col1.ensure((size_t)N * 576 * P4);
-        colout = ws.col1.p;
-      }
-      launch_deform_conv_fused(ws.a42t.p, ws.off1.p, layers[L_def1].wf, P(layers[L_def1].bi), ws.a51.p, ws.a51t.p, colout, N, 64, H4,
-                               W4, 32 * P4, 64, 1, SLOPE, s);
-    } else {
-      launch_deform_sample(ws.a42.p, ws.off1.p, ws.col1.p, N, 64, H4, W4, 32 * P4, s);
-      ConvDesc g = fwd_desc(layers[L_def1], ws.col1.p, 576 * P4, H4, W4, 0, ws.a51.p, 64 * P4, N);
-      g.act = 1;
-      launch_igemm_conv(g, s);
+    if (!ws.a42t_written) launch_nchw_to_nhwc64(ws.a42.p, ws.a42t.p, N, (int)P4, s);
+    // (round 6: the layer's weight gradient re-samples -- deform_wgrad64_fused_kernel -- so a retained pass no longer writes the
+    //  191 MB sample matrix from this kernel's tap loop; only the unfused backward path still reads it)
+    float* colout = nullptr;
+    if (keep && !f1.wgrad_fused) {
+      ws.col1.ensure((size_t)N * 576 * P4);
+      colout = ws.col1.p;
     }
+    deform_layer_forward(*this, &layers[L_def1], f1, ws.a42.p, ws.a42t.p, ws.off1.p, 32 * P4, nullptr, P(layers[L_def1].bi), ws.a51.p, ws.a51t.p,
+                         colout, nullptr, N, 64, H4, W4, 64, 1, s);
   }
   // ---- deformable conv 2 (:574) ----
-  {
-    if (x3) {
-      x3_launch(layers[L_off2], ws.a51t.p, 0, H4, W4, nullptr, ws.off2.p, 0);
-    } else {
-      ConvDesc d = prec(fwd_desc(layers[L_off2], ws.a51.p, 64 * P4, H4, W4, 0, ws.off2.p, 32 * P4, N), 16);
-      launch_igemm_conv(d, s);
-      if (keep && csr_early) {
-        DBM_HIP(hipEventRecord(ws.ev_off[1], s));
-        ws.csr_marked = true;
-      }
+  if (x3_tail) {
+    x3_launch(layers[L_off2], ws.a51t.p, 0, H4, W4, nullptr, ws.off2.p, 0);
+  } else {
+    ConvDesc d = prec(fwd_desc(layers[L_off2], ws.a51.p, 64 * P4, H4, W4, 0, ws.off2.p, 32 * P4, N), 16);
+    launch_igemm_conv(d, s);
+    if (keep && csr_early) {
+      DBM_HIP(hipEventRecord(ws.ev_off[1], s));
+      ws.csr_marked = true;
     }
-    if (dfused) {
-      static const bool premul = !(getenv("DBM_DEFORM1_PREMUL") && atoi(getenv("DBM_DEFORM1_PREMUL")) == 0);
-      if (premul) ws.zdef.ensure((size_t)N * 9 * out_ch * P4);
-      launch_deform_conv_fused(ws.a51t.p, ws.off2.p, P(T_def2W), P(T_def2b), y, nullptr, nullptr, N, 64, H4, W4, 32 * P4, out_ch, 0, SLOPE, s,
-                               premul ? ws.zdef.p : nullptr);
-      ws.zdef_kept = premul && keep && out_ch == 1;
-      // (unfused backward only: the 64 -> 1 layer's weight gradient then reads its sample matrix)
-      if (keep && !deform_bwd_fused(H4, W4)) {
-        ws.col2.ensure((size_t)N * 576 * P4);
-        launch_deform_sample(ws.a51.p, ws.off2.p, ws.col2.p, N, 64, H4, W4, 32 * P4, s);
-      }
-    } else {
-      DBM_CHECK(out_ch == 1, "the unfused deformable tail serves out_channels == 1 only");
-      float* col = keep ? ws.col2.p : ws.col1.p;
-      launch_deform_sample(ws.a51.p, ws.off2.p, col, N, 64, H4, W4, 32 * P4, s);
-      launch_gemv_cols(col, P(T_def2W), P(T_def2b), y, N, 576, (int)P4, s);
-    }
+  }
+  if (f2.premul) ws.zdef.ensure((size_t)N * 9 * out_ch * P4);
+  deform_layer_forward(*this, nullptr, f2, ws.a51.p, ws.a51t.p, ws.off2.p, 32 * P4, P(T_def2W), P(T_def2b), y, nullptr, nullptr,
+                       f2.premul ? ws.zdef.p : nullptr, N, 64, H4, W4, out_ch, 0, s);
+  ws.zdef_kept = f2.premul && keep && out_ch == 1;
+  // (unfused backward only: the 64 -> 1 layer's weight gradient then reads its sample matrix)
+  if (keep && !f2.bwd_fused) {
+    ws.col2.ensure((size_t)N * 576 * P4);
+    launch_deform_sample(ws.a51.p, ws.off2.p, ws.col2.p, N, 64, H4, W4, 32 * P4, s);
   }
   ws.bw_in[0] = x; ws.bw_in[1] = w1; ws.bw_in[2] = w2; ws.bw_in[3] = w3;
   ws.have_graph = keep;
@@ -567,7 +527,8 @@ void Generator::prebuild_csr(GenWorkspace& ws, hipStream_t aux) {
   ws.csr_marked = false;
   const int N = ws.N, H4 = 4 * (ws.H - 2), W4 = 4 * (ws.W - 2);
   const long P4 = (long)H4 * W4;
-  if (!deform_bwd_fused(H4, W4) || !deform_csr_lists_ok(64, H4, W4)) return;
+  // (a plane that fits the CSR input-gradient kernel -- 18 plane-sized LDS arrays -- fits the list builder's 10: deform_csr_lists_ok is implied)
+  if (!deform_layer_forms(64, 1, H4, W4).bwd_fused) return;
   ws.csr_ws.ensure(deform_csr_workspace_floats(N, H4, W4));
   ws.csr_ws2.ensure(deform_csr_workspace_floats(N, H4, W4));
   if (!ws.ev_csr) DBM_HIP(hipEventCreateWithFlags(&ws.ev_csr, hipEventDisableTiming));
@@ -588,14 +549,14 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
   const long hw = (long)h * w, P4 = 16 * hw;
   const int H4 = 4 * h, W4 = 4 * w, nrdb = 3 * n_rrdb;
   for (auto& b : ws.wbs) b.cleared_target = cleared;
-  // ---- final_conv_layer2 (deformable, 64 -> 1) ----
-  const bool bfused = deform_bwd_fused(H4, W4);
-  const bool pre_csr = ws.csr_prebuilt && bfused;   // (prebuild_csr: both layers' sampling lists are already being built on another stream)
+  // ---- final_conv_layer2 (deformable, 64 -> 1): deform_layer.hip has the forms and the launch sequences ----
+  const DeformForms f1 = deform_layer_forms(64, 64, H4, W4), f2 = deform_layer_forms(64, 1, H4, W4);
+  const bool pre_csr = ws.csr_prebuilt && f2.bwd_fused;   // (prebuild_csr: both layers' sampling lists are already being built on another stream)
   ws.csr_prebuilt = false;
-  if (bfused) {
-    // offset gradients + the layer's weight / bias gradient from one pass over the channels-last input (no sample matrix);
-    // on the aux stream next to the input-gradient gather when the caller has one
-    hipStream_t sg = s;
+  hipStream_t sg = s;
+  const float* z2 = ws.zdef_kept ? ws.zdef.p : nullptr;   // (the retained forward's premultiplied planes)
+  if (f2.bwd_fused) {
+    // (the gathering form's offset / weight-gradient pass: on the aux stream next to the input-gradient gather when the caller has one)
     if (use_aux) {
       ctx->fork(s, ctx->chain[0], 2);
       sg = ctx->chain[0];
@@ -604,65 +565,37 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
     ws.csr_ws.ensure(deform_csr_workspace_floats(N, H4, W4));
     if (pre_csr) DBM_HIP(hipStreamWaitEvent(s, ws.ev_csr, 0));
     DBM_MARK(s, "G:backward_begin");   // (behind the wait for the prebuilt sampling lists)
-    // Round 5: in the premultiplied form of the forward pass (z_t = sum_c w[c][t] x_c kept from it) the layer's whole backward is a
-    // CSR gather of ONE value per list entry, four single-float gathers per (position, tap) and one pass over the input -- instead of
-    // gathering 9 x 4 x 256 bytes per position for the offset / weight gradients (150 us) and 64 values per entry for the input gradient.
-    // DBM_DEFORM1_PREMUL_BWD=0: the gathering kernels (A/B).
-    static const bool premul_bwd = !(getenv("DBM_DEFORM1_PREMUL_BWD") && atoi(getenv("DBM_DEFORM1_PREMUL_BWD")) == 0);
-    if (premul_bwd && ws.zdef_kept) {
-      ws.gt2.ensure((size_t)N * 9 * P4);
-      launch_deform_bwd1_premul(ws.a51t.p, ws.off2.p, P(T_def2W), gy, ws.zdef.p, ws.goff2.p, ws.g_a51.p, G(T_def2W), G(T_def2b), ws.dw2_partial.p,
-                                pre_csr ? ws.csr_ws2.p : ws.csr_ws.p, ws.gt2.p, N, H4, W4, 32 * P4, s, pre_csr);
-    } else {
-      launch_deform_bwd1_fused(ws.a51t.p, ws.off2.p, P(T_def2W), gy, ws.goff2.p, G(T_def2W), G(T_def2b), ws.dw2_partial.p, N, H4, W4, 32 * P4, sg);
-      launch_deform_input_grad(ws.a51.p, ws.off2.p, nullptr, P(T_def2W), gy, ws.g_a51.p, N, 64, H4, W4, 32 * P4, s, pre_csr ? ws.csr_ws2.p : ws.csr_ws.p,
-                               pre_csr);
-    }
-    if (sg != s) ctx->fork(sg, s, 3);
+    if (f2.premul_bwd && z2) ws.gt2.ensure((size_t)N * 9 * P4);
   } else {
     // (its weight gradient only needs gy and the retained columns: side stream, underneath the sampler's backward)
     ctx->fork_to_side(5);
-    launch_gemv_cols_wgrad(ws.col2.p, gy, G(T_def2W), G(T_def2b), N, 576, (int)P4, ctx->side);
-    launch_deform_backward(ws.a51.p, ws.off2.p, nullptr, P(T_def2W), gy, ws.g_a51.p, ws.goff2.p, N, 64, H4, W4, 32 * P4, s,
-                           use_aux ? ctx->chain[0] : nullptr, use_aux ? &ctx->ev_fork[2] : nullptr);
   }
+  deform1_backward(f2, ws.a51.p, ws.a51t.p, ws.off2.p, 32 * P4, P(T_def2W), gy, z2, ws.col2.p, ws.g_a51.p, ws.goff2.p, G(T_def2W), G(T_def2b),
+                   ws.dw2_partial.p, pre_csr ? ws.csr_ws2.p : ws.csr_ws.p, ws.gt2.p, pre_csr, N, 64, H4, W4, s, sg, ctx->side);
+  if (sg != s) ctx->fork(sg, s, 3);
   {
     const IgLayer& L = layers[L_off2];
     run_wgrad(L, ws.a51.p, 64 * P4, H4, W4, 0, ws.goff2.p, 32 * P4, H4, W4, N, 1.f, &ws.wbs[0]);
-    ConvDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x = ws.goff2.p; d.xsn = 32 * P4; d.N = N;
-    d.y = ws.g_a51.p; d.ysn = 64 * P4; d.accumulate = 1; d.s1 = 1.f; d.s2 = 1.f;
+    ConvDesc d = dgrad_desc(ws.goff2.p, 32 * P4, ws.g_a51.p, 64 * P4, N);
+    d.accumulate = 1;
     d.mask = ws.a51.p; d.masksn = 64 * P4; d.mask_c0 = 0;  // through F.leaky_relu (:573)
     run_dgrad(L, d, H4, W4);
   }
   // ---- final_conv_layer1 (deformable, 64 -> 64): g_a51 now holds d loss / d (pre-activation) ----
   {
     const IgLayer& L = layers[L_def1];
-    // (its weight gradient: sampler-fused, launched with the tail's batch on the side stream below -- deform_wgrad_fused; else from the
-    //  retained sample matrix through the batched 1x1 form)
-    if (!deform_wgrad_fused(H4, W4)) run_wgrad(L, ws.col1.p, 576 * P4, H4, W4, 0, ws.g_a51.p, 64 * P4, H4, W4, N, 1.f, &ws.wbs[0]);
-    if (bfused) {
-      // column gradients W^T gy on the MFMAs, offset gradients from the same LDS tile; then the input-gradient gather
-      launch_deform_bwd64_fused(ws.a42t.p, ws.off1.p, L.wb[1], ws.g_a51.p, ws.gcol.p, ws.goff1.p, N, H4, W4, 32 * P4, s);
-      launch_deform_input_grad(ws.a42.p, ws.off1.p, ws.gcol.p, nullptr, nullptr, ws.g_a42.p, N, 64, H4, W4, 32 * P4, s, ws.csr_ws.p, pre_csr);
-    } else {
-      ConvDesc d;
-      memset(&d, 0, sizeof(d));
-      d.x = ws.g_a51.p; d.xsn = 64 * P4; d.N = N;
-      d.y = ws.gcol.p; d.ysn = 576 * P4; d.s1 = 1.f; d.s2 = 1.f;
-      run_dgrad(L, d, H4, W4);
-      launch_deform_backward(ws.a42.p, ws.off1.p, ws.gcol.p, nullptr, nullptr, ws.g_a42.p, ws.goff1.p, N, 64, H4, W4, 32 * P4, s,
-                             use_aux ? ctx->chain[0] : nullptr, use_aux ? &ctx->ev_fork[2] : nullptr);
-    }
+    // (its weight gradient: sampler-fused, launched with the tail's batch on the side stream below; else from the retained sample matrix
+    //  through the batched 1x1 form)
+    if (!f1.wgrad_fused)
+      deform64_wgrad(*this, L, f1, ws.a42t.p, ws.col1.p, ws.off1.p, 32 * P4, ws.g_a51.p, G(L.wi), G(L.bi), nullptr, N, H4, W4, s, &ws.wbs[0]);
+    deform64_backward_data(*this, L, f1, ws.a42.p, ws.a42t.p, ws.off1.p, 32 * P4, ws.g_a51.p, ws.gcol.p, ws.g_a42.p, ws.goff1.p, ws.csr_ws.p, pre_csr,
+                           N, H4, W4, s);
   }
   {
     const IgLayer& L = layers[L_off1];
     run_wgrad(L, ws.a42.p, 64 * P4, H4, W4, 0, ws.goff1.p, 32 * P4, H4, W4, N, 1.f, &ws.wbs[0]);
-    ConvDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x = ws.goff1.p; d.xsn = 32 * P4; d.N = N;
-    d.y = ws.g_a42.p; d.ysn = 64 * P4; d.accumulate = 1; d.s1 = 1.f; d.s2 = 1.f;
+    ConvDesc d = dgrad_desc(ws.goff1.p, 32 * P4, ws.g_a42.p, 64 * P4, N);
+    d.accumulate = 1;
     d.mask = ws.a42.p; d.masksn = 64 * P4; d.mask_c0 = 0;  // through F.leaky_relu (:568)
     run_dgrad(L, d, H4, W4);
   }
@@ -670,33 +603,21 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
   {
     const IgLayer& L = layers[L_up2];
     run_wgrad(L, ws.a41.p, 64 * 4 * hw, 2 * h, 2 * w, 1, ws.g_a42.p, 64 * P4, H4, W4, N, 1.f, &ws.wbs[0]);
-    ConvDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x = ws.g_a42.p; d.xsn = 64 * P4; d.N = N;
-    d.y = ws.g_u2.p; d.ysn = 64 * P4; d.s1 = 1.f; d.s2 = 1.f;
-    run_dgrad(L, d, H4, W4);
+    run_dgrad(L, dgrad_desc(ws.g_a42.p, 64 * P4, ws.g_u2.p, 64 * P4, N), H4, W4);
     launch_sumpool2(ws.g_u2.p, ws.a41.p, ws.g_z41.p, (long)N * 64, 2 * h, 2 * w, SLOPE, s);  // resize bwd + lrelu' (:560)
   }
   // ---- post_upsample_conv_layer_1 on resize(a3) ----
   {
     const IgLayer& L = layers[L_up1];
     run_wgrad(L, ws.a3.p, 64 * hw, h, w, 1, ws.g_z41.p, 64 * 4 * hw, 2 * h, 2 * w, N, 1.f, &ws.wbs[0]);
-    ConvDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x = ws.g_z41.p; d.xsn = 64 * 4 * hw; d.N = N;
-    d.y = ws.g_u1.p; d.ysn = 64 * 4 * hw; d.s1 = 1.f; d.s2 = 1.f;
-    run_dgrad(L, d, 2 * h, 2 * w);
+    run_dgrad(L, dgrad_desc(ws.g_z41.p, 64 * 4 * hw, ws.g_u1.p, 64 * 4 * hw, N), 2 * h, 2 * w);
     launch_sumpool2(ws.g_u1.p, nullptr, ws.g_a3.p, (long)N * 64, h, w, SLOPE, s);
   }
   // ---- post_residual_conv_layer: a3 = a1 + conv(a2) ----
   {
     const IgLayer& L = layers[L_post];
     run_wgrad(L, ws.cat[nrdb].p, 192 * hw, h, w, 0, ws.g_a3.p, 64 * hw, h, w, N, 1.f, &ws.wbs[0]);
-    ConvDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x = ws.g_a3.p; d.xsn = 64 * hw; d.N = N;
-    d.y = ws.dA[nrdb].p; d.ysn = 64 * hw; d.s1 = 1.f; d.s2 = 1.f;
-    run_dgrad(L, d, h, w);
+    run_dgrad(L, dgrad_desc(ws.g_a3.p, 64 * hw, ws.dA[nrdb].p, 64 * hw, N), h, w);
   }
   // Weight gradients never feed the data-gradient chain, and that chain (one short, latency-bound kernel per conv)
   // leaves most of the chip idle: the batches go to the side stream as soon as their inputs are final.
@@ -704,9 +625,10 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
   ctx->fork_to_side(0);
   static const int iter_abl = DBM_MEASURE_ENV("ITER_ABL");  // (libdbm_measure.so only: 2 = no trunk weight gradients, 4 = none of the tail's)
   if (!(iter_abl & 4)) ws.wbs[0].launch(ctx->side);
-  if (deform_wgrad_fused(H4, W4) && !(iter_abl & 4)) {   // final_conv_layer1's weight / bias gradient (g_a51 and the offsets are final)
+  if (f1.wgrad_fused && !(iter_abl & 4)) {   // final_conv_layer1's weight / bias gradient (g_a51 and the offsets are final)
+    const IgLayer& L = layers[L_def1];
     ws.dw1_partial.ensure(deform_wgrad64_partial_floats(N, H4, W4));
-    launch_deform_wgrad64_fused(ws.a42t.p, ws.off1.p, ws.g_a51.p, G(layers[L_def1].wi), G(layers[L_def1].bi), ws.dw1_partial.p, N, H4, W4, 32 * P4, ctx->side);
+    deform64_wgrad(*this, L, f1, ws.a42t.p, nullptr, ws.off1.p, 32 * P4, ws.g_a51.p, G(L.wi), G(L.bi), ws.dw1_partial.p, N, H4, W4, ctx->side, nullptr);
   }
   if (ws.col_stale) {  // (fused input block: the im2col images the wide branches' weight gradients read -- wbs[6], launched last)
     launch_im2col(ws.bw_in[1] ? ws.bw_in[1] : ws.in_w1.p, ws.colW1.p, N, 1, 10 * H, 10 * W, 30, 30, 10, h, w, layers[L_in[1]].CinP, ctx->side);
@@ -826,11 +748,8 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
     {  // conv_layer5: out = a5*rs + a0
       const IgLayer& L = layers[L_rdb[j * 5 + 4]];
       run_wgrad(L, C, 192 * hw, h, w, 0, Gout, gsn, h, w, N, sc, &ws.wbs[grp]);
-      ConvDesc d;
-      memset(&d, 0, sizeof(d));
-      d.x = Gout; d.xsn = gsn; d.N = N;
-      d.y = D; d.ysn = 192 * hw;
-      d.s1 = sc; d.s2 = 1.f;
+      ConvDesc d = dgrad_desc(Gout, gsn, D, 192 * hw, N);
+      d.s1 = sc;
       d.r1 = Gout; d.r1sn = gsn; d.r1_nch = 64; d.r1s = third ? rs : 1.f;
       d.mask = C; d.masksn = 192 * hw; d.mask_c0 = 160;
       for (int c = 0; c < nsplit; ++c) run_dgrad(L, chunk(d, c), h, w, cstream(c));
@@ -839,10 +758,8 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
       const int lo = 64 + 32 * k;   // channel offset of a_{k+1} = number of input channels of this conv
       const IgLayer& L = layers[L_rdb[j * 5 + k]];
       run_wgrad(L, C, 192 * hw, h, w, 0, D + (long)lo * hw, 192 * hw, h, w, N, 1.f, &ws.wbs[grp]);
-      ConvDesc d;
-      memset(&d, 0, sizeof(d));
-      d.x = D + (long)lo * hw; d.xsn = 192 * hw; d.N = N;
-      d.y = D; d.ysn = 192 * hw; d.accumulate = 1; d.s1 = 1.f; d.s2 = 1.f;
+      ConvDesc d = dgrad_desc(D + (long)lo * hw, 192 * hw, D, 192 * hw, N);
+      d.accumulate = 1;
       if (k > 0) {
         d.mask = C; d.masksn = 192 * hw; d.mask_c0 = lo - 32;
       } else {
@@ -867,11 +784,7 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
     // (its inputs -- a0 and the chain's last output -- are final when the chain is: the pre-residual weight gradient rides in the
     //  trunk's last launch (same kernel form) instead of being a 50-us launch + fold of its own in the serial tail behind it)
     run_wgrad(L, ws.a0.p, 128 * hw, h, w, 0, ws.dA[0].p, 192 * hw, h, w, N, 1.f, &ws.wbs[prev_grp >= 0 ? prev_grp : 6]);
-    ConvDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x = ws.dA[0].p; d.xsn = 192 * hw; d.N = N;
-    d.y = ws.g_a0.p; d.ysn = 128 * hw; d.s1 = 1.f; d.s2 = 1.f;
-    run_dgrad(L, d, h, w);
+    run_dgrad(L, dgrad_desc(ws.dA[0].p, 192 * hw, ws.g_a0.p, 128 * hw, N), h, w);
     struct { const float* in; int Cin, Hin, Win, K, stride; } br[4] = {{ws.in_x.p, 1, H, W, 3, 1},
                                                                     {ws.in_w1.p, 1, 10 * H, 10 * W, 30, 10},
                                                                     {ws.in_w2.p, 2, 2 * H, 2 * W, 6, 2},

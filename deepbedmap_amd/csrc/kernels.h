@@ -39,7 +39,7 @@ void launch_im2col(const float* x, float* col, int N, int Cin, int Hin, int Win,
                    int KP, hipStream_t s);
 void launch_deform_sample(const float* x, const float* off, float* col, int N, int C, int H, int W, long offsn, hipStream_t s);
 void launch_deform_backward(const float* x, const float* off, const float* gcol, const float* w1o, const float* gy,
-                            float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s, hipStream_t aux = nullptr, hipEvent_t* ev = nullptr);
+                            float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s);
 // sampler fused into the GEMM (deform_fused.hip): no column matrix.  C == 64, O == 64 (w = packed [576][64] image) or 1 (w = OIHW).
 // xt = the layer input channels-last (N * H * W, 64); yt (optional, O == 64) = the output channels-last as well;
 // colout (optional, O == 64) = the sample matrix (N, 576, H, W) as a by-product (a retained pass: the weight gradient reads it)
@@ -73,11 +73,10 @@ void launch_deform_csr_build(const float* off, float* ws, int N, int H, int W, l
 void launch_deform_bwd1_fused(const float* xt, const float* off, const float* w, const float* gy, float* goff, float* gw, float* gb,
                               float* partial, int N, int H, int W, long offsn, hipStream_t s);
 bool deform_input_grad_ok(int C, int H, int W);
-// ws (optional, deform_csr_workspace_floats floats): the sampling lists are built once per (image, tap) there and a
-// register-only kernel gathers (otherwise every channel-group workgroup rebuilds them in LDS)
+// ws (deform_csr_workspace_floats floats): the sampling lists are built once per (image, tap) there and a register-only kernel gathers
 size_t deform_csr_workspace_floats(int N, int H, int W);
-void launch_deform_input_grad(const float* x, const float* off, const float* gcol, const float* w1o, const float* gy, float* gx, int N,
-                              int C, int H, int W, long offsn, hipStream_t s, float* ws = nullptr, bool lists_built = false);
+void launch_deform_input_grad(const float* off, const float* gcol, const float* w1o, const float* gy, float* gx, int N, int C, int H, int W,
+                              long offsn, hipStream_t s, float* ws, bool lists_built = false);
 void launch_gemv_cols(const float* col, const float* w, const float* bias, float* y, int N, int K, int plane, hipStream_t s);
 void launch_gemv_cols_wgrad(const float* col, const float* gy, float* gw, float* gb, int N, int K, int plane, hipStream_t s);
 void launch_sumpool2(const float* g, const float* mask, float* out, long nc, int H, int W, float slope, hipStream_t s);

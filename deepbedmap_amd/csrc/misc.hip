@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256) void deform_goff_kernel(const float* __restric
 
 // gx is fully overwritten; goff[n][0:18] is overwritten (channels 18.. of a padded offset tensor are left alone).
 void launch_deform_backward(const float* x, const float* off, const float* gcol, const float* w1o, const float* gy,
-                            float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s, hipStream_t aux, hipEvent_t* ev) {
+                            float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s) {
   const long plane = (long)H * W;
   constexpr int CH = 8;
   const size_t lds = sizeof(float) * ((size_t)2 * CH * plane + 10 * plane + 1);
@@ -568,25 +568,15 @@ void launch_deform_backward(const float* x, const float* off, const float* gcol,
       attr_set = true;
     }
     if (g_wgrad_deterministic) {
-      // the offset gradients read the same inputs and write a different output: on `aux` (when the caller has a free
-      // stream and two events) they run next to the gather kernel instead of behind it
       const long total = (long)N * 9 * plane;
-      hipStream_t sg = s;
-      if (aux && ev) {
-        DBM_HIP(hipEventRecord(ev[0], s));
-        DBM_HIP(hipStreamWaitEvent(aux, ev[0], 0));
-        sg = aux;
-      }
-      hipLaunchKernelGGL(deform_goff_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sg, x, off, gcol, w1o, gy, goff, N, C,
+      hipLaunchKernelGGL(deform_goff_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, off, gcol, w1o, gy, goff, N, C,
                          H, W, offsn);
-      if (sg != s) DBM_HIP(hipEventRecord(ev[1], aux));
       if (wide)
         hipLaunchKernelGGL((deform_backward_csr_kernel<CHD, 1024, true>), dim3(N, C / CHD), dim3(1024), lds_det, s, x, off, gcol, w1o,
                            gy, gx, goff, N, C, H, W, offsn);
       else
         hipLaunchKernelGGL((deform_backward_csr_kernel<CH, 1024, true>), dim3(N, C / CH), dim3(1024), lds_det, s, x, off, gcol, w1o,
                            gy, gx, goff, N, C, H, W, offsn);
-      if (sg != s) DBM_HIP(hipStreamWaitEvent(s, ev[1], 0));
     } else {
       DBM_HIP(hipMemset2DAsync(goff, sizeof(float) * offsn, 0, sizeof(float) * 18 * plane, N, s));
       hipLaunchKernelGGL((deform_backward_csr_kernel<CH, 1024, false>), dim3(N, C / CH), dim3(1024), lds, s, x, off, gcol, w1o, gy, gx,
@@ -755,8 +745,7 @@ size_t deform_csr_workspace_floats(int N, int H, int W) {  // offsets, then the 
 }
 
 // Input gradient only: the atomic-free CSR gather above without the offset gradients (which the fused kernels of
-// deform_fused.hip produce).  Returns false when a plane does not fit the kernel's LDS lists (the caller then takes
-// launch_deform_backward).
+// deform_fused.hip produce).  False when a plane does not fit (the caller then takes launch_deform_backward).
 bool deform_input_grad_ok(int C, int H, int W) {
   const long plane = (long)H * W;
   return C % 8 == 0 && sizeof(float) * ((size_t)8 * plane + 10 * plane + 1) <= 150 * 1024;
@@ -781,38 +770,17 @@ void launch_deform_csr_build(const float* off, float* ws, int N, int H, int W, l
   DBM_HIP(hipGetLastError());
 }
 
-void launch_deform_input_grad(const float* x, const float* off, const float* gcol, const float* w1o, const float* gy, float* gx, int N,
-                              int C, int H, int W, long offsn, hipStream_t s, float* ws, bool lists_built) {
+// ws: deform_csr_workspace_floats floats -- the sampling lists are built once per (image, tap) there (unless `lists_built`), then a
+// register-only kernel gathers per (image, 16 channels)
+void launch_deform_input_grad(const float* off, const float* gcol, const float* w1o, const float* gy, float* gx, int N, int C, int H, int W,
+                              long offsn, hipStream_t s, float* ws, bool lists_built) {
   DBM_CHECK(deform_input_grad_ok(C, H, W), "deformable input gradient: plane too large for the CSR kernel");
+  DBM_CHECK(ws && deform_csr_lists_ok(C, H, W), "deformable input gradient: needs a list workspace and C % 16 == 0");
   const long plane = (long)H * W;
-  DBM_CHECK(!lists_built || (ws && deform_csr_lists_ok(C, H, W)), "deformable input gradient: no prebuilt lists for this shape");
-  if (ws && deform_csr_lists_ok(C, H, W)) {
-    // lists built once per (image, tap), then a register-only gather per (image, 16 channels)
-    int* g_offs = (int*)ws;
-    int2* g_ent = (int2*)(ws + (((size_t)N * 9 * (plane + 1) + 1) & ~(size_t)1));
-    if (!lists_built) launch_deform_csr_build(off, ws, N, H, W, offsn, s);
-    hipLaunchKernelGGL((deform_csr_gather_kernel<16, 1024>), dim3(N, C / 16), dim3(1024), 0, s, g_offs, g_ent, gcol, w1o, gy, gx, C,
-                       (int)plane);
-    DBM_HIP(hipGetLastError());
-    return;
-  }
-  constexpr int CH = 8, CHD = 16;
-  const bool wide = C % CHD == 0 && sizeof(float) * ((size_t)CHD * plane + 10 * plane + 1) <= 150 * 1024;
-  const size_t lds = sizeof(float) * ((size_t)(wide ? CHD : CH) * plane + 10 * plane + 1);
-  static bool attr_set = false;
-  if (!attr_set) {
-    DBM_HIP(hipFuncSetAttribute((const void*)deform_backward_csr_kernel<CH, 1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                152 * 1024));
-    DBM_HIP(hipFuncSetAttribute((const void*)deform_backward_csr_kernel<CHD, 1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                152 * 1024));
-    attr_set = true;
-  }
-  if (wide)
-    hipLaunchKernelGGL((deform_backward_csr_kernel<CHD, 1024, true>), dim3(N, C / CHD), dim3(1024), lds, s, x, off, gcol, w1o, gy, gx,
-                       nullptr, N, C, H, W, offsn);
-  else
-    hipLaunchKernelGGL((deform_backward_csr_kernel<CH, 1024, true>), dim3(N, C / CH), dim3(1024), lds, s, x, off, gcol, w1o, gy, gx,
-                       nullptr, N, C, H, W, offsn);
+  int* g_offs = (int*)ws;
+  int2* g_ent = (int2*)(ws + (((size_t)N * 9 * (plane + 1) + 1) & ~(size_t)1));
+  if (!lists_built) launch_deform_csr_build(off, ws, N, H, W, offsn, s);
+  hipLaunchKernelGGL((deform_csr_gather_kernel<16, 1024>), dim3(N, C / 16), dim3(1024), 0, s, g_offs, g_ent, gcol, w1o, gy, gx, C, (int)plane);
   DBM_HIP(hipGetLastError());
 }
 

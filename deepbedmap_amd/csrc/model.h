@@ -12,6 +12,14 @@ struct DevBuf {
   void release();
 };
 
+// A temporary of one call: released when the scope ends, also when a DBM_CHECK throws on the way.
+struct ScopedBuf : DevBuf {
+  ScopedBuf() = default;
+  ScopedBuf(const ScopedBuf&) = delete;
+  ScopedBuf& operator=(const ScopedBuf&) = delete;
+  ~ScopedBuf() { release(); }
+};
+
 struct dbm_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -184,11 +192,50 @@ struct dbm_model {
   virtual void pack_extra(hipStream_t) {}        // model-specific images, same launch point
   // helpers building descriptors
   ConvDesc fwd_desc(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, float* y, long ysn, int N) const;
+  // run_dgrad's `base` for the gradient dy (image stride dysn) -> gx (gxsn): zeroed, s1 = s2 = 1; the caller adds accumulate / mask* / r1*
+  static ConvDesc dgrad_desc(const float* dy, long dysn, float* gx, long gxsn, int N);
   void run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_fwd, hipStream_t s = nullptr) const;
-  // weight gradient of layer L: queued on `batch` (launched later, all layers at once) or run immediately
+  // weight gradient of layer L into its own gradient tensors; run_wgrad queues it on `batch` (launched later, all layers at once) or runs
+  // it immediately
+  WgradDesc wgrad_desc(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, const float* dy, long dysn, int OH, int OW,
+                       int N, float scale) const;
   void run_wgrad(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, const float* dy, long dysn,
                  int OH, int OW, int N, float scale, WgradBatch* batch = nullptr) const;
 };
+
+// ---- the deformable layers' launch sequences (deform_layer.hip): one copy for Generator::forward / backward and the op-level entry points ----
+// Which forms a deformable layer of (C, O) channels takes on an H x W plane.  The only reader of DBM_DEFORM1_PREMUL, DBM_DEFORM1_PREMUL_BWD
+// and DBM_DEFORM_WGRAD_FUSED.
+struct DeformForms {
+  bool fwd_fused;    // the sampler fused into the GEMM, fed from the channels-last input (else: sample matrix + GEMM / GEMV)
+  bool fwd_packed;   // the forward reads the layer's packed image (IgLayer::wf); else the OIHW tensor itself
+  bool bwd_fused;    // the fused backward kernels + the CSR input-gradient gather (else: launch_deform_backward on the sample matrix)
+  bool premul;       // O <= 16 forward: the multiplication before the sampler (needs the z scratch)
+  bool premul_bwd;   // 64 -> 1 backward in premultiplied form, when the forward's z planes are there
+  bool wgrad_fused;  // 64 -> 64 weight gradient with the sampler fused in (no sample matrix)
+};
+DeformForms deform_layer_forms(int C, int O, int H, int W);
+// y (N, O, H, W) = [lrelu](W * sample(x, off) + b).  Fused: reads xt (channels-last input); yt (channels-last output), col (the sample
+// matrix as a by-product) and z (N * 9 * O * H * W floats: the premultiplied form) are optional.  Unfused: reads x, col is required scratch.
+// L: the layer's packed images where f.fwd_packed (the unfused GEMM takes its bias from there); w / bias: the OIHW tensor and the bias.
+void deform_layer_forward(const dbm_model& m, const IgLayer* L, const DeformForms& f, const float* x, const float* xt, const float* off,
+                          long offsn, const float* w, const float* bias, float* y, float* yt, float* col, float* z, int N, int C, int H,
+                          int W, int O, int act, hipStream_t s);
+// Backward of the C -> 1 layer: gx and goff[:, 0:18] overwritten, gw (C * 9) / gb accumulated.  Fused forms: xt, partial
+// (deform_bwd1_partial_floats), csr_ws (deform_csr_workspace_floats; lists_built: its lists are final), z (the forward's premultiplied
+// planes or null) and Gt (N * 9 * H * W floats, with z); the gathering form's offset / weight gradients go to s_goff.  Unfused: x and the
+// sample matrix col; the weight gradient goes to s_wgrad.
+void deform1_backward(const DeformForms& f, const float* x, const float* xt, const float* off, long offsn, const float* w, const float* gy,
+                      const float* z, const float* col, float* gx, float* goff, float* gw, float* gb, float* partial, float* csr_ws,
+                      float* Gt, bool lists_built, int N, int C, int H, int W, hipStream_t s, hipStream_t s_goff, hipStream_t s_wgrad);
+// Data and offset gradients of the 64 -> 64 layer L (1x1 view; ensure_packed_bwd done): gcol (N, C * 9, H, W) scratch, gx and goff[:, 0:18] overwritten
+void deform64_backward_data(const dbm_model& m, const IgLayer& L, const DeformForms& f, const float* x, const float* xt, const float* off,
+                            long offsn, const float* gy, float* gcol, float* gx, float* goff, float* csr_ws, bool lists_built, int N, int H,
+                            int W, hipStream_t s);
+// ... and its weight gradient, gw / gb accumulated: sampler-fused from xt on `s` (partial: deform_wgrad64_partial_floats), or from the sample
+// matrix col through the 1x1 form, queued on `batch` or launched on `s`
+void deform64_wgrad(const dbm_model& m, const IgLayer& L, const DeformForms& f, const float* xt, const float* col, const float* off, long offsn,
+                    const float* gy, float* gw, float* gb, float* partial, int N, int H, int W, hipStream_t s, WgradBatch* batch);
 
 // Everything one forward / backward pass of the generator leaves behind or works in: activations, gradients, scratch, the record of
 // the retained graph and the batches planned over these buffers.  Allocates nothing until a pass sizes it (Generator::ensure_ws).
@@ -262,8 +309,6 @@ struct Generator : dbm_model {
   const float** tf_bsrc = nullptr;
   void pack_extra(hipStream_t s) override;
   bool trunk_fused_ok(int h, int w) const;
-  bool deform_bwd_fused(int H4, int W4) const;
-  bool deform_wgrad_fused(int H4, int W4) const;
   ~Generator() override;
   Generator(dbm_ctx* c, int n, float r, int oc);
   // The passes below run in the workspace they are given, on ctx->stream.

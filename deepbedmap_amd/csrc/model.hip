@@ -330,6 +330,14 @@ ConvDesc dbm_model::fwd_desc(const IgLayer& L, const float* x, long xsn, int Hin
   return d;
 }
 
+ConvDesc dbm_model::dgrad_desc(const float* dy, long dysn, float* gx, long gxsn, int N) {
+  ConvDesc d;
+  memset(&d, 0, sizeof(d));
+  d.x = dy; d.xsn = dysn; d.N = N;
+  d.y = gx; d.ysn = gxsn; d.s1 = 1.f; d.s2 = 1.f;
+  return d;
+}
+
 // Data gradient of layer L.  `base` carries the gradient input (x, xsn = dY and its image stride), the output
 // (y, ysn) and every epilogue field; geometry and weights are filled here.  Hin_fwd/Win_fwd: forward INPUT dims
 // (after upsample), i.e. the dims of the gradient being produced.
@@ -380,8 +388,8 @@ void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_
   }
 }
 
-void dbm_model::run_wgrad(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, const float* dy,
-                          long dysn, int OH, int OW, int N, float scale, WgradBatch* batch) const {
+WgradDesc dbm_model::wgrad_desc(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, const float* dy, long dysn, int OH,
+                                int OW, int N, float scale) const {
   WgradDesc w;
   memset(&w, 0, sizeof(w));
   w.x = x; w.xsn = xsn; w.xsc = Hin * Win; w.Cin = L.Cview; w.Hin = Hin; w.Win = Win; w.ups = ups;
@@ -390,6 +398,12 @@ void dbm_model::run_wgrad(const IgLayer& L, const float* x, long xsn, int Hin, i
   w.N = N; w.scale = scale;
   w.gW = G(L.wi);
   w.gb = L.bi >= 0 ? G(L.bi) : nullptr;
+  return w;
+}
+
+void dbm_model::run_wgrad(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, const float* dy,
+                          long dysn, int OH, int OW, int N, float scale, WgradBatch* batch) const {
+  const WgradDesc w = wgrad_desc(L, x, xsn, Hin, Win, ups, dy, dysn, OH, OW, N, scale);
   if (batch) batch->add(w);
   else launch_wgrad(w, ctx->stream);
 }

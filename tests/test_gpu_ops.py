@@ -200,10 +200,14 @@ def test_conv2d_backward(dbm, case):
 @pytest.mark.parametrize("O,scale,shape", [(64, 0.3, (2, 12, 10)), (1, 0.3, (2, 12, 10)), (64, 3.0, (2, 12, 10)), (1, 3.0, (2, 12, 10)),
                                            # the model's own plane: 3 x 1296 positions = 60.75 tiles of the fused kernels (ragged
                                            # last workgroup, tiles straddling images), CSR lists of a full 36 x 36 plane
-                                           (64, 1.0, (3, 36, 36)), (1, 1.0, (3, 36, 36))])
+                                           (64, 1.0, (3, 36, 36)), (1, 1.0, (3, 36, 36)),
+                                           # 2304 positions, the first square plane past the CSR input-gradient kernel's 2133: the
+                                           # unfused backward (sample matrix, launch_deform_backward, the GEMV's weight gradient)
+                                           (64, 1.0, (1, 48, 48)), (1, 1.0, (1, 48, 48))])
 def test_deform_conv_forward_backward(dbm, O, scale, shape):
     """final_conv_layer1 (64->64) and final_conv_layer2 (64->1); scale 3.0 drives samples out of the image
-    so that the border clipping and the coordinate-gradient masks are exercised."""
+    so that the border clipping and the coordinate-gradient masks are exercised.  The entry points run the generator's own
+    launch sequences (deform_layer.hip)."""
     d, _lib, ctx = dbm
     (N, H, W), Cc = shape, 64
     rs = np.random.RandomState(int(scale * 10) + O)
