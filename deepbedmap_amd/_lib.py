@@ -111,6 +111,10 @@ SIGNATURES = {
     "dbm_points_region": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int],
     "dbm_points_blockmedian": [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_size_t,
                                C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int],
+    "dbm_grid_tension_surface": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                 C.POINTER(C.c_double)],
+    "dbm_grid_distance_mask": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int],
+    "dbm_grid_to_pixel": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_double, C.c_void_p],
     "dbm_adam_setup": [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double],
     "dbm_adam_update": [C.c_void_p, C.c_double],
     "dbm_discriminator_step": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -135,7 +139,8 @@ class DbmError(RuntimeError):
     # libdbm status.  7: a persistent kernel timed out; the call that reports it enqueued nothing (re-issue it), the
     # optimizer updates queued since the event were skipped (`Context.timeout_info()`).  8: the same in a data-parallel
     # run -- fatal, the replicas have diverged.  9 (dbm_adam_update only): the gradients about to be applied come from a
-    # void pass; nothing was applied -- repeat forward + backward, then update.
+    # void pass; nothing was applied -- repeat forward + backward, then update.  10 (dbm_grid_tension_surface only): the solve did not
+    # converge within max_iter; the output holds the last iterate.
     code = None
 
 

@@ -1209,6 +1209,55 @@ int dbm_points_blockmedian(dbm_ctx* ctx, const double* points, size_t n, const d
   DBM_API_END
 }
 
+// ---- from block medians to the 250 m raster (surface.hip, track.hip) ----
+int dbm_grid_tension_surface(dbm_ctx* ctx, const float* data_dev, long H, long W, double tension, double tol, int max_iter, float* out_dev,
+                             double info[4]) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && data_dev != nullptr && out_dev != nullptr && info != nullptr, "dbm_grid_tension_surface: NULL argument");
+  DBM_CHECK(H >= 3 && W >= 3, "dbm_grid_tension_surface: the raster needs at least 3 x 3 nodes");
+  DBM_CHECK(H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31), "dbm_grid_tension_surface: H W must stay below 2^31 nodes");
+  DBM_CHECK(tension > 0.0 && tension <= 1.0, "dbm_grid_tension_surface: the tension must lie in (0, 1]");
+  DBM_CHECK(tol > 0.0 && tol < 1.0, "dbm_grid_tension_surface: tol must lie in (0, 1)");
+  DBM_CHECK(max_iter >= 1 && max_iter <= 1000000, "dbm_grid_tension_surface: max_iter must lie in 1..1000000");
+  ScopedBuf ws;   // this call's own: x, r, p, Ap (float64 planes), the free-node mask, the partial sums; released on every path
+  ws.ensure((surface_workspace(H, W) + 3) / 4);
+  SurfaceLaunch a;
+  a.data = data_dev;
+  a.H = H; a.W = W;
+  a.tension = tension; a.tol = tol;
+  a.max_iter = max_iter;
+  a.out = out_dev;
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  const bool converged = surface_solve(a, ws.p, ctx->stream, info);
+  if (!converged)
+    throw DbmError(10, "dbm_grid_tension_surface: not converged in " + std::to_string(max_iter) + " iterations (relative residual " +
+                           std::to_string(info[1]) + ", tol " + std::to_string(tol) + "); out_dev holds the last iterate");
+  DBM_API_END
+}
+
+int dbm_grid_distance_mask(dbm_ctx* ctx, const float* data_dev, float* grid_dev, long H, long W, int radius) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && data_dev != nullptr && grid_dev != nullptr, "dbm_grid_distance_mask: NULL argument");
+  DBM_CHECK(H >= 1 && W >= 1 && H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31), "dbm_grid_distance_mask: H W must lie in 1..2^31 - 1");
+  DBM_CHECK(radius >= 0 && radius <= 32, "dbm_grid_distance_mask: the radius must lie in 0..32 nodes");
+  DBM_CHECK((const void*)data_dev != (const void*)grid_dev, "dbm_grid_distance_mask: the grid must not be the data raster");
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  launch_distance_mask(data_dev, grid_dev, H, W, radius, ctx->stream);
+  DBM_API_END
+}
+
+int dbm_grid_to_pixel(dbm_ctx* ctx, const float* in_dev, long H, long W, double threshold, float* out_dev) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && in_dev != nullptr && out_dev != nullptr, "dbm_grid_to_pixel: NULL argument");
+  DBM_CHECK(H >= 2 && W >= 2, "dbm_grid_to_pixel: the grid needs at least 2 x 2 nodes");
+  DBM_CHECK(H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31), "dbm_grid_to_pixel: H W must stay below 2^31 nodes");
+  DBM_CHECK(threshold > 0.0 && threshold <= 1.0, "dbm_grid_to_pixel: threshold must lie in (0, 1]");
+  DBM_CHECK((const void*)in_dev != (const void*)out_dev, "dbm_grid_to_pixel: the output must not be the input");
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  launch_grid_to_pixel(in_dev, H, W, threshold, out_dev, ctx->stream);
+  DBM_API_END
+}
+
 // ---- optimizer ----
 int dbm_adam_setup(dbm_model* m, double alpha, double beta1, double beta2, double eps) {
   DBM_API_BEGIN(m->ctx)

@@ -260,6 +260,10 @@ struct TrackLaunch {
 int grid_track_blocks(long n);   // workgroups of the sampling launch (depends on n only): partials needed
 void launch_grid_track(const TrackLaunch& a, double* stats, hipStream_t s);
 
+// Gridline -> pixel registration (track.hip; dbm_grid_to_pixel, `grdsample -T`): out (H - 1, W - 1) = the bicubic interpolant of
+// launch_grid_track (same weights, ghost nodes, NaN / threshold rule) at the cell centres (c + 1/2, r + 1/2), rounded to float32 once
+void launch_grid_to_pixel(const float* in, long H, long W, double threshold, float* out, hipStream_t s);
+
 // Cutting tiles from a resident raster (tile.hip; dbm_grid_tile): out[k * out_stride + r * out_w + c] for n windows of (out_h, out_w).
 // mode 1: windows = n x (left, bottom, right, top) doubles, bilinear at np.linspace coordinates of resolution res; mode 0: windows =
 // n x (row0, col0, row step, column step) int64, a copy (every node inside the raster: checked by the caller).  counts (n ints,
@@ -354,3 +358,19 @@ size_t blockmedian_workspace(long n, long hw);   // bytes
 void blockmedian_carve(BlockMedianLaunch& a, void* ws);
 void launch_blockmedian_count(const BlockMedianLaunch& a, hipStream_t s);
 void launch_blockmedian_select(const BlockMedianLaunch& a, const unsigned* totals, hipStream_t s);
+
+// Tension-spline surface through the non-NaN nodes of a float32 raster (surface.hip; dbm_grid_tension_surface), float64 conjugate
+// gradients on the device; ws: surface_workspace(H, W) bytes, 256-byte aligned.  surface_solve synchronises the stream, fills info =
+// {iterations, |r| / |b|, constraint nodes, free nodes}, always writes out (the last iterate) and returns whether |r| <= tol |b| was
+// reached within max_iter; it throws status 1 before writing anything when no node is a constraint.
+struct SurfaceLaunch {
+  const float* data;
+  long H, W;
+  double tension, tol;
+  int max_iter;
+  float* out;
+};
+size_t surface_workspace(long H, long W);
+bool surface_solve(const SurfaceLaunch& a, void* ws, hipStream_t s, double info[4]);
+// grid[r, c] = NaN unless a non-NaN node of data lies within `radius` nodes (Euclidean, integer arithmetic) (dbm_grid_distance_mask)
+void launch_distance_mask(const float* data, float* grid, long H, long W, int radius, hipStream_t s);

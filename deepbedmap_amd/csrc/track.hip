@@ -192,6 +192,15 @@ __global__ __launch_bounds__(TRACK_THREADS) void grid_track_finish_kernel(const 
   stats[5] = m.n > 0.0 ? sqrt(m.ss / m.n) : nan;
 }
 
+// `grdsample -T`: one lane per cell centre of the unit-geometry gridline grid
+__global__ __launch_bounds__(TRACK_THREADS) void grid_to_pixel_kernel(TrackLaunch a, float* __restrict__ out) {
+  const long wo = a.W - 1, stride = (long)gridDim.x * TRACK_THREADS;
+  for (long i = (long)blockIdx.x * TRACK_THREADS + threadIdx.x; i < a.n; i += stride) {
+    const long r = i / wo, c = i - r * wo;
+    out[i] = (float)sample<2>(a, (double)c + 0.5, (double)r + 0.5);
+  }
+}
+
 }  // namespace
 
 int grid_track_blocks(long n) {
@@ -214,4 +223,22 @@ void launch_grid_track(const TrackLaunch& a, double* stats, hipStream_t s) {
     hipLaunchKernelGGL(grid_track_finish_kernel, dim3(1), dim3(TRACK_THREADS), 0, s, a.part, a.n > 0 ? blocks : 0, stats);
     DBM_HIP(hipGetLastError());
   }
+}
+
+void launch_grid_to_pixel(const float* in, long H, long W, double threshold, float* out, hipStream_t s) {
+  TrackLaunch a;
+  a.grid = in;
+  a.H = H; a.W = W;
+  a.x0 = 0.0; a.y0 = 0.0; a.dx = 1.0; a.dy = 1.0;
+  a.tlo = 0.0; a.thi = (double)(W - 1);
+  a.slo = 0.0; a.shi = (double)(H - 1);
+  a.points = nullptr;
+  a.n = (H - 1) * (W - 1);
+  a.ncol = 2;
+  a.interp = 2;
+  a.threshold = threshold;
+  a.z_out = nullptr;
+  a.part = nullptr;
+  hipLaunchKernelGGL(grid_to_pixel_kernel, dim3(grid_track_blocks(a.n)), dim3(TRACK_THREADS), 0, s, a, out);
+  DBM_HIP(hipGetLastError());
 }

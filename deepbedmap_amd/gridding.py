@@ -6,8 +6,15 @@ with `gmt info -I` (get_region) and thins the cloud with `gmt.blockmedian` befor
 the largest tables of the workflow -- tens of millions of float64 rows per survey -- run here on the GPU (dbm_points_polar_stereographic,
 dbm_points_region, dbm_points_blockmedian, include/dbm.h); what they produce is what `grdtrack`, `DevicePoints`, `make_test_area_score`
 (the table) and `Raster`, `tile_training_set` (the raster) take.  Semantics, the tie rule and what is unverified against GMT: DESIGN.md
-"Gridding point clouds".  NOT built: GMT `surface`, `gmt info -Is<inc>`, the CSV reading of ascii_to_xyz, `grdsample -T`.  No CPU
-fallback: without a GPU every call that computes raises DbmError.
+"Gridding point clouds".
+
+The second half of xyz_to_grid (data_prep.py:409-441: `gmt.surface(T=0.35, M="3c")`, then `grdsample -T`) runs on the GPU as well:
+`tension_surface` interpolates the block-median raster with a tension spline (dbm_grid_tension_surface: float64 conjugate gradients on
+the device), `mask_far_from_data` blanks nodes further than three cells from data (dbm_grid_distance_mask), `to_pixel_registration`
+resamples gridline -> pixel (dbm_grid_to_pixel) and `xyz_to_grid` chains all four stages without leaving the device.  The surface is this
+project's own, completely defined one -- constraints on nodes, natural edges, a residual stopping rule -- NOT a reproduction of GMT
+`surface`: DESIGN.md "Tension surface" lists every difference.  NOT built: `gmt info -Is<inc>`, the CSV reading of ascii_to_xyz.  No
+CPU fallback: without a GPU every call that computes raises DbmError.
 """
 import ctypes as C
 
@@ -15,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from .evaluation import DevicePoints, GridGeometry
-from .srgan import DeviceArray
+from .srgan import DeviceArray, to_device
 
 # EPSG method 9829 parameters {a, 1/f, latitude of true scale, longitude of origin, false easting, false northing}
 EPSG3031 = (6378137.0, 298.257223563, -71.0, 0.0, 0.0, 0.0)
@@ -238,8 +245,129 @@ def blockmedian(table, region, spacing=250, ctx=None):
 
 def blockmedian_grid(points, region, spacing=250, counts=False, download=True, ctx=None):
     """The block medians of z as a raster: (grid (H, W) float32 with NaN in empty blocks, GridGeometry[, counts (H, W) int32]).  With
-    download=False the grid is a DeviceArray, used in place by `Raster`, `grdtrack` and `standard_deviation_2d`.  This is the cloud
-    binned, NOT interpolated: GMT `surface` is not built."""
+    download=False the grid is a DeviceArray, used in place by `Raster`, `grdtrack`, `standard_deviation_2d` and `tension_surface`.
+    This is the cloud binned, NOT interpolated: `tension_surface` / `xyz_to_grid` fill the empty blocks."""
     _, grid, cnt, geometry = _blockmedian(points, region, spacing, True, bool(counts), ctx)
     g = grid.get() if download else grid
     return (g, geometry, cnt) if counts else (g, geometry)
+
+
+def _resident(grid, ctx, what):
+    """(DeviceArray (H, W), ctx): a DeviceArray is used in place, anything else is uploaded as float32"""
+    if isinstance(grid, DeviceArray):
+        if len(grid.shape) != 2:
+            raise ValueError(f"{what}: the grid must be (H, W); got {grid.shape}")
+        return grid, grid.ctx
+    host = np.asarray(grid, dtype=np.float32)
+    if host.ndim != 2:
+        raise ValueError(f"{what}: the grid must be (H, W); got {host.shape}")
+    ctx = ctx or _lib.default_context()
+    return to_device(host, ctx), ctx
+
+
+def _surface_arguments(shape, tension, tol, max_iter):
+    H, W = (int(v) for v in shape)
+    if H < 3 or W < 3:
+        raise ValueError(f"tension_surface: the grid needs at least 3 x 3 nodes, got {H} x {W}")
+    if H * W >= 2 ** 31:
+        raise ValueError(f"tension_surface: {H} x {W} nodes: the grid must stay below 2^31 nodes")
+    tension, tol = float(tension), float(tol)
+    if not (0.0 < tension <= 1.0):
+        raise ValueError(f"tension_surface: the tension must lie in (0, 1], got {tension}")
+    if not (0.0 < tol < 1.0):
+        raise ValueError(f"tension_surface: tol must lie in (0, 1), got {tol}")
+    if int(max_iter) != max_iter or not (1 <= int(max_iter) <= 10 ** 6):
+        raise ValueError(f"tension_surface: max_iter must be an integer in 1..10^6, got {max_iter!r}")
+    return H, W, tension, tol, int(max_iter)
+
+
+def tension_surface(grid, tension=0.35, tol=1e-9, max_iter=20000, download=True, ctx=None):
+    """The `gmt.surface(T=tension)` step of xyz_to_grid (data_prep.py:410-419) as this project defines it (DESIGN.md "Tension surface",
+    include/dbm.h dbm_grid_tension_surface): the minimiser of (1 - T) bending + T stretching energy of the differences that fit inside
+    the grid, equal to `grid` on its non-NaN nodes (constraints ON nodes, natural edges; NOT GMT's off-node constraints and edge rows).
+    grid: (H, W) array or DeviceArray with NaN in the free nodes -- what `blockmedian_grid` returns.  Returns (surface, info): surface
+    a float32 array, or a DeviceArray with download=False; info = {"iterations", "residual" (final |r| / |b|), "constraints", "free"}.
+    Raises ValueError for arguments out of range, DbmError (code 1) for a grid without data and DbmError (code 10) if the conjugate
+    gradients have not reached tol within max_iter."""
+    shape = grid.shape if isinstance(grid, DeviceArray) else np.shape(grid)
+    if len(shape) != 2:
+        raise ValueError(f"tension_surface: the grid must be (H, W); got {tuple(shape)}")
+    H, W, tension, tol, max_iter = _surface_arguments(shape, tension, tol, max_iter)
+    dgrid, ctx = _resident(grid, ctx, "tension_surface")
+    out = DeviceArray((H, W), ctx)
+    info = np.zeros(4, dtype=np.float64)
+    _lib.check(_lib.lib().dbm_grid_tension_surface(ctx.handle, C.c_void_p(dgrid.ptr), H, W, tension, tol, max_iter, C.c_void_p(out.ptr),
+                                                   info.ctypes.data_as(C.POINTER(C.c_double))), ctx.handle)
+    out._gen += 1
+    report = {"iterations": int(info[0]), "residual": float(info[1]), "constraints": int(info[2]), "free": int(info[3])}
+    return (out.get() if download else out), report
+
+
+def _mask_radius(radius):
+    if int(radius) != radius or not (0 <= int(radius) <= 32):
+        raise ValueError(f"mask_far_from_data: the radius must be an integer number of cells in 0..32, got {radius!r}")
+    return int(radius)
+
+
+def mask_far_from_data(surface, data, radius=3):
+    """The `M="3c"` of `gmt.surface` (data_prep.py:416): NaN wherever no non-NaN node of `data` lies within `radius` cells (Euclidean
+    node-to-node distance: this project's reading of GMT's `c` unit).  surface, data: (H, W) arrays or DeviceArrays.  A DeviceArray
+    `surface` is masked IN PLACE and returned; an array is copied and a masked float32 array returned."""
+    radius = _mask_radius(radius)
+    sshape = surface.shape if isinstance(surface, DeviceArray) else np.shape(surface)
+    dshape = data.shape if isinstance(data, DeviceArray) else np.shape(data)
+    if len(sshape) != 2 or tuple(sshape) != tuple(dshape):
+        raise ValueError(f"mask_far_from_data: surface and data must have the same (H, W) shape; got {tuple(sshape)} and {tuple(dshape)}")
+    if surface is data:
+        raise ValueError("mask_far_from_data: the surface must not be the data raster")
+    ctx = surface.ctx if isinstance(surface, DeviceArray) else (data.ctx if isinstance(data, DeviceArray) else None)
+    dsurf, ctx = _resident(surface, ctx, "mask_far_from_data")
+    ddata, _ = _resident(data, ctx, "mask_far_from_data")
+    if ddata.ctx is not dsurf.ctx:
+        raise ValueError("mask_far_from_data: the surface and the data live on different contexts")
+    H, W = (int(v) for v in sshape)
+    _lib.check(_lib.lib().dbm_grid_distance_mask(ctx.handle, C.c_void_p(ddata.ptr), C.c_void_p(dsurf.ptr), H, W, radius), ctx.handle)
+    dsurf._gen += 1
+    return dsurf if isinstance(surface, DeviceArray) else dsurf.get()
+
+
+def to_pixel_registration(grid, geometry, threshold=0.5, download=None, ctx=None):
+    """`gmt grdsample -T` (data_prep.py:420-441): the gridline-registered (H, W) grid resampled at its cell centres with `grdtrack`'s
+    bicubic interpolant (ghost nodes, NaN rule and threshold included).  Returns (grid (H - 1, W - 1), GridGeometry(x0 + dx / 2,
+    y0 + dy / 2, dx, dy, "pixel")): a DeviceArray if given one (download=None) or with download=False, else a float32 array."""
+    if not isinstance(geometry, GridGeometry):
+        raise TypeError("geometry must be a GridGeometry")
+    if geometry.registration != "gridline":
+        raise ValueError("to_pixel_registration: the grid must be gridline-registered")
+    if not (0.0 < float(threshold) <= 1.0):
+        raise ValueError(f"threshold must lie in (0, 1], got {threshold}")
+    shape = grid.shape if isinstance(grid, DeviceArray) else np.shape(grid)
+    if len(shape) != 2 or shape[0] < 2 or shape[1] < 2:
+        raise ValueError(f"to_pixel_registration: the grid must be (H, W) with at least 2 x 2 nodes; got {tuple(shape)}")
+    if download is None:
+        download = not isinstance(grid, DeviceArray)
+    dgrid, ctx = _resident(grid, ctx, "to_pixel_registration")
+    H, W = dgrid.shape
+    out = DeviceArray((H - 1, W - 1), ctx)
+    _lib.check(_lib.lib().dbm_grid_to_pixel(ctx.handle, C.c_void_p(dgrid.ptr), H, W, float(threshold), C.c_void_p(out.ptr)), ctx.handle)
+    out._gen += 1
+    pixel = GridGeometry(x0=geometry.x0 + geometry.dx / 2, y0=geometry.y0 + geometry.dy / 2, dx=geometry.dx, dy=geometry.dy,
+                         registration="pixel")
+    return (out.get() if download else out), pixel
+
+
+def xyz_to_grid(xyz_data, region, spacing=250, tension=0.35, mask_cell_radius=3, download=True, ctx=None):
+    """xyz_to_grid (data_prep.py:381-441) without its `outfile`: block medians on the gridline grid of `spacing` over `region`
+    (`blockmedian_grid`), the tension surface through them (`tension_surface`, its defaults for tol and max_iter), the distance mask
+    (`mask_far_from_data`; mask_cell_radius=None skips it) and the pixel-registered resampling (`to_pixel_registration`).  Nothing
+    leaves the device between the stages.  xyz_data: (n, 3) array, DataFrame with columns x, y, z, or DevicePoints.  Returns
+    (grid (H - 1, W - 1), GridGeometry, pixel-registered): a float32 array, or a DeviceArray with download=False.  Write it with
+    `save_array_to_grid`.  The result is this project's surface, not GMT's (DESIGN.md "Tension surface")."""
+    if mask_cell_radius is not None:
+        mask_cell_radius = _mask_radius(mask_cell_radius)
+    _surface_arguments(block_shape(region, spacing), tension, 1e-9, 20000)
+    medians, geometry = blockmedian_grid(xyz_data, region, spacing, download=False, ctx=ctx)
+    surface, _ = tension_surface(medians, tension=tension, download=False)
+    if mask_cell_radius is not None:
+        mask_far_from_data(surface, medians, mask_cell_radius)
+    return to_pixel_registration(surface, geometry, download=download)

@@ -20,7 +20,8 @@
  *     dbm_adam_update is the other exception: whenever an event has been handled (by any call) since the model's gradient arena
  *     was last cleared, the arena may hold the sums of a void pass -- it returns status 9, applies nothing, and the caller clears
  *     the gradients and repeats forward + backward before updating (the step entry points clear them themselves).  Status 8:
- *     the same in a data-parallel run, where a local retry cannot keep the replicas identical -- fatal, abort the job;
+ *     the same in a data-parallel run, where a local retry cannot keep the replicas identical -- fatal, abort the job.  Status 10
+ *     (dbm_grid_tension_surface only): the solve did not converge within max_iter; the output holds the last iterate;
  *   - tensors are NCHW float32, C-contiguous; weights OIHW, exactly the arrays stored by
  *     chainer.serializers.save_npz (key layout: SURVEY.md Appendix B);
  *   - pointers are HOST pointers unless flags contains DBM_DEVICE_PTRS, in which case they are
@@ -331,8 +332,10 @@ int dbm_grid_rolling_std(dbm_ctx* ctx, const float* in_dev, long H, long W, int 
 /* ---- gridding: survey point clouds -> the `points` table and the 250 m ground-truth raster (data_prep.py:322-334 the
  * `filters.reprojection` step of ascii_to_xyz; :353-378 get_region; :406-407 the `gmt.blockmedian` preprocessing of xyz_to_grid) ----
  * Point tables are C-contiguous float64 (n, ncol), as dbm_grid_track takes them; all arithmetic is float64.  flags: DBM_DEVICE_PTRS =
- * the table arguments are device pointers; otherwise host pointers, staged, and the call synchronises.  NOT built: GMT
- * `surface`, `gmt info -Is<inc>` (the surface-friendly widening), the CSV reading of ascii_to_xyz, `grdsample -T`.
+ * the table arguments are device pointers; otherwise host pointers, staged, and the call synchronises.  NOT built:
+ * `gmt info -Is<inc>` (the surface-friendly widening) and the CSV reading of ascii_to_xyz.  The second half of xyz_to_grid -- a tension
+ * surface through the block medians, the distance mask and `grdsample -T` -- is the next group of entry points (it is this project's own,
+ * fully defined surface, NOT a reproduction of GMT `surface`: DESIGN.md 6f).
  *
  * dbm_points_polar_stereographic (data_prep.py:322-334, what pyproj's EPSG:4326 -> EPSG:3031 transformer computes): EPSG method 9829
  * (Polar Stereographic, variant B), south-pole case, Guidance Note 7-2.  Columns 0 and 1 -- longitude, latitude in degrees -- become
@@ -374,6 +377,45 @@ int dbm_points_region(dbm_ctx* ctx, const double* points, size_t n, int ncol, do
                       int flags);
 int dbm_points_blockmedian(dbm_ctx* ctx, const double* points, size_t n, const double region[4], double spacing, double* table_out,
                            size_t table_capacity, int64_t* n_blocks_out, float* grid_dev, int* counts_dev, int flags);
+
+/* ---- from block medians to the 250 m raster: the second half of xyz_to_grid (data_prep.py:410-419 `gmt.surface(T=0.35, M="3c")`,
+ * :420-441 `grdsample -T`) ----
+ * dbm_grid_tension_surface (data_prep.py:410-419).  data_dev: float32 (H, W), device, square cells; NaN = free node, any other value =
+ * constraint (what dbm_points_blockmedian writes to grid_dev).  out_dev (H, W, device) = the unique minimiser u, with u = data on the
+ * constraint nodes, of
+ *     E(u) = (1 - T) (sum sxx^2 + sum syy^2 + 2 sum sxy^2) + T (sum sx^2 + sum sy^2),   T = tension,
+ * sxx[r, c] = u[r, c-1] - 2 u[r, c] + u[r, c+1] for 1 <= c <= W-2, syy the same along rows, sxy[r, c] = u[r+1, c+1] - u[r+1, c] -
+ * u[r, c+1] + u[r, c] for r <= H-2, c <= W-2, sx, sy the first differences.  A difference whose stencil does not fit inside the grid does
+ * not exist: that is the whole boundary condition (the plate's natural free edge, no ghost rows).  In the interior the Euler equation is
+ * GMT's, (1 - T) del^4 u - T del^2 u = 0 (at T = 0.35: 14.4 at the node, -5.55 at the four neighbours, 1.3 at the diagonals, 0.65 at
+ * distance two).  Solved in float64: the data are shifted by the value m of the constraint node with the lowest row-major index,
+ * A_FF x = b = -[A (d - m on constraints, 0 elsewhere)]_F by Jacobi-preconditioned conjugate gradients from x = 0 until |r| <= tol |b|
+ * (the recursively updated residual; b = 0: zero iterations, no division), u = x + m on free nodes, rounded to float32 once; constraint
+ * nodes are copied bit for bit.  No float atomics, launch shapes depend on H and W only: the same bytes from call to call.  The residual
+ * is read back every 32 iterations; the iterations stop on the device at the one that converged.  info (HOST, 4 doubles) =
+ * {iterations, final |r| / |b| (0 for b = 0), constraint nodes, free nodes}.  The call allocates its workspace (33 bytes per node),
+ * frees it on every path, and synchronises.
+ * DIFFERENT FROM GMT `surface`: constraints sit ON nodes (a block median's sub-cell offset is ignored: no Briggs off-node
+ * terms); natural boundary rows instead of GMT's edge conditions; no plane detrending, only the constant shift; a residual stopping rule
+ * instead of GMT's per-node change limit; no multigrid schedule (it changes the path, not the minimiser).  Results differ from GMT's
+ * wherever data do not sit on nodes; the reference's nine-number doctest (data_prep.py:393-404) is not reproduced.
+ * Status 1 (refused, nothing written): H or W < 3, H W >= 2^31, tension outside (0, 1] (T = 0 needs three non-collinear constraints
+ * and is left out), tol outside (0, 1), max_iter outside 1..10^6, NULL pointers, no constraint node (found by one counting launch).
+ * Status 10: not converged within max_iter; out_dev holds the last iterate and info is filled.
+ *
+ * dbm_grid_distance_mask (`M="3c"`): grid_dev[r, c] (device, in place) becomes NaN unless some non-NaN node (r', c') of data_dev has
+ * (r - r')^2 + (c - c')^2 <= radius^2 (integers).  The Euclidean node-to-node distance is this project's reading of GMT's `c` unit
+ * (cells); GMT measures from the data POINTS, which sit up to half a cell from their nodes.  Asynchronous.  Status 1: radius outside
+ * 0..32, grid_dev == data_dev, NULL pointers, H W outside 1..2^31 - 1.
+ *
+ * dbm_grid_to_pixel (`grdsample -T`, data_prep.py:420-441): out_dev (H - 1, W - 1) = dbm_grid_track's bicubic interpolant (same Keys
+ * weights, linear ghost nodes, NaN nodes and threshold rule) of in_dev (H, W) at the cell centres, node coordinates (c + 1/2, r + 1/2),
+ * rounded to float32 once: the gridline-registered grid becomes the pixel-registered grid of the same region, node (0, 0) at
+ * (x0 + dx / 2, y0 + dy / 2).  Asynchronous.  Status 1: H or W < 2, H W >= 2^31, threshold outside (0, 1], out_dev == in_dev, NULL. */
+int dbm_grid_tension_surface(dbm_ctx* ctx, const float* data_dev, long H, long W, double tension, double tol, int max_iter,
+                             float* out_dev, double info[4]);
+int dbm_grid_distance_mask(dbm_ctx* ctx, const float* data_dev, float* grid_dev, long H, long W, int radius);
+int dbm_grid_to_pixel(dbm_ctx* ctx, const float* in_dev, long H, long W, double threshold, float* out_dev);
 
 /* ---- optimizer ---- */
 /* chainer.optimizers.Adam(alpha, eps=1e-8).setup(model): srgan_train.py:1043-1048 */
