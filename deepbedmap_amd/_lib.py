@@ -111,6 +111,11 @@ SIGNATURES = {
     "dbm_points_region": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int],
     "dbm_points_blockmedian": [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_size_t,
                                C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int],
+    "dbm_text_count_lines": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_int64), C.c_int],
+    "dbm_text_parse": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t,
+                       C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_int],
+    "dbm_text_columns": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                         C.POINTER(C.c_int)],
     "dbm_grid_tension_surface": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_double, C.c_double, C.c_int, C.c_void_p,
                                  C.POINTER(C.c_double)],
     "dbm_grid_distance_mask": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int],

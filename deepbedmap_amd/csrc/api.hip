@@ -1209,6 +1209,145 @@ int dbm_points_blockmedian(dbm_ctx* ctx, const double* points, size_t n, const d
   DBM_API_END
 }
 
+// ---- reading survey text tables (text.hip) ----
+static void text_arguments(const char* who, dbm_ctx* ctx, const void* text, size_t nbytes, int separator, int flags) {
+  const std::string w(who);
+  DBM_CHECK(ctx != nullptr, w + ": NULL context");
+  DBM_CHECK(separator == ',' || separator == '\t' || separator == DBM_TEXT_SEP_WHITESPACE,
+            w + ": the separator must be ',', a tab or DBM_TEXT_SEP_WHITESPACE");
+  DBM_CHECK(nbytes == 0 || text != nullptr, w + ": NULL text");
+  DBM_CHECK(!(flags & DBM_DEVICE_PTRS) || ((uintptr_t)text & 15) == 0, w + ": a device text pointer must be 16-byte aligned");
+}
+
+// the text on the device (host text: staged in `staged`, released with it) and the structure pass behind it; totals = {lines, non-blank}
+static void text_structure(dbm_ctx* ctx, TextLaunch& a, const void* text, size_t nbytes, int separator, int flags, ScopedBuf& staged,
+                           unsigned long long totals[2]) {
+  a.len = nbytes;
+  a.sep = separator;
+  if (flags & DBM_DEVICE_PTRS) {
+    a.text = (const unsigned char*)text;
+  } else {
+    staged.ensure(nbytes / 4 + 4);
+    DBM_HIP(hipMemcpyAsync(staged.p, text, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    a.text = (const unsigned char*)staged.p;
+  }
+  ctx->points_tmp.ensure((text_structure_workspace(nbytes) + 3) / 4);
+  text_structure_carve(a, ctx->points_tmp.p);
+  launch_text_structure(a, ctx->stream);
+  DBM_HIP(hipMemcpyAsync(totals, a.totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+}
+
+int dbm_text_count_lines(dbm_ctx* ctx, const void* text, size_t nbytes, int separator, int64_t* counts_out, int flags) {
+  DBM_API_BEGIN(ctx)
+  text_arguments("dbm_text_count_lines", ctx, text, nbytes, separator, flags);
+  DBM_CHECK(counts_out != nullptr, "dbm_text_count_lines: NULL counts_out");
+  counts_out[0] = counts_out[1] = 0;
+  if (nbytes == 0) return 0;
+  TextLaunch a = {};
+  ScopedBuf staged;
+  unsigned long long totals[2];
+  text_structure(ctx, a, text, nbytes, separator, flags, staged, totals);
+  counts_out[0] = (int64_t)totals[0];
+  counts_out[1] = (int64_t)totals[1];
+  DBM_API_END
+}
+
+int dbm_text_parse(dbm_ctx* ctx, const void* text, size_t nbytes, int separator, int skip, int nfields, uint64_t use_mask,
+                   const char* na_values, int n_na, double* table_out, size_t table_capacity, int64_t* repair_out, size_t repair_capacity,
+                   int64_t* result_out, int flags) {
+  DBM_API_BEGIN(ctx)
+  text_arguments("dbm_text_parse", ctx, text, nbytes, separator, flags);
+  DBM_CHECK(result_out != nullptr, "dbm_text_parse: NULL result_out");
+  DBM_CHECK(skip >= 0, "dbm_text_parse: skip must not be negative");
+  DBM_CHECK(nfields >= 1 && nfields <= DBM_TEXT_MAX_FIELDS, "dbm_text_parse: nfields must lie in 1..DBM_TEXT_MAX_FIELDS");
+  DBM_CHECK(use_mask != 0 && (nfields == 64 || (use_mask >> nfields) == 0), "dbm_text_parse: use_mask must mark at least one of the nfields fields and no other");
+  DBM_CHECK(n_na >= 0 && n_na <= DBM_TEXT_MAX_NA && (n_na == 0 || na_values != nullptr), "dbm_text_parse: n_na must lie in 0..DBM_TEXT_MAX_NA");
+  DBM_CHECK(table_capacity == 0 || table_out != nullptr, "dbm_text_parse: NULL table_out");
+  DBM_CHECK(repair_capacity == 0 || repair_out != nullptr, "dbm_text_parse: NULL repair_out");
+  TextLaunch a = {};
+  a.skip1 = (unsigned long long)skip + 1ull;
+  a.nfields = nfields;
+  a.use_mask = use_mask;
+  a.nuse = __builtin_popcountll(use_mask);
+  a.n_na = n_na;
+  for (int k = 0; k < n_na; ++k) {
+    const size_t len = strlen(na_values);
+    DBM_CHECK(len >= 1 && len <= DBM_TEXT_MAX_NA_BYTES, "dbm_text_parse: an NA string must hold 1..DBM_TEXT_MAX_NA_BYTES bytes");
+    a.na_len[k] = (int)len;
+    for (size_t i = 0; i < len; ++i)
+      (i < 8 ? a.na_lo[k] : a.na_hi[k]) |= (unsigned long long)(unsigned char)na_values[i] << (8 * (i & 7));
+    na_values += len + 1;
+  }
+  result_out[0] = result_out[1] = result_out[3] = 0;
+  result_out[2] = -1;
+  if (nbytes == 0) return 0;
+  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
+  ScopedBuf staged, scratch, list, table;
+  unsigned long long totals[5];
+  text_structure(ctx, a, text, nbytes, separator, flags, staged, totals);
+  if (totals[1] < a.skip1) return 0;
+  a.ncand = totals[1] - a.skip1;
+  result_out[3] = (int64_t)a.ncand;
+  if (a.ncand == 0) return 0;
+  scratch.ensure((text_parse_workspace(a.ncand, a.nuse) + 3) / 4);
+  text_parse_carve(a, scratch.p);
+  launch_text_parse(a, ctx->stream);
+  DBM_HIP(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  if (totals[2] != ~0ull) {
+    result_out[2] = (int64_t)totals[2];
+    return 0;
+  }
+  const size_t kept = totals[3], nrep = totals[4];
+  DBM_CHECK(kept <= table_capacity, "dbm_text_parse: the table holds " + std::to_string(table_capacity) + " rows, " + std::to_string(kept) +
+                                        " are kept; nothing was written");
+  DBM_CHECK(nrep <= repair_capacity, "dbm_text_parse: the repair list holds " + std::to_string(repair_capacity) + " pairs, " +
+                                         std::to_string(nrep) + " are needed; nothing was written");
+  if (kept > 0) {
+    ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+    list.ensure(4 * (nrep > 0 ? nrep : 1));
+    a.repair = (long long*)list.p;
+    if (dev) {
+      a.table = table_out;
+    } else {
+      table.ensure(2 * kept * (size_t)a.nuse);
+      a.table = (double*)table.p;
+    }
+    launch_text_compact(a, ctx->stream);
+    if (nrep > 0) DBM_HIP(hipMemcpyAsync(repair_out, a.repair, 16 * nrep, hipMemcpyDeviceToHost, ctx->stream));
+    if (!dev) DBM_HIP(hipMemcpyAsync(table_out, a.table, 8 * kept * (size_t)a.nuse, hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  result_out[0] = (int64_t)kept;
+  result_out[1] = (int64_t)nrep;
+  DBM_API_END
+}
+
+int dbm_text_columns(dbm_ctx* ctx, const double* in_dev, size_t n, int ncol_in, double* out_dev, int ncol_out, const int* a, const int* op,
+                     const int* b) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && a != nullptr && op != nullptr && b != nullptr, "dbm_text_columns: NULL argument");
+  DBM_CHECK(ncol_in >= 1 && ncol_out >= 1 && ncol_out <= DBM_TEXT_MAX_COLUMNS, "dbm_text_columns: ncol_in >= 1 and ncol_out in 1..DBM_TEXT_MAX_COLUMNS");
+  DBM_CHECK(n == 0 || (in_dev != nullptr && out_dev != nullptr), "dbm_text_columns: NULL table");
+  ColumnsLaunch c = {};
+  c.in = in_dev;
+  c.out = out_dev;
+  c.n = n;
+  c.ncol_in = ncol_in;
+  c.ncol_out = ncol_out;
+  for (int k = 0; k < ncol_out; ++k) {
+    DBM_CHECK(op[k] >= 0 && op[k] <= 2, "dbm_text_columns: op must be 0 (copy), 1 (add) or 2 (subtract)");
+    DBM_CHECK(a[k] >= 0 && a[k] < ncol_in && (op[k] == 0 || (b[k] >= 0 && b[k] < ncol_in)), "dbm_text_columns: a column index lies outside the input");
+    c.a[k] = a[k];
+    c.op[k] = op[k];
+    c.b[k] = op[k] == 0 ? a[k] : b[k];
+  }
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  launch_text_columns(c, ctx->stream);
+  DBM_API_END
+}
+
 // ---- from block medians to the 250 m raster (surface.hip, track.hip) ----
 int dbm_grid_tension_surface(dbm_ctx* ctx, const float* data_dev, long H, long W, double tension, double tol, int max_iter, float* out_dev,
                              double info[4]) {

@@ -359,6 +359,54 @@ void blockmedian_carve(BlockMedianLaunch& a, void* ws);
 void launch_blockmedian_count(const BlockMedianLaunch& a, hipStream_t s);
 void launch_blockmedian_select(const BlockMedianLaunch& a, const unsigned* totals, hipStream_t s);
 
+// Survey text tables (text.hip; dbm_text_count_lines, dbm_text_parse): the bytes of a delimited text file -> the float64 rows that
+// pandas.read_csv + dropna keep.  launch_text_structure counts and scans the lines per tile of DBM_TEXT_TILE_BYTES (totals[0], [1] =
+// lines, non-blank lines); the host reads them and sizes the candidates' scratch (ncand = non-blank lines behind the first skip1);
+// launch_text_parse fills it and scans the flags (totals[2] = smallest byte offset of an offending line or ~0, [3], [4] = rows kept,
+// rows with a field the device leaves to the host); launch_text_compact writes table (kept rows, file order) and repair (byte offset,
+// final row per such row).  text must be 16-byte aligned.
+struct TextPair {
+  unsigned long long a, b;
+};
+struct TextLaunch {
+  const unsigned char* text;
+  unsigned long long len;
+  int sep;                        // the separator byte, or DBM_TEXT_SEP_WHITESPACE
+  unsigned long long skip1;       // non-blank lines discarded unparsed (skip + 1)
+  int nfields, nuse;              // names; used names
+  unsigned long long use_mask;    // bit f: field f is used
+  int n_na;                       // the caller's NA strings, packed little-endian
+  int na_len[DBM_TEXT_MAX_NA];
+  unsigned long long na_lo[DBM_TEXT_MAX_NA], na_hi[DBM_TEXT_MAX_NA];
+  TextPair* tiles;                // per tile: (lines, non-blank lines) started there, then the counts in front of the tile
+  unsigned long long* totals;     // 5
+  unsigned long long* first_error;
+  unsigned long long ncand;
+  double* rows;                   // ncand x nuse scratch
+  unsigned long long* offs;       // ncand: byte offset of the candidate's line
+  unsigned char* flags;           // ncand: bit 0 kept, bit 1 needs the host
+  TextPair* parts;                // per scan tile of the flags
+  double* table;
+  long long* repair;
+};
+long text_tiles(size_t nbytes);
+size_t text_structure_workspace(size_t nbytes);
+void text_structure_carve(TextLaunch& a, void* ws);
+size_t text_parse_workspace(size_t ncand, int nuse);
+void text_parse_carve(TextLaunch& a, void* ws);
+void launch_text_structure(const TextLaunch& a, hipStream_t s);
+void launch_text_parse(const TextLaunch& a, hipStream_t s);
+void launch_text_compact(const TextLaunch& a, hipStream_t s);
+// The steps behind the read (dbm_text_columns): column c of out = column a[c] of in, plus (op 1) or minus (op 2) column b[c]
+struct ColumnsLaunch {
+  const double* in;
+  double* out;
+  unsigned long long n;
+  int ncol_in, ncol_out;
+  int a[DBM_TEXT_MAX_COLUMNS], op[DBM_TEXT_MAX_COLUMNS], b[DBM_TEXT_MAX_COLUMNS];
+};
+void launch_text_columns(const ColumnsLaunch& a, hipStream_t s);
+
 // Tension-spline surface through the non-NaN nodes of a float32 raster (surface.hip; dbm_grid_tension_surface), float64 conjugate
 // gradients on the device; ws: surface_workspace(H, W) bytes, 256-byte aligned.  surface_solve synchronises the stream, fills info =
 // {iterations, |r| / |b|, constraint nodes, free nodes}, always writes out (the last iterate) and returns whether |r| <= tol |b| was

@@ -105,6 +105,14 @@ class DevicePoints:
                        self.ctx.handle)
         self._out = None   # device: z_interpolated (n doubles), then 8 doubles of statistics
 
+    @classmethod
+    def adopt(cls, ptr, n, ncol, ctx):
+        """A table that is resident already (what `ascii_to_xyz(download=False)` parsed): `ptr` -- from ctx.malloc, at least 8 n ncol
+        bytes, float64 (n, ncol) -- becomes the object's own and is freed with it.  Nothing is uploaded."""
+        self = cls.__new__(cls)
+        self.ctx, self.n, self.ncol, self.ptr, self._out = ctx, int(n), int(ncol), ptr, None
+        return self
+
     def outputs(self):
         if self._out is None:
             self._out = self.ctx.malloc(8 * (self.n + 8))

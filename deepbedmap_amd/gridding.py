@@ -13,8 +13,8 @@ The second half of xyz_to_grid (data_prep.py:409-441: `gmt.surface(T=0.35, M="3c
 the device), `mask_far_from_data` blanks nodes further than three cells from data (dbm_grid_distance_mask), `to_pixel_registration`
 resamples gridline -> pixel (dbm_grid_to_pixel) and `xyz_to_grid` chains all four stages without leaving the device.  The surface is this
 project's own, completely defined one -- constraints on nodes, natural edges, a residual stopping rule -- NOT a reproduction of GMT
-`surface`: DESIGN.md "Tension surface" lists every difference.  NOT built: `gmt info -Is<inc>`, the CSV reading of ascii_to_xyz.  No
-CPU fallback: without a GPU every call that computes raises DbmError.
+`surface`: DESIGN.md "Tension surface" lists every difference.  NOT built: `gmt info -Is<inc>`.  (The CSV reading of
+ascii_to_xyz, the step in front of these, is deepbedmap_amd/ascii_table.py.)  No CPU fallback: without a GPU every call that computes raises DbmError.
 """
 import ctypes as C
 

@@ -66,6 +66,18 @@ enum {
   DBM_BLOCKMEDIAN_LDS = 2048,
   DBM_BLOCKMEDIAN_CLASSES = 5
 };
+/* dbm_text_*: bytes of text a workgroup stages and parses the lines of, its threads (text.hip: a thread owns the lines that start in
+ * its TILE_BYTES / THREADS bytes), the separator value that stands for runs of spaces and tabs (`\s+`), and the limits of the reader
+ * description.  Listed here so that tests can put newlines, numbers and long lines on both sides of every tile edge. */
+enum {
+  DBM_TEXT_TILE_BYTES = 16384,
+  DBM_TEXT_THREADS = 256,
+  DBM_TEXT_SEP_WHITESPACE = 256,
+  DBM_TEXT_MAX_FIELDS = 64,
+  DBM_TEXT_MAX_NA = 8,
+  DBM_TEXT_MAX_NA_BYTES = 16,
+  DBM_TEXT_MAX_COLUMNS = 8
+};
 
 /* ---- context ---- */
 int dbm_init(int hip_device, dbm_ctx** out);      /* replaces model.to_gpu(): srgan_train.py:1038-1040, deepbedmap.py:659 */
@@ -333,7 +345,7 @@ int dbm_grid_rolling_std(dbm_ctx* ctx, const float* in_dev, long H, long W, int 
  * `filters.reprojection` step of ascii_to_xyz; :353-378 get_region; :406-407 the `gmt.blockmedian` preprocessing of xyz_to_grid) ----
  * Point tables are C-contiguous float64 (n, ncol), as dbm_grid_track takes them; all arithmetic is float64.  flags: DBM_DEVICE_PTRS =
  * the table arguments are device pointers; otherwise host pointers, staged, and the call synchronises.  NOT built:
- * `gmt info -Is<inc>` (the surface-friendly widening) and the CSV reading of ascii_to_xyz.  The second half of xyz_to_grid -- a tension
+ * `gmt info -Is<inc>` (the surface-friendly widening).  The CSV reading of ascii_to_xyz: dbm_text_*, below.  The second half of xyz_to_grid -- a tension
  * surface through the block medians, the distance mask and `grdsample -T` -- is the next group of entry points (it is this project's own,
  * fully defined surface, NOT a reproduction of GMT `surface`: DESIGN.md 6f).
  *
@@ -513,6 +525,49 @@ int dbm_op_deform_conv2d_form(dbm_ctx* ctx, const float* x, const float* off, co
                               int W, int O, int form, int lrelu);
 int dbm_op_deform_conv2d_backward(dbm_ctx* ctx, const float* x, const float* off, const float* w, const float* gy,
                                   float* gx, float* goff, float* gw, float* gb, int N, int C, int H, int W, int O);
+
+/* ---- reading survey text tables: the `pandas.read_csv` + `dropna` of ascii_to_xyz (data_prep.py:298-305) ----
+ * text: nbytes bytes of one file, host or (DBM_DEVICE_PTRS) device, a device pointer 16-byte aligned; offsets are 64-bit, files above
+ * 4 GiB work.  The dialect: lines end at '\n', one '\r' before it is dropped, a last line without '\n' counts.  A line is
+ * blank when it holds nothing but spaces and tabs (a tab is not blank space when it is the separator); blank lines are skipped, then the
+ * first skip + 1 non-blank lines are discarded unparsed (`header=skip`: the line after the skipped ones is taken for the header, so with
+ * skip = 1 and one header line the first data row is lost, as in the reference).  separator: ',' or '\t' (every occurrence separates),
+ * or DBM_TEXT_SEP_WHITESPACE (maximal runs of spaces and tabs separate, leading and trailing runs are ignored).  Quotes are NOT
+ * interpreted.  Field f of a line belongs to name f of nfields names; bit f of use_mask marks it used; the table's columns are the used
+ * fields in file order.  Only used fields are looked at.  A used field, trimmed of spaces and tabs, is NaN if it is empty, equals one of
+ * the n_na strings of na_values (NUL-terminated one after the other, each 1..DBM_TEXT_MAX_NA_BYTES bytes, compared byte for byte -- NOT
+ * pandas' numeric comparison) or one of pandas' default NA strings (#N/A, #N/A N/A, #NA, -1.#IND, -1.#QNAN, -NaN, -nan, 1.#IND, 1.#QNAN,
+ * <NA>, N/A, NA, NULL, NaN, None, n/a, nan, null); +-inf for [+-]?(inf|infinity) in any case; the correctly rounded double for
+ * [+-]?(digits[.digits*] | .digits)([eE][+-]?digits)?; anything else is an error.  A field missing at the end of a short line is NaN; a
+ * line with more than nfields fields is an error.  A row is kept unless a used field is NaN (+-inf is kept), in file order.
+ * The device converts a number exactly when its significant digits (at most 19) give an integer w <= 2^53 and its decimal exponent e
+ * has |e| <= 22: double(w) * 10^e or double(w) / 10^-e, one IEEE operation on exact operands.  Any other number is NOT guessed: the row
+ * is kept, its other fields converted, and (byte offset of its line, its row in table_out) appended to the repair list, in file order;
+ * the caller converts that line (strtod, Python float) and patches the row.
+ *
+ * dbm_text_count_lines: counts_out (HOST, 2) = {lines, non-blank lines}; max(0, non-blank lines - skip - 1) bounds the rows of any
+ * parse of this text.  Synchronises.
+ * dbm_text_parse: table_out (table_capacity rows of popcount(use_mask) doubles; host or, with DBM_DEVICE_PTRS, device), repair_out
+ * (HOST, repair_capacity pairs of int64; may be NULL with capacity 0), result_out (HOST, 4) = {rows kept, repair pairs, byte offset of
+ * the FIRST line in file order that holds an error or -1, candidate lines}.  With an error nothing is written to table_out and rows
+ * kept = repair pairs = 0 (status 0: the caller names the line).  The call reads counts back twice, so it synchronises even with
+ * DBM_DEVICE_PTRS; its scratch (8 popcount + 9 bytes per candidate line) is freed on every path.  Kept rows are compacted with flags
+ * and an exclusive scan, no atomic append: the same bytes from call to call.  Status 1 (refused, nothing written): a separator other
+ * than the three, skip < 0, nfields outside 1..DBM_TEXT_MAX_FIELDS, use_mask empty or with a bit at or above nfields, n_na outside
+ * 0..DBM_TEXT_MAX_NA or a string outside 1..DBM_TEXT_MAX_NA_BYTES bytes, a misaligned device pointer, NULL pointers, table_capacity <
+ * rows kept, repair_capacity < repair pairs.
+ *
+ * dbm_text_columns: the steps of ascii_to_xyz behind the read (data_prep.py:298-305 the table, :307-320 `df.eval("A-B")`, `drop`, the
+ * columns sorted by name).  in_dev (n, ncol_in) and out_dev (n, ncol_out) are float64 DEVICE tables that do not overlap; column c of
+ * out is column a[c] of in (op[c] = 0), a[c] + b[c] (op[c] = 1) or a[c] - b[c] (op[c] = 2): one IEEE operation, no contraction.  a, op,
+ * b: HOST arrays of ncol_out ints (the expression is parsed by the caller).  Asynchronous.  Status 1: ncol_out outside
+ * 1..DBM_TEXT_MAX_COLUMNS, ncol_in < 1, an index outside the input's columns, an op outside 0..2, NULL pointers with n > 0. */
+int dbm_text_count_lines(dbm_ctx* ctx, const void* text, size_t nbytes, int separator, int64_t* counts_out, int flags);
+int dbm_text_parse(dbm_ctx* ctx, const void* text, size_t nbytes, int separator, int skip, int nfields, uint64_t use_mask,
+                   const char* na_values, int n_na, double* table_out, size_t table_capacity, int64_t* repair_out, size_t repair_capacity,
+                   int64_t* result_out, int flags);
+int dbm_text_columns(dbm_ctx* ctx, const double* in_dev, size_t n, int ncol_in, double* out_dev, int ncol_out, const int* a, const int* op,
+                     const int* b);
 
 #ifdef __cplusplus
 }
