@@ -120,6 +120,9 @@ SIGNATURES = {
                                  C.POINTER(C.c_double)],
     "dbm_grid_distance_mask": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int],
     "dbm_grid_to_pixel": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_double, C.c_void_p],
+    "dbm_grid_polygon_mask": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_long, C.c_long, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p,
+                              C.c_size_t, C.c_int],
+    "dbm_grid_polygon_stats": [C.c_void_p, C.POINTER(C.c_int64)],
     "dbm_adam_setup": [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double],
     "dbm_adam_update": [C.c_void_p, C.c_double],
     "dbm_discriminator_step": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1397,6 +1397,75 @@ int dbm_grid_to_pixel(dbm_ctx* ctx, const float* in_dev, long H, long W, double 
   DBM_API_END
 }
 
+// ---- nodes inside a buffered polygon set (polygon.hip) ----
+// list sizes of each context's last successful dbm_grid_polygon_mask (dbm_grid_polygon_stats); kept beside the contexts, not in them
+static std::map<dbm_ctx*, std::vector<long long>> g_poly_stats;
+int dbm_grid_polygon_mask(dbm_ctx* ctx, const double* edges, size_t n_edges, long H, long W, const double geom[4], double buffer,
+                          unsigned char* mask_dev, float* grid_dev, size_t workspace_limit, int flags) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && geom != nullptr, "dbm_grid_polygon_mask: NULL context or geometry");
+  DBM_CHECK(H >= 1 && W >= 1, "dbm_grid_polygon_mask: empty raster");
+  DBM_CHECK(H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31), "dbm_grid_polygon_mask: H W must stay below 2^31 nodes");
+  DBM_CHECK(n_edges < ((size_t)1 << 31), "dbm_grid_polygon_mask: n_edges must stay below 2^31");
+  DBM_CHECK(std::isfinite(geom[0]) && std::isfinite(geom[1]) && std::isfinite(geom[2]) && std::isfinite(geom[3]) && geom[2] != 0.0 &&
+                geom[3] != 0.0, "dbm_grid_polygon_mask: the geometry must be finite with non-zero dx and dy");
+  DBM_CHECK(std::isfinite(buffer), "dbm_grid_polygon_mask: the buffer must be finite");
+  DBM_CHECK(mask_dev != nullptr || grid_dev != nullptr, "dbm_grid_polygon_mask: both outputs are NULL");
+  DBM_CHECK(n_edges == 0 || edges != nullptr, "dbm_grid_polygon_mask: NULL edge table");
+  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
+  if (!dev)
+    for (size_t i = 0; i < 4 * n_edges; ++i)
+      DBM_CHECK(std::isfinite(edges[i]), "dbm_grid_polygon_mask: edge " + std::to_string(i / 4) + " has a non-finite coordinate");
+  PolyLaunch a;
+  a.n = (long)n_edges;
+  a.H = H; a.W = W;
+  a.x0 = geom[0]; a.y0 = geom[1]; a.dx = geom[2]; a.dy = geom[3];
+  a.buffer = buffer;
+  polygon_geometry(a);
+  ScopedBuf ws, bins;   // this call's own, released on every path
+  ws.ensure((polygon_workspace(a, !dev) + 3) / 4);
+  double* staged = polygon_carve(a, ws.p, !dev);
+  a.edges = edges;
+  if (!dev && n_edges > 0) {
+    DBM_HIP(hipMemcpyAsync(staged, edges, 32 * n_edges, hipMemcpyHostToDevice, ctx->stream));
+    a.edges = staged;
+  }
+  a.entries = nullptr;
+  a.nP = a.nB = 0u;
+  a.mask = mask_dev;
+  a.grid = grid_dev;
+  launch_polygon_cull(a, ctx->stream);
+  unsigned long long totals[8];
+  DBM_HIP(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  DBM_CHECK(totals[2] == 0ull, "dbm_grid_polygon_mask: " + std::to_string(totals[2]) + " edges have a non-finite coordinate; nothing was written");
+  if (totals[3] != 0ull) a.identity = 1;
+  a.nP = (unsigned)totals[0];
+  a.nB = (unsigned)totals[1];
+  const unsigned long long entries = totals[4] + totals[5];
+  const size_t limit = workspace_limit ? workspace_limit : DBM_POLY_WORKSPACE_DEFAULT;
+  const bool binned = !a.identity && n_edges > 0 && entries < (1ull << 31) && 4 * entries <= limit;
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  if (binned) {
+    bins.ensure(entries > 0 ? (size_t)entries : 1);
+    a.entries = (unsigned*)bins.p;
+    launch_polygon_bin(a, ctx->stream);
+  }
+  launch_polygon_classify(a, ctx->stream);
+  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
+  g_poly_stats[ctx] = {(long long)totals[0], (long long)totals[1], (long long)totals[4], (long long)totals[5],
+                       a.identity ? 2LL : (binned ? 1LL : 0LL), (long long)n_edges};
+  DBM_API_END
+}
+
+int dbm_grid_polygon_stats(dbm_ctx* ctx, int64_t out[6]) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && out != nullptr, "dbm_grid_polygon_stats: NULL argument");
+  const auto it = g_poly_stats.find(ctx);
+  for (int k = 0; k < 6; ++k) out[k] = it == g_poly_stats.end() ? 0 : (int64_t)it->second[k];
+  DBM_API_END
+}
+
 // ---- optimizer ----
 int dbm_adam_setup(dbm_model* m, double alpha, double beta1, double beta2, double eps) {
   DBM_API_BEGIN(m->ctx)

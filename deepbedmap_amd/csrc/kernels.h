@@ -422,3 +422,36 @@ size_t surface_workspace(long H, long W);
 bool surface_solve(const SurfaceLaunch& a, void* ws, hipStream_t s, double info[4]);
 // grid[r, c] = NaN unless a non-NaN node of data lies within `radius` nodes (Euclidean, integer arithmetic) (dbm_grid_distance_mask)
 void launch_distance_mask(const float* data, float* grid, long H, long W, int radius, hipStream_t s);
+
+// Nodes inside a buffered polygon set (polygon.hip; dbm_grid_polygon_mask): edges (n, 4) float64 (xa, ya, xb, yb) on the device, 16-byte
+// aligned.  polygon_geometry fills the tiling, the nodes' extent and `identity` (coordinates beyond 2^480: no culling, no shortcuts) from
+// H, W, x0, y0, dx, dy, buffer; polygon_carve hands out polygon_workspace bytes (256-byte aligned; returns the staging area for a host
+// table if asked for).  launch_polygon_cull fills listP / listB / cnt and totals = {proximity edges, parity edges, non-finite edges, wild
+// edges, tile bin entries, band bin entries}; the host reads totals, sets nP, nB, identity and -- if it bins -- entries (totals[4] +
+// totals[5] indices), then launch_polygon_bin; launch_polygon_classify writes mask (0 / 1, may be null) and NaN into grid (may be null).
+constexpr size_t DBM_POLY_WORKSPACE_DEFAULT = (size_t)256 << 20;   // bytes of bin entries above which a call runs unbinned
+struct PolyLaunch {
+  const double* edges;
+  long n, H, W;
+  double x0, y0, dx, dy, buffer;
+  double gmag, gx0, gx1, gy0, gy1;   // largest magnitude of a node coordinate or the buffer; the nodes' extent
+  long tiles_x, tiles_y, nbins;      // node tiles per row, tile rows (= bands); tiles_x tiles_y + tiles_y bins
+  unsigned* listP;                   // n: culled proximity edges
+  unsigned* listB;                   // n: culled parity edges
+  unsigned* cnt;                     // nbins
+  unsigned* cursor;                  // nbins
+  unsigned* off;                     // nbins + 1
+  unsigned* part;                    // per scan tile
+  unsigned long long* totals;        // 8
+  unsigned* entries;                 // null: unbinned
+  int identity;
+  unsigned nP, nB;
+  unsigned char* mask;
+  float* grid;
+};
+void polygon_geometry(PolyLaunch& a);
+size_t polygon_workspace(const PolyLaunch& a, bool stage_edges_too);
+double* polygon_carve(PolyLaunch& a, void* ws, bool stage_edges_too);
+void launch_polygon_cull(const PolyLaunch& a, hipStream_t s);
+void launch_polygon_bin(const PolyLaunch& a, hipStream_t s);
+void launch_polygon_classify(const PolyLaunch& a, hipStream_t s);

@@ -66,6 +66,12 @@ enum {
   DBM_BLOCKMEDIAN_LDS = 2048,
   DBM_BLOCKMEDIAN_CLASSES = 5
 };
+/* dbm_grid_polygon_mask: the side of a node tile (one 256-thread workgroup classifies TILE x TILE nodes) and the number of edges a
+ * workgroup stages into LDS at a time (polygon.hip).  Listed here so that tests can put grids and edge counts on both sides of them. */
+enum {
+  DBM_POLY_TILE = 16,
+  DBM_POLY_CHUNK = 256
+};
 /* dbm_text_*: bytes of text a workgroup stages and parses the lines of, its threads (text.hip: a thread owns the lines that start in
  * its TILE_BYTES / THREADS bytes), the separator value that stands for runs of spaces and tabs (`\s+`), and the limits of the reader
  * description.  Listed here so that tests can put newlines, numbers and long lines on both sides of every tile edge. */
@@ -428,6 +434,44 @@ int dbm_grid_tension_surface(dbm_ctx* ctx, const float* data_dev, long H, long W
                              float* out_dev, double info[4]);
 int dbm_grid_distance_mask(dbm_ctx* ctx, const float* data_dev, float* grid_dev, long H, long W, int radius);
 int dbm_grid_to_pixel(dbm_ctx* ctx, const float* in_dev, long H, long W, double threshold, float* out_dev);
+
+/* ---- tiles inside the buffered grounding line (data_prep.py:582-616, "Subset tiles to those within grounding line":
+ * `gline.geometry.buffer(distance=10000)` at :602, `gpd.sjoin(tile_gdf, op="within", gline)` at :606) ----
+ * dbm_grid_polygon_mask marks the nodes of a raster that lie inside a polygon set dilated (buffer >= 0) or eroded (buffer < 0) by
+ * |buffer|.  It is this project's own, exactly defined selection, NOT a reproduction of GEOS: GEOS replaces the arcs of
+ * the offset curve by polygons (8 segments per quadrant: up to 10 000 (1 - cos(pi / 32)) ~ 48 m inside the true 10 km offset) and tests
+ * boxes, not nodes.
+ * Polygon set: edges is (n_edges, 4) float64 rows (xa, ya, xb, yb), C-contiguous -- ALL rings of ALL parts pooled, holes included, each
+ * ring closed (the last vertex joined to the first); a host table, or with DBM_DEVICE_PTRS a device table (16-byte aligned).
+ * Node (r, c) sits at x = x0 + c dx, y = y0 + r dy, geom = {x0, y0, dx, dy} as dbm_grid_tile takes it: one multiplication and one
+ * addition, each rounded.  All arithmetic is float64 IEEE, no fused multiply-add, IEEE division.
+ * Inside: the even-odd rule over all edges.  An edge counts iff (ya <= y) != (yb <= y) and x < xa + ((y - ya) * (xb - xa)) / (yb - ya);
+ * inside = the count is odd.  Ring orientation therefore does not matter, a hole is simply another ring, and where two parts overlap
+ * they CANCEL (the overlap is outside) -- unlike a union.  Horizontal edges never count.
+ * Distance: ex = xb - xa, ey = yb - ya, px = x - xa, py = y - ya, L = ex ex + ey ey; t = L > 0 ? (px ex + py ey) / L : 0, clamped to
+ * [0, 1]; qx = px - t ex, qy = py - t ey, d2 = qx qx + qy qy; near = some edge has d2 <= buffer * buffer.
+ * Mask: buffer >= 0 (-0.0 included): inside || near -- the closed Euclidean dilation with round joins, boundary nodes are in;
+ * buffer < 0: inside && !near -- the erosion.  No edges: 0 everywhere.
+ * mask_dev (H W bytes of 0 / 1, ALWAYS device, may be NULL); grid_dev (H W float32, ALWAYS device, may be NULL): changed in place, NaN
+ * where the mask is 0, every other node's bits untouched; at least one of the two.  Tile selection (data_prep.py:606) is then
+ * dbm_grid_filled_windows on that raster: a window is kept iff every one of its nodes is in the mask and holds data.
+ * Both results are order-independent (a parity and an "any"): the same bytes from call to call, under any permutation of the edges, and on
+ * either schedule -- edges binned per tile of DBM_POLY_TILE^2 nodes, or, when the bins would take more than workspace_limit bytes (0: a
+ * default of 256 MiB), every tile running over the culled lists.  Culling never changes a result: boxes are grown by |buffer| plus a
+ * margin of 2^-30 of the coordinate magnitude, far above the rounding of d2 (polygon.hip).  Integer atomics place list entries; no float
+ * atomics.  The call allocates its workspace (about 8 bytes per edge, 12 per node tile, 4 per bin entry; 32 per edge more for a host
+ * table), frees it on every path, and synchronises the context's stream: once to read the list sizes back (and, for a device table,
+ * whether a coordinate was not finite -- before anything is written) and once before the workspace is released.
+ * Relation to the reference: a box within the true dilation has all its nodes in it, so this selection CONTAINS the true one; the two
+ * differ only for windows where the offset curve passes within half a pixel diagonal of the window's box (177 m at 250 m pixels), the
+ * same order as GEOS's own 48 m.  The reference's 4028-tile list cannot be reproduced without its shapefile; nothing is claimed about it.
+ * Refused (status 1, nothing written): NULL ctx or geom, H or W < 1, H W >= 2^31, n_edges >= 2^31, geom not finite or dx or dy zero,
+ * buffer not finite, a non-finite edge coordinate, both outputs NULL, NULL edges with n_edges > 0.
+ * dbm_grid_polygon_stats: out (HOST) = {proximity edges kept by the cull, parity edges kept, tile bin entries, band bin entries,
+ * schedule (0 unbinned, 1 binned, 2 no culling: a coordinate beyond 2^480), n_edges} of the context's last successful call. */
+int dbm_grid_polygon_mask(dbm_ctx* ctx, const double* edges, size_t n_edges, long H, long W, const double geom[4], double buffer,
+                          unsigned char* mask_dev, float* grid_dev, size_t workspace_limit, int flags);
+int dbm_grid_polygon_stats(dbm_ctx* ctx, int64_t out[6]);
 
 /* ---- optimizer ---- */
 /* chainer.optimizers.Adam(alpha, eps=1e-8).setup(model): srgan_train.py:1043-1048 */
