@@ -105,6 +105,10 @@ SIGNATURES = {
     "dbm_grid_tile": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.POINTER(C.c_double), C.c_void_p, C.c_long, C.c_int, C.c_double,
                       C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
     "dbm_grid_filled_windows": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "dbm_grid_fill_gaps": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double), C.c_void_p,
+                           C.c_long, C.c_long, C.POINTER(C.c_double), C.c_void_p],
+    "dbm_tiff_decode": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                        C.c_long, C.c_long],
     "dbm_grid_rescale": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "dbm_grid_rolling_std": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_void_p],
     "dbm_points_polar_stereographic": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int],
@@ -148,7 +152,7 @@ class DbmError(RuntimeError):
     # optimizer updates queued since the event were skipped (`Context.timeout_info()`).  8: the same in a data-parallel
     # run -- fatal, the replicas have diverged.  9 (dbm_adam_update only): the gradients about to be applied come from a
     # void pass; nothing was applied -- repeat forward + backward, then update.  10 (dbm_grid_tension_surface only): the solve did not
-    # converge within max_iter; the output holds the last iterate.
+    # converge within max_iter; the output holds the last iterate.  11 (dbm_tiff_decode only): a block's LZW stream is malformed.
     code = None
 
 

@@ -1038,6 +1038,94 @@ int dbm_grid_filled_windows(dbm_ctx* ctx, const float* grid_dev, long H, long W,
   DBM_API_END
 }
 
+int dbm_grid_fill_gaps(dbm_ctx* ctx, const float* fine_dev, long H, long W, const double bounds[4], double resolution, const double* fine_nodata,
+                       const float* coarse_dev, long cH, long cW, const double coarse_geom[4], float* out_dev) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && bounds != nullptr && coarse_geom != nullptr, "dbm_grid_fill_gaps: NULL argument");
+  DBM_CHECK(fine_dev != nullptr && coarse_dev != nullptr && out_dev != nullptr, "dbm_grid_fill_gaps: NULL raster or output");
+  DBM_CHECK(H >= 1 && W >= 1 && H < (1L << 31) && W < (1L << 31), "dbm_grid_fill_gaps: H and W must lie in 1..2^31 - 1");
+  DBM_CHECK(cH >= 2 && cW >= 2, "dbm_grid_fill_gaps: bilinear needs at least 2 x 2 coarse nodes");
+  DBM_CHECK(std::isfinite(coarse_geom[0]) && std::isfinite(coarse_geom[1]) && std::isfinite(coarse_geom[2]) && std::isfinite(coarse_geom[3]) &&
+                coarse_geom[2] != 0.0 && coarse_geom[3] != 0.0, "dbm_grid_fill_gaps: x0, y0 finite, dx, dy finite and non-zero");
+  DBM_CHECK(std::isfinite(bounds[0]) && std::isfinite(bounds[1]) && std::isfinite(bounds[2]) && std::isfinite(bounds[3]),
+            "dbm_grid_fill_gaps: the bounds must be finite");
+  DBM_CHECK(std::isfinite(resolution) && resolution > 0.0, "dbm_grid_fill_gaps: the resolution must be positive");
+  DBM_CHECK(fine_nodata == nullptr || std::isnan(*fine_nodata) || std::isfinite(*fine_nodata), "dbm_grid_fill_gaps: nodata must be finite or NaN");
+  DBM_CHECK((const void*)coarse_dev != (const void*)out_dev, "dbm_grid_fill_gaps: the output must not be the coarse raster");
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  TileLaunch a;
+  a.grid = coarse_dev;
+  a.H = cH; a.W = cW;
+  a.x0 = coarse_geom[0]; a.y0 = coarse_geom[1]; a.dx = coarse_geom[2]; a.dy = coarse_geom[3];
+  a.n = 1;
+  a.out_h = (int)H; a.out_w = (int)W; a.mode = 1;
+  a.res = resolution;
+  a.has_nodata = 0; a.nodata = 0.0; a.nodata_band = 0.0;   // (no gap filler: masking changes no value of dbm_grid_tile)
+  a.has_fill = 0; a.fill = 0.0f; a.fill_nan = 0;
+  a.out = out_dev; a.out_stride = H * W; a.counts = nullptr; a.windows = nullptr;
+  const bool has = fine_nodata != nullptr && !std::isnan(*fine_nodata);
+  launch_grid_fill_gaps(a, bounds, fine_dev, has ? 1 : 0, has ? (float)*fine_nodata : 0.0f, out_dev, ctx->stream);
+  DBM_API_END
+}
+
+// ---- GeoTIFF blocks -> a float32 plane (tiff_decode.hip) ----
+int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host, int n_blocks, int compression,
+                    int predictor, int sample_type, int block_w, int block_h, float* out_dev, long out_h, long out_w) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_tiff_decode: NULL context");
+  DBM_CHECK(n_blocks >= 0, "dbm_tiff_decode: negative number of blocks");
+  DBM_CHECK(compression == 1 || compression == 5, "dbm_tiff_decode: compression must be 1 (decoded bytes) or 5 (LZW)");
+  DBM_CHECK(sample_type >= 0 && sample_type <= 5, "dbm_tiff_decode: sample_type must lie in 0..5");
+  static const int kBytes[6] = {1, 2, 2, 4, 4, 8};
+  const int bytes = kBytes[sample_type];
+  DBM_CHECK(predictor == 1 || predictor == 2 || (predictor == 3 && sample_type >= 4), "dbm_tiff_decode: predictor must be 1, 2, or 3 with float samples");
+  DBM_CHECK(block_w >= 1 && block_h >= 1 && (long)block_w * block_h * bytes < (1L << 31), "dbm_tiff_decode: a block must hold 1..2^31 - 1 bytes");
+  DBM_CHECK(out_h >= 1 && out_w >= 1, "dbm_tiff_decode: empty output plane");
+  DBM_CHECK(n_blocks == 0 || (streams_host != nullptr && blocks_host != nullptr && out_dev != nullptr), "dbm_tiff_decode: NULL streams, blocks or output");
+  DBM_CHECK((long)n_blocks * block_h < (1L << 31), "dbm_tiff_decode: more than 2^31 block rows in one call");
+  if (n_blocks == 0) return 0;
+  const bool lzw = compression == 5;
+  for (int b = 0; b < n_blocks; ++b) {
+    const int64_t* e = blocks_host + 8 * (size_t)b;
+    const std::string name = "dbm_tiff_decode: block " + std::to_string(e[5]);
+    DBM_CHECK(e[0] >= 0 && e[1] >= 0 && (uint64_t)e[0] + (uint64_t)e[1] <= (uint64_t)streams_bytes, name + ": its bytes lie outside the streams");
+    DBM_CHECK(e[2] >= 1 && e[2] <= block_h, name + ": its rows must lie in 1..block_h");
+    DBM_CHECK(lzw || (e[0] % 8 == 0 && e[1] >= e[2] * (int64_t)block_w * bytes), name + ": decoded bytes must be 8-byte aligned and complete");
+    DBM_CHECK(e[3] > -(1L << 40) && e[3] < (1L << 40) && e[4] > -(1L << 40) && e[4] < (1L << 40), name + ": placement out of range");
+  }
+  TiffDecodeLaunch a;
+  a.n_blocks = n_blocks; a.lzw = lzw ? 1 : 0;
+  a.block_w = block_w; a.block_h = block_h; a.bytes = bytes; a.sample_type = sample_type; a.predictor = predictor;
+  a.block_stride = (((long)block_w * block_h * bytes) + 15) / 16 * 16;
+  a.out = out_dev; a.out_h = out_h; a.out_w = out_w;
+  ScopedBuf up, table, stage;   // this call's own, released on every path
+  up.ensure((streams_bytes + 16 + 3) / 4);
+  table.ensure(((size_t)n_blocks * (64 + 4) + 3) / 4);
+  DBM_HIP(hipMemcpyAsync(up.p, streams_host, streams_bytes, hipMemcpyHostToDevice, ctx->stream));
+  DBM_HIP(hipMemcpyAsync(table.p, blocks_host, 64 * (size_t)n_blocks, hipMemcpyHostToDevice, ctx->stream));
+  a.streams = (const uint8_t*)up.p;
+  a.blocks = (const long*)table.p;
+  a.status = (int*)((uint8_t*)table.p + 64 * (size_t)n_blocks);
+  a.stage = (uint8_t*)up.p;
+  if (lzw) {
+    stage.ensure(((size_t)n_blocks * (size_t)a.block_stride + 3) / 4);
+    a.stage = (uint8_t*)stage.p;
+    launch_tiff_lzw(a, ctx->stream);
+    std::vector<int> status((size_t)n_blocks);
+    DBM_HIP(hipMemcpyAsync(status.data(), a.status, sizeof(int) * (size_t)n_blocks, hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));
+    for (int b = 0; b < n_blocks; ++b)
+      if (status[b] != 0)
+        throw DbmError(11, "dbm_tiff_decode: block " + std::to_string(blocks_host[8 * (size_t)b + 5]) +
+                               (status[b] == 1 ? ": malformed LZW stream" : ": the LZW stream does not decode to the block's size") +
+                               "; nothing of this call was written");
+  }
+  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  launch_tiff_rows(a, ctx->stream);
+  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
+  DBM_API_END
+}
+
 int dbm_grid_rescale(dbm_ctx* ctx, const float* in_dev, long H, long W, long out_h, long out_w, int order, int anti_aliasing, int clip,
                      int input_cast, float* out_dev) {
   DBM_API_BEGIN(ctx)

@@ -284,6 +284,34 @@ struct TileLaunch {
   int* counts;
 };
 void launch_grid_tile(const TileLaunch& a, hipStream_t s);
+// Gaps of a fine raster filled from a coarse one (tile.hip; dbm_grid_fill_gaps): `a` describes the mode 1 cut of the COARSE raster with
+// ONE window (a.windows: host values passed by value in `window`), out_h x out_w = the fine raster; out[i] = fine[i] unless fine[i] is
+// NaN or (has_fine_nodata) equals fine_nodata, then the value launch_grid_tile would write at i.  out may be fine.
+void launch_grid_fill_gaps(const TileLaunch& a, const double window[4], const float* fine, int has_fine_nodata, float fine_nodata, float* out,
+                           hipStream_t s);
+
+// GeoTIFF blocks -> a float32 plane (tiff_decode.hip; dbm_tiff_decode).  blocks: n_blocks x 8 int64 on the device = {offset of the
+// block's bytes in `streams`, their count, rows the block holds, output row of the block's row 0, output column of its column 0, id, 0, 0}.
+// lzw: launch_tiff_lzw decodes streams + offset into stage + b * block_stride and writes status[b] (0 good, 1 malformed, 2 the decoded
+// size is not rows * block_w * bytes); launch_tiff_rows then reads from there.  Not lzw: stage == streams, the block's decoded bytes lie
+// at stage + offset (8-byte aligned).  launch_tiff_rows changes the decoded bytes in place (the predictor) and writes out (out_h, out_w).
+struct TiffDecodeLaunch {
+  const uint8_t* streams;
+  uint8_t* stage;
+  const long* blocks;
+  int* status;
+  int n_blocks, lzw;
+  long block_stride;           // bytes between decoded blocks in stage (lzw), a multiple of 8, >= block_h * block_w * bytes
+  int block_w, block_h, bytes; // samples per block row, rows of a whole block, bytes per sample
+  int sample_type;             // 0 uint8, 1 int16, 2 uint16, 3 int32, 4 float32, 5 float64
+  int predictor;               // 1 none, 2 horizontal differencing, 3 floating point
+  float* out;
+  long out_h, out_w;
+};
+void launch_tiff_lzw(const TiffDecodeLaunch& a, hipStream_t s);
+void launch_tiff_rows(const TiffDecodeLaunch& a, hipStream_t s);
+// lzw_decode_lanes with one lane on the host: the decoded size or (size_t)-1 (tools/lzw_twin_check.cpp compares it with dbm_lzw_decode)
+size_t tiff_lzw_decode_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
 
 // Fully filled windows of a raster (tile.hip; dbm_grid_filled_windows): flags[uly * nx + ulx] = 1 iff no node of rows [uly step, uly step
 // + size) x columns [ulx step, ulx step + size) is NaN, rows counted from the north (flip_rows: raster row 0 is the south edge), columns

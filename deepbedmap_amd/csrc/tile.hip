@@ -67,6 +67,27 @@ __device__ inline bool find_cell(double c, double x0, double dx, long n, long* a
   return true;
 }
 
+// Mode 1: the raster at row r, column c of the window w = (left, bottom, right, top), in float64 (NaN outside the raster)
+__device__ inline double tile_bilinear(const TileLaunch& a, const double* w, int r, int c) {
+  const double half = a.res * 0.5;
+  const double y = linspace_at(w[3] - half, w[1] + half, a.out_h, r);
+  const double x = linspace_at(w[0] + half, w[2] - half, a.out_w, c);
+  long r0, r1, c0, c1;
+  double ty, tx;
+  double v = __builtin_nan("");
+  if (find_cell(y, a.y0, a.dy, a.H, &r0, &r1, &ty) && find_cell(x, a.x0, a.dx, a.W, &c0, &c1, &tx)) {
+    const float* p0 = a.grid + r0 * a.W;
+    const float* p1 = a.grid + r1 * a.W;
+    const double z00 = p0[c0], z01 = p0[c1], z10 = p1[c0], z11 = p1[c1];
+    const double uy = 1.0 - ty, ux = 1.0 - tx;
+    v = 0.0 + z00 * (uy * ux);   // (scipy starts from 0.: a first term of -0.0 becomes +0.0)
+    v = v + z01 * (uy * tx);
+    v = v + z10 * (ty * ux);
+    v = v + z11 * (ty * tx);
+  }
+  return v;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(TILE_THREADS) void grid_tile_kernel(TileLaunch a) {
   const long idx = (long)blockIdx.x * TILE_THREADS + threadIdx.x;
@@ -84,23 +105,7 @@ __global__ __launch_bounds__(TILE_THREADS) void grid_tile_kernel(TileLaunch a) {
       const long rr = w[0] + (long)r * w[2], cc = w[1] + (long)c * w[3];   // (inside the raster: checked on the host for every window)
       v = (double)a.grid[rr * a.W + cc];
     } else {
-      const double* w = (const double*)a.windows + 4 * k;   // left, bottom, right, top
-      const double half = a.res * 0.5;
-      const double y = linspace_at(w[3] - half, w[1] + half, a.out_h, r);
-      const double x = linspace_at(w[0] + half, w[2] - half, a.out_w, c);
-      long r0, r1, c0, c1;
-      double ty, tx;
-      v = __builtin_nan("");
-      if (find_cell(y, a.y0, a.dy, a.H, &r0, &r1, &ty) && find_cell(x, a.x0, a.dx, a.W, &c0, &c1, &tx)) {
-        const float* p0 = a.grid + r0 * a.W;
-        const float* p1 = a.grid + r1 * a.W;
-        const double z00 = p0[c0], z01 = p0[c1], z10 = p1[c0], z11 = p1[c1];
-        const double uy = 1.0 - ty, ux = 1.0 - tx;
-        v = 0.0 + z00 * (uy * ux);   // (scipy starts from 0.: a first term of -0.0 becomes +0.0)
-        v = v + z01 * (uy * tx);
-        v = v + z10 * (ty * ux);
-        v = v + z11 * (ty * tx);
-      }
+      v = tile_bilinear(a, (const double*)a.windows + 4 * k, r, c);
     }
     if (a.has_nodata) masked = fabs(v - a.nodata) <= a.nodata_band;   // (false for NaN v)
     if (a.fill_nan && v != v) masked = true;
@@ -119,6 +124,22 @@ __global__ __launch_bounds__(TILE_THREADS) void grid_tile_kernel(TileLaunch a) {
       atomicAdd(a.counts + k, 1);
     }
   }
+}
+
+// dbm_grid_fill_gaps: one lane per node of the fine raster = of the one tile that grid_tile_kernel<1> would cut from the coarse raster
+struct FillWindow { double w[4]; };
+__global__ __launch_bounds__(TILE_THREADS) void grid_fill_gaps_kernel(TileLaunch a, FillWindow win, const float* fine, int has_fine_nodata,
+                                                                      float fine_nodata, float* out) {
+  const long idx = (long)blockIdx.x * TILE_THREADS + threadIdx.x;
+  if (idx >= (long)a.out_h * a.out_w) return;
+  const float z = fine[idx];
+  const bool gap = z != z || (has_fine_nodata && z == fine_nodata);
+  float o = z;
+  if (gap) {
+    const long r = idx / a.out_w;
+    o = (float)tile_bilinear(a, win.w, (int)r, (int)(idx - r * a.out_w));
+  }
+  if (gap || out != fine) ((unsigned*)out)[idx] = __float_as_uint(o);   // (nodes with data: the same bits)
 }
 
 // Row pass: block (segment sgm of logical row lr) -> rowany[lr * nx + ulx] = 1 iff a node of columns [ulx step, ulx step + size) of
@@ -169,6 +190,18 @@ void launch_grid_tile(const TileLaunch& a, hipStream_t s) {
     hipLaunchKernelGGL(grid_tile_kernel<0>, dim3((unsigned)blocks), dim3(TILE_THREADS), 0, s, a);
   else
     hipLaunchKernelGGL(grid_tile_kernel<1>, dim3((unsigned)blocks), dim3(TILE_THREADS), 0, s, a);
+  DBM_HIP(hipGetLastError());
+}
+
+void launch_grid_fill_gaps(const TileLaunch& a, const double window[4], const float* fine, int has_fine_nodata, float fine_nodata, float* out,
+                           hipStream_t s) {
+  const long total = (long)a.out_h * a.out_w;
+  if (total <= 0) return;
+  const long blocks = (total + TILE_THREADS - 1) / TILE_THREADS;
+  DBM_CHECK(blocks < (1L << 31), "gap filling: more than 2^39 nodes in one call");
+  FillWindow win;
+  for (int k = 0; k < 4; ++k) win.w[k] = window[k];
+  hipLaunchKernelGGL(grid_fill_gaps_kernel, dim3((unsigned)blocks), dim3(TILE_THREADS), 0, s, a, win, fine, has_fine_nodata, fine_nodata, out);
   DBM_HIP(hipGetLastError());
 }
 

@@ -8,6 +8,10 @@ tags ModelPixelScale / ModelTiepoint / GeoKeyDirectory with ProjectedCSType = EP
 from libdbm (dbm_lzw_encode_tiles: TIFF 6.0 LZW, host threads over tiles) and the int16 cast of a device-resident canvas
 from the GPU (dbm_f32_to_i16: NumPy's astype semantics, NaN frame -> 0).  `read_geotiff` decodes the file again
 (bit-exact round trip; the tests also decode it with Pillow / libtiff).
+
+Reading rasters as GDAL and libtiff write them (reference data_prep.py:668, :845-877; deepbedmap.py:164-204, through rasterio): the
+second half of this file -- `open_geotiff` (header, geometry, block plan, refusals: host), `read_geotiff_resident` (the blocks decoded on
+the GPU by dbm_tiff_decode: LZW, predictors, float32 conversion, placement; deflate inflated on host threads).  DESIGN.md 6i.
 """
 import ctypes as C
 import os
@@ -242,3 +246,327 @@ def read_geotiff(path):
     info = {"pixel_scale": tags.get(33550), "tiepoint": tags.get(33922), "geokeys": tags.get(34735),
             "nodata": tags.get(42113, b"").rstrip(b"\0").decode(), "bigtiff": big, "compression": comp, "tile": (th, tw)}
     return out[None, :H, :W], info
+
+
+# ---- opening GeoTIFFs as GDAL and libtiff write them: header and block plan on the host, blocks decoded on the GPU ----
+_FIELD_TYPES = {1: ("B", 1), 2: ("s", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8), 6: ("b", 1), 7: ("B", 1), 8: ("h", 2), 9: ("i", 4),
+                10: ("ii", 8), 11: ("f", 4), 12: ("d", 8), 13: ("I", 4), 16: ("Q", 8), 17: ("q", 8), 18: ("Q", 8)}
+# (BitsPerSample, SampleFormat) -> (NumPy dtype, dbm_tiff_decode's sample_type)
+_SAMPLES = {(8, 1): ("u1", 0), (16, 2): ("<i2", 1), (16, 1): ("<u2", 2), (32, 2): ("<i4", 3), (32, 3): ("<f4", 4), (64, 3): ("<f8", 5)}
+_COMPRESSIONS = {1: "none", 5: "lzw", 8: "deflate", 32946: "deflate"}
+WORKSPACE_DEFAULT = 1 << 30   # bytes of block staging per batch of read_geotiff_resident
+
+
+class BlockPlan:
+    """What one (windowed) read takes from the file.  `window` = (row0, col0, H, W) in image pixels; `blocks` = int64 (n, 6), one row
+    per block that meets the window, in file order of the block index: file offset, byte count, rows the block holds (the last strip
+    is short; tiles are whole), row and column of the block's pixel (0, 0) in the OUTPUT plane (negative where the block starts
+    before the window), block index."""
+    OFFSET, BYTES, ROWS, OUT_ROW, OUT_COL, INDEX = range(6)
+
+    def __init__(self, window, blocks):
+        self.window, self.blocks = tuple(int(v) for v in window), blocks
+
+    def __len__(self):
+        return len(self.blocks)
+
+
+class GeoTiffFile:
+    """The first image of a TIFF / BigTIFF file as `open_geotiff` accepts it (one sample per pixel, little endian)."""
+
+    def __init__(self, path, bigtiff, tags):
+        self.path, self.bigtiff, self.tags = path, bigtiff, tags
+
+        def one(tag, default=None):
+            v = tags.get(tag)
+            return default if v is None else v[0]
+
+        self.width, self.height = one(256), one(257)
+        if self.width is None or self.height is None or self.width < 1 or self.height < 1:
+            raise ValueError(f"{path}: ImageWidth (256) = {self.width}, ImageLength (257) = {self.height}: not an image")
+        spp = one(277, 1)
+        if spp != 1:
+            raise ValueError(f"{path}: SamplesPerPixel (277) = {spp}: only one sample per pixel is read (multi-band files are out of scope)")
+        bits, fmt = one(258, 1), one(339, 1)
+        if (bits, fmt) not in _SAMPLES:
+            raise ValueError(f"{path}: BitsPerSample (258) = {bits} with SampleFormat (339) = {fmt}: the sample types read are uint8, int16, "
+                             "uint16, int32, float32 and float64")
+        self.dtype, self.sample_type = np.dtype(_SAMPLES[(bits, fmt)][0]), _SAMPLES[(bits, fmt)][1]
+        self.compression = one(259, 1)
+        if self.compression not in _COMPRESSIONS:
+            raise ValueError(f"{path}: Compression (259) = {self.compression}: only 1 (none), 5 (LZW) and 8 / 32946 (deflate) are read")
+        if one(266, 1) != 1:
+            raise ValueError(f"{path}: FillOrder (266) = {one(266)}: only 1 (most significant bit first) is read")
+        self.predictor = one(317, 1)
+        if self.predictor not in (1, 2, 3) or (self.predictor == 3 and self.dtype.kind != "f"):
+            raise ValueError(f"{path}: Predictor (317) = {self.predictor} with {self.dtype.name} samples: 1, 2, and 3 for floating point "
+                             "samples, are read")
+        if self.compression == 1:
+            self.predictor = 1   # libtiff's predictors are part of its LZW / deflate codecs: on uncompressed data the tag has no effect
+        self.tiled = 322 in tags or 323 in tags
+        if self.tiled:
+            if not (322 in tags and 323 in tags and 324 in tags and 325 in tags):
+                raise ValueError(f"{path}: a tiled file needs TileWidth (322), TileLength (323), TileOffsets (324) and TileByteCounts (325)")
+            self.block_w, self.block_h, self.offsets, self.counts = one(322), one(323), tags[324], tags[325]
+        else:
+            if not (273 in tags and 279 in tags):
+                raise ValueError(f"{path}: StripOffsets (273) and StripByteCounts (279) are missing")
+            self.block_w, self.block_h = self.width, min(one(278, self.height), self.height)
+            self.offsets, self.counts = tags[273], tags[279]
+        if self.block_w < 1 or self.block_h < 1:
+            raise ValueError(f"{path}: blocks of {self.block_h} x {self.block_w}")
+        self.blocks_y, self.blocks_x = -(-self.height // self.block_h), -(-self.width // self.block_w)
+        n = self.blocks_y * self.blocks_x
+        if len(self.offsets) != n or len(self.counts) != n:
+            raise ValueError(f"{path}: {len(self.offsets)} block offsets and {len(self.counts)} byte counts for {n} blocks")
+        if self.block_h * self.block_w * self.dtype.itemsize >= 1 << 31:
+            raise ValueError(f"{path}: blocks of {self.block_h} x {self.block_w} samples hold 2^31 bytes or more")
+        self.nodata = tags.get(42113, b"").split(b"\0")[0].decode("ascii", "replace").strip()
+        self.pixel_scale, self.tiepoint, self.geokeys = tags.get(33550), tags.get(33922), tags.get(34735)
+        self._geometry = self._parse_geometry()
+
+    def _raster_type(self):
+        """GTRasterTypeGeoKey (1025): 1 PixelIsArea (the default), 2 PixelIsPoint."""
+        k = self.geokeys or []
+        for i in range(4, len(k) - 3, 4):
+            if k[i] == 1025 and k[i + 1] == 0:
+                return k[i + 3]
+        return 1
+
+    def _parse_geometry(self):
+        """GridGeometry of the whole image, or the ValueError that asking for it raises."""
+        from .evaluation import GridGeometry
+
+        point = self._raster_type() == 2
+        shift = 0.0 if point else 0.5   # PixelIsPoint: the nodes sit on the tiepoint, not half a pixel in
+        m = self.tags.get(34264)
+        if self.pixel_scale is not None and self.tiepoint is not None and len(self.pixel_scale) >= 2 and len(self.tiepoint) >= 6:
+            px, py = self.pixel_scale[0], self.pixel_scale[1]
+            i, j, _, x, y, _ = self.tiepoint[:6]
+            x0, y0, dx, dy = x + (shift - i) * px, y - (shift - j) * py, px, -py
+        elif m is not None and len(m) == 16:
+            if m[1] != 0 or m[4] != 0:
+                return ValueError(f"{self.path}: ModelTransformation (34264) = {list(m[:8])}...: rotated or sheared rasters are not read")
+            x0, y0, dx, dy = m[3] + shift * m[0], m[7] + shift * m[5], m[0], m[5]
+        else:
+            return ValueError(f"{self.path}: no georeference: ModelPixelScale (33550) with ModelTiepoint (33922), or ModelTransformation "
+                              "(34264), is missing")
+        try:
+            return GridGeometry(x0=x0, y0=y0, dx=dx, dy=dy, registration="pixel")
+        except ValueError as e:
+            return ValueError(f"{self.path}: ModelPixelScale (33550) = {self.pixel_scale}, ModelTiepoint (33922) = {self.tiepoint}: {e}")
+
+    @property
+    def geometry(self):
+        if isinstance(self._geometry, Exception):
+            raise self._geometry
+        return self._geometry
+
+    @property
+    def shape(self):
+        return self.height, self.width
+
+    def window(self, window_bound=None):
+        """(row0, col0, H, W): the pixels whose centres lie in [minx, maxx) x (miny, maxy] -- for bounds on pixel edges the
+        reference's `rasterio.windows.from_bounds(...).round_offsets()` --, clipped to the image.  None: the whole image."""
+        if window_bound is None:
+            return 0, 0, self.height, self.width
+        minx, miny, maxx, maxy = (float(v) for v in window_bound)
+        if not all(np.isfinite(v) for v in (minx, miny, maxx, maxy)):
+            raise ValueError("window_bound must be finite")
+        g = self.geometry
+        xc = np.arange(self.width, dtype=np.float64) * g.dx + g.x0    # (node coordinates as everywhere: multiply, then add)
+        yc = np.arange(self.height, dtype=np.float64) * g.dy + g.y0
+        cols = np.flatnonzero((xc >= minx) & (xc < maxx))
+        rows = np.flatnonzero((yc > miny) & (yc <= maxy))
+        if cols.size == 0 or rows.size == 0:
+            raise ValueError(f"{self.path}: window_bound {(minx, miny, maxx, maxy)} holds no pixel centre of the raster")
+        return int(rows[0]), int(cols[0]), int(rows[-1] - rows[0] + 1), int(cols[-1] - cols[0] + 1)
+
+    def plan(self, window_bound=None):
+        """The blocks a read of `window_bound` (None: everything) needs: a BlockPlan."""
+        row0, col0, H, W = self.window(window_bound)
+        ty = np.arange(row0 // self.block_h, (row0 + H - 1) // self.block_h + 1, dtype=np.int64)
+        tx = np.arange(col0 // self.block_w, (col0 + W - 1) // self.block_w + 1, dtype=np.int64)
+        ty, tx = (a.ravel() for a in np.meshgrid(ty, tx, indexing="ij"))
+        index = ty * self.blocks_x + tx
+        blocks = np.empty((index.size, 6), dtype=np.int64)
+        blocks[:, BlockPlan.OFFSET] = np.asarray(self.offsets, dtype=np.uint64)[index].astype(np.int64)
+        blocks[:, BlockPlan.BYTES] = np.asarray(self.counts, dtype=np.uint64)[index].astype(np.int64)
+        blocks[:, BlockPlan.ROWS] = self.block_h if self.tiled else np.minimum(self.block_h, self.height - ty * self.block_h)
+        blocks[:, BlockPlan.OUT_ROW] = ty * self.block_h - row0
+        blocks[:, BlockPlan.OUT_COL] = tx * self.block_w - col0
+        blocks[:, BlockPlan.INDEX] = index
+        size = os.path.getsize(self.path)
+        for b in blocks:
+            tagname = "TileByteCounts (325)" if self.tiled else "StripByteCounts (279)"
+            if b[BlockPlan.BYTES] < 1:
+                raise ValueError(f"{self.path}: {tagname}[{b[BlockPlan.INDEX]}] = {b[BlockPlan.BYTES]}: sparse (absent) blocks are not read")
+            if b[BlockPlan.OFFSET] < 0 or b[BlockPlan.OFFSET] + b[BlockPlan.BYTES] > size:
+                raise ValueError(f"{self.path}: block {b[BlockPlan.INDEX]} (offset {b[BlockPlan.OFFSET]}, {b[BlockPlan.BYTES]} bytes) lies "
+                                 f"outside the file ({size} bytes)")
+        return BlockPlan((row0, col0, H, W), blocks)
+
+
+def _read_tags(f, path):
+    head = f.read(16)
+    if head[:2] == b"MM":
+        raise ValueError(f"{path}: byte order 'MM': big-endian TIFFs are not read")
+    if len(head) < 8 or head[:2] != b"II":
+        raise ValueError(f"{path}: byte order {head[:2]!r}: not a TIFF file")
+    magic = struct.unpack_from("<H", head, 2)[0]
+    if magic not in (42, 43):
+        raise ValueError(f"{path}: TIFF version {magic}: neither classic TIFF (42) nor BigTIFF (43)")
+    big = magic == 43
+    if big and struct.unpack_from("<HH", head, 4) != (8, 0):
+        raise ValueError(f"{path}: BigTIFF offset size {struct.unpack_from('<HH', head, 4)}: must be (8, 0)")
+    ifd = struct.unpack_from("<Q", head, 8)[0] if big else struct.unpack_from("<I", head, 4)[0]
+    size = os.fstat(f.fileno()).st_size
+
+    def at(pos, n, what):
+        if pos < 0 or pos + n > size:
+            raise ValueError(f"{path}: {what} at offset {pos} ({n} bytes) lies outside the file ({size} bytes)")
+        f.seek(pos)
+        return f.read(n)
+
+    cnt_fmt, cnt_size, entry_size, inline = ("<Q", 8, 20, 8) if big else ("<H", 2, 12, 4)
+    n = struct.unpack(cnt_fmt, at(ifd, cnt_size, "the first IFD"))[0]
+    table = at(ifd + cnt_size, n * entry_size, "the first IFD's entries")
+    tags = {}
+    for k in range(n):
+        tag, typ, count = struct.unpack_from("<HHQ" if big else "<HHI", table, k * entry_size)
+        if typ not in _FIELD_TYPES:
+            continue   # (a field type of a later TIFF revision: the tag is unknown to this reader anyway)
+        fmt, esize = _FIELD_TYPES[typ]
+        vpos = k * entry_size + (12 if big else 8)
+        if count * esize <= inline:
+            data = table[vpos:vpos + count * esize]
+        else:
+            data = at(struct.unpack_from("<Q" if big else "<I", table, vpos)[0], count * esize, f"the values of tag {tag}")
+        if typ == 2:
+            tags[tag] = data
+        elif len(fmt) == 1 and count > 64:
+            tags[tag] = np.frombuffer(data, dtype=np.dtype("<" + {"B": "u1", "b": "i1", "H": "u2", "h": "i2", "I": "u4", "i": "i4", "Q": "u8",
+                                                                   "q": "i8", "f": "f4", "d": "f8"}[fmt]))
+        else:
+            tags[tag] = list(struct.unpack("<" + fmt * count, data))
+    return big, tags
+
+
+def open_geotiff(path):
+    """Parses the header and the first image directory of a TIFF / BigTIFF file as GDAL and libtiff write them: little endian,
+    strips or tiles, one sample per pixel of uint8 / int16 / uint16 / int32 / float32 / float64, Compression 1 / 5 (LZW) / 8 or
+    32946 (deflate), Predictor 1 / 2 / 3.  Everything else raises ValueError naming the tag and its value -- here, before any
+    device work.  Returns a GeoTiffFile."""
+    path = os.fspath(path)
+    with open(path, "rb") as f:
+        big, tags = _read_tags(f, path)
+        gf = GeoTiffFile(path, big, tags)
+        if gf.compression == 5:
+            # old-style LZW (TIFF 5.0 writers: least significant bit first) starts with the bytes 00 01; TIFF 6.0 streams with ClearCode
+            for o, c in zip(gf.offsets, gf.counts):
+                if c >= 2:
+                    f.seek(int(o))
+                    first = f.read(2)
+                    if len(first) == 2 and first[0] == 0 and first[1] & 1:
+                        raise ValueError(f"{path}: Compression (259) = 5 with a stream that starts {first.hex()}: old-style LZW (least "
+                                         "significant bit first) is not read")
+                    break
+    return gf
+
+
+def _batches(gf, plan, limit):
+    """Consecutive runs of the plan's blocks whose staging (stream + decoded block) stays within `limit` bytes; never an empty run."""
+    decoded = -(-gf.block_h * gf.block_w * gf.dtype.itemsize // 16) * 16
+    runs, start, used = [], 0, 0
+    for k, b in enumerate(plan.blocks):
+        cost = decoded + (int(b[BlockPlan.BYTES]) if gf.compression == 5 else 16)
+        if k > start and used + cost > limit:
+            runs.append((start, k))
+            start, used = k, 0
+        used += cost
+    runs.append((start, len(plan.blocks)))
+    return runs
+
+
+def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=None):
+    """Decodes a GeoTIFF (`open_geotiff`'s dialect) into HBM: LZW, the predictors, the conversion to float32 (NumPy's `astype`) and
+    the placement run on the GPU (dbm_tiff_decode); deflate streams are inflated on host threads first.  window_bound = (minx, miny,
+    maxx, maxy) reads the pixels whose centres lie in [minx, maxx) x (miny, maxy] and only the blocks that hold them.
+    workspace_limit: bytes of block staging per batch (default 1 GiB; at least one block goes through at a time).
+    Returns (DeviceArray (H, W), info): read_geotiff's keys plus predictor, dtype, window (row0, col0, H, W) and geometry (the
+    window's GridGeometry, None for a file without georeference)."""
+    import dataclasses
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+
+    from .srgan import DeviceArray
+
+    if workspace_limit is None:
+        workspace_limit = WORKSPACE_DEFAULT
+    workspace_limit = int(workspace_limit)
+    if workspace_limit < 1:
+        raise ValueError("workspace_limit must be positive")
+    gf = open_geotiff(path)
+    if window_bound is None:
+        geometry = None if isinstance(gf._geometry, Exception) else gf._geometry
+    else:
+        geometry = gf.geometry
+    plan = gf.plan(window_bound)
+    row0, col0, H, W = plan.window
+    if geometry is not None:
+        geometry = dataclasses.replace(geometry, x0=col0 * geometry.dx + geometry.x0, y0=row0 * geometry.dy + geometry.y0)
+    ctx = ctx or _lib.default_context()
+    out = DeviceArray((H, W), ctx)
+    lib = _lib.lib()
+    itemsize = gf.dtype.itemsize
+    with open(gf.path, "rb") as f:
+        for start, stop in _batches(gf, plan, workspace_limit):
+            part = plan.blocks[start:stop]
+            streams = []
+            for b in part:
+                f.seek(int(b[BlockPlan.OFFSET]))
+                s = f.read(int(b[BlockPlan.BYTES]))
+                if len(s) != b[BlockPlan.BYTES]:
+                    raise _lib.DbmError(f"{gf.path}: block {b[BlockPlan.INDEX]}: the file ends inside its {b[BlockPlan.BYTES]} bytes")
+                streams.append(s)
+            table = np.zeros((len(part), 8), dtype=np.int64)
+            table[:, 2:6] = part[:, BlockPlan.ROWS:BlockPlan.INDEX + 1]
+            if gf.compression == 5:
+                sizes = np.array([len(s) for s in streams], dtype=np.int64)
+                table[:, 0] = np.cumsum(sizes) - sizes
+                table[:, 1] = sizes
+                payload = np.frombuffer(b"".join(streams), dtype=np.uint8)
+                mode = 5
+            else:
+                if gf.compression != 1:
+                    def inflate(k):
+                        try:
+                            return zlib.decompress(streams[k])
+                        except zlib.error as e:
+                            raise _lib.DbmError(f"{gf.path}: block {part[k, BlockPlan.INDEX]}: malformed deflate stream ({e})") from None
+                    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+                        streams = list(pool.map(inflate, range(len(streams))))
+                want = part[:, BlockPlan.ROWS] * gf.block_w * itemsize
+                stride = -(-gf.block_h * gf.block_w * itemsize // 16) * 16
+                payload = np.zeros(len(part) * stride, dtype=np.uint8)
+                for k, s in enumerate(streams):
+                    if len(s) < want[k]:
+                        raise _lib.DbmError(f"{gf.path}: block {part[k, BlockPlan.INDEX]}: {len(s)} decoded bytes, {want[k]} expected")
+                    payload[k * stride:k * stride + want[k]] = np.frombuffer(s, dtype=np.uint8, count=int(want[k]))
+                table[:, 0] = np.arange(len(part), dtype=np.int64) * stride
+                table[:, 1] = want
+                mode = 1
+            try:
+                _lib.check(lib.dbm_tiff_decode(ctx.handle, payload.ctypes.data_as(C.c_void_p), payload.size, table.ctypes.data_as(C.c_void_p),
+                                               len(part), mode, gf.predictor, gf.sample_type, gf.block_w, gf.block_h, C.c_void_p(out.ptr), H, W),
+                           ctx.handle)
+            except _lib.DbmError as e:
+                err = _lib.DbmError(f"{gf.path}: {e}")
+                err.code = e.code
+                raise err from None
+    out._gen += 1
+    info = {"pixel_scale": gf.pixel_scale, "tiepoint": gf.tiepoint, "geokeys": gf.geokeys, "nodata": gf.nodata, "bigtiff": gf.bigtiff,
+            "compression": gf.compression, "tile": (gf.block_h, gf.block_w), "predictor": gf.predictor, "dtype": gf.dtype,
+            "window": plan.window, "geometry": geometry}
+    return out, info

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .evaluation import GridGeometry, _grid_plane
-from .geotiff import read_geotiff
+from .geotiff import read_geotiff, read_geotiff_resident
 from .srgan import DeviceArray, to_device
 
 
@@ -49,6 +49,23 @@ class Raster:
         geometry = GridGeometry(x0=x + (0.5 - i) * px, y0=y - (0.5 - j) * py, dx=px, dy=-py, registration="pixel")
         nodata = float(info["nodata"]) if info["nodata"] else None
         return cls(array[0].astype(np.float32), geometry, nodata=nodata, ctx=ctx)
+
+    @classmethod
+    def open(cls, path, window_bound=None, ctx=None):
+        """A GeoTIFF as GDAL and libtiff write them (`geotiff.open_geotiff`'s dialect), decoded on the GPU and resident from the
+        start: the file's geometry (GTRasterTypeGeoKey honoured), shifted to the window (minx, miny, maxx, maxy) if one is given
+        -- only its blocks are read --, and its GDAL_NODATA.  A file without georeference raises ValueError."""
+        from .geotiff import open_geotiff
+
+        open_geotiff(path).geometry   # (raises before any device work)
+        array, info = read_geotiff_resident(path, window_bound=window_bound, ctx=ctx)
+        try:
+            nodata = float(info["nodata"]) if info["nodata"] else None
+        except ValueError:
+            raise ValueError(f"{path}: GDAL_NODATA (42113) = {info['nodata']!r} is not a number") from None
+        if nodata is not None and np.isinf(nodata):
+            nodata = None   # (GDAL writes "inf" / "-inf" too; a Raster's nodata is finite or NaN)
+        return cls(array, info["geometry"], nodata=nodata)
 
     @property
     def shape(self):
@@ -317,3 +334,35 @@ def tile_training_set(highres, bedmap2, rema, velocity_x, velocity_y, accumulati
             "W2": _two_channels(velocity_x, velocity_y, windows, 1000, None),
             "W3": selective_tile(accumulation, windows, padding=1000),
             "Y": Y}
+
+
+def fill_gaps(fine, coarse, inplace=False):
+    """data_prep.py:838-877 (REMA at 100 m patched from the 200 m mosaic) on resident rasters: every node of `fine` that is NaN or
+    equal to `fine.nodata` takes the value `selective_tile(coarse, [bounds of fine], resolution=fine.dx)` has at that node -- this
+    package's bilinear rule (scipy's interpn), NaN outside `coarse`, NOT GDAL's mask-renormalised resampler; nodes
+    with data keep their bits.  `fine` must be north-up with square pixels.  Returns a Raster with fine's geometry and nodata: a new
+    plane, or with inplace=True `fine` itself, patched where it lies."""
+    if not isinstance(fine, Raster) or not isinstance(coarse, Raster):
+        raise TypeError("fine and coarse must be Rasters")
+    g = fine.geometry
+    if not (g.dx > 0 and g.dy < 0 and g.dx == -g.dy):
+        raise ValueError(f"fill_gaps needs a north-up fine raster with square pixels, it has dx {g.dx}, dy {g.dy}")
+    if coarse.H < 2 or coarse.W < 2:
+        raise ValueError(f"bilinear interpolation needs at least 2 x 2 nodes, the coarse raster is {coarse.H} x {coarse.W}")
+    west, north = g.x0 - g.dx / 2, g.y0 + g.dx / 2   # the raster's edges lie half a pixel outside its outermost nodes
+    bounds = (west, north - fine.H * g.dx, west + fine.W * g.dx, north)
+    if tile_shape([bounds], 0, g.dx) != fine.shape:
+        raise ValueError(f"fill_gaps: the bounds {bounds} of the fine raster do not give its shape {fine.shape} at resolution {g.dx}")
+    src, cgrid = fine.device(), coarse.device()
+    ctx = src.ctx
+    if cgrid.ctx is not ctx:
+        raise ValueError("fill_gaps: fine and coarse live on different contexts")
+    out = src if inplace else DeviceArray(src.shape, ctx)
+    wb = np.asarray(bounds, dtype=np.float64)
+    cgeom = coarse.geometry.as_array()
+    nodata = None if fine.nodata is None else C.byref(C.c_double(fine.nodata))
+    _lib.check(_lib.lib().dbm_grid_fill_gaps(ctx.handle, C.c_void_p(src.ptr), fine.H, fine.W, wb.ctypes.data_as(C.POINTER(C.c_double)), float(g.dx),
+                                             nodata, C.c_void_p(cgrid.ptr), coarse.H, coarse.W, cgeom.ctypes.data_as(C.POINTER(C.c_double)),
+                                             C.c_void_p(out.ptr)), ctx.handle)
+    out._gen += 1
+    return fine if inplace else Raster(out, g, nodata=fine.nodata)

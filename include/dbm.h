@@ -324,6 +324,17 @@ int dbm_grid_tile(dbm_ctx* ctx, const float* grid_dev, long H, long W, const dou
  * with the caller.  Refused (status 1): size odd, < 2 or > 8192, step < 1, H or W < size, NULL pointers. */
 int dbm_grid_filled_windows(dbm_ctx* ctx, const float* grid_dev, long H, long W, int size, int step, int flip_rows, int flip_cols,
                             unsigned char* flags_dev);
+/* Gap filling of a fine raster from a coarse one (data_prep.py:838-877: REMA at 100 m patched from the 200 m mosaic).  fine_dev
+ * (H, W) float32, north-up, is the raster whose pixel edges are bounds = {minx, miny, maxx, maxy} at `resolution`.  out_dev[r, c] =
+ * fine_dev[r, c] bit for bit unless that value is NaN or (fine_nodata != NULL, *fine_nodata not NaN) equals (float)*fine_nodata; at
+ * such a node it is what dbm_grid_tile(coarse_dev, mode 1, windows = {bounds}, resolution, out_h = H, out_w = W, no gap filler)
+ * writes at [r, c]: the package's bilinear rule above (the same code), NaN outside the coarse raster, a coarse nodata value
+ * interpolated like any other (mask it afterwards if need be).  This is NOT GDAL's mask-renormalised resampler.
+ * out_dev may be fine_dev (in place: only the gap nodes are written).  Asynchronous on the context's stream.  Refused (status 1,
+ * nothing launched): NULL pointers, H or W outside 1..2^31 - 1, cH or cW < 2, coarse_geom = {x0, y0, dx, dy} not finite or with a
+ * zero spacing, bounds not finite, a resolution that is not positive, an infinite nodata, out_dev == coarse_dev. */
+int dbm_grid_fill_gaps(dbm_ctx* ctx, const float* fine_dev, long H, long W, const double bounds[4], double resolution, const double* fine_nodata,
+                       const float* coarse_dev, long cH, long cW, const double coarse_geom[4], float* out_dev);
 
 /* ---- comparison grids: the bicubic BEDMAP2 baseline and the synthetic grid at 250 m (deepbedmap.py:323-331, 348-356:
  * `skimage.transform.rescale(image.astype(np.int32), scale, order, mode="reflect", anti_aliasing=True, preserve_range=True)`; again at
@@ -503,7 +514,7 @@ int dbm_discriminator_step(dbm_model* g, dbm_model* d, int N, int H, int W, cons
  * (its bit 1); bit 2 (4) = consume the forward that step prefetched (its bit 2): the caller asserts that the five
  * arrays are the same, UNCHANGED, device arrays.  The library additionally checks pointers, shapes, the parameter
  * version and its own record of writes to device memory (dbm_memcpy_h2d, dbm_gather_rows, dbm_fill_f32,
- * dbm_memcpy2d_d2d, dbm_grid_tile, dbm_grid_filled_windows, dbm_grid_rescale, dbm_grid_rolling_std, dbm_malloc, dbm_free); writes by anybody else (another library filling the same buffer in
+ * dbm_memcpy2d_d2d, dbm_grid_tile, dbm_grid_filled_windows, dbm_grid_fill_gaps, dbm_tiff_decode, dbm_grid_rescale, dbm_grid_rolling_std, dbm_malloc, dbm_free); writes by anybody else (another library filling the same buffer in
  * place) are invisible to it, hence the explicit bit.  Without it the prefetched pass is discarded and the forward is
  * recomputed.  bit 4 (16) = see dbm_discriminator_step. */
 int dbm_generator_step(dbm_model* g, dbm_model* d, int N, int H, int W, const float* X, const float* W1,
@@ -523,6 +534,33 @@ int dbm_f32_to_i16(dbm_ctx* ctx, const float* src_dev, void* dst_dev, size_t n);
 int dbm_lzw_encode_tiles(const void* tiles, size_t tile_bytes, int ntiles, void* out, size_t out_stride, size_t* out_sizes,
                          int nthreads);
 int dbm_lzw_decode(const void* src, size_t nbytes, void* dst, size_t cap, size_t* out_bytes);
+
+/* ---- opening rasters: GeoTIFF blocks decoded on the device (replaces the rasterio / GDAL reads of data_prep.py:668, :845-877 and
+ * deepbedmap.py:164-204; header parsing, the block plan, file reads and inflate stay with the host shim deepbedmap_amd/geotiff.py) ----
+ * dbm_tiff_decode turns n_blocks blocks (strips or tiles) of one-sample pixels into their places of the float32 plane out_dev (out_h,
+ * out_w), ALWAYS a device pointer.  streams_host (streams_bytes bytes, HOST, uploaded once per call) holds the blocks' bytes;
+ * blocks_host (HOST) has 8 int64 per block: {offset of its bytes in streams_host, their count, rows the block holds (1..block_h: the
+ * last strip is short, tiles are whole), output row of the block's row 0, output column of its column 0 (either may be negative or
+ * beyond the plane: samples outside [0, out_h) x [0, out_w) are dropped -- tile padding, the part outside a window), id (only named
+ * in error messages), 0, 0}.  A block row has block_w samples.
+ * compression 5: the bytes are a TIFF 6.0 LZW stream (MSB-first codes, 9..12 bits, early change, ClearCode 256, EndOfInformation 257:
+ * what dbm_lzw_decode reads), decoded by one wavefront per block; a stream may end without EndOfInformation if the block is complete.
+ * compression 1: the bytes ARE the decoded block (uncompressed files; deflate inflated by the caller), offset a multiple of 8, count
+ * >= rows * block_w * bytes.
+ * predictor (TIFF tag 317) 1: none; 2: every row is a running sum of its samples, wrapping in the sample's width (float samples:
+ * on their bit patterns); 3 (float samples): every row's block_w * bytes bytes are a running sum modulo 256, then byte plane k
+ * (block_w bytes) holds byte k of every sample, most significant first.
+ * sample_type 0 uint8, 1 int16, 2 uint16, 3 int32, 4 float32, 5 float64, little endian; converted as numpy.astype(float32) does
+ * (float32 samples keep their bits, NaN payloads included).
+ * The call allocates its workspace (streams_bytes + 68 per block; for LZW also block_w * block_h * bytes, rounded up to 16, per
+ * block), frees it on every path and synchronises the context's stream; the caller bounds the workspace by batching.
+ * Status 11: an LZW stream is malformed (a first code above 255, a code above the next free one, more output than the block holds) or
+ * does not decode to rows * block_w * bytes bytes; the message names the block's id and nothing of this call has been written.
+ * Refused (status 1, nothing launched): compression not 1 or 5, sample_type outside 0..5, predictor not 1, 2 or 3 (3: float samples
+ * only), block_w or block_h < 1, a block of 2^31 bytes or more, n_blocks * block_h >= 2^31, an empty plane, NULL pointers with
+ * n_blocks > 0, bytes outside streams_host, rows outside 1..block_h, decoded bytes misaligned or short.  n_blocks = 0 succeeds. */
+int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host, int n_blocks, int compression,
+                    int predictor, int sample_type, int block_w, int block_h, float* out_dev, long out_h, long out_w);
 
 /* One minibatch of `trainer` (srgan_train.py:1286-1309) as ONE call: train_eval_discriminator (:1084-1166) with its
  * optimizer update, then train_eval_generator (:1170-1263) with its update; both optimizers must have been set up
