@@ -1,13 +1,13 @@
-// extern "C" surface of libdbm.so (include/dbm.h).  No exception crosses the boundary.
-#include "model.h"
-#include <cmath>
+// extern "C" surface of libdbm.so (include/dbm.h), training: contexts and streams, models and tensors, losses and metrics, the
+// optimizer, the fused steps, dbm_op_*.  (Data preparation: api_data.hip.)
+#include "api_common.h"
 
 static thread_local std::string g_last_error;
+void api_record_error(dbm_ctx* ctx, const char* what) {
+  g_last_error = what;
+  if (ctx) ctx->err = what;
+}
 
-#define DBM_API_BEGIN(ctxptr) \
-  dbm_ctx* _ectx = (ctxptr);  \
-  (void)_ectx;                \
-  try {
 // ---- a persistent trunk kernel that gives up (bounded spins: another process starving the GPU, a partitioned device) ----
 // It raises the context's error word (host-mapped) and a STICKY device flag.  While the flag is up, every kernel that commits
 // training state is a no-op: the optimizer launches (gated ONCE per launch by adam_gate_kernel, so an update is all or
@@ -85,20 +85,6 @@ static void dbm_step_entry(dbm_ctx* c, bool counts_as_iteration) {
   }
 }
 
-#define DBM_API_END                                   \
-  return 0;                                           \
-  }                                                   \
-  catch (const DbmError& e) {                         \
-    g_last_error = e.what();                          \
-    if (_ectx) _ectx->err = e.what();                 \
-    return e.code;                                    \
-  }                                                   \
-  catch (const std::exception& e) {                   \
-    g_last_error = e.what();                          \
-    if (_ectx) _ectx->err = e.what();                 \
-    return 3;                                         \
-  }
-
 // metrics finalisation -----------------------------------------------------------------------------
 __global__ void gen_metrics_kernel(const float* part, int N, const float* adv, float* out, float nhw, float npool, float nwin,
                                    float cw, float aw, float tw, float sw) {
@@ -123,20 +109,20 @@ static void gaussian9(float* w, double sigma) {
 
 // staging helpers for the host-pointer forms ---------------------------------------------------------
 static const float* stage_in(dbm_ctx* c, int slot, const float* host, size_t n, int flags) {
-  if (flags & DBM_DEVICE_PTRS) return host;
+  if (device_ptrs(flags)) return host;
   if (!host) return nullptr;
   c->stage[slot].ensure(n);
   DBM_HIP(hipMemcpyAsync(c->stage[slot].p, host, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   return c->stage[slot].p;
 }
 static float* stage_out(dbm_ctx* c, int slot, float* host, size_t n, int flags) {
-  if (flags & DBM_DEVICE_PTRS) return host;
+  if (device_ptrs(flags)) return host;
   if (!host) return nullptr;
   c->stage[slot].ensure(n);
   return c->stage[slot].p;
 }
 static void finish_out(dbm_ctx* c, int slot, float* host, size_t n, int flags) {
-  if ((flags & DBM_DEVICE_PTRS) || !host) return;
+  if (device_ptrs(flags) || !host) return;
   DBM_HIP(hipMemcpyAsync(host, c->stage[slot].p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 }
 // End of a host-synchronising entry point (host pointers: the results are about to be read by the caller).  The stream is
@@ -144,7 +130,7 @@ static void finish_out(dbm_ctx* c, int slot, float* host, size_t n, int flags) {
 // here (like at a step entry) and the call returns status 7 / 8 -- re-issue it, it then runs on the layer-by-layer kernels.
 // Calls on device pointers only enqueue: their callers observe the condition with dbm_check_timeout after synchronising.
 static void finish_sync(dbm_ctx* c, int flags) {
-  if (flags & DBM_DEVICE_PTRS) return;
+  if (device_ptrs(flags)) return;
   DBM_HIP(hipStreamSynchronize(c->stream));
   if (c->dev_err && *(volatile int*)c->dev_err) {
     const bool dp = c->comm_active();
@@ -249,8 +235,8 @@ int dbm_shutdown(dbm_ctx* ctx) {
 }
 
 int dbm_set_stream(dbm_ctx* ctx, void* hip_stream) {
-  DBM_API_BEGIN(ctx)  // (a pending iteration tail has been joined into the OLD stream by the line above: drain it)
-  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  DBM_API_BEGIN(ctx)
+  DBM_HIP(hipStreamSynchronize(ctx->stream));  // whatever earlier calls enqueued on the OLD stream is done before the switch
   ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
   DBM_API_END
 }
@@ -390,7 +376,7 @@ int dbm_profile_end_records(dbm_ctx* ctx, char* buf, size_t cap, size_t* len) {
 int dbm_memcpy2d_d2d(dbm_ctx* ctx, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes,
                      size_t height) {
   DBM_API_BEGIN(ctx)
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  note_device_write(ctx);
   if (width_bytes && height)
     DBM_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width_bytes, height, hipMemcpyDeviceToDevice, ctx->stream));
   DBM_API_END
@@ -398,27 +384,27 @@ int dbm_memcpy2d_d2d(dbm_ctx* ctx, void* dst, size_t dpitch, const void* src, si
 
 int dbm_gather_rows(dbm_ctx* ctx, void* dst, const void* src, const int* idx_host, int n, size_t row_bytes) {
   DBM_API_BEGIN(ctx)
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  note_device_write(ctx);
   DBM_CHECK(n >= 0 && row_bytes % 4 == 0, "dbm_gather_rows: rows must be whole float32 elements");
   if (n && row_bytes) {
     DBM_CHECK(idx_host != nullptr, "dbm_gather_rows: idx is NULL");
-    ctx->stage[7].ensure((size_t)n);  // (floats: 4 bytes each, like the int indices)
-    DBM_HIP(hipMemcpyAsync(ctx->stage[7].p, idx_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    launch_gather_rows(src, dst, (const int*)ctx->stage[7].p, n, row_bytes, ctx->stream);
+    int* idx = ctx->stage[7].as<int>((size_t)n);
+    DBM_HIP(hipMemcpyAsync(idx, idx_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    launch_gather_rows(src, dst, idx, n, row_bytes, ctx->stream);
   }
   DBM_API_END
 }
 
 int dbm_fill_f32(dbm_ctx* ctx, float* dst, size_t n, float value) {
   DBM_API_BEGIN(ctx)
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  note_device_write(ctx);
   if (n) launch_fill(dst, (long)n, value, ctx->stream);
   DBM_API_END
 }
 
 int dbm_clip_min_f32(dbm_ctx* ctx, float* dst, size_t n, float lo) {
   DBM_API_BEGIN(ctx)
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  note_device_write(ctx);
   if (n) launch_clip_min(dst, (long)n, lo, ctx->stream);
   DBM_API_END
 }
@@ -501,7 +487,7 @@ int dbm_phase_marks(dbm_ctx* ctx, int enable, char* out, int cap) {
 
 int dbm_malloc(dbm_ctx* ctx, size_t bytes, void** dptr) {
   DBM_API_BEGIN(ctx)
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  note_device_write(ctx);
   // 128-byte guards on both sides (see DevBuf): kernels may read one word outside a tensor
   char* base = nullptr;
   DBM_HIP(hipMalloc((void**)&base, bytes + 256));
@@ -512,14 +498,14 @@ int dbm_malloc(dbm_ctx* ctx, size_t bytes, void** dptr) {
 }
 int dbm_free(dbm_ctx* ctx, void* dptr) {
   DBM_API_BEGIN(ctx)
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  note_device_write(ctx);
   DBM_HIP(hipStreamSynchronize(ctx->stream));
   DBM_HIP(hipFree(dptr ? (char*)dptr - 128 : nullptr));
   DBM_API_END
 }
 int dbm_memcpy_h2d(dbm_ctx* ctx, void* dst, const void* src, size_t bytes) {
   DBM_API_BEGIN(ctx)
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
+  note_device_write(ctx);
   DBM_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
   DBM_HIP(hipStreamSynchronize(ctx->stream));
   DBM_API_END
@@ -737,8 +723,7 @@ int dbm_discriminator_loss(dbm_ctx* ctx, const float* real, const float* fake, i
 int dbm_discriminator_loss_t(dbm_ctx* ctx, const float* real, const float* fake, int N, const int* t_rf, const int* t_fr,
                              float* out2, float* g_real, float* g_fake, int flags) {
   if (!t_rf || !t_fr) {
-    g_last_error = "dbm_discriminator_loss_t: both target arrays are required";
-    if (ctx) ctx->err = g_last_error;
+    api_record_error(ctx, "dbm_discriminator_loss_t: both target arrays are required");
     return 1;
   }
   return discriminator_loss_impl(ctx, real, fake, N, 1, 0, t_rf, t_fr, out2, g_real, g_fake, flags);
@@ -828,8 +813,7 @@ int dbm_generator_loss_t(dbm_ctx* ctx, const float* y_pred, const float* y_true,
                          const float* fake_logits, int N, int H, int W, const float weights[4], const int* t_rf, const int* t_fr,
                          int ssim_window, float* out3, float* gy, int flags) {
   if (!t_rf || !t_fr) {
-    g_last_error = "dbm_generator_loss_t: both target arrays are required";
-    if (ctx) ctx->err = g_last_error;
+    api_record_error(ctx, "dbm_generator_loss_t: both target arrays are required");
     return 1;
   }
   return generator_loss_impl(ctx, y_pred, y_true, x, real_logits, fake_logits, N, H, W, weights, 0, 1, t_rf, t_fr, ssim_window,
@@ -902,655 +886,6 @@ int dbm_ssim_ex(dbm_ctx* ctx, const float* y_pred, const float* y_true, int N, i
   hipLaunchKernelGGL(ssim_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, sums, N, nwin, dout);
   finish_out(ctx, 2, out, 1, flags);
   finish_sync(ctx, flags);
-  DBM_API_END
-}
-
-int dbm_grid_track(dbm_ctx* ctx, const float* grid_dev, long H, long W, const double geom[5], const double* points, size_t n,
-                   int ncol, int interp, double threshold, double* z_out, double* stats, int flags) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && geom != nullptr, "dbm_grid_track: NULL argument");
-  DBM_CHECK(interp >= 0 && interp <= 2, "dbm_grid_track: interp must be 0 (nearest), 1 (bilinear) or 2 (bicubic)");
-  DBM_CHECK(H >= 1 && W >= 1, "dbm_grid_track: empty grid");
-  DBM_CHECK(interp == 0 || (H >= 2 && W >= 2), "dbm_grid_track: bilinear and bicubic need at least 2 x 2 nodes");
-  DBM_CHECK(threshold > 0.0 && threshold <= 1.0, "dbm_grid_track: threshold must lie in (0, 1]");
-  DBM_CHECK(ncol == 2 || ncol == 3, "dbm_grid_track: points have 2 (x, y) or 3 (x, y, z) columns");
-  DBM_CHECK(std::isfinite(geom[0]) && std::isfinite(geom[1]) && std::isfinite(geom[2]) && std::isfinite(geom[3]) && geom[2] != 0.0 &&
-                geom[3] != 0.0, "dbm_grid_track: x0, y0 finite, dx, dy finite and non-zero");
-  DBM_CHECK(geom[4] == 0.0 || geom[4] == 1.0, "dbm_grid_track: registration must be 0 (gridline) or 1 (pixel)");
-  DBM_CHECK(n == 0 || (grid_dev != nullptr && points != nullptr), "dbm_grid_track: NULL grid or points");
-  const bool reduce = ncol == 3 && stats != nullptr;
-  const double half = geom[4] == 1.0 ? 0.5 : 0.0;
-  TrackLaunch a;
-  a.grid = grid_dev;
-  a.H = H;
-  a.W = W;
-  a.x0 = geom[0]; a.y0 = geom[1]; a.dx = geom[2]; a.dy = geom[3];
-  a.tlo = -half; a.thi = (double)(W - 1) + half;
-  a.slo = -half; a.shi = (double)(H - 1) + half;
-  a.n = (long)n;
-  a.ncol = ncol;
-  a.interp = interp;
-  a.threshold = threshold;
-  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
-  // host forms: points in stage[0], z_interpolated in stage[1] (sizes in floats)
-  if (dev || n == 0) {
-    a.points = points;
-  } else {
-    ctx->stage[0].ensure(2 * n * (size_t)ncol);
-    DBM_HIP(hipMemcpyAsync(ctx->stage[0].p, points, n * ncol * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    a.points = (const double*)ctx->stage[0].p;
-  }
-  a.z_out = nullptr;
-  if (z_out && n > 0) {
-    if (dev) {
-      a.z_out = z_out;
-    } else {
-      ctx->stage[1].ensure(2 * n);
-      a.z_out = (double*)ctx->stage[1].p;
-    }
-  }
-  const int blocks = grid_track_blocks((long)n);
-  ctx->track_tmp.ensure(2 * (8 + 6 * (size_t)blocks));
-  double* dstats = (double*)ctx->track_tmp.p;
-  a.part = reduce ? dstats + 8 : nullptr;
-  launch_grid_track(a, dstats, ctx->stream);
-  if (!dev) {
-    if (a.z_out) DBM_HIP(hipMemcpyAsync(z_out, a.z_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (reduce) DBM_HIP(hipMemcpyAsync(stats, dstats, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipStreamSynchronize(ctx->stream));
-  } else if (reduce) {
-    DBM_HIP(hipMemcpyAsync(stats, dstats, 6 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  DBM_API_END
-}
-
-int dbm_grid_tile(dbm_ctx* ctx, const float* grid_dev, long H, long W, const double geom[4], const void* windows_host, long n, int mode,
-                  double resolution, int out_h, int out_w, const double* nodata, const float* gapfiller, int fill_nan, float* out_dev,
-                  size_t window_stride, int* counts_dev) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && geom != nullptr, "dbm_grid_tile: NULL argument");
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  DBM_CHECK(mode == 0 || mode == 1, "dbm_grid_tile: mode must be 0 (slicing) or 1 (bilinear)");
-  DBM_CHECK(n >= 0, "dbm_grid_tile: negative number of windows");
-  DBM_CHECK(out_h >= 1 && out_w >= 1, "dbm_grid_tile: empty tiles");
-  DBM_CHECK((long)out_h * out_w < (1L << 31), "dbm_grid_tile: one tile must stay below 2^31 values");
-  DBM_CHECK(H >= 1 && W >= 1, "dbm_grid_tile: empty raster");
-  DBM_CHECK(mode == 0 || (H >= 2 && W >= 2), "dbm_grid_tile: bilinear needs at least 2 x 2 nodes");
-  DBM_CHECK(std::isfinite(geom[0]) && std::isfinite(geom[1]) && std::isfinite(geom[2]) && std::isfinite(geom[3]) && geom[2] != 0.0 &&
-                geom[3] != 0.0, "dbm_grid_tile: x0, y0 finite, dx, dy finite and non-zero");
-  DBM_CHECK(mode == 0 || (std::isfinite(resolution) && resolution > 0.0), "dbm_grid_tile: the resolution must be positive");
-  DBM_CHECK(window_stride >= (size_t)out_h * (size_t)out_w, "dbm_grid_tile: the window stride is smaller than one tile");
-  DBM_CHECK(n == 0 || (grid_dev != nullptr && out_dev != nullptr && windows_host != nullptr), "dbm_grid_tile: NULL raster, windows or output");
-  DBM_CHECK(nodata == nullptr || std::isnan(*nodata) || std::isfinite(*nodata), "dbm_grid_tile: nodata must be finite or NaN");
-  if (mode == 0) {  // a pure copy: every window must lie inside the raster
-    const long* w = (const long*)windows_host;
-    for (long k = 0; k < n; ++k, w += 4) {
-      const long r1 = w[0] + (long)(out_h - 1) * w[2], c1 = w[1] + (long)(out_w - 1) * w[3];
-      DBM_CHECK((w[2] == 1 || w[2] == -1) && (w[3] == 1 || w[3] == -1) && w[0] >= 0 && w[0] < H && r1 >= 0 && r1 < H && w[1] >= 0 &&
-                    w[1] < W && c1 >= 0 && c1 < W, "dbm_grid_tile: window " + std::to_string(k) + " does not lie inside the raster");
-    }
-  }
-  if (n > 0) {
-    TileLaunch a;
-    a.grid = grid_dev;
-    a.H = H; a.W = W;
-    a.x0 = geom[0]; a.y0 = geom[1]; a.dx = geom[2]; a.dy = geom[3];
-    a.n = n;
-    a.out_h = out_h; a.out_w = out_w; a.mode = mode;
-    a.res = resolution;
-    a.has_nodata = nodata != nullptr && !std::isnan(*nodata);   // (a NaN nodata masks nothing: data_prep.py:702)
-    a.nodata = a.has_nodata ? *nodata : 0.0;
-    a.nodata_band = 1e-8 + 1e-5 * std::fabs(a.nodata);
-    a.has_fill = gapfiller != nullptr;
-    a.fill = gapfiller ? *gapfiller : 0.0f;
-    a.fill_nan = fill_nan != 0;
-    a.out = out_dev;
-    a.out_stride = (long)window_stride;
-    a.counts = counts_dev;
-    ctx->stage[7].ensure(8 * (size_t)n);  // (floats: 4 x 8 bytes per window)
-    DBM_HIP(hipMemcpyAsync(ctx->stage[7].p, windows_host, 32 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    a.windows = ctx->stage[7].p;
-    if (counts_dev) DBM_HIP(hipMemsetAsync(counts_dev, 0, sizeof(int) * (size_t)n, ctx->stream));
-    launch_grid_tile(a, ctx->stream);
-  }
-  DBM_API_END
-}
-
-int dbm_grid_filled_windows(dbm_ctx* ctx, const float* grid_dev, long H, long W, int size, int step, int flip_rows, int flip_cols,
-                            unsigned char* flags_dev) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr, "dbm_grid_filled_windows: NULL context");
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  DBM_CHECK(size >= 2 && size % 2 == 0 && size <= FILLED_LDS_BYTES, "dbm_grid_filled_windows: the window size must be even, 2..8192");
-  DBM_CHECK(step >= 1, "dbm_grid_filled_windows: the step must be positive");
-  DBM_CHECK(H >= size && W >= size, "dbm_grid_filled_windows: the raster is smaller than one window");
-  DBM_CHECK(grid_dev != nullptr && flags_dev != nullptr, "dbm_grid_filled_windows: NULL raster or flags");
-  FilledLaunch a;
-  a.grid = grid_dev;
-  a.H = H; a.W = W;
-  a.size = size; a.step = step;
-  a.flip_rows = flip_rows != 0; a.flip_cols = flip_cols != 0;
-  filled_windows_geometry(a);
-  ctx->tile_tmp.ensure(((size_t)a.rows * (size_t)a.nx + 3) / 4);
-  a.rowany = (unsigned char*)ctx->tile_tmp.p;
-  a.flags = flags_dev;
-  launch_filled_windows(a, ctx->stream);
-  DBM_API_END
-}
-
-int dbm_grid_fill_gaps(dbm_ctx* ctx, const float* fine_dev, long H, long W, const double bounds[4], double resolution, const double* fine_nodata,
-                       const float* coarse_dev, long cH, long cW, const double coarse_geom[4], float* out_dev) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && bounds != nullptr && coarse_geom != nullptr, "dbm_grid_fill_gaps: NULL argument");
-  DBM_CHECK(fine_dev != nullptr && coarse_dev != nullptr && out_dev != nullptr, "dbm_grid_fill_gaps: NULL raster or output");
-  DBM_CHECK(H >= 1 && W >= 1 && H < (1L << 31) && W < (1L << 31), "dbm_grid_fill_gaps: H and W must lie in 1..2^31 - 1");
-  DBM_CHECK(cH >= 2 && cW >= 2, "dbm_grid_fill_gaps: bilinear needs at least 2 x 2 coarse nodes");
-  DBM_CHECK(std::isfinite(coarse_geom[0]) && std::isfinite(coarse_geom[1]) && std::isfinite(coarse_geom[2]) && std::isfinite(coarse_geom[3]) &&
-                coarse_geom[2] != 0.0 && coarse_geom[3] != 0.0, "dbm_grid_fill_gaps: x0, y0 finite, dx, dy finite and non-zero");
-  DBM_CHECK(std::isfinite(bounds[0]) && std::isfinite(bounds[1]) && std::isfinite(bounds[2]) && std::isfinite(bounds[3]),
-            "dbm_grid_fill_gaps: the bounds must be finite");
-  DBM_CHECK(std::isfinite(resolution) && resolution > 0.0, "dbm_grid_fill_gaps: the resolution must be positive");
-  DBM_CHECK(fine_nodata == nullptr || std::isnan(*fine_nodata) || std::isfinite(*fine_nodata), "dbm_grid_fill_gaps: nodata must be finite or NaN");
-  DBM_CHECK((const void*)coarse_dev != (const void*)out_dev, "dbm_grid_fill_gaps: the output must not be the coarse raster");
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  TileLaunch a;
-  a.grid = coarse_dev;
-  a.H = cH; a.W = cW;
-  a.x0 = coarse_geom[0]; a.y0 = coarse_geom[1]; a.dx = coarse_geom[2]; a.dy = coarse_geom[3];
-  a.n = 1;
-  a.out_h = (int)H; a.out_w = (int)W; a.mode = 1;
-  a.res = resolution;
-  a.has_nodata = 0; a.nodata = 0.0; a.nodata_band = 0.0;   // (no gap filler: masking changes no value of dbm_grid_tile)
-  a.has_fill = 0; a.fill = 0.0f; a.fill_nan = 0;
-  a.out = out_dev; a.out_stride = H * W; a.counts = nullptr; a.windows = nullptr;
-  const bool has = fine_nodata != nullptr && !std::isnan(*fine_nodata);
-  launch_grid_fill_gaps(a, bounds, fine_dev, has ? 1 : 0, has ? (float)*fine_nodata : 0.0f, out_dev, ctx->stream);
-  DBM_API_END
-}
-
-// ---- GeoTIFF blocks -> a float32 plane (tiff_decode.hip) ----
-int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host, int n_blocks, int compression,
-                    int predictor, int sample_type, int block_w, int block_h, float* out_dev, long out_h, long out_w) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr, "dbm_tiff_decode: NULL context");
-  DBM_CHECK(n_blocks >= 0, "dbm_tiff_decode: negative number of blocks");
-  DBM_CHECK(compression == 1 || compression == 5, "dbm_tiff_decode: compression must be 1 (decoded bytes) or 5 (LZW)");
-  DBM_CHECK(sample_type >= 0 && sample_type <= 5, "dbm_tiff_decode: sample_type must lie in 0..5");
-  static const int kBytes[6] = {1, 2, 2, 4, 4, 8};
-  const int bytes = kBytes[sample_type];
-  DBM_CHECK(predictor == 1 || predictor == 2 || (predictor == 3 && sample_type >= 4), "dbm_tiff_decode: predictor must be 1, 2, or 3 with float samples");
-  DBM_CHECK(block_w >= 1 && block_h >= 1 && (long)block_w * block_h * bytes < (1L << 31), "dbm_tiff_decode: a block must hold 1..2^31 - 1 bytes");
-  DBM_CHECK(out_h >= 1 && out_w >= 1, "dbm_tiff_decode: empty output plane");
-  DBM_CHECK(n_blocks == 0 || (streams_host != nullptr && blocks_host != nullptr && out_dev != nullptr), "dbm_tiff_decode: NULL streams, blocks or output");
-  DBM_CHECK((long)n_blocks * block_h < (1L << 31), "dbm_tiff_decode: more than 2^31 block rows in one call");
-  if (n_blocks == 0) return 0;
-  const bool lzw = compression == 5;
-  for (int b = 0; b < n_blocks; ++b) {
-    const int64_t* e = blocks_host + 8 * (size_t)b;
-    const std::string name = "dbm_tiff_decode: block " + std::to_string(e[5]);
-    DBM_CHECK(e[0] >= 0 && e[1] >= 0 && (uint64_t)e[0] + (uint64_t)e[1] <= (uint64_t)streams_bytes, name + ": its bytes lie outside the streams");
-    DBM_CHECK(e[2] >= 1 && e[2] <= block_h, name + ": its rows must lie in 1..block_h");
-    DBM_CHECK(lzw || (e[0] % 8 == 0 && e[1] >= e[2] * (int64_t)block_w * bytes), name + ": decoded bytes must be 8-byte aligned and complete");
-    DBM_CHECK(e[3] > -(1L << 40) && e[3] < (1L << 40) && e[4] > -(1L << 40) && e[4] < (1L << 40), name + ": placement out of range");
-  }
-  TiffDecodeLaunch a;
-  a.n_blocks = n_blocks; a.lzw = lzw ? 1 : 0;
-  a.block_w = block_w; a.block_h = block_h; a.bytes = bytes; a.sample_type = sample_type; a.predictor = predictor;
-  a.block_stride = (((long)block_w * block_h * bytes) + 15) / 16 * 16;
-  a.out = out_dev; a.out_h = out_h; a.out_w = out_w;
-  ScopedBuf up, table, stage;   // this call's own, released on every path
-  up.ensure((streams_bytes + 16 + 3) / 4);
-  table.ensure(((size_t)n_blocks * (64 + 4) + 3) / 4);
-  DBM_HIP(hipMemcpyAsync(up.p, streams_host, streams_bytes, hipMemcpyHostToDevice, ctx->stream));
-  DBM_HIP(hipMemcpyAsync(table.p, blocks_host, 64 * (size_t)n_blocks, hipMemcpyHostToDevice, ctx->stream));
-  a.streams = (const uint8_t*)up.p;
-  a.blocks = (const long*)table.p;
-  a.status = (int*)((uint8_t*)table.p + 64 * (size_t)n_blocks);
-  a.stage = (uint8_t*)up.p;
-  if (lzw) {
-    stage.ensure(((size_t)n_blocks * (size_t)a.block_stride + 3) / 4);
-    a.stage = (uint8_t*)stage.p;
-    launch_tiff_lzw(a, ctx->stream);
-    std::vector<int> status((size_t)n_blocks);
-    DBM_HIP(hipMemcpyAsync(status.data(), a.status, sizeof(int) * (size_t)n_blocks, hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < n_blocks; ++b)
-      if (status[b] != 0)
-        throw DbmError(11, "dbm_tiff_decode: block " + std::to_string(blocks_host[8 * (size_t)b + 5]) +
-                               (status[b] == 1 ? ": malformed LZW stream" : ": the LZW stream does not decode to the block's size") +
-                               "; nothing of this call was written");
-  }
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  launch_tiff_rows(a, ctx->stream);
-  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
-  DBM_API_END
-}
-
-int dbm_grid_rescale(dbm_ctx* ctx, const float* in_dev, long H, long W, long out_h, long out_w, int order, int anti_aliasing, int clip,
-                     int input_cast, float* out_dev) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr, "dbm_grid_rescale: NULL context");
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  DBM_CHECK(order == 1 || order == 3, "dbm_grid_rescale: order must be 1 (linear) or 3 (cubic B-spline)");
-  DBM_CHECK(H >= 2 && W >= 2, "dbm_grid_rescale: the input needs at least 2 x 2 nodes");
-  DBM_CHECK(out_h >= 1 && out_w >= 1, "dbm_grid_rescale: empty output");
-  DBM_CHECK(in_dev != nullptr && out_dev != nullptr, "dbm_grid_rescale: NULL input or output");
-  DBM_CHECK((const void*)in_dev != (const void*)out_dev, "dbm_grid_rescale: the output must not be the input");
-  RescaleLaunch a;
-  a.in = in_dev;
-  a.H = H; a.W = W; a.out_h = out_h; a.out_w = out_w;
-  a.order = order;
-  a.anti_aliasing = anti_aliasing != 0; a.clip = clip != 0; a.input_cast = input_cast != 0;
-  a.out = out_dev;
-  ctx->resample_tmp.ensure(2 * grid_rescale_workspace(a));   // (DevBuf counts floats)
-  a.ws = (double*)ctx->resample_tmp.p;
-  launch_grid_rescale(a, ctx->stream);
-  DBM_API_END
-}
-
-int dbm_grid_rolling_std(dbm_ctx* ctx, const float* in_dev, long H, long W, int window, float* out_dev) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr, "dbm_grid_rolling_std: NULL context");
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  DBM_CHECK(window >= 1 && window <= 63 && window % 2 == 1, "dbm_grid_rolling_std: the window must be odd, 1..63");
-  DBM_CHECK(H >= 1 && W >= 1, "dbm_grid_rolling_std: empty grid");
-  DBM_CHECK(in_dev != nullptr && out_dev != nullptr, "dbm_grid_rolling_std: NULL input or output");
-  DBM_CHECK((const void*)in_dev != (const void*)out_dev, "dbm_grid_rolling_std: the output must not be the input");
-  launch_rolling_std(in_dev, H, W, window, out_dev, ctx->stream);
-  DBM_API_END
-}
-
-// ---- gridding point clouds (points.hip) ----
-// table arguments of the dbm_points_* entry points without DBM_DEVICE_PTRS: staged in ctx->stage[k] (DevBuf counts floats)
-static double* points_stage(dbm_ctx* ctx, int k, size_t doubles) {
-  ctx->stage[k].ensure(2 * (doubles > 0 ? doubles : 1));
-  return (double*)ctx->stage[k].p;
-}
-
-int dbm_points_polar_stereographic(dbm_ctx* ctx, const double* points_in, size_t n, int ncol, const double proj[6], double* points_out,
-                                   int flags) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && proj != nullptr, "dbm_points_polar_stereographic: NULL argument");
-  DBM_CHECK(ncol >= 2, "dbm_points_polar_stereographic: a table has at least 2 columns (longitude, latitude)");
-  DBM_CHECK(n < ((size_t)1 << 31), "dbm_points_polar_stereographic: n must stay below 2^31");
-  DBM_CHECK(std::isfinite(proj[0]) && proj[0] > 0.0 && std::isfinite(proj[1]) && proj[1] > 1.0,
-            "dbm_points_polar_stereographic: the semi-major axis must be positive and the inverse flattening above 1");
-  DBM_CHECK(proj[2] >= -90.0 && proj[2] < 0.0, "dbm_points_polar_stereographic: the latitude of true scale must lie in [-90, 0) (south-pole case)");
-  DBM_CHECK(std::isfinite(proj[3]) && std::isfinite(proj[4]) && std::isfinite(proj[5]),
-            "dbm_points_polar_stereographic: longitude of origin, false easting and false northing must be finite");
-  DBM_CHECK(n == 0 || (points_in != nullptr && points_out != nullptr), "dbm_points_polar_stereographic: NULL table");
-  if (n == 0) return 0;
-  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
-  const double rad = 3.14159265358979323846 / 180.0;
-  const double f = 1.0 / proj[1], e = std::sqrt(2.0 * f - f * f);
-  const double cc = std::sqrt(std::pow(1.0 + e, 1.0 + e) * std::pow(1.0 - e, 1.0 - e));
-  const double sf = std::sin(proj[2] * rad), esf = e * sf;
-  const double tf = std::tan((45.0 + 0.5 * proj[2]) * rad) / std::pow((1.0 + esf) / (1.0 - esf), 0.5 * e);
-  const double mf = std::cos(proj[2] * rad) / std::sqrt(1.0 - e * e * sf * sf);
-  // phi_F = -90: m_F = t_F = 0 and the scale at the pole is taken as 1 (variant A with k0 = 1)
-  const double k0 = proj[2] == -90.0 ? 1.0 : mf * cc / (2.0 * tf);
-  ProjLaunch a;
-  a.n = (long)n;
-  a.ncol = ncol;
-  a.e = e;
-  a.half_e = 0.5 * e;
-  a.scale = 2.0 * proj[0] * k0 / cc;
-  a.lon0 = proj[3] * rad;
-  a.fe = proj[4];
-  a.fn = proj[5];
-  if (dev) {
-    ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-    a.in = points_in;
-    a.out = points_out;
-  } else {
-    double* st = points_stage(ctx, 0, n * (size_t)ncol);
-    DBM_HIP(hipMemcpyAsync(st, points_in, n * ncol * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    a.in = a.out = st;
-  }
-  launch_points_project(a, ctx->stream);
-  if (!dev) {
-    DBM_HIP(hipMemcpyAsync(points_out, a.out, n * ncol * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  DBM_API_END
-}
-
-int dbm_points_region(dbm_ctx* ctx, const double* points, size_t n, int ncol, double increment, double* region_out, int64_t* count_out,
-                      int flags) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && region_out != nullptr && count_out != nullptr, "dbm_points_region: NULL argument");
-  DBM_CHECK(ncol >= 2, "dbm_points_region: a table has at least 2 columns (x, y)");
-  DBM_CHECK(n < ((size_t)1 << 31), "dbm_points_region: n must stay below 2^31");
-  DBM_CHECK(std::isfinite(increment) && increment > 0.0, "dbm_points_region: the increment must be positive and finite");
-  DBM_CHECK(n == 0 || points != nullptr, "dbm_points_region: NULL table");
-  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
-  const size_t ws = points_region_workspace((long)n);
-  ctx->points_tmp.ensure((ws + 64) / 4);
-  char* scratch = (char*)ctx->points_tmp.p;
-  double* dregion = dev ? region_out : (double*)(scratch + ws);
-  long long* dcount = dev ? (long long*)count_out : (long long*)(scratch + ws + 32);
-  const double* dpts = points;
-  if (!dev && n > 0) {
-    double* st = points_stage(ctx, 0, n * (size_t)ncol);
-    DBM_HIP(hipMemcpyAsync(st, points, n * ncol * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    dpts = st;
-  }
-  if (dev) ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  launch_points_region(dpts, (long)n, ncol, increment, scratch, dregion, dcount, ctx->stream);
-  if (!dev) {
-    DBM_HIP(hipMemcpyAsync(region_out, dregion, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipMemcpyAsync(count_out, dcount, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  DBM_API_END
-}
-
-int dbm_points_blockmedian(dbm_ctx* ctx, const double* points, size_t n, const double region[4], double spacing, double* table_out,
-                           size_t table_capacity, int64_t* n_blocks_out, float* grid_dev, int* counts_dev, int flags) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && region != nullptr && n_blocks_out != nullptr, "dbm_points_blockmedian: NULL argument");
-  DBM_CHECK(n < ((size_t)1 << 31), "dbm_points_blockmedian: n must stay below 2^31");
-  DBM_CHECK(std::isfinite(spacing) && spacing > 0.0, "dbm_points_blockmedian: the spacing must be positive and finite");
-  DBM_CHECK(std::isfinite(region[0]) && std::isfinite(region[1]) && std::isfinite(region[2]) && std::isfinite(region[3]) &&
-                region[1] >= region[0] && region[3] >= region[2], "dbm_points_blockmedian: the region must be finite with max >= min");
-  const double wd = (region[1] - region[0]) / spacing, hd = (region[3] - region[2]) / spacing;
-  DBM_CHECK(wd < 2147483647.0 && hd < 2147483647.0, "dbm_points_blockmedian: H W must stay below 2^31 blocks");
-  const long W = (long)std::llrint(wd) + 1, H = (long)std::llrint(hd) + 1;
-  DBM_CHECK(H * W < (1L << 31), "dbm_points_blockmedian: H W must stay below 2^31 blocks");
-  DBM_CHECK(n == 0 || points != nullptr, "dbm_points_blockmedian: NULL table");
-  DBM_CHECK(table_capacity == 0 || table_out != nullptr, "dbm_points_blockmedian: NULL table_out");
-  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
-  BlockMedianLaunch a;
-  a.n = (long)n;
-  a.H = H;
-  a.W = W;
-  a.xmin = region[0];
-  // the north edge fitted to the increment (+e): the region's own ymax when the spacing divides the region, else ymin + (H - 1) inc
-  const double span = (double)(H - 1) * spacing;
-  a.ymax = span == region[3] - region[2] ? region[3] : region[2] + span;
-  a.inc = spacing;
-  ctx->points_tmp.ensure((blockmedian_workspace(a.n, H * W) + 3) / 4);
-  blockmedian_carve(a, ctx->points_tmp.p);
-  a.points = points;
-  if (!dev && n > 0) {
-    double* st = points_stage(ctx, 0, 3 * n);
-    DBM_HIP(hipMemcpyAsync(st, points, 3 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    a.points = st;
-  }
-  launch_blockmedian_count(a, ctx->stream);
-  unsigned totals[1 + DBM_BLOCKMEDIAN_CLASSES];
-  DBM_HIP(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
-  DBM_HIP(hipStreamSynchronize(ctx->stream));
-  const size_t m = totals[0];
-  DBM_CHECK(m <= table_capacity, "dbm_points_blockmedian: the table holds " + std::to_string(table_capacity) + " rows, " +
-                                     std::to_string(m) + " blocks are not empty; nothing was written");
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  a.table = dev ? table_out : points_stage(ctx, 1, 3 * m);
-  a.grid = grid_dev;
-  a.counts = counts_dev;
-  launch_blockmedian_select(a, totals, ctx->stream);
-  *n_blocks_out = (int64_t)m;
-  if (!dev) {
-    if (m > 0) DBM_HIP(hipMemcpyAsync(table_out, a.table, 3 * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  DBM_API_END
-}
-
-// ---- reading survey text tables (text.hip) ----
-static void text_arguments(const char* who, dbm_ctx* ctx, const void* text, size_t nbytes, int separator, int flags) {
-  const std::string w(who);
-  DBM_CHECK(ctx != nullptr, w + ": NULL context");
-  DBM_CHECK(separator == ',' || separator == '\t' || separator == DBM_TEXT_SEP_WHITESPACE,
-            w + ": the separator must be ',', a tab or DBM_TEXT_SEP_WHITESPACE");
-  DBM_CHECK(nbytes == 0 || text != nullptr, w + ": NULL text");
-  DBM_CHECK(!(flags & DBM_DEVICE_PTRS) || ((uintptr_t)text & 15) == 0, w + ": a device text pointer must be 16-byte aligned");
-}
-
-// the text on the device (host text: staged in `staged`, released with it) and the structure pass behind it; totals = {lines, non-blank}
-static void text_structure(dbm_ctx* ctx, TextLaunch& a, const void* text, size_t nbytes, int separator, int flags, ScopedBuf& staged,
-                           unsigned long long totals[2]) {
-  a.len = nbytes;
-  a.sep = separator;
-  if (flags & DBM_DEVICE_PTRS) {
-    a.text = (const unsigned char*)text;
-  } else {
-    staged.ensure(nbytes / 4 + 4);
-    DBM_HIP(hipMemcpyAsync(staged.p, text, nbytes, hipMemcpyHostToDevice, ctx->stream));
-    a.text = (const unsigned char*)staged.p;
-  }
-  ctx->points_tmp.ensure((text_structure_workspace(nbytes) + 3) / 4);
-  text_structure_carve(a, ctx->points_tmp.p);
-  launch_text_structure(a, ctx->stream);
-  DBM_HIP(hipMemcpyAsync(totals, a.totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-  DBM_HIP(hipStreamSynchronize(ctx->stream));
-}
-
-int dbm_text_count_lines(dbm_ctx* ctx, const void* text, size_t nbytes, int separator, int64_t* counts_out, int flags) {
-  DBM_API_BEGIN(ctx)
-  text_arguments("dbm_text_count_lines", ctx, text, nbytes, separator, flags);
-  DBM_CHECK(counts_out != nullptr, "dbm_text_count_lines: NULL counts_out");
-  counts_out[0] = counts_out[1] = 0;
-  if (nbytes == 0) return 0;
-  TextLaunch a = {};
-  ScopedBuf staged;
-  unsigned long long totals[2];
-  text_structure(ctx, a, text, nbytes, separator, flags, staged, totals);
-  counts_out[0] = (int64_t)totals[0];
-  counts_out[1] = (int64_t)totals[1];
-  DBM_API_END
-}
-
-int dbm_text_parse(dbm_ctx* ctx, const void* text, size_t nbytes, int separator, int skip, int nfields, uint64_t use_mask,
-                   const char* na_values, int n_na, double* table_out, size_t table_capacity, int64_t* repair_out, size_t repair_capacity,
-                   int64_t* result_out, int flags) {
-  DBM_API_BEGIN(ctx)
-  text_arguments("dbm_text_parse", ctx, text, nbytes, separator, flags);
-  DBM_CHECK(result_out != nullptr, "dbm_text_parse: NULL result_out");
-  DBM_CHECK(skip >= 0, "dbm_text_parse: skip must not be negative");
-  DBM_CHECK(nfields >= 1 && nfields <= DBM_TEXT_MAX_FIELDS, "dbm_text_parse: nfields must lie in 1..DBM_TEXT_MAX_FIELDS");
-  DBM_CHECK(use_mask != 0 && (nfields == 64 || (use_mask >> nfields) == 0), "dbm_text_parse: use_mask must mark at least one of the nfields fields and no other");
-  DBM_CHECK(n_na >= 0 && n_na <= DBM_TEXT_MAX_NA && (n_na == 0 || na_values != nullptr), "dbm_text_parse: n_na must lie in 0..DBM_TEXT_MAX_NA");
-  DBM_CHECK(table_capacity == 0 || table_out != nullptr, "dbm_text_parse: NULL table_out");
-  DBM_CHECK(repair_capacity == 0 || repair_out != nullptr, "dbm_text_parse: NULL repair_out");
-  TextLaunch a = {};
-  a.skip1 = (unsigned long long)skip + 1ull;
-  a.nfields = nfields;
-  a.use_mask = use_mask;
-  a.nuse = __builtin_popcountll(use_mask);
-  a.n_na = n_na;
-  for (int k = 0; k < n_na; ++k) {
-    const size_t len = strlen(na_values);
-    DBM_CHECK(len >= 1 && len <= DBM_TEXT_MAX_NA_BYTES, "dbm_text_parse: an NA string must hold 1..DBM_TEXT_MAX_NA_BYTES bytes");
-    a.na_len[k] = (int)len;
-    for (size_t i = 0; i < len; ++i)
-      (i < 8 ? a.na_lo[k] : a.na_hi[k]) |= (unsigned long long)(unsigned char)na_values[i] << (8 * (i & 7));
-    na_values += len + 1;
-  }
-  result_out[0] = result_out[1] = result_out[3] = 0;
-  result_out[2] = -1;
-  if (nbytes == 0) return 0;
-  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
-  ScopedBuf staged, scratch, list, table;
-  unsigned long long totals[5];
-  text_structure(ctx, a, text, nbytes, separator, flags, staged, totals);
-  if (totals[1] < a.skip1) return 0;
-  a.ncand = totals[1] - a.skip1;
-  result_out[3] = (int64_t)a.ncand;
-  if (a.ncand == 0) return 0;
-  scratch.ensure((text_parse_workspace(a.ncand, a.nuse) + 3) / 4);
-  text_parse_carve(a, scratch.p);
-  launch_text_parse(a, ctx->stream);
-  DBM_HIP(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
-  DBM_HIP(hipStreamSynchronize(ctx->stream));
-  if (totals[2] != ~0ull) {
-    result_out[2] = (int64_t)totals[2];
-    return 0;
-  }
-  const size_t kept = totals[3], nrep = totals[4];
-  DBM_CHECK(kept <= table_capacity, "dbm_text_parse: the table holds " + std::to_string(table_capacity) + " rows, " + std::to_string(kept) +
-                                        " are kept; nothing was written");
-  DBM_CHECK(nrep <= repair_capacity, "dbm_text_parse: the repair list holds " + std::to_string(repair_capacity) + " pairs, " +
-                                         std::to_string(nrep) + " are needed; nothing was written");
-  if (kept > 0) {
-    ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-    list.ensure(4 * (nrep > 0 ? nrep : 1));
-    a.repair = (long long*)list.p;
-    if (dev) {
-      a.table = table_out;
-    } else {
-      table.ensure(2 * kept * (size_t)a.nuse);
-      a.table = (double*)table.p;
-    }
-    launch_text_compact(a, ctx->stream);
-    if (nrep > 0) DBM_HIP(hipMemcpyAsync(repair_out, a.repair, 16 * nrep, hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev) DBM_HIP(hipMemcpyAsync(table_out, a.table, 8 * kept * (size_t)a.nuse, hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  result_out[0] = (int64_t)kept;
-  result_out[1] = (int64_t)nrep;
-  DBM_API_END
-}
-
-int dbm_text_columns(dbm_ctx* ctx, const double* in_dev, size_t n, int ncol_in, double* out_dev, int ncol_out, const int* a, const int* op,
-                     const int* b) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && a != nullptr && op != nullptr && b != nullptr, "dbm_text_columns: NULL argument");
-  DBM_CHECK(ncol_in >= 1 && ncol_out >= 1 && ncol_out <= DBM_TEXT_MAX_COLUMNS, "dbm_text_columns: ncol_in >= 1 and ncol_out in 1..DBM_TEXT_MAX_COLUMNS");
-  DBM_CHECK(n == 0 || (in_dev != nullptr && out_dev != nullptr), "dbm_text_columns: NULL table");
-  ColumnsLaunch c = {};
-  c.in = in_dev;
-  c.out = out_dev;
-  c.n = n;
-  c.ncol_in = ncol_in;
-  c.ncol_out = ncol_out;
-  for (int k = 0; k < ncol_out; ++k) {
-    DBM_CHECK(op[k] >= 0 && op[k] <= 2, "dbm_text_columns: op must be 0 (copy), 1 (add) or 2 (subtract)");
-    DBM_CHECK(a[k] >= 0 && a[k] < ncol_in && (op[k] == 0 || (b[k] >= 0 && b[k] < ncol_in)), "dbm_text_columns: a column index lies outside the input");
-    c.a[k] = a[k];
-    c.op[k] = op[k];
-    c.b[k] = op[k] == 0 ? a[k] : b[k];
-  }
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  launch_text_columns(c, ctx->stream);
-  DBM_API_END
-}
-
-// ---- from block medians to the 250 m raster (surface.hip, track.hip) ----
-int dbm_grid_tension_surface(dbm_ctx* ctx, const float* data_dev, long H, long W, double tension, double tol, int max_iter, float* out_dev,
-                             double info[4]) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && data_dev != nullptr && out_dev != nullptr && info != nullptr, "dbm_grid_tension_surface: NULL argument");
-  DBM_CHECK(H >= 3 && W >= 3, "dbm_grid_tension_surface: the raster needs at least 3 x 3 nodes");
-  DBM_CHECK(H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31), "dbm_grid_tension_surface: H W must stay below 2^31 nodes");
-  DBM_CHECK(tension > 0.0 && tension <= 1.0, "dbm_grid_tension_surface: the tension must lie in (0, 1]");
-  DBM_CHECK(tol > 0.0 && tol < 1.0, "dbm_grid_tension_surface: tol must lie in (0, 1)");
-  DBM_CHECK(max_iter >= 1 && max_iter <= 1000000, "dbm_grid_tension_surface: max_iter must lie in 1..1000000");
-  ScopedBuf ws;   // this call's own: x, r, p, Ap (float64 planes), the free-node mask, the partial sums; released on every path
-  ws.ensure((surface_workspace(H, W) + 3) / 4);
-  SurfaceLaunch a;
-  a.data = data_dev;
-  a.H = H; a.W = W;
-  a.tension = tension; a.tol = tol;
-  a.max_iter = max_iter;
-  a.out = out_dev;
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  const bool converged = surface_solve(a, ws.p, ctx->stream, info);
-  if (!converged)
-    throw DbmError(10, "dbm_grid_tension_surface: not converged in " + std::to_string(max_iter) + " iterations (relative residual " +
-                           std::to_string(info[1]) + ", tol " + std::to_string(tol) + "); out_dev holds the last iterate");
-  DBM_API_END
-}
-
-int dbm_grid_distance_mask(dbm_ctx* ctx, const float* data_dev, float* grid_dev, long H, long W, int radius) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && data_dev != nullptr && grid_dev != nullptr, "dbm_grid_distance_mask: NULL argument");
-  DBM_CHECK(H >= 1 && W >= 1 && H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31), "dbm_grid_distance_mask: H W must lie in 1..2^31 - 1");
-  DBM_CHECK(radius >= 0 && radius <= 32, "dbm_grid_distance_mask: the radius must lie in 0..32 nodes");
-  DBM_CHECK((const void*)data_dev != (const void*)grid_dev, "dbm_grid_distance_mask: the grid must not be the data raster");
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  launch_distance_mask(data_dev, grid_dev, H, W, radius, ctx->stream);
-  DBM_API_END
-}
-
-int dbm_grid_to_pixel(dbm_ctx* ctx, const float* in_dev, long H, long W, double threshold, float* out_dev) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && in_dev != nullptr && out_dev != nullptr, "dbm_grid_to_pixel: NULL argument");
-  DBM_CHECK(H >= 2 && W >= 2, "dbm_grid_to_pixel: the grid needs at least 2 x 2 nodes");
-  DBM_CHECK(H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31), "dbm_grid_to_pixel: H W must stay below 2^31 nodes");
-  DBM_CHECK(threshold > 0.0 && threshold <= 1.0, "dbm_grid_to_pixel: threshold must lie in (0, 1]");
-  DBM_CHECK((const void*)in_dev != (const void*)out_dev, "dbm_grid_to_pixel: the output must not be the input");
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  launch_grid_to_pixel(in_dev, H, W, threshold, out_dev, ctx->stream);
-  DBM_API_END
-}
-
-// ---- nodes inside a buffered polygon set (polygon.hip) ----
-// list sizes of each context's last successful dbm_grid_polygon_mask (dbm_grid_polygon_stats); kept beside the contexts, not in them
-static std::map<dbm_ctx*, std::vector<long long>> g_poly_stats;
-int dbm_grid_polygon_mask(dbm_ctx* ctx, const double* edges, size_t n_edges, long H, long W, const double geom[4], double buffer,
-                          unsigned char* mask_dev, float* grid_dev, size_t workspace_limit, int flags) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && geom != nullptr, "dbm_grid_polygon_mask: NULL context or geometry");
-  DBM_CHECK(H >= 1 && W >= 1, "dbm_grid_polygon_mask: empty raster");
-  DBM_CHECK(H < (1L << 31) && W < (1L << 31) && H * W < (1L << 31), "dbm_grid_polygon_mask: H W must stay below 2^31 nodes");
-  DBM_CHECK(n_edges < ((size_t)1 << 31), "dbm_grid_polygon_mask: n_edges must stay below 2^31");
-  DBM_CHECK(std::isfinite(geom[0]) && std::isfinite(geom[1]) && std::isfinite(geom[2]) && std::isfinite(geom[3]) && geom[2] != 0.0 &&
-                geom[3] != 0.0, "dbm_grid_polygon_mask: the geometry must be finite with non-zero dx and dy");
-  DBM_CHECK(std::isfinite(buffer), "dbm_grid_polygon_mask: the buffer must be finite");
-  DBM_CHECK(mask_dev != nullptr || grid_dev != nullptr, "dbm_grid_polygon_mask: both outputs are NULL");
-  DBM_CHECK(n_edges == 0 || edges != nullptr, "dbm_grid_polygon_mask: NULL edge table");
-  const bool dev = (flags & DBM_DEVICE_PTRS) != 0;
-  if (!dev)
-    for (size_t i = 0; i < 4 * n_edges; ++i)
-      DBM_CHECK(std::isfinite(edges[i]), "dbm_grid_polygon_mask: edge " + std::to_string(i / 4) + " has a non-finite coordinate");
-  PolyLaunch a;
-  a.n = (long)n_edges;
-  a.H = H; a.W = W;
-  a.x0 = geom[0]; a.y0 = geom[1]; a.dx = geom[2]; a.dy = geom[3];
-  a.buffer = buffer;
-  polygon_geometry(a);
-  ScopedBuf ws, bins;   // this call's own, released on every path
-  ws.ensure((polygon_workspace(a, !dev) + 3) / 4);
-  double* staged = polygon_carve(a, ws.p, !dev);
-  a.edges = edges;
-  if (!dev && n_edges > 0) {
-    DBM_HIP(hipMemcpyAsync(staged, edges, 32 * n_edges, hipMemcpyHostToDevice, ctx->stream));
-    a.edges = staged;
-  }
-  a.entries = nullptr;
-  a.nP = a.nB = 0u;
-  a.mask = mask_dev;
-  a.grid = grid_dev;
-  launch_polygon_cull(a, ctx->stream);
-  unsigned long long totals[8];
-  DBM_HIP(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
-  DBM_HIP(hipStreamSynchronize(ctx->stream));
-  DBM_CHECK(totals[2] == 0ull, "dbm_grid_polygon_mask: " + std::to_string(totals[2]) + " edges have a non-finite coordinate; nothing was written");
-  if (totals[3] != 0ull) a.identity = 1;
-  a.nP = (unsigned)totals[0];
-  a.nB = (unsigned)totals[1];
-  const unsigned long long entries = totals[4] + totals[5];
-  const size_t limit = workspace_limit ? workspace_limit : DBM_POLY_WORKSPACE_DEFAULT;
-  const bool binned = !a.identity && n_edges > 0 && entries < (1ull << 31) && 4 * entries <= limit;
-  ctx->data_epoch++;  // caller-visible device memory changes: retained generator forwards keyed on it go stale
-  if (binned) {
-    bins.ensure(entries > 0 ? (size_t)entries : 1);
-    a.entries = (unsigned*)bins.p;
-    launch_polygon_bin(a, ctx->stream);
-  }
-  launch_polygon_classify(a, ctx->stream);
-  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
-  g_poly_stats[ctx] = {(long long)totals[0], (long long)totals[1], (long long)totals[4], (long long)totals[5],
-                       a.identity ? 2LL : (binned ? 1LL : 0LL), (long long)n_edges};
-  DBM_API_END
-}
-
-int dbm_grid_polygon_stats(dbm_ctx* ctx, int64_t out[6]) {
-  DBM_API_BEGIN(ctx)
-  DBM_CHECK(ctx != nullptr && out != nullptr, "dbm_grid_polygon_stats: NULL argument");
-  const auto it = g_poly_stats.find(ctx);
-  for (int k = 0; k < 6; ++k) out[k] = it == g_poly_stats.end() ? 0 : (int64_t)it->second[k];
   DBM_API_END
 }
 

@@ -8,7 +8,13 @@
 struct DevBuf {
   float* p = nullptr;
   size_t n = 0;
-  void ensure(size_t count, bool zero = false);
+  void ensure(size_t count);  // room for `count` floats; only grows, and a fresh allocation is zeroed
+  // the same for `count` elements of T (bytes: T = char), rounded up to whole floats: callers that think in doubles or bytes
+  // state their size in their own unit
+  template <class T> T* as(size_t count) {
+    ensure((count * sizeof(T) + sizeof(float) - 1) / sizeof(float));
+    return reinterpret_cast<T*>(p);
+  }
   void release();
 };
 
@@ -86,7 +92,7 @@ struct dbm_ctx {
   void comm_join(hipStream_t consumer);
   int trunk_imgs = 64;        // images per launch of the persistent trunk kernels: min(64, CUs / 3) (one workgroup per CU)
   std::vector<struct dbm_model*> models;  // every model of this context (optimizer bookkeeping after a kernel timeout)
-  long data_epoch = 0;        // bumped by every entry point that writes / frees caller-visible device memory
+  long data_epoch = 0;        // bumped by every entry point that writes / frees caller-visible device memory (note_device_write)
   int* dev_err = nullptr;     // host-mapped word a persistent kernel raises when a bounded spin runs out (checked by every API call)
   int* dev_err_d = nullptr;   // its device address
   int* dev_err_flag = nullptr;  // the same flag in device memory, STICKY until the host handles it (the optimizer launches and
@@ -101,6 +107,7 @@ struct dbm_ctx {
   DevBuf tile_tmp;            // dbm_grid_filled_windows: the row pass's byte plane
   DevBuf resample_tmp;        // dbm_grid_rescale: min / max, Gaussian weights and the float64 planes (doubles)
   DevBuf points_tmp;          // dbm_points_region: the workgroups' boxes; dbm_points_blockmedian: block indices, histogram, scan, lists
+  long long poly_stats[6] = {};  // list sizes of the last successful dbm_grid_polygon_mask (dbm_grid_polygon_stats)
 };
 
 void dbm_comm_unique_id_impl(void* out128);  // comm.hip: ncclGetUniqueId

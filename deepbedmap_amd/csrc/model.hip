@@ -3,21 +3,18 @@
 
 static const size_t GUARD = 32;  // floats on each side: the row-tap loads of igemm touch one word outside a tensor
 
-void DevBuf::ensure(size_t count, bool zero) {
-  if (count > n) {
-    if (p) DBM_HIP(hipFree(p - GUARD));
-    p = nullptr;
-    float* base = nullptr;
-    DBM_HIP(hipMalloc((void**)&base, (count + 2 * GUARD) * sizeof(float)));
-    n = count;
-    zero = true;  // fresh allocations are always zeroed (padding channels rely on it)
-    DBM_HIP(hipMemset(base, 0, (count + 2 * GUARD) * sizeof(float)));
-    p = base + GUARD;
-    // the memset runs on the NULL stream, which the context's non-blocking stream does not wait for
-    DBM_HIP(hipDeviceSynchronize());
-    return;
-  }
-  (void)zero;
+void DevBuf::ensure(size_t count) {
+  if (count <= n) return;
+  if (p) DBM_HIP(hipFree(p - GUARD));
+  p = nullptr;
+  float* base = nullptr;
+  DBM_HIP(hipMalloc((void**)&base, (count + 2 * GUARD) * sizeof(float)));
+  n = count;
+  // fresh allocations are always zeroed (padding channels rely on it)
+  DBM_HIP(hipMemset(base, 0, (count + 2 * GUARD) * sizeof(float)));
+  p = base + GUARD;
+  // the memset runs on the NULL stream, which the context's non-blocking stream does not wait for
+  DBM_HIP(hipDeviceSynchronize());
 }
 
 void dbm_ctx::fork_to_side(int k) {

@@ -267,6 +267,31 @@ def test_every_path_gives_the_same_bytes(dbm, ctx, abi):
     assert dev.dtype == np.uint8 and dev.shape == shape and np.array_equal(dev.get(), want.astype(np.uint8))
 
 
+def test_statistics_belong_to_the_context(dbm):
+    """dbm_grid_polygon_stats reports the context's own last mask: a context created after another was shut down starts from zeros
+    (wherever the allocator puts it), and the same mask on it gives the same statistics."""
+    shape, g = (8, 8), dbm.GridGeometry(*GEOM)
+    ring = [xy(GEOM, 1.5, 1.5), xy(GEOM, 5.5, 1.5), xy(GEOM, 5.5, 5.5), xy(GEOM, 1.5, 5.5)]
+    want = pr.mask(GEOM, shape, pr.ring_edges([ring]), 0.0)
+    assert want.sum() == 16
+
+    def masked(c):
+        square = dbm.Polygons.from_rings([ring])     # (its device table is freed with it, while the context lives)
+        assert np.array_equal(dbm.polygon_mask(g, shape, square, ctx=c), want)
+        return dbm.polygons.last_stats(c)
+
+    a = dbm.Context()
+    stats_a = masked(a)
+    assert stats_a["edges"] == 4
+    dbm._lib.check(dbm._lib.lib().dbm_shutdown(a.handle))
+    b = dbm.Context()
+    try:
+        assert set(dbm.polygons.last_stats(b).values()) == {0}
+        assert masked(b) == stats_a
+    finally:
+        dbm._lib.check(dbm._lib.lib().dbm_shutdown(b.handle))
+
+
 def test_grid_output_keeps_every_other_bit(abi):
     shape = (T + 1, 2 * T + 1)
     edges = zoo(GEOM, shape)

@@ -151,5 +151,5 @@ def test_status_10_is_documented_where_callers_look():
 
     assert "10 (dbm_grid_tension_surface only)" in inspect.getsource(_lib.DbmError)
     assert "code 10" in gridding.tension_surface.__doc__
-    api = open(os.path.join(ROOT, "deepbedmap_amd", "csrc", "api.hip")).read()
+    api = open(os.path.join(ROOT, "deepbedmap_amd", "csrc", "api_data.hip")).read()     # (where dbm_grid_tension_surface lives)
     assert "DbmError(10," in api and "out_dev holds the last iterate" in api
