@@ -4,10 +4,13 @@ The HIP library is the ONLY compute path of this package: if it is missing or no
 visible, importing the symbols works (so CPU-only tooling can inspect the ABI) but creating a
 context raises -- there is no CPU fallback.
 """
+import contextlib
 import ctypes as C
 import os
 import re
 import subprocess
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdbm.so")
@@ -267,6 +270,33 @@ class Context:
 
     def free(self, ptr):
         check(lib().dbm_free(self.handle, C.c_void_p(ptr)), self.handle)
+
+    def call(self, name, *args):
+        """`name(handle, *args)` of the library, its status checked: for the entry points whose first argument is the context."""
+        check(getattr(lib(), name)(self.handle, *args), self.handle)
+
+    @contextlib.contextmanager
+    def scratch(self, nbytes):
+        """`with ctx.scratch(nbytes) as ptr:` -- device memory that is freed when the block is left, also by an exception."""
+        ptr = self.malloc(nbytes)
+        try:
+            yield ptr
+        finally:
+            self.free(ptr)
+
+    def upload(self, ptr, host):
+        """The bytes of the C-contiguous NumPy array `host` to device memory at `ptr`; nothing is called for an empty array."""
+        if host.nbytes:
+            self.call("dbm_memcpy_h2d", C.c_void_p(ptr), host.ctypes.data_as(C.c_void_p), host.nbytes)
+
+    def download(self, ptr, dtype=None, shape=None, out=None):
+        """Device memory at `ptr` as a new NumPy array of `dtype` and `shape`, or into the C-contiguous array `out`; returns the
+        array.  Nothing is called for an empty array."""
+        if out is None:
+            out = np.empty(shape, dtype=dtype)
+        if out.nbytes:
+            self.call("dbm_memcpy_d2h", out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), out.nbytes)
+        return out
 
 
 def default_context():

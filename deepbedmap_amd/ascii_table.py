@@ -32,8 +32,8 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from .evaluation import DevicePoints
-from .gridding import _SRS_PAIRS, reproject
+from .gridding import SRS_PAIRS, reproject
+from .resident import DevicePoints, devptr
 
 # include/dbm.h: bytes of text per workgroup, its threads, the separator value of `\s+` and the limits of a reader description.
 # tests/test_ascii_host.py holds them to the header.
@@ -156,8 +156,8 @@ def parse_pipeline(pipeline_file):
     if "filters.reprojection" in by_type:
         p = by_type["filters.reprojection"]
         srs = (str(p["in_srs"]), str(p["out_srs"]))
-        if (srs[0].upper(), srs[1].upper()) not in _SRS_PAIRS:
-            raise ValueError(f"{pipeline_file}: only {sorted(_SRS_PAIRS)} can be reprojected, got {srs[0]!r} -> {srs[1]!r}")
+        if (srs[0].upper(), srs[1].upper()) not in SRS_PAIRS:
+            raise ValueError(f"{pipeline_file}: only {sorted(SRS_PAIRS)} can be reprojected, got {srs[0]!r} -> {srs[1]!r}")
     return reader, srs
 
 
@@ -218,45 +218,36 @@ def _separator_code(sep):
 
 
 def _read_resident(buf, reader, ctx):
-    """(device pointer or 0, rows, nuse): the table of one file's bytes, resident"""
-    lib, names = _lib.lib(), reader.names
+    """The table of one file's bytes as a DevicePoints of the used columns, which owns it; without a row it owns nothing (ptr 0)"""
+    names = reader.names
     nuse = len(reader.usecols)
+    empty = DevicePoints.adopt(0, 0, nuse, ctx)
     if buf.size == 0:
-        return 0, 0, nuse
+        return empty
     mask = sum(1 << k for k, n in enumerate(names) if n in reader.usecols)
     na = b"".join(s.encode() + b"\0" for s in reader.na_values)
     sep = _separator_code(reader.separator)
-    text = ctx.malloc(buf.size + 16)
-    table = 0
-    try:
-        _lib.check(lib.dbm_memcpy_h2d(ctx.handle, C.c_void_p(text), buf.ctypes.data_as(C.c_void_p), buf.size), ctx.handle)
+    with ctx.scratch(buf.size + 16) as text:
+        ctx.upload(text, buf)
         counts = (C.c_int64 * 2)()
-        _lib.check(lib.dbm_text_count_lines(ctx.handle, C.c_void_p(text), buf.size, sep, counts, _lib.DEVICE_PTRS), ctx.handle)
+        ctx.call("dbm_text_count_lines", devptr(text), buf.size, sep, counts, _lib.DEVICE_PTRS)
         cap = max(int(counts[1]) - reader.skip - 1, 0)   # every non-blank line behind the discarded ones may be a row
         if cap == 0:
-            return 0, 0, nuse
-        table = ctx.malloc(8 * nuse * cap)
+            return empty
+        table = DevicePoints.adopt(ctx.malloc(8 * nuse * cap), 0, nuse, ctx)
         repair = np.empty((cap, 2), dtype=np.int64)      # (untouched pages cost nothing)
         result = (C.c_int64 * 4)()
-        _lib.check(lib.dbm_text_parse(ctx.handle, C.c_void_p(text), buf.size, sep, reader.skip, len(names), mask, na, len(reader.na_values),
-                                      C.c_void_p(table), cap, repair.ctypes.data_as(C.c_void_p), cap, result, _lib.DEVICE_PTRS), ctx.handle)
-        rows, nrep, bad = int(result[0]), int(result[1]), int(result[2])
+        ctx.call("dbm_text_parse", devptr(text), buf.size, sep, reader.skip, len(names), mask, na, len(reader.na_values), devptr(table), cap,
+                 devptr(repair), cap, result, _lib.DEVICE_PTRS)
+        table.n, nrep, bad = int(result[0]), int(result[1]), int(result[2])
         if bad >= 0:
             where = f"line {int(np.count_nonzero(buf[:bad] == 10)) + 1}"
             _host_row(_line_at(buf, bad), reader, where)
             raise ValueError(f"{where}: cannot be parsed")   # (the device and the host disagree: not reachable by design)
         for off, row in repair[:nrep]:
             vals = np.array(_host_row(_line_at(buf, int(off)), reader, f"byte {int(off)}"), dtype=np.float64)
-            _lib.check(lib.dbm_memcpy_h2d(ctx.handle, C.c_void_p(table + 8 * nuse * int(row)), vals.ctypes.data_as(C.c_void_p), vals.nbytes),
-                       ctx.handle)
-        if rows == 0:
-            return 0, 0, nuse
-        out, table = table, 0
-        return out, rows, nuse
-    finally:
-        ctx.free(text)
-        if table:
-            ctx.free(table)
+            ctx.upload(table.ptr + 8 * nuse * int(row), vals)
+        return table if table.n else empty
 
 
 def read_text_table(data, reader, download=True, ctx=None):
@@ -268,17 +259,12 @@ def read_text_table(data, reader, download=True, ctx=None):
     reader = check_reader(reader)
     buf = _bytes_array(data)
     ctx = ctx or _lib.default_context()
-    ptr, rows, nuse = _read_resident(buf, reader, ctx)
+    table = _read_resident(buf, reader, ctx)
     cols = table_columns(reader)
     if not download:
-        return DevicePoints.adopt(ptr or ctx.malloc(8), rows, nuse, ctx), cols
-    out = np.empty((rows, nuse), dtype=np.float64)
-    if ptr:
-        try:
-            _lib.check(_lib.lib().dbm_memcpy_d2h(ctx.handle, out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), out.nbytes), ctx.handle)
-        finally:
-            ctx.free(ptr)
-    return out, cols
+        table.ptr = table.ptr or ctx.malloc(8)
+        return table, cols
+    return ctx.download(table.ptr, np.float64, (table.n, table.ncol)), cols
 
 
 def _file_bytes(path):
@@ -306,37 +292,27 @@ def ascii_to_xyz(pipeline_file, download=True, ctx=None):
     if not files:
         raise ValueError(f"no file matches {pattern!r}")
     ctx = ctx or _lib.default_context()
-    lib = _lib.lib()
     parts = []
-    try:
-        for path in files:
-            try:
-                parts.append(_read_resident(_file_bytes(path), reader, ctx))
-            except ValueError as e:
-                raise ValueError(f"{path}: {e}") from None
-        n = sum(rows for _, rows, _ in parts)
-        if n >= 2 ** 31:
-            raise ValueError(f"{n} rows: a point table must stay below 2^31 rows")
-        points = DevicePoints.adopt(ctx.malloc(max(24 * n, 8)), n, 3, ctx)
-        a = (C.c_int * 3)(*[p[0] for p in plan])
-        b = (C.c_int * 3)(*[p[2] for p in plan])
-        op = (C.c_int * 3)(*[{None: 0, "+": 1, "-": 2}[p[1]] for p in plan])
-        at = 0
-        for ptr, rows, nuse in parts:
-            if rows:
-                _lib.check(lib.dbm_text_columns(ctx.handle, C.c_void_p(ptr), rows, nuse, C.c_void_p(points.ptr + 24 * at), 3, a, op, b),
-                           ctx.handle)
-            at += rows
-        ctx.synchronize()
-    finally:
-        for ptr, _, _ in parts:
-            if ptr:
-                ctx.free(ptr)
+    for path in files:
+        try:
+            parts.append(_read_resident(_file_bytes(path), reader, ctx))
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+    n = sum(len(part) for part in parts)
+    if n >= 2 ** 31:
+        raise ValueError(f"{n} rows: a point table must stay below 2^31 rows")
+    points = DevicePoints.adopt(ctx.malloc(max(24 * n, 8)), n, 3, ctx)
+    a = (C.c_int * 3)(*[p[0] for p in plan])
+    b = (C.c_int * 3)(*[p[2] for p in plan])
+    op = (C.c_int * 3)(*[{None: 0, "+": 1, "-": 2}[p[1]] for p in plan])
+    at = 0
+    for part in parts:
+        if len(part):
+            ctx.call("dbm_text_columns", devptr(part), part.n, part.ncol, devptr(points.ptr + 24 * at), 3, a, op, b)
+        at += len(part)
+    ctx.synchronize()
     if srs is not None and n:
         reproject(points, srs[0], srs[1])
     if not download:
         return points
-    out = np.empty((n, 3), dtype=np.float64)
-    if n:
-        _lib.check(lib.dbm_memcpy_d2h(ctx.handle, out.ctypes.data_as(C.c_void_p), C.c_void_p(points.ptr), out.nbytes), ctx.handle)
-    return out
+    return ctx.download(points.ptr, np.float64, (n, 3))

@@ -8,13 +8,11 @@ grids that already lie in HBM and run there (dbm_grid_rescale, dbm_grid_rolling_
 samples in place.  Semantics: DESIGN.md "Comparison grids" (`rescale` is the scipy.ndimage chain of current scikit-image
 releases; the reference's pinned 0.15 interpolates differently).  No CPU fallback: without a GPU every call raises DbmError.
 """
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
-from .evaluation import DevicePoints, GridGeometry, _grid_plane, _points_array, grdtrack
-from .srgan import DeviceArray, to_device
+from .evaluation import grdtrack
+from .resident import DeviceArray, DevicePoints, GridGeometry, devptr, plane_shape, points_table, resident_plane
+from .resident import to_device  # noqa: F401  (re-exported)
 
 
 def rescale_output_shape(shape, scale):
@@ -34,51 +32,40 @@ def rescale_output_shape(shape, scale):
     return int(out[0]), int(out[1])
 
 
-def _resident(grid, H, W, ctx):
-    """(DeviceArray holding the (H, W) plane, its context): a DeviceArray as it is, anything else uploaded as float32"""
-    if isinstance(grid, DeviceArray):
-        return grid, grid.ctx
-    ctx = ctx or _lib.default_context()
-    return to_device(np.asarray(grid, dtype=np.float32).reshape(H, W), ctx), ctx
-
-
 def rescale(image, scale, order=1, anti_aliasing=True, clip=True, as_int=False, ctx=None):
     """`skimage.transform.rescale(image, scale, order=order, mode="reflect", anti_aliasing=anti_aliasing, clip=clip,
     preserve_range=True)` on the GPU, as current scikit-image computes it; as_int: the reference's `.astype(np.int32)` on the way
     in (deepbedmap.py:324, 349).  image: NumPy array or DeviceArray of shape (H, W), (1, H, W) or (1, 1, H, W); returns a
     DeviceArray of the same rank holding round(scale * (H, W)) nodes.  Orders 1 and 3; H, W >= 2; NaN nodes are outside the contract."""
-    H, W = _grid_plane(image)
+    H, W = plane_shape(image)
     if order not in (1, 3):
         raise ValueError(f"order must be 1 (linear) or 3 (cubic), got {order!r}")
     if H < 2 or W < 2:
         raise ValueError(f"rescale needs at least 2 x 2 nodes, the grid is {H} x {W}")
     out_h, out_w = rescale_output_shape((H, W), scale)
     lead = tuple(image.shape)[:-2]
-    src, ctx = _resident(image, H, W, ctx)
+    src, ctx = resident_plane(image, ctx)
     out = DeviceArray(lead + (out_h, out_w), ctx)
-    _lib.check(_lib.lib().dbm_grid_rescale(ctx.handle, C.c_void_p(src.ptr), H, W, out_h, out_w, int(order), int(bool(anti_aliasing)),
-                                           int(bool(clip)), int(bool(as_int)), C.c_void_p(out.ptr)), ctx.handle)
-    out._gen += 1
-    return out
+    ctx.call("dbm_grid_rescale", devptr(src), H, W, out_h, out_w, int(order), int(bool(anti_aliasing)), int(bool(clip)), int(bool(as_int)),
+             devptr(out))
+    return out.written()
 
 
 def standard_deviation_2d(grid, window_length, ctx=None):
     """paper_figures.py:847-867: the standard deviation (ddof 0) of each node's centred window_length x window_length neighbourhood,
     NaN nodes and nodes beyond the edges skipped, NaN where the window holds no valid node.  window_length odd, 1..63.  grid: NumPy
     array or DeviceArray of shape (H, W), (1, H, W) or (1, 1, H, W); returns a DeviceArray of the same shape."""
-    H, W = _grid_plane(grid)
+    H, W = plane_shape(grid)
     if isinstance(window_length, bool) or not isinstance(window_length, (int, np.integer)):
         raise TypeError(f"window_length must be an integer, got {window_length!r}")
     if window_length % 2 != 1 or not 1 <= window_length <= 63:
         raise ValueError(f"window_length must be odd and lie in 1..63, got {window_length}")
     if H < 1 or W < 1:
         raise ValueError(f"empty grid ({H} x {W})")
-    src, ctx = _resident(grid, H, W, ctx)
+    src, ctx = resident_plane(grid, ctx)
     out = DeviceArray(tuple(grid.shape), ctx)
-    _lib.check(_lib.lib().dbm_grid_rolling_std(ctx.handle, C.c_void_p(src.ptr), H, W, int(window_length), C.c_void_p(out.ptr)),
-               ctx.handle)
-    out._gen += 1
-    return out
+    ctx.call("dbm_grid_rolling_std", devptr(src), H, W, int(window_length), devptr(out))
+    return out.written()
 
 
 def cubic_bedmap(X_tile, ctx=None):
@@ -94,9 +81,8 @@ def cubic_bedmap(X_tile, ctx=None):
     if isinstance(X_tile, DeviceArray):
         ctx = X_tile.ctx
         inner = DeviceArray((h - 2, w - 2), ctx)
-        _lib.check(_lib.lib().dbm_memcpy2d_d2d(ctx.handle, C.c_void_p(inner.ptr), 4 * (w - 2), C.c_void_p(X_tile.ptr + 4 * (w + 1)), 4 * w,
-                                               4 * (w - 2), h - 2), ctx.handle)
-        inner._gen += 1
+        ctx.call("dbm_memcpy2d_d2d", devptr(inner), 4 * (w - 2), devptr(X_tile.ptr + 4 * (w + 1)), 4 * w, 4 * (w - 2), h - 2)
+        inner.written()
     else:
         inner = np.asarray(X_tile, dtype=np.float32)[0, 0, 1:-1, 1:-1]
     out = rescale(inner, 4, order=3, anti_aliasing=True, clip=True, as_int=True, ctx=ctx)
@@ -115,9 +101,9 @@ def compare_on_tracks(points, grids, interpolation="bicubic", threshold=0.5, ctx
     for name, entry in grids.items():
         if not isinstance(entry, (tuple, list)) or len(entry) != 2 or not isinstance(entry[1], GridGeometry):
             raise TypeError(f"grids[{name!r}] must be (grid, GridGeometry)")
-        _grid_plane(entry[0])
+        plane_shape(entry[0])
         entries.append((name, entry[0], entry[1]))
-    if (points.ncol if isinstance(points, DevicePoints) else _points_array(points).shape[1]) != 3:
+    if (points.ncol if isinstance(points, DevicePoints) else points_table(points).shape[1]) != 3:
         raise ValueError("compare_on_tracks: the points need a z column")
     if not isinstance(points, DevicePoints):
         for _, g, _ in entries:

@@ -20,6 +20,7 @@ import struct
 import numpy as np
 
 from . import _lib
+from .resident import DeviceArray, GridGeometry, devptr
 
 TILE = 256  # GDAL's default block size for tiled=True
 EPSG_ANTARCTIC_POLAR_STEREOGRAPHIC = 3031  # "+proj=stere +lat_0=-90 +lat_ts=-71 +lon_0=0 ..." (data_prep.py:784)
@@ -30,20 +31,11 @@ _TYPES = {1: ("B", 1), 2: ("s", 1), 3: ("H", 2), 4: ("I", 4), 12: ("d", 8), 16: 
 def canvas_to_int16(canvas):
     """`Y_hat.astype(np.int16)` (deepbedmap.py:752) for a NumPy array or a DeviceArray (converted on the GPU: half the
     bytes cross PCIe).  Returns a NumPy int16 array of the same shape."""
-    from .srgan import DeviceArray
-
     if isinstance(canvas, DeviceArray):
         ctx = canvas.ctx
-        n = canvas.size
-        dst = ctx.malloc(2 * n + 16)
-        try:
-            lib = _lib.lib()
-            _lib.check(lib.dbm_f32_to_i16(ctx.handle, C.c_void_p(canvas.ptr), C.c_void_p(dst), n), ctx.handle)
-            out = np.empty(canvas.shape, dtype=np.int16)
-            _lib.check(lib.dbm_memcpy_d2h(ctx.handle, out.ctypes.data_as(C.c_void_p), C.c_void_p(dst), 2 * n), ctx.handle)
-        finally:
-            ctx.free(dst)
-        return out
+        with ctx.scratch(2 * canvas.size + 16) as dst:
+            ctx.call("dbm_f32_to_i16", devptr(canvas), devptr(dst), canvas.size)
+            return ctx.download(dst, np.int16, canvas.shape)
     with np.errstate(invalid="ignore"):
         return np.asarray(canvas).astype(np.int16)
 
@@ -335,8 +327,6 @@ class GeoTiffFile:
 
     def _parse_geometry(self):
         """GridGeometry of the whole image, or the ValueError that asking for it raises."""
-        from .evaluation import GridGeometry
-
         point = self._raster_type() == 2
         shift = 0.0 if point else 0.5   # PixelIsPoint: the nodes sit on the tiepoint, not half a pixel in
         m = self.tags.get(34264)
@@ -500,8 +490,6 @@ def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=Non
     import zlib
     from concurrent.futures import ThreadPoolExecutor
 
-    from .srgan import DeviceArray
-
     if workspace_limit is None:
         workspace_limit = WORKSPACE_DEFAULT
     workspace_limit = int(workspace_limit)
@@ -518,7 +506,6 @@ def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=Non
         geometry = dataclasses.replace(geometry, x0=col0 * geometry.dx + geometry.x0, y0=row0 * geometry.dy + geometry.y0)
     ctx = ctx or _lib.default_context()
     out = DeviceArray((H, W), ctx)
-    lib = _lib.lib()
     itemsize = gf.dtype.itemsize
     with open(gf.path, "rb") as f:
         for start, stop in _batches(gf, plan, workspace_limit):
@@ -558,14 +545,13 @@ def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=Non
                 table[:, 1] = want
                 mode = 1
             try:
-                _lib.check(lib.dbm_tiff_decode(ctx.handle, payload.ctypes.data_as(C.c_void_p), payload.size, table.ctypes.data_as(C.c_void_p),
-                                               len(part), mode, gf.predictor, gf.sample_type, gf.block_w, gf.block_h, C.c_void_p(out.ptr), H, W),
-                           ctx.handle)
+                ctx.call("dbm_tiff_decode", devptr(payload), payload.size, devptr(table), len(part), mode, gf.predictor, gf.sample_type, gf.block_w,
+                         gf.block_h, devptr(out), H, W)
             except _lib.DbmError as e:
                 err = _lib.DbmError(f"{gf.path}: {e}")
                 err.code = e.code
                 raise err from None
-    out._gen += 1
+    out.written()
     info = {"pixel_scale": gf.pixel_scale, "tiepoint": gf.tiepoint, "geokeys": gf.geokeys, "nodata": gf.nodata, "bigtiff": gf.bigtiff,
             "compression": gf.compression, "tile": (gf.block_h, gf.block_w), "predictor": gf.predictor, "dtype": gf.dtype,
             "window": plan.window, "geometry": geometry}

@@ -21,12 +21,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .evaluation import DevicePoints, GridGeometry
-from .srgan import DeviceArray, to_device
+from .resident import DeviceArray, DevicePoints, GridGeometry, devptr, f64ptr, points_table, resident_plane, shape_of
+from .resident import to_device  # noqa: F401  (re-exported)
 
 # EPSG method 9829 parameters {a, 1/f, latitude of true scale, longitude of origin, false easting, false northing}
 EPSG3031 = (6378137.0, 298.257223563, -71.0, 0.0, 0.0, 0.0)
-_SRS_PAIRS = {("EPSG:4326", "EPSG:3031"): EPSG3031}
+SRS_PAIRS = {("EPSG:4326", "EPSG:3031"): EPSG3031}   # (in_srs, out_srs), upper case, that `reproject` converts
 
 # include/dbm.h: threads per workgroup of the point passes; the largest block population of each size class of the block medians'
 # selection, in ascending order (8 lanes, 32 lanes, a wavefront, a workgroup sorting in LDS; larger blocks: selection out of global
@@ -37,17 +37,6 @@ BLOCKMEDIAN_SUB32 = 32
 BLOCKMEDIAN_WAVE = 64
 BLOCKMEDIAN_LDS = 2048
 BLOCKMEDIAN_CLASS_BOUNDARIES = (BLOCKMEDIAN_SUB8, BLOCKMEDIAN_SUB32, BLOCKMEDIAN_WAVE, BLOCKMEDIAN_LDS)
-
-
-def _table(points, ncols, what):
-    """float64 C-contiguous (n, ncol) from an array or a DataFrame with columns x, y[, z] (no pandas import)"""
-    if hasattr(points, "columns"):
-        cols = ["x", "y", "z"] if "z" in points.columns else ["x", "y"]
-        points = points[cols].to_numpy()
-    pts = np.ascontiguousarray(points, dtype=np.float64)
-    if pts.ndim != 2 or not ncols(pts.shape[1]):
-        raise ValueError(f"{what}; got shape {pts.shape}")
-    return pts
 
 
 def _like(points, values):
@@ -126,27 +115,24 @@ def reproject(points, in_srs="EPSG:4326", out_srs="EPSG:3031", ctx=None):
     is converted IN PLACE and returned.  A latitude outside [-90, 0] is refused with ValueError before anything is converted (a resident
     table is inspected on the device, over its rows whose x, y[, z] are all finite: the rows every later stage keeps)."""
     key = (str(in_srs).upper(), str(out_srs).upper())
-    if key not in _SRS_PAIRS:
-        raise ValueError(f"reproject: only {sorted(_SRS_PAIRS)} are supported, got {in_srs!r} -> {out_srs!r}")
-    proj = np.array(_SRS_PAIRS[key], dtype=np.float64)
-    lib_args = (proj.ctypes.data_as(C.POINTER(C.c_double)),)
+    if key not in SRS_PAIRS:
+        raise ValueError(f"reproject: only {sorted(SRS_PAIRS)} are supported, got {in_srs!r} -> {out_srs!r}")
+    proj = f64ptr(np.array(SRS_PAIRS[key], dtype=np.float64))
     if isinstance(points, DevicePoints):
         # the latitudes' range, on the device: with an increment of 2^-20 degrees (-90 is a multiple) the outward rounding of
         # dbm_points_region moves ymin below -90 iff a latitude lies below it and ymax above 0 iff a latitude lies above it
         (_, _, lat_lo, lat_hi), count = region_of(points, 2.0 ** -20)
         if count and (lat_lo < -90.0 or lat_hi > 0.0):
             raise ValueError("reproject: latitudes must lie in [-90, 0] (the south-pole case of the polar stereographic projection)")
-        _lib.check(_lib.lib().dbm_points_polar_stereographic(points.ctx.handle, C.c_void_p(points.ptr), points.n, points.ncol, *lib_args,
-                                                             C.c_void_p(points.ptr), _lib.DEVICE_PTRS), points.ctx.handle)
+        points.ctx.call("dbm_points_polar_stereographic", devptr(points), points.n, points.ncol, proj, devptr(points), _lib.DEVICE_PTRS)
         return points
-    pts = _table(points, lambda c: c >= 2, "reproject: points must be (n, >= 2) longitude, latitude[, ...]")
+    pts = points_table(points, lambda c: c >= 2, "reproject: points must be (n, >= 2) longitude, latitude[, ...]")
     lat = pts[:, 1]
     if np.any(lat[np.isfinite(lat)] > 0.0) or np.any(lat[np.isfinite(lat)] < -90.0):
         raise ValueError("reproject: latitudes must lie in [-90, 0] (the south-pole case of the polar stereographic projection)")
     ctx = ctx or _lib.default_context()
     out = np.empty_like(pts)
-    _lib.check(_lib.lib().dbm_points_polar_stereographic(ctx.handle, pts.ctypes.data_as(C.c_void_p), pts.shape[0], pts.shape[1], *lib_args,
-                                                         out.ctypes.data_as(C.c_void_p), 0), ctx.handle)
+    ctx.call("dbm_points_polar_stereographic", devptr(pts), pts.shape[0], pts.shape[1], proj, devptr(out), 0)
     return _like(points, out)
 
 
@@ -157,19 +143,13 @@ def region_of(xyz_data, round_increment=250, ctx=None):
     region, count = np.empty(4, dtype=np.float64), C.c_int64(0)
     if isinstance(xyz_data, DevicePoints):
         ctx = xyz_data.ctx
-        out = ctx.malloc(64)
-        try:
-            _lib.check(_lib.lib().dbm_points_region(ctx.handle, C.c_void_p(xyz_data.ptr), xyz_data.n, xyz_data.ncol, inc, C.c_void_p(out),
-                                                    C.c_void_p(out + 32), _lib.DEVICE_PTRS), ctx.handle)
-            host = np.empty(5, dtype=np.float64)
-            _lib.check(_lib.lib().dbm_memcpy_d2h(ctx.handle, host.ctypes.data_as(C.c_void_p), C.c_void_p(out), 40), ctx.handle)
-        finally:
-            ctx.free(out)
+        with ctx.scratch(64) as out:
+            ctx.call("dbm_points_region", devptr(xyz_data), xyz_data.n, xyz_data.ncol, inc, devptr(out), devptr(out + 32), _lib.DEVICE_PTRS)
+            host = ctx.download(out, np.float64, 5)
         return tuple(float(v) for v in host[:4]), int(host[4:].view(np.int64)[0])
-    pts = _table(xyz_data, lambda c: c >= 2, "get_region: the table must be (n, >= 2) x, y[, z]")
+    pts = points_table(xyz_data, lambda c: c >= 2, "get_region: the table must be (n, >= 2) x, y[, z]")
     ctx = ctx or _lib.default_context()
-    _lib.check(_lib.lib().dbm_points_region(ctx.handle, pts.ctypes.data_as(C.c_void_p), pts.shape[0], pts.shape[1], inc,
-                                            region.ctypes.data_as(C.c_void_p), C.byref(count), 0), ctx.handle)
+    ctx.call("dbm_points_region", devptr(pts), pts.shape[0], pts.shape[1], inc, devptr(region), C.byref(count), 0)
     return tuple(float(v) for v in region), int(count.value)
 
 
@@ -195,40 +175,21 @@ def _blockmedian(table, region, spacing, want_grid, want_counts, ctx):
             raise ValueError(f"blockmedian: the table must be (n, 3) x, y, z; got {table.ncol} columns")
         ctx, n, pts = table.ctx, table.n, None
     else:
-        pts = _table(table, lambda c: c == 3, "blockmedian: the table must be (n, 3) x, y, z")
+        pts = points_table(table, lambda c: c == 3, "blockmedian: the table must be (n, 3) x, y, z")
         ctx, n = ctx or _lib.default_context(), pts.shape[0]
-    lib = _lib.lib()
     grid = DeviceArray((H, W), ctx) if want_grid else None
-    cdev = ctx.malloc(4 * H * W) if want_counts else None
+    cdev = DeviceArray((H, W), ctx, dtype=np.int32) if want_counts else None
     cap = max(min(n, H * W), 1)
     m = C.c_int64(0)
-    try:
-        args = (r4.ctypes.data_as(C.POINTER(C.c_double)), s)
-        tail = (cap, C.byref(m), C.c_void_p(grid.ptr) if grid is not None else None, C.c_void_p(cdev) if cdev else None)
-        if pts is None:
-            tdev = ctx.malloc(24 * cap)
-            try:
-                _lib.check(lib.dbm_points_blockmedian(ctx.handle, C.c_void_p(table.ptr), n, *args, C.c_void_p(tdev), *tail, _lib.DEVICE_PTRS),
-                           ctx.handle)
-                out = np.empty((int(m.value), 3), dtype=np.float64)
-                if out.size:
-                    _lib.check(lib.dbm_memcpy_d2h(ctx.handle, out.ctypes.data_as(C.c_void_p), C.c_void_p(tdev), out.nbytes), ctx.handle)
-            finally:
-                ctx.free(tdev)
-        else:
-            out = np.empty((cap, 3), dtype=np.float64)
-            _lib.check(lib.dbm_points_blockmedian(ctx.handle, pts.ctypes.data_as(C.c_void_p), n, *args, out.ctypes.data_as(C.c_void_p), *tail, 0),
-                       ctx.handle)
-            out = out[:int(m.value)].copy()
-        counts = None
-        if cdev:
-            counts = np.empty((H, W), dtype=np.int32)
-            _lib.check(lib.dbm_memcpy_d2h(ctx.handle, counts.ctypes.data_as(C.c_void_p), C.c_void_p(cdev), counts.nbytes), ctx.handle)
-    finally:
-        if cdev:
-            ctx.free(cdev)
+    if pts is None:
+        src, dst, flags = table, DeviceArray((cap, 3), ctx, dtype=np.float64), _lib.DEVICE_PTRS
+    else:
+        src, dst, flags = pts, np.empty((cap, 3), dtype=np.float64), 0
+    ctx.call("dbm_points_blockmedian", devptr(src), n, f64ptr(r4), s, devptr(dst), cap, C.byref(m), devptr(grid), devptr(cdev), flags)
+    out = ctx.download(dst.ptr, np.float64, (int(m.value), 3)) if pts is None else dst[:int(m.value)].copy()
+    counts = cdev.get() if want_counts else None
     if grid is not None:
-        grid._gen += 1
+        grid.written()
     return out, grid, counts, geometry
 
 
@@ -250,19 +211,6 @@ def blockmedian_grid(points, region, spacing=250, counts=False, download=True, c
     _, grid, cnt, geometry = _blockmedian(points, region, spacing, True, bool(counts), ctx)
     g = grid.get() if download else grid
     return (g, geometry, cnt) if counts else (g, geometry)
-
-
-def _resident(grid, ctx, what):
-    """(DeviceArray (H, W), ctx): a DeviceArray is used in place, anything else is uploaded as float32"""
-    if isinstance(grid, DeviceArray):
-        if len(grid.shape) != 2:
-            raise ValueError(f"{what}: the grid must be (H, W); got {grid.shape}")
-        return grid, grid.ctx
-    host = np.asarray(grid, dtype=np.float32)
-    if host.ndim != 2:
-        raise ValueError(f"{what}: the grid must be (H, W); got {host.shape}")
-    ctx = ctx or _lib.default_context()
-    return to_device(host, ctx), ctx
 
 
 def _surface_arguments(shape, tension, tol, max_iter):
@@ -289,16 +237,15 @@ def tension_surface(grid, tension=0.35, tol=1e-9, max_iter=20000, download=True,
     a float32 array, or a DeviceArray with download=False; info = {"iterations", "residual" (final |r| / |b|), "constraints", "free"}.
     Raises ValueError for arguments out of range, DbmError (code 1) for a grid without data and DbmError (code 10) if the conjugate
     gradients have not reached tol within max_iter."""
-    shape = grid.shape if isinstance(grid, DeviceArray) else np.shape(grid)
+    shape = shape_of(grid)
     if len(shape) != 2:
         raise ValueError(f"tension_surface: the grid must be (H, W); got {tuple(shape)}")
     H, W, tension, tol, max_iter = _surface_arguments(shape, tension, tol, max_iter)
-    dgrid, ctx = _resident(grid, ctx, "tension_surface")
+    dgrid, ctx = resident_plane(grid, ctx, "tension_surface")
     out = DeviceArray((H, W), ctx)
     info = np.zeros(4, dtype=np.float64)
-    _lib.check(_lib.lib().dbm_grid_tension_surface(ctx.handle, C.c_void_p(dgrid.ptr), H, W, tension, tol, max_iter, C.c_void_p(out.ptr),
-                                                   info.ctypes.data_as(C.POINTER(C.c_double))), ctx.handle)
-    out._gen += 1
+    ctx.call("dbm_grid_tension_surface", devptr(dgrid), H, W, tension, tol, max_iter, devptr(out), f64ptr(info))
+    out.written()
     report = {"iterations": int(info[0]), "residual": float(info[1]), "constraints": int(info[2]), "free": int(info[3])}
     return (out.get() if download else out), report
 
@@ -314,20 +261,19 @@ def mask_far_from_data(surface, data, radius=3):
     node-to-node distance: this project's reading of GMT's `c` unit).  surface, data: (H, W) arrays or DeviceArrays.  A DeviceArray
     `surface` is masked IN PLACE and returned; an array is copied and a masked float32 array returned."""
     radius = _mask_radius(radius)
-    sshape = surface.shape if isinstance(surface, DeviceArray) else np.shape(surface)
-    dshape = data.shape if isinstance(data, DeviceArray) else np.shape(data)
+    sshape, dshape = shape_of(surface), shape_of(data)
     if len(sshape) != 2 or tuple(sshape) != tuple(dshape):
         raise ValueError(f"mask_far_from_data: surface and data must have the same (H, W) shape; got {tuple(sshape)} and {tuple(dshape)}")
     if surface is data:
         raise ValueError("mask_far_from_data: the surface must not be the data raster")
     ctx = surface.ctx if isinstance(surface, DeviceArray) else (data.ctx if isinstance(data, DeviceArray) else None)
-    dsurf, ctx = _resident(surface, ctx, "mask_far_from_data")
-    ddata, _ = _resident(data, ctx, "mask_far_from_data")
+    dsurf, ctx = resident_plane(surface, ctx, "mask_far_from_data")
+    ddata, _ = resident_plane(data, ctx, "mask_far_from_data")
     if ddata.ctx is not dsurf.ctx:
         raise ValueError("mask_far_from_data: the surface and the data live on different contexts")
     H, W = (int(v) for v in sshape)
-    _lib.check(_lib.lib().dbm_grid_distance_mask(ctx.handle, C.c_void_p(ddata.ptr), C.c_void_p(dsurf.ptr), H, W, radius), ctx.handle)
-    dsurf._gen += 1
+    ctx.call("dbm_grid_distance_mask", devptr(ddata), devptr(dsurf), H, W, radius)
+    dsurf.written()
     return dsurf if isinstance(surface, DeviceArray) else dsurf.get()
 
 
@@ -341,16 +287,16 @@ def to_pixel_registration(grid, geometry, threshold=0.5, download=None, ctx=None
         raise ValueError("to_pixel_registration: the grid must be gridline-registered")
     if not (0.0 < float(threshold) <= 1.0):
         raise ValueError(f"threshold must lie in (0, 1], got {threshold}")
-    shape = grid.shape if isinstance(grid, DeviceArray) else np.shape(grid)
+    shape = shape_of(grid)
     if len(shape) != 2 or shape[0] < 2 or shape[1] < 2:
         raise ValueError(f"to_pixel_registration: the grid must be (H, W) with at least 2 x 2 nodes; got {tuple(shape)}")
     if download is None:
         download = not isinstance(grid, DeviceArray)
-    dgrid, ctx = _resident(grid, ctx, "to_pixel_registration")
+    dgrid, ctx = resident_plane(grid, ctx, "to_pixel_registration")
     H, W = dgrid.shape
     out = DeviceArray((H - 1, W - 1), ctx)
-    _lib.check(_lib.lib().dbm_grid_to_pixel(ctx.handle, C.c_void_p(dgrid.ptr), H, W, float(threshold), C.c_void_p(out.ptr)), ctx.handle)
-    out._gen += 1
+    ctx.call("dbm_grid_to_pixel", devptr(dgrid), H, W, float(threshold), devptr(out))
+    out.written()
     pixel = GridGeometry(x0=geometry.x0 + geometry.dx / 2, y0=geometry.y0 + geometry.dy / 2, dx=geometry.dx, dy=geometry.dy,
                          registration="pixel")
     return (out.get() if download else out), pixel

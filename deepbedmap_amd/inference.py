@@ -8,13 +8,12 @@ exactly like the reference's `xp.asarray(...)` (deepbedmap.py:707-722); `predict
 input grids and the output canvas in HBM (12.5 GB for the whole continent: 4 % of an MI355X) and crops / pastes
 with pitched device-to-device copies, so that nothing crosses PCIe between the upload and the final download.
 """
-import ctypes as C
 import dataclasses
 
 import numpy as np
 
-from . import _lib
-from .srgan import DeviceArray, to_device, using_config
+from .resident import DeviceArray, devptr, to_device
+from .srgan import using_config
 
 
 @dataclasses.dataclass(frozen=True)
@@ -30,9 +29,8 @@ def clip_inputs(W1_tile, W2_tile, W3_tile):
     out = []
     for a in (W1_tile, W2_tile, W3_tile):
         if isinstance(a, DeviceArray):
-            _lib.check(_lib.lib().dbm_clip_min_f32(a.ctx.handle, C.c_void_p(a.ptr), a.size, 0.0), a.ctx.handle)
-            a._gen += 1
-            out.append(a)
+            a.ctx.call("dbm_clip_min_f32", devptr(a), a.size, 0.0)
+            out.append(a.written())
         else:
             out.append(np.clip(a=a, a_min=0.0, a_max=None))
     return tuple(out)
@@ -106,7 +104,6 @@ def predict_tiled_resident(model, X_tile, W1_tile, W2_tile, W3_tile, final_shape
     crops_per_batch > 1: crops of equal shape go through the generator that many at a time (the reference's loop, :704-741, is one
     crop per forward; per crop the arithmetic is the same, so is the canvas) -- 6.5 -> 5.9 ms per 288 x 288 bf16 crop at 8."""
     ctx = model.ctx
-    lib = _lib.lib()
     if stride.y < ary_shape.y or stride.x < ary_shape.x:
         # overlapping pastes: the reference's loop order decides which tile's pixels survive; grouping by crop shape would change it
         raise ValueError("predict_tiled_resident needs stride >= ary_shape (non-overlapping pasted regions); use predict_tiled")
@@ -115,11 +112,10 @@ def predict_tiled_resident(model, X_tile, W1_tile, W2_tile, W3_tile, final_shape
         grids[1:] = clip_inputs(*grids[1:])
     scale = (1, 10, 2, 1)  # pixels of each grid per low-resolution pixel
     canvas = DeviceArray((1, final_shape.y, final_shape.x), ctx)
-    _lib.check(lib.dbm_fill_f32(ctx.handle, C.c_void_p(canvas.ptr), canvas.size, float("nan")), ctx.handle)
+    ctx.call("dbm_fill_f32", devptr(canvas), canvas.size, float("nan"))
 
     def copy2d(dst, dpitch, src, spitch, width, height):  # in floats
-        _lib.check(lib.dbm_memcpy2d_d2d(ctx.handle, C.c_void_p(dst), 4 * dpitch, C.c_void_p(src), 4 * spitch, 4 * width,
-                                        height), ctx.handle)
+        ctx.call("dbm_memcpy2d_d2d", devptr(dst), 4 * dpitch, devptr(src), 4 * spitch, 4 * width, height)
 
     # the rank's tiles grouped by crop shape (320 of the continent's 396 crops are 288 x 288), each group in batches of
     # `crops_per_batch` crops per generator forward: same arithmetic per crop, fewer and fuller launches
@@ -141,6 +137,8 @@ def predict_tiled_resident(model, X_tile, W1_tile, W2_tile, W3_tile, final_shape
                     for c in range(nc):
                         copy2d(b.ptr + 4 * ((j * nc + c) * (k * h) * (k * w)), k * w, g.ptr + 4 * (c * H * W + (k * y0) * W + k * x0), W,
                                k * w, k * h)
+            for b in bufs:
+                b.written()
             ins = bufs if nb == nb_max else [DeviceArray((nb,) + b.shape[1:], ctx, ptr=b.ptr, owner=b) for b in bufs]
             with using_config(name="enable_backprop", value=False), using_config(name="dtype", value=dtype):
                 Y_pred = model.forward(x=ins[0], w1=ins[1], w2=ins[2], w3=ins[3])
@@ -154,6 +152,7 @@ def predict_tiled_resident(model, X_tile, W1_tile, W2_tile, W3_tile, final_shape
     # process holding the GPU) is reported here instead of in a canvas with wrong tiles -- status 7: run the sweep again
     ctx.synchronize()
     ctx.check_timeout()
+    canvas.written()
     return canvas.get() if download else canvas
 
 

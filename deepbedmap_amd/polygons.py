@@ -15,8 +15,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from .evaluation import GridGeometry
-from .srgan import DeviceArray
+from .resident import DeviceArray, GridGeometry, devptr, f64ptr
 from .tiling import Raster, get_window_bounds
 
 TILE = 16          # DBM_POLY_TILE: nodes along the side of a tile (one workgroup)
@@ -28,30 +27,7 @@ class MaskArray(DeviceArray):
     """uint8 C-contiguous array of 0 / 1 resident in HBM."""
 
     def __init__(self, shape, ctx=None):
-        super().__init__(shape, ctx)
-        self.dtype = np.dtype(np.uint8)
-
-    @property
-    def nbytes(self):
-        return self.size
-
-    def set(self, host):
-        host = np.ascontiguousarray(host, dtype=np.uint8)
-        assert host.size == self.size, (host.shape, self.shape)
-        self._gen += 1
-        _lib.check(_lib.lib().dbm_memcpy_h2d(self.ctx.handle, C.c_void_p(self.ptr), host.ctypes.data_as(C.c_void_p), self.nbytes),
-                   self.ctx.handle)
-        return self
-
-    def get(self):
-        out = np.empty(self.shape, dtype=np.uint8)
-        _lib.check(_lib.lib().dbm_memcpy_d2h(self.ctx.handle, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr), self.nbytes),
-                   self.ctx.handle)
-        return out
-
-    @property
-    def __cuda_array_interface__(self):
-        return {"shape": self.shape, "typestr": "|u1", "data": (self.ptr, False), "version": 2, "strides": None}
+        super().__init__(shape, ctx, dtype=np.uint8)
 
 
 class Polygons:
@@ -108,11 +84,8 @@ class Polygons:
         """The edge table in HBM: one upload per context, reused across grids.  Returns the device pointer."""
         ctx = ctx or _lib.default_context()
         if ctx not in self._dev:
-            ptr = ctx.malloc(max(self.edges.nbytes, 32))
-            if self.edges.nbytes:
-                _lib.check(_lib.lib().dbm_memcpy_h2d(ctx.handle, C.c_void_p(ptr), self.edges.ctypes.data_as(C.c_void_p), self.edges.nbytes),
-                           ctx.handle)
-            self._dev[ctx] = ptr
+            self._dev[ctx] = ctx.malloc(max(self.edges.nbytes, 32))
+            ctx.upload(self._dev[ctx], self.edges)
         return self._dev[ctx]
 
     def __del__(self):
@@ -230,11 +203,11 @@ def _arguments(geometry, shape, polygons, buffer, workspace_limit):
     return H, W, buffer, workspace_limit
 
 
-def _run(ctx, geometry, H, W, polygons, buffer, workspace_limit, mask_ptr, grid_ptr):
-    geom = geometry.as_array()
-    _lib.check(_lib.lib().dbm_grid_polygon_mask(ctx.handle, C.c_void_p(polygons.device(ctx)), len(polygons), H, W,
-                                                geom.ctypes.data_as(C.POINTER(C.c_double)), buffer, C.c_void_p(mask_ptr) if mask_ptr else None,
-                                                C.c_void_p(grid_ptr) if grid_ptr else None, workspace_limit, _lib.DEVICE_PTRS), ctx.handle)
+def _run(ctx, geometry, H, W, polygons, buffer, workspace_limit, mask, grid):
+    """dbm_grid_polygon_mask into `mask` (a uint8 DeviceArray) or onto `grid` (a float32 one), the other None"""
+    ctx.call("dbm_grid_polygon_mask", devptr(polygons.device(ctx)), len(polygons), H, W, f64ptr(geometry.as_array()), buffer, devptr(mask),
+             devptr(grid), workspace_limit, _lib.DEVICE_PTRS)
+    (grid if mask is None else mask).written()
 
 
 def last_stats(ctx=None):
@@ -242,7 +215,7 @@ def last_stats(ctx=None):
     context's last polygon_mask / mask_outside call."""
     ctx = ctx or _lib.default_context()
     out = (C.c_int64 * 6)()
-    _lib.check(_lib.lib().dbm_grid_polygon_stats(ctx.handle, out), ctx.handle)
+    ctx.call("dbm_grid_polygon_stats", out)
     return dict(zip(("proximity_edges", "parity_edges", "tile_entries", "band_entries", "schedule", "edges"), (int(v) for v in out)))
 
 
@@ -254,8 +227,7 @@ def polygon_mask(geometry, shape, polygons, buffer=0.0, download=True, workspace
     H, W, buffer, workspace_limit = _arguments(geometry, shape, polygons, buffer, workspace_limit)
     ctx = ctx or _lib.default_context()
     out = MaskArray((H, W), ctx)
-    _run(ctx, geometry, H, W, polygons, buffer, workspace_limit, out.ptr, None)
-    out._gen += 1
+    _run(ctx, geometry, H, W, polygons, buffer, workspace_limit, out, None)
     return out.get().astype(bool) if download else out
 
 
@@ -268,9 +240,8 @@ def mask_outside(raster, polygons, buffer=0.0, workspace_limit=None):
     src = raster.device()
     ctx = src.ctx
     out = DeviceArray((H, W), ctx)
-    _lib.check(_lib.lib().dbm_memcpy2d_d2d(ctx.handle, C.c_void_p(out.ptr), 4 * W, C.c_void_p(src.ptr), 4 * W, 4 * W, H), ctx.handle)
-    _run(ctx, raster.geometry, H, W, polygons, buffer, workspace_limit, None, out.ptr)
-    out._gen += 1
+    ctx.call("dbm_memcpy2d_d2d", devptr(out), 4 * W, devptr(src), 4 * W, 4 * W, H)
+    _run(ctx, raster.geometry, H, W, polygons, buffer, workspace_limit, None, out)
     return Raster(out, raster.geometry, nodata=raster.nodata)
 
 

@@ -19,6 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import BF16, DbmError, KEEP_GRAPH, BN_TRAIN, DEVICE_PTRS
+from .resident import DeviceArray, to_device  # noqa: F401  (re-exported: srgan.DeviceArray is resident.DeviceArray)
 
 
 # --------------------------------------------------------------------------------------
@@ -47,7 +48,7 @@ config = global_config
 _applied_deterministic = [None]
 
 
-def _apply_config(ctx):
+def apply_config(ctx):
     """Push process-wide library switches that mirror chainer.global_config (cheap: only on change)."""
     want = bool(global_config.cudnn_deterministic)
     if _applied_deterministic[0] != want:
@@ -65,74 +66,12 @@ def using_config(name, value):
         setattr(global_config, name, old)
 
 
-# --------------------------------------------------------------------------------------
-# device arrays
-# --------------------------------------------------------------------------------------
-class DeviceArray:
-    """float32 C-contiguous array resident in HBM (owned unless wrapping foreign memory)."""
-
-    def __init__(self, shape, ctx=None, ptr=None, owner=None):
-        self.ctx = ctx or _lib.default_context()
-        self.shape = tuple(int(s) for s in shape)
-        self.size = int(np.prod(self.shape)) if self.shape else 1
-        self.dtype = np.dtype(np.float32)
-        self._own = ptr is None
-        self.ptr = self.ctx.malloc(4 * max(self.size, 1)) if ptr is None else int(ptr)
-        self._owner = owner
-        self._gen = 0  # content version: bumped by every write through this object
-
-    @property
-    def nbytes(self):
-        return 4 * self.size
-
-    def __len__(self):
-        return self.shape[0]
-
-    def data_ptr(self):
-        return self.ptr
-
-    def set(self, host):
-        host = np.ascontiguousarray(host, dtype=np.float32)
-        assert host.size == self.size, (host.shape, self.shape)
-        self._gen += 1
-        _lib.check(_lib.lib().dbm_memcpy_h2d(self.ctx.handle, C.c_void_p(self.ptr), host.ctypes.data_as(C.c_void_p),
-                                             self.nbytes), self.ctx.handle)
-        return self
-
-    def get(self):
-        out = np.empty(self.shape, dtype=np.float32)
-        _lib.check(_lib.lib().dbm_memcpy_d2h(self.ctx.handle, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr),
-                                             self.nbytes), self.ctx.handle)
-        return out
-
-    def __array__(self, dtype=None, copy=None):
-        a = self.get()
-        return a.astype(dtype) if dtype is not None else a
-
-    @property
-    def __cuda_array_interface__(self):
-        return {"shape": self.shape, "typestr": "<f4", "data": (self.ptr, False), "version": 2, "strides": None}
-
-    def __del__(self):
-        try:
-            if self._own and self.ptr:
-                self.ctx.free(self.ptr)
-                self.ptr = 0
-        except Exception:
-            pass
-
-
-def to_device(a, ctx=None):
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    return DeviceArray(a.shape, ctx).set(a)
-
-
-def _is_device(a):
+def is_device(a):
     return isinstance(a, DeviceArray) or hasattr(a, "data_ptr") or (
         hasattr(a, "__cuda_array_interface__") and not isinstance(a, np.ndarray))
 
 
-def _dev_ptr(a):
+def dev_ptr(a):
     if isinstance(a, DeviceArray):
         return a.ptr
     if hasattr(a, "data_ptr"):  # torch CUDA tensor (plumbing only)
@@ -355,7 +294,7 @@ class GeneratorModel(_Link):
             flags |= BF16
         elif global_config.dtype != "float32":
             raise ValueError(f"unknown dtype {global_config.dtype!r}")
-        device = _is_device(x)
+        device = is_device(x)
         n, _, h, w = x.shape
         exp = {"w1": (n, 1, 10 * h, 10 * w), "w2": (n, 2, 2 * h, 2 * w), "w3": (n, 1, h, w)}
         for name, arr in (("w1", w1), ("w2", w2), ("w3", w3)):
@@ -369,7 +308,7 @@ class GeneratorModel(_Link):
         if device:
             y = DeviceArray(oshape, self.ctx)
             self._held_inputs = (x, w1, w2, w3)  # the input-block weight gradient reads them in backward
-            _lib.check(l.dbm_gen_forward(self._h, n, h, w, _dev_ptr(x), _dev_ptr(w1), _dev_ptr(w2), _dev_ptr(w3),
+            _lib.check(l.dbm_gen_forward(self._h, n, h, w, dev_ptr(x), dev_ptr(w1), dev_ptr(w2), dev_ptr(w3),
                                          y.ptr, flags | DEVICE_PTRS), self.ctx.handle)
             out = y
         else:
@@ -386,9 +325,9 @@ class GeneratorModel(_Link):
 
     def backward(self, gy):
         """d loss / d output of the last retained forward -> parameter gradients (accumulated)."""
-        _apply_config(self.ctx)
-        if _is_device(gy):
-            _lib.check(_lib.lib().dbm_gen_backward(self._h, _dev_ptr(gy), DEVICE_PTRS), self.ctx.handle)
+        apply_config(self.ctx)
+        if is_device(gy):
+            _lib.check(_lib.lib().dbm_gen_backward(self._h, dev_ptr(gy), DEVICE_PTRS), self.ctx.handle)
         else:
             g = _f32(gy)
             _lib.check(_lib.lib().dbm_gen_backward(self._h, _hp(g), 0), self.ctx.handle)
@@ -425,9 +364,9 @@ class DiscriminatorModel(_Link):
         if c != 1:
             raise ValueError("DiscriminatorModel expects one input channel")
         l = _lib.lib()
-        if _is_device(x):
+        if is_device(x):
             out = DeviceArray((n, 1), self.ctx)
-            _lib.check(l.dbm_disc_forward(self._h, n, h, w, _dev_ptr(x), out.ptr, flags | DEVICE_PTRS, slot),
+            _lib.check(l.dbm_disc_forward(self._h, n, h, w, dev_ptr(x), out.ptr, flags | DEVICE_PTRS, slot),
                        self.ctx.handle)
         else:
             xs = _f32(x)
@@ -443,9 +382,9 @@ class DiscriminatorModel(_Link):
     __call__ = forward
 
     def backward(self, slot, glogits):
-        _apply_config(self.ctx)
-        if _is_device(glogits):
-            _lib.check(_lib.lib().dbm_disc_backward(self._h, slot, _dev_ptr(glogits), DEVICE_PTRS), self.ctx.handle)
+        apply_config(self.ctx)
+        if is_device(glogits):
+            _lib.check(_lib.lib().dbm_disc_backward(self._h, slot, dev_ptr(glogits), DEVICE_PTRS), self.ctx.handle)
         else:
             g = _f32(glogits)
             _lib.check(_lib.lib().dbm_disc_backward(self._h, slot, _hp(g), 0), self.ctx.handle)

@@ -13,9 +13,8 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .evaluation import GridGeometry, _grid_plane
 from .geotiff import read_geotiff, read_geotiff_resident
-from .srgan import DeviceArray, to_device
+from .resident import DeviceArray, GridGeometry, devptr, f64ptr, plane_shape, to_device
 
 
 class Raster:
@@ -26,7 +25,7 @@ class Raster:
     def __init__(self, array, geometry, nodata=None, ctx=None):
         if not isinstance(geometry, GridGeometry):
             raise TypeError("geometry must be a GridGeometry")
-        self.H, self.W = _grid_plane(array)
+        self.H, self.W = plane_shape(array)
         if self.H < 1 or self.W < 1:
             raise ValueError(f"empty raster ({self.H} x {self.W})")
         if nodata is not None:
@@ -174,23 +173,12 @@ def _cut(raster, plan, gapfiller, fill_nan, out_ptr, stride, want_counts):
     grid = raster.device()
     ctx = grid.ctx
     n = len(windows)
-    geom = raster.geometry.as_array()
     nodata = None if raster.nodata is None else C.byref(C.c_double(raster.nodata))
     fill = None if gapfiller is None else C.byref(C.c_float(gapfiller))
-    cdev = ctx.malloc(4 * n) if want_counts else None
-    try:
-        _lib.check(_lib.lib().dbm_grid_tile(ctx.handle, C.c_void_p(grid.ptr), raster.H, raster.W, geom.ctypes.data_as(C.POINTER(C.c_double)),
-                                            windows.ctypes.data_as(C.c_void_p), n, mode, resolution, out_h, out_w, nodata, fill,
-                                            int(bool(fill_nan)), C.c_void_p(out_ptr), stride, C.c_void_p(cdev) if cdev else None),
-                   ctx.handle)
-        if not want_counts:
-            return None
-        counts = np.empty(n, dtype=np.int32)
-        _lib.check(_lib.lib().dbm_memcpy_d2h(ctx.handle, counts.ctypes.data_as(C.c_void_p), C.c_void_p(cdev), counts.nbytes), ctx.handle)
-        return counts
-    finally:
-        if cdev:
-            ctx.free(cdev)
+    counts = DeviceArray((n,), ctx, dtype=np.int32) if want_counts else None
+    ctx.call("dbm_grid_tile", devptr(grid), raster.H, raster.W, f64ptr(raster.geometry.as_array()), devptr(windows), n, mode, resolution,
+             out_h, out_w, nodata, fill, int(bool(fill_nan)), devptr(out_ptr), stride, devptr(counts))
+    return counts.get() if want_counts else None
 
 
 def selective_tile(raster, window_bounds, padding=0, resolution=None, gapfiller=None, interpolate=True, fill_nan=False, out=None,
@@ -224,7 +212,7 @@ def selective_tile(raster, window_bounds, padding=0, resolution=None, gapfiller=
     can_mask = fill_nan or (raster.nodata is not None and not np.isnan(raster.nodata))
     counts = _cut(raster, plan, gapfiller, fill_nan, out.ptr + 4 * int(channel) * out_h * out_w, channels * out_h * out_w,
                   want_counts=can_mask and gapfiller is None)
-    out._gen += 1
+    out.written()
     if counts is not None and counts.any():
         warnings.warn(f"selective_tile: tiles {np.flatnonzero(counts).tolist()} have missing data, try passing in a number to "
                       "'gapfiller'", stacklevel=2)
@@ -263,14 +251,10 @@ def get_window_bounds(raster, height=36, width=36, step=3):
     grid = raster.device()
     ctx = grid.ctx
     ny, nx = (raster.H - height) // step + 1, (raster.W - width) // step + 1
-    fdev = ctx.malloc(ny * nx)
-    try:
-        _lib.check(_lib.lib().dbm_grid_filled_windows(ctx.handle, C.c_void_p(grid.ptr), raster.H, raster.W, height, step,
-                                                      int(raster.geometry.dy > 0), int(raster.geometry.dx < 0), C.c_void_p(fdev)), ctx.handle)
-        flags = np.empty((ny, nx), dtype=np.uint8)
-        _lib.check(_lib.lib().dbm_memcpy_d2h(ctx.handle, flags.ctypes.data_as(C.c_void_p), C.c_void_p(fdev), flags.nbytes), ctx.handle)
-    finally:
-        ctx.free(fdev)
+    with ctx.scratch(ny * nx) as fdev:
+        ctx.call("dbm_grid_filled_windows", devptr(grid), raster.H, raster.W, height, step, int(raster.geometry.dy > 0),
+                 int(raster.geometry.dx < 0), devptr(fdev))
+        flags = ctx.download(fdev, np.uint8, (ny, nx))
     return bounds_from_flags(flags, raster.geometry, raster.shape, height, step)
 
 
@@ -328,7 +312,7 @@ def tile_training_set(highres, bedmap2, rema, velocity_x, velocity_y, accumulati
         if counts is not None and counts.any():
             warnings.warn(f"tile_training_set: groundtruth tiles {(done + np.flatnonzero(counts)).tolist()} have missing data", stacklevel=2)
         done += len(plan[1])
-    Y._gen += 1
+    Y.written()
     return {"X": selective_tile(bedmap2, windows, padding=1000),
             "W1": selective_tile(rema, windows, padding=1000),
             "W2": _two_channels(velocity_x, velocity_y, windows, 1000, None),
@@ -358,11 +342,8 @@ def fill_gaps(fine, coarse, inplace=False):
     if cgrid.ctx is not ctx:
         raise ValueError("fill_gaps: fine and coarse live on different contexts")
     out = src if inplace else DeviceArray(src.shape, ctx)
-    wb = np.asarray(bounds, dtype=np.float64)
-    cgeom = coarse.geometry.as_array()
     nodata = None if fine.nodata is None else C.byref(C.c_double(fine.nodata))
-    _lib.check(_lib.lib().dbm_grid_fill_gaps(ctx.handle, C.c_void_p(src.ptr), fine.H, fine.W, wb.ctypes.data_as(C.POINTER(C.c_double)), float(g.dx),
-                                             nodata, C.c_void_p(cgrid.ptr), coarse.H, coarse.W, cgeom.ctypes.data_as(C.POINTER(C.c_double)),
-                                             C.c_void_p(out.ptr)), ctx.handle)
-    out._gen += 1
+    ctx.call("dbm_grid_fill_gaps", devptr(src), fine.H, fine.W, f64ptr(np.asarray(bounds, dtype=np.float64)), float(g.dx), nodata, devptr(cgrid),
+             coarse.H, coarse.W, f64ptr(coarse.geometry.as_array()), devptr(out))
+    out.written()
     return fine if inplace else Raster(out, g, nodata=fine.nodata)

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .srgan import (Adam, DeviceArray, DiscriminatorModel, GeneratorModel, global_config, save_npz, to_device,
-                    _apply_config, _dev_ptr, _is_device)
+                    apply_config, dev_ptr, is_device)
 
 LOSS_WEIGHTS = (1e-2, 2e-2, 2e-3, 5.25e-0)  # calculate_generator_loss defaults (srgan_train.py:849-852)
 
@@ -37,7 +37,7 @@ def _content_token(dev):
     tok = []
     for k in _KEYS:
         a = dev[k]
-        tok.append((id(a), _dev_ptr(a), getattr(a, "_gen", None), getattr(a, "_version", None)))
+        tok.append((id(a), dev_ptr(a), getattr(a, "_gen", None), getattr(a, "_version", None)))
     return tuple(tok)
 
 
@@ -50,7 +50,7 @@ def _metrics_buffer(ctx):
 def device_batch(input_arrays, ctx=None):
     """Upload a dict of NumPy arrays once; device arrays pass through (chainer: arrays already `to_gpu`'d,
     srgan_train.py:110-116)."""
-    return {k: (v if _is_device(v) else to_device(v, ctx)) for k, v in input_arrays.items()}
+    return {k: (v if is_device(v) else to_device(v, ctx)) for k, v in input_arrays.items()}
 
 
 def _check_batch(arrs):
@@ -123,8 +123,8 @@ def train_eval_discriminator(input_arrays, g_model, d_model, d_optimizer=None, t
     dev = device_batch(input_arrays, g_model.ctx)
     n, h, w = _check_batch(dev)
     m = metrics if metrics is not None else _metrics_buffer(g_model.ctx)  # >= 8 floats on the device
-    _apply_config(g_model.ctx)
-    _lib.check(_lib.lib().dbm_discriminator_step(g_model._h, d_model._h, n, h, w, *[_dev_ptr(dev[k]) for k in _KEYS],
+    apply_config(g_model.ctx)
+    _lib.check(_lib.lib().dbm_discriminator_step(g_model._h, d_model._h, n, h, w, *[dev_ptr(dev[k]) for k in _KEYS],
                                                  int(bool(train)) | (2 if share_generator_forward else 0) |
                                                  (4 if prefetch_generator_forward else 0) |
                                                  (comm.step_flags(g_model.ctx) if hasattr(comm, "step_flags") else
@@ -154,9 +154,9 @@ def train_eval_generator(input_arrays, g_model, d_model, g_optimizer=None, train
     m = metrics if metrics is not None else _metrics_buffer(g_model.ctx)
     wts = (C.c_float * 4)(*LOSS_WEIGHTS)
     win = {"gaussian": 0, "uniform": 1}[global_config.ssim_window]
-    _apply_config(g_model.ctx)
+    apply_config(g_model.ctx)
     use_prefetched = _prefetch_tokens.pop(id(g_model), None) == _content_token(dev)
-    _lib.check(_lib.lib().dbm_generator_step(g_model._h, d_model._h, n, h, w, *[_dev_ptr(dev[k]) for k in _KEYS], wts,
+    _lib.check(_lib.lib().dbm_generator_step(g_model._h, d_model._h, n, h, w, *[dev_ptr(dev[k]) for k in _KEYS], wts,
                                              win, int(bool(train)) | (2 if share_generator_forward else 0) |
                                              (4 if use_prefetched else 0), m.ptr),
                g_model.ctx.handle)
@@ -221,7 +221,7 @@ def concat_examples(dataset, batch):
     out = {}
     idx = None
     for k, v in dataset.items():
-        if _is_device(v):
+        if is_device(v):
             if idx is None:
                 idx = np.ascontiguousarray(batch, dtype=np.int32)
                 if idx.size and (idx.min() < 0 or idx.max() >= len(v)):
@@ -238,7 +238,7 @@ def concat_examples(dataset, batch):
 
 def dataset_to_device(dataset, ctx=None):
     """`chainer.backend.cuda.to_gpu` over the five arrays of the DictDataset (srgan_train.py:107-121)."""
-    return {k: (v if _is_device(v) else to_device(v, ctx)) for k, v in dataset.items()}
+    return {k: (v if is_device(v) else to_device(v, ctx)) for k, v in dataset.items()}
 
 
 def split_dataset_random(dataset, first_size: int, seed=None):
@@ -312,9 +312,9 @@ def train_iteration(train_arrays, g_model, g_optimizer, d_model, d_optimizer, me
     m = metrics if metrics is not None else _metrics_buffer(g_model.ctx)
     wts = (C.c_float * 4)(*LOSS_WEIGHTS)
     win = {"gaussian": 0, "uniform": 1}[global_config.ssim_window]
-    _apply_config(g_model.ctx)
+    apply_config(g_model.ctx)
     _prefetch_tokens.pop(id(g_model), None)
-    _lib.check(_lib.lib().dbm_train_iteration(g_model._h, d_model._h, n, h, w, *[_dev_ptr(train_arrays[k]) for k in _KEYS], wts,
+    _lib.check(_lib.lib().dbm_train_iteration(g_model._h, d_model._h, n, h, w, *[dev_ptr(train_arrays[k]) for k in _KEYS], wts,
                                               win, _lib.ONE_GEN_FORWARD if share_generator_forward else 0, m.ptr), g_model.ctx.handle)
     d_optimizer.t += 1
     g_optimizer.t += 1
@@ -336,7 +336,7 @@ def train_minibatch(train_arrays, g_model, g_optimizer, d_model, d_optimizer, co
     comm_ok = comm is None or (hasattr(comm, "exchanges_in_step") and comm.exchanges_in_step(g_model.ctx)
                                and not getattr(comm, "sync_batch_stats", False))
     if (fused and (prefetch or share_generator_forward) and comm_ok and g_optimizer is not None and d_optimizer is not None
-            and all(_is_device(train_arrays[k]) for k in _KEYS)):
+            and all(is_device(train_arrays[k]) for k in _KEYS)):
         # ONE library call for the whole minibatch (dbm_train_iteration): the same numbers as the two calls below, bit for
         # bit, with the generator's backward pass scheduled underneath the discriminator's
         m = train_iteration(train_arrays, g_model, g_optimizer, d_model, d_optimizer, metrics=row,

@@ -418,3 +418,31 @@ def test_select_tiles(dbm, ctx):
     west, north = GEOM[0] - PX / 2, GEOM[1] + PX / 2
     c, rr = int(round((wins[0][0] - west) / PX)), int(round((north - wins[0][3]) / PX))
     assert np.array_equal(y[0, 0], grid[rr:rr + 36, c:c + 36])
+
+
+def test_device_array_of_every_dtype(dbm, ctx):
+    """The array type under the masks and every other resident plane (deepbedmap_amd/resident.py): set -> get is the identity on the
+    bits for each supported dtype, the sizes and the typestr follow the dtype, and `written()` -- what a stage calls after the library
+    wrote into an array -- moves training's content token of a batch that holds the array."""
+    from deepbedmap_amd import training
+
+    r = np.random.default_rng(7)
+    typestr = {np.float32: "<f4", np.float64: "<f8", np.int32: "<i4", np.uint8: "|u1"}
+    for dtype, want in typestr.items():
+        for shape in [(1,), (3, 5), (7, 1, 2)]:
+            host = r.integers(0, 2 ** 32, size=int(np.prod(shape)) * np.dtype(dtype).itemsize // 4 + 1, dtype=np.uint32)
+            host = host.view(np.uint8)[:int(np.prod(shape)) * np.dtype(dtype).itemsize].view(dtype).reshape(shape)   # any bits, NaNs too
+            a = dbm.DeviceArray(shape, ctx, dtype=dtype)
+            assert a.dtype == np.dtype(dtype) and a.shape == shape and a.nbytes == host.nbytes
+            assert a.__cuda_array_interface__["typestr"] == want and a.__cuda_array_interface__["data"] == (a.ptr, False)
+            got = a.set(host).get()
+            assert got.dtype == host.dtype and got.shape == shape and got.tobytes() == host.tobytes()
+    plain = dbm.DeviceArray((2, 2), ctx)
+    assert plain.dtype == np.float32 and plain.nbytes == 16 and plain.__cuda_array_interface__["typestr"] == "<f4"
+    mask = _pg.MaskArray((3, 5), ctx)
+    assert isinstance(mask, dbm.DeviceArray) and mask.dtype == np.uint8 and mask.nbytes == 15
+    batch = {k: dbm.DeviceArray((1,), ctx) for k in ("X", "W1", "W2", "W3", "Y")}
+    before = training._content_token(batch)
+    assert training._content_token(batch) == before
+    assert batch["W2"].written() is batch["W2"]
+    assert training._content_token(batch) != before
