@@ -205,6 +205,84 @@ int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes
   DBM_API_END
 }
 
+// ---- a float32 plane -> GeoTIFF blocks (tiff_encode.hip) ----
+int dbm_tiff_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sample_type, int block_h, int block_w, int tiled, int predictor,
+                    int compression, long first, int n_blocks, void* out_host, size_t out_capacity, size_t* sizes_host) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_tiff_encode: NULL context");
+  DBM_CHECK(plane_dev != nullptr, "dbm_tiff_encode: NULL plane");
+  check_plane("dbm_tiff_encode", H, W, 1, "H W must stay below 2^31 samples", "empty plane");
+  DBM_CHECK(sample_type == 1 || sample_type == 4, "dbm_tiff_encode: sample_type must be 1 (int16, by cast) or 4 (float32)");
+  const int bytes = sample_type == 1 ? 2 : 4;
+  DBM_CHECK(compression == 1 || compression == 5, "dbm_tiff_encode: compression must be 1 (raw bytes) or 5 (LZW)");
+  DBM_CHECK(predictor == 1 || predictor == 2, "dbm_tiff_encode: predictor must be 1 or 2");
+  DBM_CHECK(block_w >= 1 && block_h >= 1 && (long)block_w * block_h * bytes < (1L << 31), "dbm_tiff_encode: a block must hold 1..2^31 - 1 bytes");
+  DBM_CHECK(tiled != 0 || (block_w == W && block_h <= H), "dbm_tiff_encode: strips are W wide and at most H high");
+  const long blocks_x = (W + block_w - 1) / block_w, blocks_y = (H + block_h - 1) / block_h;
+  DBM_CHECK(first >= 0 && n_blocks >= 0 && first + (long)n_blocks <= blocks_x * blocks_y, "dbm_tiff_encode: the block range lies outside the image's " +
+                                                                                              std::to_string(blocks_x * blocks_y) + " blocks");
+  DBM_CHECK((long)n_blocks * block_h < (1L << 31), "dbm_tiff_encode: more than 2^31 block rows in one call");
+  DBM_CHECK(n_blocks == 0 || (out_host != nullptr && sizes_host != nullptr), "dbm_tiff_encode: NULL output or sizes");
+  const bool lzw = compression == 5;
+  const size_t block_bytes = (size_t)block_w * (size_t)block_h * (size_t)bytes;
+  const size_t slot_cap = block_bytes * 3 / 2 + 64;   // dbm_lzw_encode_tiles' bound
+  const size_t worst = lzw ? slot_cap : block_bytes;
+  DBM_CHECK(out_capacity / ((worst + 1) & ~(size_t)1) >= (size_t)n_blocks, "dbm_tiff_encode: the output holds " + std::to_string(out_capacity) +
+                                                                                " bytes, the worst case of " + std::to_string(n_blocks) + " blocks is " +
+                                                                                std::to_string((size_t)n_blocks * ((worst + 1) & ~(size_t)1)));
+  if (n_blocks == 0) return 0;
+  TiffEncodeLaunch a;
+  a.plane = plane_dev;
+  a.H = H; a.W = W;
+  a.sample_type = sample_type; a.bytes = bytes;
+  a.block_h = block_h; a.block_w = block_w; a.tiled = tiled != 0;
+  a.predictor = predictor;
+  a.first = first; a.blocks_x = blocks_x; a.n_blocks = n_blocks;
+  a.raw_stride = (long)((block_bytes + 15) / 16 * 16);
+  a.slot_cap = slot_cap;
+  ScopedBuf raw, slots, words, packed;   // this call's own, released on every path
+  const size_t nb = (size_t)n_blocks;
+  a.raw = raw.as<uint8_t>(nb * (size_t)a.raw_stride);
+  // per block: the encoder's {size, status word} (8 bytes), then the packer's {offset, size} (16 bytes)
+  a.result = (uint32_t*)words.as<uint8_t>(nb * 24);
+  unsigned long long* table_dev = (unsigned long long*)((uint8_t*)words.p + nb * 8);
+  launch_tiff_blocks(a, ctx->stream);
+  std::vector<unsigned long long> table(2 * nb);
+  if (lzw) {
+    a.slots = slots.as<uint8_t>(nb * slot_cap);
+    launch_tiff_lzw_encode(a, ctx->stream);
+    std::vector<uint32_t> result(2 * nb);
+    DBM_HIP(hipMemcpyAsync(result.data(), a.result, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t b = 0; b < nb; ++b) {
+      if (result[2 * b + 1] != 0 || result[2 * b] == 0 || result[2 * b] > slot_cap)
+        throw DbmError(12, "dbm_tiff_encode: block " + std::to_string(first + (long)b) + ": its LZW stream does not fit the slot of " +
+                               std::to_string(slot_cap) + " bytes; nothing of this call was written");
+      table[2 * b + 1] = result[2 * b];
+    }
+  } else {
+    a.slots = nullptr;
+    for (size_t b = 0; b < nb; ++b) {
+      const long by = (first + (long)b) / blocks_x, left = H - by * block_h;
+      const long rows = a.tiled || left > block_h ? (long)block_h : left;
+      table[2 * b + 1] = (unsigned long long)rows * (unsigned long long)block_w * (unsigned long long)bytes;
+    }
+  }
+  size_t total = 0;   // even-aligned offsets: TIFF wants its blocks on word boundaries
+  for (size_t b = 0; b < nb; ++b) {
+    table[2 * b] = total;
+    total += (size_t)((table[2 * b + 1] + 1ull) & ~1ull);
+  }
+  DBM_CHECK(total <= out_capacity, "dbm_tiff_encode: the streams outgrow the output");   // (implied by the worst-case check)
+  uint8_t* packed_dev = packed.as<uint8_t>(total + 16);
+  DBM_HIP(hipMemcpyAsync(table_dev, table.data(), nb * 16, hipMemcpyHostToDevice, ctx->stream));
+  launch_tiff_pack(lzw ? a.slots : a.raw, lzw ? slot_cap : (size_t)a.raw_stride, table_dev, n_blocks, packed_dev, ctx->stream);
+  DBM_HIP(hipMemcpyAsync(out_host, packed_dev, total, hipMemcpyDeviceToHost, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
+  for (size_t b = 0; b < nb; ++b) sizes_host[b] = (size_t)table[2 * b + 1];
+  DBM_API_END
+}
+
 int dbm_grid_rescale(dbm_ctx* ctx, const float* in_dev, long H, long W, long out_h, long out_w, int order, int anti_aliasing, int clip,
                      int input_cast, float* out_dev) {
   DBM_API_BEGIN(ctx)

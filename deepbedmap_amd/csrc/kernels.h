@@ -313,6 +313,41 @@ void launch_tiff_rows(const TiffDecodeLaunch& a, hipStream_t s);
 // lzw_decode_lanes with one lane on the host: the decoded size or (size_t)-1 (tools/lzw_twin_check.cpp compares it with dbm_lzw_decode)
 size_t tiff_lzw_decode_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
 
+// numpy.ndarray.astype(int16) of a float32 on x86-64: truncation to int32 (cvttss2si: NaN and |x| >= 2^31 give INT32_MIN), then the low
+// 16 bits -- NaN (the canvas frame that no tile covers), +-inf and out-of-range values become 0.  The one cast of f32_to_i16_kernel
+// (tiff_lzw.hip) and tiff_blocks_kernel (tiff_encode.hip).
+__device__ inline short dbm_cast_i16(float x) {
+  const int v = (x == x && x > -2147483648.f && x < 2147483648.f) ? (int)x : (int)0x80000000;
+  return (short)(v & 0xffff);
+}
+
+// A float32 plane -> the blocks (strips or tiles) of a GeoTIFF (tiff_encode.hip; dbm_tiff_encode).  The call's blocks are first ..
+// first + n_blocks - 1 of the image, row-major over blocks_x columns of blocks.  launch_tiff_blocks writes block b's raw bytes (cast,
+// padding, predictor) at raw + b * raw_stride; launch_tiff_lzw_encode encodes them into slots + b * slot_cap (slot_cap bytes of room)
+// and writes result[2 b] = the stream's size, result[2 b + 1] = its status word (1: it did not fit; size 0); launch_tiff_pack copies
+// n_blocks streams (block b at src + b * src_stride; table = {offset in packed, size} per block, on the device) to their offsets.
+struct TiffEncodeLaunch {
+  const float* plane;
+  long H, W;
+  int sample_type;             // 1 int16 (by cast), 4 float32 (the bits): dbm_tiff_decode's numbering
+  int bytes;                   // bytes per sample
+  int block_h, block_w, tiled; // tiled: blocks are whole (zero padded); else strips of block_w == W, the last one short
+  int predictor;               // 1 none, 2 horizontal differencing
+  long first, blocks_x;
+  int n_blocks;
+  uint8_t* raw;
+  long raw_stride;             // a multiple of 16, >= block_h * block_w * bytes
+  uint8_t* slots;
+  size_t slot_cap;
+  uint32_t* result;
+};
+void launch_tiff_blocks(const TiffEncodeLaunch& a, hipStream_t s);
+void launch_tiff_lzw_encode(const TiffEncodeLaunch& a, hipStream_t s);
+void launch_tiff_pack(const uint8_t* src, size_t src_stride, const unsigned long long* table, int n_blocks, uint8_t* packed, hipStream_t s);
+// lzw_encode_lanes with one lane on the host: the encoded size, or 0 if cap is too small (tools/lzw_encode_twin_check.cpp compares it
+// with dbm_lzw_encode_tiles)
+size_t tiff_lzw_encode_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
+
 // Fully filled windows of a raster (tile.hip; dbm_grid_filled_windows): flags[uly * nx + ulx] = 1 iff no node of rows [uly step, uly step
 // + size) x columns [ulx step, ulx step + size) is NaN, rows counted from the north (flip_rows: raster row 0 is the south edge), columns
 // from the west (flip_cols).  rowany: rows * nx bytes of scratch.  filled_windows_geometry fills ny, nx, rows, nw, nseg from H, W,

@@ -129,11 +129,7 @@ size_t lzw_decode_one(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
 
 __global__ __launch_bounds__(256) void f32_to_i16_kernel(const float* __restrict__ src, short* __restrict__ dst, long n) {
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-    const float x = src[e];
-    // numpy.ndarray.astype(int16) on x86-64: truncation to int32 (cvttss2si: NaN and |x| >= 2^31 give INT32_MIN), then
-    // the low 16 bits -- NaN (the canvas frame that no tile covers), +-inf and out-of-range values become 0
-    const int v = (x == x && x > -2147483648.f && x < 2147483648.f) ? (int)x : (int)0x80000000;
-    dst[e] = (short)(v & 0xffff);
+    dst[e] = dbm_cast_i16(src[e]);   // numpy.ndarray.astype(int16): kernels.h
   }
 }
 

@@ -7,7 +7,9 @@ container is written here (classic TIFF or BigTIFF, little endian, 256 x 256 til
 tags ModelPixelScale / ModelTiepoint / GeoKeyDirectory with ProjectedCSType = EPSG:3031, GDAL_NODATA), the LZW streams come
 from libdbm (dbm_lzw_encode_tiles: TIFF 6.0 LZW, host threads over tiles) and the int16 cast of a device-resident canvas
 from the GPU (dbm_f32_to_i16: NumPy's astype semantics, NaN frame -> 0).  `read_geotiff` decodes the file again
-(bit-exact round trip; the tests also decode it with Pillow / libtiff).
+(bit-exact round trip; the tests also decode it with Pillow / libtiff).  `write_geotiff_resident` writes the same file from a plane in
+HBM without downloading it: cast, tile cutting, predictor 2 and LZW run on the GPU (dbm_tiff_encode), only the streams
+cross PCIe; both writers share the tags (`_image_tags`) and the container (`_write_container`).
 
 Reading rasters as GDAL and libtiff write them (reference data_prep.py:668, :845-877; deepbedmap.py:164-204, through rasterio): the
 second half of this file -- `open_geotiff` (header, geometry, block plan, refusals: host), `read_geotiff_resident` (the blocks decoded on
@@ -95,55 +97,28 @@ def _epsg_of(crs):
                      "PROJ string of the reference (EPSG:3031)")
 
 
-def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=EPSG_ANTARCTIC_POLAR_STEREOGRAPHIC, dtype=None,
-                       nodataval=-2000, tiled=False, compression="none", bigtiff=True, nthreads=None):
-    """data_prep.py:779-834 without rasterio: writes `{outfilepath}.tif` and returns its path.
+_OFFSETS, _COUNTS = object(), object()   # tag values that `_write_container` fills in: where it put the streams, and their sizes
 
-    window_bound = (minx, miny, maxx, maxy); array is CHW with one channel (a NumPy array, or a DeviceArray canvas when
-    dtype is int16); compression "none" or "lzw" (rasterio.enums.Compression values); tiled=False writes one strip per
-    row block of 256 rows."""
-    if save_netcdf:
-        raise NotImplementedError("NetCDF output (xarray) is outside this framework; convert the GeoTIFF with GDAL")
-    assert len(array.shape) == 3 and array.shape[0] == 1  # one band, CHW (data_prep.py:800-801)
-    dt = np.dtype(dtype if dtype is not None else getattr(array, "dtype", np.float32))
-    if dt == np.int16 and not isinstance(array, np.ndarray):
-        band = canvas_to_int16(array)[0]
-    else:
-        band = np.asarray(array)[0]
-        if band.dtype != dt:
-            with np.errstate(invalid="ignore"):
-                band = band.astype(dt)
-    band = np.ascontiguousarray(band.astype(dt.newbyteorder("<"), copy=False))
-    H, W = band.shape
-    if dt.kind == "f":
-        sample_format = 3
-    elif dt.kind == "i":
-        sample_format = 2
-    elif dt.kind == "u":
-        sample_format = 1
-    else:
-        raise ValueError(f"unsupported dtype {dt}")
-    epsg = _epsg_of(crs)
-    th, tw = (TILE, TILE) if tiled else (min(TILE, H), W)
-    blocks, ny, nx = _tiles_of(band, th, tw)
-    raw = blocks.reshape(len(blocks), -1).view(np.uint8)
-    # strips: the last one holds only the rows that exist (TIFF 6.0: StripByteCounts of H % RowsPerStrip rows, what GDAL
-    # writes); tiles are always whole (zero padded)
-    last_rows = H - (ny - 1) * th
-    short_last = (not tiled) and last_rows < th
-    if str(compression).lower() == "lzw":
-        if short_last:
-            streams = lzw_encode_tiles(raw[:-1], nthreads) if ny > 1 else []
-            streams += lzw_encode_tiles(np.ascontiguousarray(raw[-1:, :last_rows * tw * dt.itemsize]), nthreads)
-        else:
-            streams = lzw_encode_tiles(raw, nthreads)
-        comp = 5
-    elif str(compression).lower() in ("none", "1"):
-        streams, comp = [r.tobytes() for r in raw], 1
-        if short_last:
-            streams[-1] = streams[-1][:last_rows * tw * dt.itemsize]
-    else:
-        raise ValueError(f"unsupported compression {compression!r} (none, lzw)")
+
+def _predictor_of(predictor, who):
+    if isinstance(predictor, (bool, np.bool_)) or predictor not in (1, 2):
+        raise ValueError(f"{who}: predictor {predictor!r}: 1 (none) or 2 (horizontal differencing) are written")
+    return int(predictor)
+
+
+def _compression_of(compression, who):
+    """TIFF Compression (259) of the `compression` argument: 1 or 5."""
+    text = str(compression).lower()
+    if text == "lzw":
+        return 5
+    if text in ("none", "1"):
+        return 1
+    raise ValueError(f"{who}: unsupported compression {compression!r} (none, lzw)")
+
+
+def _image_tags(H, W, dt, comp, predictor, tiled, th, tw, window_bound, nodataval, epsg, bigtiff):
+    """The image directory both writers share: (tag, type, values) with _OFFSETS / _COUNTS where the block tables go."""
+    sample_format = {"f": 3, "i": 2, "u": 1}[dt.kind]
     minx, miny, maxx, maxy = (float(v) for v in window_bound)
     px, py = (maxx - minx) / W, (maxy - miny) / H  # rasterio.transform.from_bounds
     nodata = (repr(int(nodataval)) if float(nodataval).is_integer() else repr(float(nodataval))).encode() + b"\0"
@@ -154,20 +129,28 @@ def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=
         (284, 3, [1]), (339, 3, [sample_format]),
         (33550, 12, [px, py, 0.0]), (33922, 12, [0.0, 0.0, 0.0, minx, maxy, 0.0]), (34735, 3, geokeys), (42113, 2, [nodata]),
     ]
+    if predictor != 1:
+        tags += [(317, 3, [predictor])]
     if tiled:
-        tags += [(322, 4, [tw]), (323, 4, [th]), (324, off_t, None), (325, off_t, [len(s) for s in streams])]
+        tags += [(322, 4, [tw]), (323, 4, [th]), (324, off_t, _OFFSETS), (325, off_t, _COUNTS)]
     else:
-        tags += [(278, 4, [th]), (273, off_t, None), (279, off_t, [len(s) for s in streams])]
-    tags.sort(key=lambda t: t[0])
-    path = f"{outfilepath}.tif"
+        tags += [(278, 4, [th]), (273, off_t, _OFFSETS), (279, off_t, _COUNTS)]
+    return tags
+
+
+def _write_container(path, bigtiff, tags, streams):
+    """The file both writers share: the header, then the streams (any iterable of bytes-like objects, taken one at a time) at even
+    offsets, then the image directory with its tags sorted and the values that do not fit an entry behind it."""
+    tags = sorted(tags, key=lambda t: t[0])
     with open(path, "wb") as f:
         # header, then the pixel data, then the IFD (offsets known by then)
         f.write(struct.pack("<2sHHHQ", b"II", 43, 8, 0, 0) if bigtiff else struct.pack("<2sHI", b"II", 42, 0))
-        offsets = []
+        offsets, counts = [], []
         for s in streams:
             if f.tell() % 2:
                 f.write(b"\0")
             offsets.append(f.tell())
+            counts.append(len(s))
             f.write(s)
         if f.tell() % 2:
             f.write(b"\0")
@@ -185,8 +168,10 @@ def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=
         ifd_size = (8 + 20 * ntags + 8) if bigtiff else (2 + 12 * ntags + 4)
         extra_pos = ifd_pos + ifd_size
         for tag, typ, vals in tags:
-            if vals is None:
+            if vals is _OFFSETS:
                 vals = offsets
+            elif vals is _COUNTS:
+                vals = counts
             data = payload(typ, vals)
             count = len(data) if typ == 2 else len(vals)
             if len(data) <= inline:
@@ -203,8 +188,143 @@ def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=
     return path
 
 
+def _difference_blocks(blocks):
+    """Predictor 2 (libtiff's horizontal differencing) of blocks (n, rows, cols): per block row d[0] = s[0], d[c] = s[c] - s[c - 1] over
+    the whole row, padding columns included, wrapping in the sample's own width (floats: on the bit patterns)."""
+    u = np.ascontiguousarray(blocks).view(np.dtype("<u%d" % blocks.dtype.itemsize))
+    d = u.copy()
+    d[..., 1:] = u[..., 1:] - u[..., :-1]
+    return d.view(blocks.dtype)
+
+
+def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=EPSG_ANTARCTIC_POLAR_STEREOGRAPHIC, dtype=None,
+                       nodataval=-2000, tiled=False, compression="none", bigtiff=True, nthreads=None, predictor=1):
+    """data_prep.py:779-834 without rasterio: writes `{outfilepath}.tif` and returns its path.
+
+    window_bound = (minx, miny, maxx, maxy); array is CHW with one channel (a NumPy array, or a DeviceArray canvas when
+    dtype is int16); compression "none" or "lzw" (rasterio.enums.Compression values); tiled=False writes one strip per
+    row block of 256 rows.  predictor=2 (with "lzw"; libtiff's predictors are part of its codecs, so "none" writes the samples
+    as they are and no tag): every block row is differenced on the host before it is encoded, and Predictor (317) = 2 is written."""
+    if save_netcdf:
+        raise NotImplementedError("NetCDF output (xarray) is outside this framework; convert the GeoTIFF with GDAL")
+    assert len(array.shape) == 3 and array.shape[0] == 1  # one band, CHW (data_prep.py:800-801)
+    predictor = _predictor_of(predictor, "save_array_to_grid")
+    dt = np.dtype(dtype if dtype is not None else getattr(array, "dtype", np.float32))
+    if dt == np.int16 and not isinstance(array, np.ndarray):
+        band = canvas_to_int16(array)[0]
+    else:
+        band = np.asarray(array)[0]
+        if band.dtype != dt:
+            with np.errstate(invalid="ignore"):
+                band = band.astype(dt)
+    band = np.ascontiguousarray(band.astype(dt.newbyteorder("<"), copy=False))
+    H, W = band.shape
+    if dt.kind not in "fiu":
+        raise ValueError(f"unsupported dtype {dt}")
+    epsg = _epsg_of(crs)
+    comp = _compression_of(compression, "save_array_to_grid")
+    if comp == 1:
+        predictor = 1
+    th, tw = (TILE, TILE) if tiled else (min(TILE, H), W)
+    blocks, ny, nx = _tiles_of(band, th, tw)
+    if predictor == 2:
+        blocks = _difference_blocks(blocks)
+    raw = blocks.reshape(len(blocks), -1).view(np.uint8)
+    # strips: the last one holds only the rows that exist (TIFF 6.0: StripByteCounts of H % RowsPerStrip rows, what GDAL
+    # writes); tiles are always whole (zero padded)
+    last_rows = H - (ny - 1) * th
+    short_last = (not tiled) and last_rows < th
+    if comp == 5:
+        if short_last:
+            streams = lzw_encode_tiles(raw[:-1], nthreads) if ny > 1 else []
+            streams += lzw_encode_tiles(np.ascontiguousarray(raw[-1:, :last_rows * tw * dt.itemsize]), nthreads)
+        else:
+            streams = lzw_encode_tiles(raw, nthreads)
+    else:
+        streams = [r.tobytes() for r in raw]
+        if short_last:
+            streams[-1] = streams[-1][:last_rows * tw * dt.itemsize]
+    tags = _image_tags(H, W, dt, comp, predictor, tiled, th, tw, window_bound, nodataval, epsg, bigtiff)
+    return _write_container(f"{outfilepath}.tif", bigtiff, tags, streams)
+
+
+def write_geotiff_resident(outfilepath, window_bound, array, dtype=None, nodataval=-2000, tiled=True, compression="lzw", predictor=1,
+                           bigtiff=True, crs=EPSG_ANTARCTIC_POLAR_STEREOGRAPHIC, workspace_limit=None):
+    """The mirror of `read_geotiff_resident`: writes `{outfilepath}.tif` from a plane that lives in HBM and returns its path.  The cast
+    to int16 (NumPy's `astype`), the cutting of tiles or strips, predictor 2 and TIFF 6.0 LZW (one wavefront per block) run on the GPU
+    (dbm_tiff_encode); only the encoded streams cross PCIe.  The file is byte for byte the one `save_array_to_grid` writes from the
+    downloaded plane with the same arguments.
+
+    array: a float32 DeviceArray of shape (1, H, W) or (H, W), or a resident Raster; dtype int16 or float32 (the default);
+    compression "lzw" or "none" (the samples as they are: as in save_array_to_grid the predictor then has no effect); predictor 1 or
+    2.  workspace_limit: bytes of raw blocks plus stream slots per batch (default 1 GiB; one block always goes through).  Anything
+    else raises a ValueError that names the argument, before any device work."""
+    who = "write_geotiff_resident"
+    from .tiling import Raster
+
+    if isinstance(array, Raster):
+        if array._dev is None:
+            raise ValueError(f"{who}: array: the Raster is not resident (a NumPy raster is written by save_array_to_grid)")
+        array = array._dev
+    if not isinstance(array, DeviceArray):
+        raise ValueError(f"{who}: array must be a float32 DeviceArray or a resident Raster, not {type(array).__name__} "
+                         "(a NumPy array is written by save_array_to_grid)")
+    if array.dtype != np.float32:
+        raise ValueError(f"{who}: array holds {array.dtype.name}: only float32 planes are written")
+    shape = tuple(array.shape)
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[0] == 1)) or shape[-2] < 1 or shape[-1] < 1:
+        raise ValueError(f"{who}: array must be (1, H, W) or (H, W) and not empty; got {shape}")
+    H, W = shape[-2], shape[-1]
+    try:
+        dt = np.dtype(np.float32 if dtype is None else dtype)
+    except TypeError:
+        raise ValueError(f"{who}: dtype {dtype!r} is not a sample type") from None
+    if dt not in (np.dtype(np.int16), np.dtype(np.float32)):
+        raise ValueError(f"{who}: dtype {dt.name}: int16 (by cast) and float32 are written")
+    predictor = _predictor_of(predictor, who)
+    comp = _compression_of(compression, who)
+    if comp == 1:
+        predictor = 1
+    epsg = _epsg_of(crs)
+    if workspace_limit is None:
+        workspace_limit = WORKSPACE_DEFAULT
+    workspace_limit = int(workspace_limit)
+    if workspace_limit < 1:
+        raise ValueError(f"{who}: workspace_limit must be positive")
+    th, tw = (TILE, TILE) if tiled else (min(TILE, H), W)
+    block_bytes = th * tw * dt.itemsize
+    if block_bytes >= 1 << 31:
+        raise ValueError(f"{who}: array: blocks of {th} x {tw} samples hold 2^31 bytes or more")
+    ny, nx = -(-H // th), -(-W // tw)
+    nblocks = ny * nx
+    worst = block_bytes * 3 // 2 + 64 if comp == 5 else block_bytes   # a block's bytes in the download, before rounding up to even
+    per_batch = max(1, min(workspace_limit // (block_bytes + (worst if comp == 5 else 0)), ((1 << 31) - 1) // th, nblocks))
+    sample_type = 1 if dt == np.int16 else 4
+    ctx = array.ctx
+
+    def streams():
+        out = np.empty(per_batch * ((worst + 1) & ~1), dtype=np.uint8)
+        sizes = np.zeros(per_batch, dtype=np.uintp)
+        view = memoryview(out)
+        for first in range(0, nblocks, per_batch):
+            n = min(per_batch, nblocks - first)
+            ctx.call("dbm_tiff_encode", devptr(array), H, W, sample_type, th, tw, 1 if tiled else 0, predictor, comp, first, n, devptr(out),
+                     out.size, devptr(sizes))
+            pos = 0
+            for k in range(n):
+                size = int(sizes[k])
+                yield view[pos:pos + size]
+                pos += (size + 1) & ~1
+
+    tags = _image_tags(H, W, dt, comp, predictor, bool(tiled), th, tw, window_bound, nodataval, epsg, bigtiff)
+    return _write_container(f"{outfilepath}.tif", bool(bigtiff), tags, streams())
+
+
 def read_geotiff(path):
-    """Decodes a file written by save_array_to_grid.  Returns (array (1, H, W), info dict with the GeoTIFF tags)."""
+    """Decodes a file written by save_array_to_grid or write_geotiff_resident.  Returns (array (1, H, W), info dict with the GeoTIFF
+    tags).  Predictor 2 is undone in the package's own files, recognised by the directory its writers always write (ModelPixelScale,
+    ModelTiepoint, GeoKeyDirectory and GDAL_NODATA all present).  In any other file the Predictor tag is ignored, as it always was
+    (tests/test_geotiff_open_host.py pins that): files of other writers are read by open_geotiff / read_geotiff_resident."""
     with open(path, "rb") as f:
         buf = f.read()
     big = struct.unpack_from("<H", buf, 2)[0] == 43
@@ -229,12 +349,18 @@ def read_geotiff(path):
         tw, th, offs, cnts = W, tags[278][0], tags[273], tags[279]
     ny, nx = (H + th - 1) // th, (W + tw - 1) // tw
     out = np.zeros((ny * th, nx * tw), dtype=dt)
-    nbytes = th * tw * dt.itemsize
+    own = all(t in tags for t in (33550, 33922, 34735, 42113))   # the directory of _image_tags
+    predictor = tags.get(317, [1])[0] if own and comp == 5 else 1   # (without effect on uncompressed data)
+    assert predictor in (1, 2), predictor
     for i, (o, c) in enumerate(zip(offs, cnts)):
         ty, tx = divmod(i, nx)
         rows = th if 322 in tags else min(th, H - ty * th)  # (the last strip holds only the rows that exist)
         raw = lzw_decode(buf[o:o + c], rows * tw * dt.itemsize) if comp == 5 else np.frombuffer(buf[o:o + c], dtype=np.uint8)
-        out[ty * th:ty * th + rows, tx * tw:(tx + 1) * tw] = raw.view(dt).reshape(rows, tw)
+        block = raw.view(dt).reshape(rows, tw)
+        if predictor == 2:   # a running sum along the row, wrapping in the sample's own width (floats: on the bit patterns)
+            u = np.dtype("<u%d" % dt.itemsize)
+            block = np.cumsum(block.view(u), axis=1, dtype=u).view(dt)
+        out[ty * th:ty * th + rows, tx * tw:(tx + 1) * tw] = block
     info = {"pixel_scale": tags.get(33550), "tiepoint": tags.get(33922), "geokeys": tags.get(34735),
             "nodata": tags.get(42113, b"").rstrip(b"\0").decode(), "bigtiff": big, "compression": comp, "tile": (th, tw)}
     return out[None, :H, :W], info

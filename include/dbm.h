@@ -21,7 +21,9 @@
  *     was last cleared, the arena may hold the sums of a void pass -- it returns status 9, applies nothing, and the caller clears
  *     the gradients and repeats forward + backward before updating (the step entry points clear them themselves).  Status 8:
  *     the same in a data-parallel run, where a local retry cannot keep the replicas identical -- fatal, abort the job.  Status 10
- *     (dbm_grid_tension_surface only): the solve did not converge within max_iter; the output holds the last iterate;
+ *     (dbm_grid_tension_surface only): the solve did not converge within max_iter; the output holds the last iterate.  Status 11
+ *     (dbm_tiff_decode only): a block's LZW stream is malformed.  Status 12 (dbm_tiff_encode only): a block's LZW stream did not fit
+ *     its slot (the guard of the device encoder; it cannot occur with the slot the call allocates);
  *   - tensors are NCHW float32, C-contiguous; weights OIHW, exactly the arrays stored by
  *     chainer.serializers.save_npz (key layout: SURVEY.md Appendix B);
  *   - pointers are HOST pointers unless flags contains DBM_DEVICE_PTRS, in which case they are
@@ -561,6 +563,33 @@ int dbm_lzw_decode(const void* src, size_t nbytes, void* dst, size_t cap, size_t
  * n_blocks > 0, bytes outside streams_host, rows outside 1..block_h, decoded bytes misaligned or short.  n_blocks = 0 succeeds. */
 int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host, int n_blocks, int compression,
                     int predictor, int sample_type, int block_w, int block_h, float* out_dev, long out_h, long out_w);
+
+/* ---- writing the DEM from HBM: GeoTIFF blocks encoded on the device (deepbedmap.py:749-756: `save_array_to_grid(array=
+ * Y_hat.astype(np.int16), dtype=np.int16, tiled=True, compression=lzw)` -> data_prep.py:779-834, a tiled LZW GeoTIFF written by rasterio
+ * / GDAL; the container, its tags and the batching stay with the host shim deepbedmap_amd/geotiff.py: write_geotiff_resident) ----
+ * dbm_tiff_encode turns blocks first .. first + n_blocks - 1 (row-major over the image's blocks) of the float32 plane plane_dev (H, W),
+ * ALWAYS a device pointer, into their bytes as a TIFF holds them and downloads only those.
+ * sample_type (dbm_tiff_decode's numbering) 1: int16 by the cast of dbm_f32_to_i16 (NumPy's astype: truncation, NaN / inf / |x| >= 2^31
+ * -> 0); 4: float32, the bits (NaN payloads kept).  Little endian.
+ * tiled != 0: blocks of block_h x block_w are whole, positions right of or below the plane are zero bytes; tiled == 0: strips,
+ * block_w == W, the last strip holds only the rows that exist.
+ * predictor (TIFF tag 317) 1: none; 2: horizontal differencing per block row in the sample's own width, wrapping (int16: on uint16;
+ * float32: on the 32-bit patterns): d[0] = s[0], d[c] = s[c] - s[c - 1] over the block's row including its padding columns -- the
+ * inverse of what dbm_tiff_decode undoes.
+ * compression 5: every block becomes a TIFF 6.0 LZW stream, byte for byte the one dbm_lzw_encode_tiles writes for the same bytes,
+ * encoded by one wavefront per block; compression 1: the bytes themselves (predictor applied as asked: the caller decides).
+ * out_host (HOST, out_capacity bytes) receives the blocks one behind the other, each at the next even offset from 0 (an odd block is
+ * followed by one zero byte); sizes_host (HOST) the n_blocks sizes.  out_capacity must cover the worst case: n_blocks times
+ * block_h * block_w * bytes * 3 / 2 + 64 (compression 5) or block_h * block_w * bytes (compression 1), each rounded up to even.
+ * The call allocates its workspace (per block: the raw block rounded up to 16, 24 bytes of bookkeeping, for LZW the slot of the worst
+ * case; plus the packed streams), frees it on every path and synchronises the context's stream; the caller bounds it by batching.
+ * Status 12: a block's LZW stream did not fit its slot; the message names the block and nothing of this call was written.  It cannot
+ * occur with the slot above (incompressible bytes grow by a factor of about 1.41) and is there as the guard of the device loop.
+ * Refused (status 1, nothing launched): NULL pointers, an empty plane or H * W >= 2^31, sample_type not 1 or 4, compression not 1 or 5,
+ * predictor not 1 or 2, block_w or block_h < 1, a block of 2^31 bytes or more, strips that are not W wide, a block range outside the
+ * image, n_blocks * block_h >= 2^31, out_capacity below the worst case.  n_blocks = 0 succeeds. */
+int dbm_tiff_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sample_type, int block_h, int block_w, int tiled, int predictor,
+                    int compression, long first, int n_blocks, void* out_host, size_t out_capacity, size_t* sizes_host);
 
 /* One minibatch of `trainer` (srgan_train.py:1286-1309) as ONE call: train_eval_discriminator (:1084-1166) with its
  * optimizer update, then train_eval_generator (:1170-1263) with its update; both optimizers must have been set up
