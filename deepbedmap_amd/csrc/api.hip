@@ -1511,6 +1511,8 @@ int dbm_op_deform_conv2d_backward(dbm_ctx* ctx, const float* x, const float* off
     cws.ensure(deform_csr_workspace_floats(N, H, W));
     xt.ensure((size_t)N * C * P);
     launch_nchw_to_nhwc64(x, xt.p, N, (int)P, s);
+  } else {
+    cws.ensure(deform_backward_workspace_floats(N, C, H, W));
   }
   if (!(f.bwd_fused && O == 1)) {   // (what a retained forward leaves for the forms that read the sample matrix)
     col.ensure((size_t)N * C * 9 * P);

@@ -59,7 +59,7 @@ void deform1_backward(const DeformForms& f, const float* x, const float* xt, con
     launch_deform_input_grad(off, nullptr, w, gy, gx, N, C, H, W, offsn, s, csr_ws, lists_built);
   } else {
     // (the weight gradient only needs gy and the sample matrix: the generator runs it on its side stream, underneath the sampler's backward)
-    launch_deform_backward(x, off, nullptr, w, gy, gx, goff, N, C, H, W, offsn, s);
+    launch_deform_backward(x, off, nullptr, w, gy, gx, goff, N, C, H, W, offsn, s, csr_ws);
     launch_gemv_cols_wgrad(col, gy, gw, gb, N, C * 9, (int)P, s_wgrad);
   }
 }
@@ -74,7 +74,7 @@ void deform64_backward_data(const dbm_model& m, const IgLayer& L, const DeformFo
     launch_deform_input_grad(off, gcol, nullptr, nullptr, gx, N, L.C, H, W, offsn, s, csr_ws, lists_built);
   } else {
     m.run_dgrad(L, dbm_model::dgrad_desc(gy, L.O * P, gcol, L.C * 9 * P, N), H, W, s);
-    launch_deform_backward(x, off, gcol, nullptr, nullptr, gx, goff, N, L.C, H, W, offsn, s);
+    launch_deform_backward(x, off, gcol, nullptr, nullptr, gx, goff, N, L.C, H, W, offsn, s, csr_ws);
   }
 }
 

@@ -568,6 +568,7 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
     if (f2.premul_bwd && z2) ws.gt2.ensure((size_t)N * 9 * P4);
   } else {
     // (its weight gradient only needs gy and the retained columns: side stream, underneath the sampler's backward)
+    ws.csr_ws.ensure(deform_backward_workspace_floats(N, 64, H4, W4));
     ctx->fork_to_side(5);
   }
   deform1_backward(f2, ws.a51.p, ws.a51t.p, ws.off2.p, 32 * P4, P(T_def2W), gy, z2, ws.col2.p, ws.g_a51.p, ws.goff2.p, G(T_def2W), G(T_def2b),

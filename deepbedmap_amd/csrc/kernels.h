@@ -39,7 +39,9 @@ void launch_im2col(const float* x, float* col, int N, int Cin, int Hin, int Win,
                    int KP, hipStream_t s);
 void launch_deform_sample(const float* x, const float* off, float* col, int N, int C, int H, int W, long offsn, hipStream_t s);
 void launch_deform_backward(const float* x, const float* off, const float* gcol, const float* w1o, const float* gy,
-                            float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s);
+                            float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s, float* ws);
+// the floats of list workspace `ws` it needs (0: none; in deterministic mode a plane past its LDS kernels sorts its lists in global memory)
+size_t deform_backward_workspace_floats(int N, int C, int H, int W);
 // sampler fused into the GEMM (deform_fused.hip): no column matrix.  C == 64, O == 64 (w = packed [576][64] image) or 1 (w = OIHW).
 // xt = the layer input channels-last (N * H * W, 64); yt (optional, O == 64) = the output channels-last as well;
 // colout (optional, O == 64) = the sample matrix (N, 576, H, W) as a by-product (a retained pass: the weight gradient reads it)

@@ -545,13 +545,33 @@ __global__ __launch_bounds__(256) void deform_goff_kernel(const float* __restric
   gn[(long)(9 + t) * plane + p] = g.mv ? gv : 0.f;
 }
 
+template <int NT>
+__global__ void deform_csr_build_global_kernel(const float* __restrict__ off, int* g_offs, int2* g_ent, int* g_cur, int H, int W, long offsn);
+template <int CH, int NT>
+__global__ void deform_csr_gather_kernel(const int* __restrict__ g_offs, const int2* __restrict__ g_ent, const float* __restrict__ gcol,
+                                         const float* __restrict__ w1o, const float* __restrict__ gy, float* __restrict__ gx, int C, int plane);
+
+// (the plane fits the kernels that keep the sampling lists of one (image, tap) and two groups of eight channel planes in LDS)
+static bool deform_backward_lds_ok(int C, long plane) {
+  return C % 8 == 0 && sizeof(float) * ((size_t)2 * 8 * plane + 10 * plane + 1) <= 150 * 1024;
+}
+
+// Floats of list workspace launch_deform_backward needs (0: none): in deterministic mode a plane past the LDS kernels builds its
+// sampling lists in global memory -- deform_csr_workspace_floats for the lists, then the fill cursors.
+size_t deform_backward_workspace_floats(int N, int C, int H, int W) {
+  const long plane = (long)H * W;
+  if (!g_wgrad_deterministic || C % 8 != 0 || deform_backward_lds_ok(C, plane)) return 0;
+  return deform_csr_workspace_floats(N, H, W) + (size_t)N * 9 * plane;
+}
+
 // gx is fully overwritten; goff[n][0:18] is overwritten (channels 18.. of a padded offset tensor are left alone).
+// ws: deform_backward_workspace_floats floats (may be null where that is 0).
 void launch_deform_backward(const float* x, const float* off, const float* gcol, const float* w1o, const float* gy,
-                            float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s) {
+                            float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s, float* ws) {
   const long plane = (long)H * W;
   constexpr int CH = 8;
   const size_t lds = sizeof(float) * ((size_t)2 * CH * plane + 10 * plane + 1);
-  if (lds <= 150 * 1024 && C % CH == 0) {
+  if (deform_backward_lds_ok(C, plane)) {
     // deterministic variant: x is not staged, which leaves room for 16 channels per workgroup -- one round of N * C / 16
     // workgroups, the sampling lists built half as often, sixteen gathers in flight per list entry
     constexpr int CHD = 16;
@@ -582,6 +602,22 @@ void launch_deform_backward(const float* x, const float* off, const float* gcol,
       hipLaunchKernelGGL((deform_backward_csr_kernel<CH, 1024, false>), dim3(N, C / CH), dim3(1024), lds, s, x, off, gcol, w1o, gy, gx,
                          goff, N, C, H, W, offsn);
     }
+  } else if (g_wgrad_deterministic && C % CH == 0) {
+    // No fp32 atomics on gx on a plane of any size: the offset gradients from deform_goff_kernel, the sampling lists of every (image,
+    // tap) built and sorted in global memory (one workgroup each), then the register-only gather of launch_deform_input_grad.
+    DBM_CHECK(ws != nullptr, "deformable backward: the deterministic form past the LDS kernels needs deform_backward_workspace_floats of workspace");
+    DBM_CHECK(4 * plane < (1L << 31), "deformable backward: more than 2^29 pixels per plane");
+    const long total = (long)N * 9 * plane;
+    hipLaunchKernelGGL(deform_goff_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, off, gcol, w1o, gy, goff, N, C,
+                       H, W, offsn);
+    int* g_offs = (int*)ws;
+    int2* g_ent = (int2*)(ws + (((size_t)N * 9 * (plane + 1) + 1) & ~(size_t)1));
+    int* g_cur = (int*)(ws + deform_csr_workspace_floats(N, H, W));
+    hipLaunchKernelGGL((deform_csr_build_global_kernel<1024>), dim3(N, 9), dim3(1024), 0, s, off, g_offs, g_ent, g_cur, H, W, offsn);
+    if (C % 16 == 0)
+      hipLaunchKernelGGL((deform_csr_gather_kernel<16, 1024>), dim3(N, C / 16), dim3(1024), 0, s, g_offs, g_ent, gcol, w1o, gy, gx, C, (int)plane);
+    else
+      hipLaunchKernelGGL((deform_csr_gather_kernel<8, 1024>), dim3(N, C / 8), dim3(1024), 0, s, g_offs, g_ent, gcol, w1o, gy, gx, C, (int)plane);
   } else {
     DBM_HIP(hipMemsetAsync(gx, 0, sizeof(float) * N * C * plane, s));
     const long total = (long)N * 9 * plane;
@@ -678,6 +714,93 @@ __global__ __launch_bounds__(NT) void deform_csr_build_kernel(const float* __res
     for (int sl = s0; sl < s1; ++sl) ge[sl] = make_int2(ent_p[sl], __float_as_int(ent_w[sl]));
   }
   if (tid == 0) go[plane] = offs[plane];
+}
+
+// The same lists for a plane of any size (launch_deform_backward's deterministic form past the LDS kernels): counts, offsets, cursors
+// and entries all live in global memory -- g_offs / g_ent in deform_csr_build_kernel's layout, g_cur: plane fill cursors per (image,
+// tap).  One workgroup per (image, tap); between its phases a device-scope fence and a barrier, since the counts and cursors are
+// written by atomics (performed in L2) and read by plain loads.  The lists are sorted by position in place (Shell sort, gaps 3h + 1:
+// an insertion sort for the usual handful of entries, and no quadratic walk where many samples converge on one pixel).
+template <int NT>
+__global__ __launch_bounds__(NT) void deform_csr_build_global_kernel(const float* __restrict__ off, int* g_offs, int2* g_ent, int* g_cur,
+                                                                     int H, int W, long offsn) {
+  __shared__ int wtot[NT / 64];
+  const int plane = H * W;
+  const int n = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  int* offs = g_offs + ((long)n * 9 + t) * ((long)plane + 1);   // plane + 1  (counts, then exclusive offsets)
+  int* cur = g_cur + ((long)n * 9 + t) * plane;                  // plane      (fill cursors)
+  int2* ent = g_ent + ((long)n * 9 + t) * 4 * plane;             // 4 * plane  {output position, bilinear weight}
+  const float* on = off + (long)n * offsn;
+  const int per = (plane + NT - 1) / NT;
+  for (int e = tid; e <= plane; e += NT) offs[e] = 0;
+  __threadfence();
+  __syncthreads();
+  for (int p = tid; p < plane; p += NT) {
+    const int a = p / W, b = p - a * W;
+    const DeformGeom g = deform_geom(on[(long)t * plane + p], on[(long)(9 + t) * plane + p], a, b, t / 3, t % 3, H, W, 1);
+    const int o1 = deform_corner(g.v0, g.u0, H, W, 1), o2 = deform_corner(g.v0, g.u0 + 1, H, W, 1);
+    const int o3 = deform_corner(g.v0 + 1, g.u0, H, W, 1), o4 = deform_corner(g.v0 + 1, g.u0 + 1, H, W, 1);
+    if (o1 >= 0) atomicAdd(offs + o1, 1);
+    if (o2 >= 0) atomicAdd(offs + o2, 1);
+    if (o3 >= 0) atomicAdd(offs + o3, 1);
+    if (o4 >= 0) atomicAdd(offs + o4, 1);
+  }
+  __threadfence();
+  __syncthreads();
+  {
+    const long base = (long)tid * per;
+    int loc = 0;
+    for (int i = 0; i < per; ++i)
+      if (base + i < plane) loc += offs[base + i];
+    int inc = loc;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += v;
+    }
+    if (lane == 63) wtot[wave] = inc;
+    __syncthreads();
+    int pre = inc - loc;
+    for (int w2 = 0; w2 < wave; ++w2) pre += wtot[w2];
+    for (int i = 0; i < per; ++i)
+      if (base + i < plane) {
+        const int cnt = offs[base + i];
+        offs[base + i] = pre;
+        cur[base + i] = pre;
+        pre += cnt;
+      }
+    if (tid == NT - 1) offs[plane] = pre;  // the last thread owns the tail (possibly empty): pre == grand total
+  }
+  __threadfence();
+  __syncthreads();
+  for (int p = tid; p < plane; p += NT) {
+    const int a = p / W, b = p - a * W;
+    const DeformGeom g = deform_geom(on[(long)t * plane + p], on[(long)(9 + t) * plane + p], a, b, t / 3, t % 3, H, W, 1);
+    const int o1 = deform_corner(g.v0, g.u0, H, W, 1), o2 = deform_corner(g.v0, g.u0 + 1, H, W, 1);
+    const int o3 = deform_corner(g.v0 + 1, g.u0, H, W, 1), o4 = deform_corner(g.v0 + 1, g.u0 + 1, H, W, 1);
+    const float w1 = g.wu1 * g.wv1, w2 = g.wu0 * g.wv1, w3 = g.wu1 * g.wv0, w4 = g.wu0 * g.wv0;
+    if (o1 >= 0) ent[atomicAdd(cur + o1, 1)] = make_int2(p, __float_as_int(w1));
+    if (o2 >= 0) ent[atomicAdd(cur + o2, 1)] = make_int2(p, __float_as_int(w2));
+    if (o3 >= 0) ent[atomicAdd(cur + o3, 1)] = make_int2(p, __float_as_int(w3));
+    if (o4 >= 0) ent[atomicAdd(cur + o4, 1)] = make_int2(p, __float_as_int(w4));
+  }
+  __threadfence();
+  __syncthreads();
+  for (int q = tid; q < plane; q += NT) {  // the fill order varies from run to run: sort the entries of a pixel by position
+    const int s0 = offs[q], s1 = offs[q + 1];
+    int h = 1;
+    while (h < (s1 - s0) / 3) h = 3 * h + 1;
+    for (; h >= 1; h /= 3)
+      for (int i = s0 + h; i < s1; ++i) {
+        const int2 k = ent[i];
+        int jj = i;
+        while (jj - h >= s0 && ent[jj - h].x > k.x) {
+          ent[jj] = ent[jj - h];
+          jj -= h;
+        }
+        ent[jj] = k;
+      }
+  }
 }
 
 // gx[n][c0 .. c0 + CH)[q] = sum over taps and list entries of w * gcol[c][t][p]  (or w * gy[p] * w1o[c*9+t]): input pixel q

@@ -231,11 +231,12 @@ void deform_layer_forward(const dbm_model& m, const IgLayer* L, const DeformForm
 // Backward of the C -> 1 layer: gx and goff[:, 0:18] overwritten, gw (C * 9) / gb accumulated.  Fused forms: xt, partial
 // (deform_bwd1_partial_floats), csr_ws (deform_csr_workspace_floats; lists_built: its lists are final), z (the forward's premultiplied
 // planes or null) and Gt (N * 9 * H * W floats, with z); the gathering form's offset / weight gradients go to s_goff.  Unfused: x and the
-// sample matrix col; the weight gradient goes to s_wgrad.
+// sample matrix col, csr_ws of deform_backward_workspace_floats floats (null where that is 0); the weight gradient goes to s_wgrad.
 void deform1_backward(const DeformForms& f, const float* x, const float* xt, const float* off, long offsn, const float* w, const float* gy,
                       const float* z, const float* col, float* gx, float* goff, float* gw, float* gb, float* partial, float* csr_ws,
                       float* Gt, bool lists_built, int N, int C, int H, int W, hipStream_t s, hipStream_t s_goff, hipStream_t s_wgrad);
 // Data and offset gradients of the 64 -> 64 layer L (1x1 view; ensure_packed_bwd done): gcol (N, C * 9, H, W) scratch, gx and goff[:, 0:18] overwritten
+// (csr_ws: deform_csr_workspace_floats floats for the fused form, deform_backward_workspace_floats for the unfused one)
 void deform64_backward_data(const dbm_model& m, const IgLayer& L, const DeformForms& f, const float* x, const float* xt, const float* off,
                             long offsn, const float* gy, float* gcol, float* gx, float* goff, float* csr_ws, bool lists_built, int N, int H,
                             int W, hipStream_t s);

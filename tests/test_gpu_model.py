@@ -790,6 +790,36 @@ def test_fused_trunk_forward_backward_parity(dbm, n_blocks, n, rs):
     assert worst[0] < 5e-4, worst
 
 
+def test_generator_backward_accumulates_into_the_gradient_arena(dbm):
+    """dbm_gen_backward "accumulates into the gradient arena" (include/dbm.h): two backward passes with no cleargrads() between them
+    leave the SUM of the two gradients in every tensor.  One RRDB, two 11 x 11 tiles: the fused trunk and its batched weight-gradient
+    launch, the input block, both deformable layers.  Bound: 1e-5 of each tensor's largest value -- the second pass adds fewer than
+    64 partial sums into an element, each addition rounding at 2^-24 of the running value: < 4e-6; a form that overwrites is off by
+    O(1)."""
+    og = scaled_oracle_generator(1, 1.5, rs=0.2)
+    g = copy_params(dbm.GeneratorModel(num_residual_blocks=1, residual_scaling=0.2, initialize=False), og.params)
+    r = np.random.RandomState(17)
+    passes = [(tile_inputs(2, 41), r.normal(size=(2, 1, 36, 36)).astype(np.float32)),
+              (tile_inputs(2, 42), r.normal(size=(2, 1, 36, 36)).astype(np.float32))]
+    names = [k for k, p in g._tensors.items() if p.kind == 0]
+    separate = []
+    for ins, gy in passes:
+        g.forward(*ins)
+        g.cleargrads()
+        g.backward(gy)
+        separate.append({k: g._tensors[k].grad.astype(np.float64) for k in names})
+    g.cleargrads()
+    for ins, gy in passes:
+        g.forward(*ins)
+        g.backward(gy)
+    worst = []
+    for k in names:
+        want = separate[0][k] + separate[1][k]
+        worst.append((float(np.abs(g._tensors[k].grad - want).max() / max(np.abs(want).max(), 1e-30)), k))
+    worst = sorted(worst, reverse=True)[0]
+    assert worst[0] <= 1e-5, worst
+
+
 _FUSED_AB_SCRIPT = r"""
 import sys, numpy as np
 sys.path.insert(0, sys.argv[1])

@@ -184,15 +184,18 @@ def test_conv2d_backward(dbm, case):
     w_pad[:O] = w
     gx_ref, gw_ref, gb_ref = ops.conv2d_backward(xin, w_pad, gy, s, p)
     want_gx = Cc % 32 == 0
-    gx = d.DeviceArray(xin.shape) if want_gx else None
-    gw = dev(d, np.zeros_like(w_pad))
-    gb = dev(d, np.zeros(O_pad, np.float32))
+    # the contracts of include/dbm.h: gw / gb are ACCUMULATED (prefilled with random values of the gradient's scale; the result net
+    # of the prefill is compared), gx is OVERWRITTEN (prefilled with NaN)
+    gw0 = (rs.normal(size=w_pad.shape) * (np.abs(gw_ref).max() or 1.0)).astype(np.float32)
+    gb0 = (rs.normal(size=O_pad) * (np.abs(gb_ref).max() or 1.0)).astype(np.float32)
+    gx = dev(d, np.full(xin.shape, np.nan, np.float32)) if want_gx else None
+    gw, gb = dev(d, gw0), dev(d, gb0)
     dx, dw, dgy = dev(d, x), dev(d, w_pad), dev(d, gy)
     _lib.check(_lib.lib().dbm_op_conv2d_backward(ctx.handle, dx.ptr, dw.ptr, dgy.ptr, gx.ptr if want_gx else None,
                                                  gw.ptr, gb.ptr, N, Cc, H, W, O_pad, k, s, p, ups), ctx.handle)
     ctx.synchronize()
-    assert rel(gw.get(), gw_ref) < TOL
-    assert rel(gb.get(), gb_ref) < TOL
+    assert rel(gw.get().astype(np.float64) - gw0, gw_ref) < TOL
+    assert rel(gb.get().astype(np.float64) - gb0, gb_ref) < TOL
     if want_gx:
         assert rel(gx.get(), gx_ref) < TOL
 
