@@ -62,6 +62,7 @@ SIGNATURES = {
     "dbm_f32_to_i16": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
     "dbm_lzw_encode_tiles": [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int],
     "dbm_lzw_decode": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "dbm_inflate": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
     "dbm_debug_inject_timeout": [C.c_void_p],
     "dbm_debug_inject_timeout_async": [C.c_void_p],
     "dbm_check_timeout": [C.c_void_p],
@@ -157,7 +158,7 @@ class DbmError(RuntimeError):
     # optimizer updates queued since the event were skipped (`Context.timeout_info()`).  8: the same in a data-parallel
     # run -- fatal, the replicas have diverged.  9 (dbm_adam_update only): the gradients about to be applied come from a
     # void pass; nothing was applied -- repeat forward + backward, then update.  10 (dbm_grid_tension_surface only): the solve did not
-    # converge within max_iter; the output holds the last iterate.  11 (dbm_tiff_decode only): a block's LZW stream is malformed.
+    # converge within max_iter; the output holds the last iterate.  11 (dbm_tiff_decode only): a block's LZW or deflate stream is malformed.
     # 12 (dbm_tiff_encode only): a block's LZW stream did not fit its slot (the device encoder's guard; the message names the block).
     code = None
 

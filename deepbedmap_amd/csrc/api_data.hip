@@ -156,7 +156,7 @@ int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes
   DBM_CHECK(ctx != nullptr, "dbm_tiff_decode: NULL context");
   note_device_write(ctx);
   DBM_CHECK(n_blocks >= 0, "dbm_tiff_decode: negative number of blocks");
-  DBM_CHECK(compression == 1 || compression == 5, "dbm_tiff_decode: compression must be 1 (decoded bytes) or 5 (LZW)");
+  DBM_CHECK(compression == 1 || compression == 5 || compression == 8, "dbm_tiff_decode: compression must be 1 (decoded bytes), 5 (LZW) or 8 (deflate)");
   DBM_CHECK(sample_type >= 0 && sample_type <= 5, "dbm_tiff_decode: sample_type must lie in 0..5");
   static const int kBytes[6] = {1, 2, 2, 4, 4, 8};
   const int bytes = kBytes[sample_type];
@@ -166,7 +166,8 @@ int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes
   DBM_CHECK(n_blocks == 0 || (streams_host != nullptr && blocks_host != nullptr && out_dev != nullptr), "dbm_tiff_decode: NULL streams, blocks or output");
   DBM_CHECK((long)n_blocks * block_h < (1L << 31), "dbm_tiff_decode: more than 2^31 block rows in one call");
   if (n_blocks == 0) return 0;
-  const bool lzw = compression == 5;
+  const bool lzw = compression != 1;   // the blocks are streams: decoded into a staging area of their own (LZW or deflate)
+  const char* codec = compression == 8 ? "deflate" : "LZW";
   for (int b = 0; b < n_blocks; ++b) {
     const int64_t* e = blocks_host + 8 * (size_t)b;
     const std::string name = "dbm_tiff_decode: block " + std::to_string(e[5]);
@@ -190,14 +191,16 @@ int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes
   DBM_HIP(hipMemcpyAsync(table.p, blocks_host, table_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (lzw) {
     a.stage = stage.as<uint8_t>((size_t)n_blocks * (size_t)a.block_stride);
-    launch_tiff_lzw(a, ctx->stream);
+    if (compression == 8) launch_tiff_inflate(a, ctx->stream);
+    else launch_tiff_lzw(a, ctx->stream);
     std::vector<int> status((size_t)n_blocks);
     DBM_HIP(hipMemcpyAsync(status.data(), a.status, sizeof(int) * (size_t)n_blocks, hipMemcpyDeviceToHost, ctx->stream));
     DBM_HIP(hipStreamSynchronize(ctx->stream));
     for (int b = 0; b < n_blocks; ++b)
       if (status[b] != 0)
         throw DbmError(11, "dbm_tiff_decode: block " + std::to_string(blocks_host[8 * (size_t)b + 5]) +
-                               (status[b] == 1 ? ": malformed LZW stream" : ": the LZW stream does not decode to the block's size") +
+                               (status[b] == 1 ? std::string(": malformed ") + codec + " stream"
+                                               : std::string(": the ") + codec + " stream does not decode to the block's size") +
                                "; nothing of this call was written");
   }
   launch_tiff_rows(a, ctx->stream);

@@ -294,7 +294,8 @@ void launch_grid_fill_gaps(const TileLaunch& a, const double window[4], const fl
 
 // GeoTIFF blocks -> a float32 plane (tiff_decode.hip; dbm_tiff_decode).  blocks: n_blocks x 8 int64 on the device = {offset of the
 // block's bytes in `streams`, their count, rows the block holds, output row of the block's row 0, output column of its column 0, id, 0, 0}.
-// lzw: launch_tiff_lzw decodes streams + offset into stage + b * block_stride and writes status[b] (0 good, 1 malformed, 2 the decoded
+// lzw (set for both codecs: "the blocks are staged"): launch_tiff_lzw (TIFF 6.0 LZW) or launch_tiff_inflate (zlib streams,
+// tiff_inflate.hip) decodes streams + offset into stage + b * block_stride and writes status[b] (0 good, 1 malformed, 2 the decoded
 // size is not rows * block_w * bytes); launch_tiff_rows then reads from there.  Not lzw: stage == streams, the block's decoded bytes lie
 // at stage + offset (8-byte aligned).  launch_tiff_rows changes the decoded bytes in place (the predictor) and writes out (out_h, out_w).
 struct TiffDecodeLaunch {
@@ -311,9 +312,12 @@ struct TiffDecodeLaunch {
   long out_h, out_w;
 };
 void launch_tiff_lzw(const TiffDecodeLaunch& a, hipStream_t s);
+void launch_tiff_inflate(const TiffDecodeLaunch& a, hipStream_t s);
 void launch_tiff_rows(const TiffDecodeLaunch& a, hipStream_t s);
 // lzw_decode_lanes with one lane on the host: the decoded size or (size_t)-1 (tools/lzw_twin_check.cpp compares it with dbm_lzw_decode)
 size_t tiff_lzw_decode_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
+// inflate_lanes with one lane on the host: the decoded size or (size_t)-1 (dbm_inflate; tools/inflate_twin_check.cpp compares it with zlib)
+size_t tiff_inflate_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
 
 // numpy.ndarray.astype(int16) of a float32 on x86-64: truncation to int32 (cvttss2si: NaN and |x| >= 2^31 give INT32_MIN), then the low
 // 16 bits -- NaN (the canvas frame that no tile covers), +-inf and out-of-range values become 0.  The one cast of f32_to_i16_kernel

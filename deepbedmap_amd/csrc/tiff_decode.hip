@@ -1,5 +1,5 @@
 // Decoding the blocks (strips or tiles) of a GeoTIFF on the device (dbm_tiff_decode; the host side -- header, block plan, reading the
-// streams, inflate -- is deepbedmap_amd/geotiff.py).  Replaces the reference's rasterio / GDAL reads (data_prep.py:668, :845-877;
+// streams -- is deepbedmap_amd/geotiff.py; deflate blocks go through stage (a') in tiff_inflate.hip instead of stage (a)).  Replaces the reference's rasterio / GDAL reads (data_prep.py:668, :845-877;
 // deepbedmap.py:164-204).  Two stages:
 //
 // (a) tiff_lzw_kernel -- TIFF 6.0 LZW (MSB-first codes of 9..12 bits, "early change", ClearCode 256, EndOfInformation 257: the dialect

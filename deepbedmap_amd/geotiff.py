@@ -13,7 +13,8 @@ cross PCIe; both writers share the tags (`_image_tags`) and the container (`_wri
 
 Reading rasters as GDAL and libtiff write them (reference data_prep.py:668, :845-877; deepbedmap.py:164-204, through rasterio): the
 second half of this file -- `open_geotiff` (header, geometry, block plan, refusals: host), `read_geotiff_resident` (the blocks decoded on
-the GPU by dbm_tiff_decode: LZW, predictors, float32 conversion, placement; deflate inflated on host threads).  DESIGN.md 6i.
+the GPU by dbm_tiff_decode: LZW, deflate, predictors, float32 conversion, placement; `inflate="host"` inflates on host threads instead).
+DESIGN.md 6i.
 """
 import ctypes as C
 import os
@@ -63,6 +64,19 @@ def lzw_decode(stream, nbytes):
     rc = _lib.lib().dbm_lzw_decode(src.ctypes.data_as(C.c_void_p), src.size, dst.ctypes.data_as(C.c_void_p), dst.size, C.byref(got))
     if rc != 0 or got.value != nbytes:
         raise _lib.DbmError(f"dbm_lzw_decode failed ({rc}, {got.value} of {nbytes} bytes)")
+    return dst[:nbytes]
+
+
+def inflate(stream, nbytes):
+    """One zlib stream decoded by the device decoder's loop run with one lane on the host (dbm_inflate): `nbytes` bytes as uint8, or
+    DbmError on everything dbm_tiff_decode reports for compression 8 (a malformed stream, a size other than nbytes)."""
+    src = np.frombuffer(stream, dtype=np.uint8)
+    dst = np.empty(max(int(nbytes), 1), dtype=np.uint8)
+    got = C.c_size_t()
+    rc = _lib.lib().dbm_inflate(src.ctypes.data_as(C.c_void_p) if src.size else dst.ctypes.data_as(C.c_void_p), src.size,
+                                dst.ctypes.data_as(C.c_void_p), int(nbytes), C.byref(got))
+    if rc != 0 or got.value != nbytes:
+        raise _lib.DbmError(f"dbm_inflate failed ({rc}, {got.value} of {nbytes} bytes)")
     return dst[:nbytes]
 
 
@@ -373,6 +387,7 @@ _FIELD_TYPES = {1: ("B", 1), 2: ("s", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8)
 _SAMPLES = {(8, 1): ("u1", 0), (16, 2): ("<i2", 1), (16, 1): ("<u2", 2), (32, 2): ("<i4", 3), (32, 3): ("<f4", 4), (64, 3): ("<f8", 5)}
 _COMPRESSIONS = {1: "none", 5: "lzw", 8: "deflate", 32946: "deflate"}
 WORKSPACE_DEFAULT = 1 << 30   # bytes of block staging per batch of read_geotiff_resident
+INFLATE_DEFAULT = "device"    # where read_geotiff_resident inflates deflate blocks (the measurement that decided it)
 
 
 class BlockPlan:
@@ -591,12 +606,15 @@ def open_geotiff(path):
     return gf
 
 
-def _batches(gf, plan, limit):
-    """Consecutive runs of the plan's blocks whose staging (stream + decoded block) stays within `limit` bytes; never an empty run."""
+def _batches(gf, plan, limit, streams=None):
+    """Consecutive runs of the plan's blocks whose staging (stream + decoded block) stays within `limit` bytes; never an empty run.
+    streams: the blocks' streams are uploaded and decoded on the device (LZW always; deflate unless it is inflated on the host)."""
     decoded = -(-gf.block_h * gf.block_w * gf.dtype.itemsize // 16) * 16
+    if streams is None:
+        streams = gf.compression == 5
     runs, start, used = [], 0, 0
     for k, b in enumerate(plan.blocks):
-        cost = decoded + (int(b[BlockPlan.BYTES]) if gf.compression == 5 else 16)
+        cost = decoded + (int(b[BlockPlan.BYTES]) if streams else 16)
         if k > start and used + cost > limit:
             runs.append((start, k))
             start, used = k, 0
@@ -605,9 +623,11 @@ def _batches(gf, plan, limit):
     return runs
 
 
-def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=None):
-    """Decodes a GeoTIFF (`open_geotiff`'s dialect) into HBM: LZW, the predictors, the conversion to float32 (NumPy's `astype`) and
-    the placement run on the GPU (dbm_tiff_decode); deflate streams are inflated on host threads first.  window_bound = (minx, miny,
+def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=None, inflate=INFLATE_DEFAULT):
+    """Decodes a GeoTIFF (`open_geotiff`'s dialect) into HBM: LZW, deflate, the predictors, the conversion to float32 (NumPy's `astype`)
+    and the placement run on the GPU (dbm_tiff_decode), so only the compressed bytes cross PCIe.  inflate="host" inflates deflate
+    streams with zlib on host threads and uploads the decoded blocks instead (DESIGN.md 6i has the measurements behind the default);
+    files that are not deflate read the same either way.  window_bound = (minx, miny,
     maxx, maxy) reads the pixels whose centres lie in [minx, maxx) x (miny, maxy] and only the blocks that hold them.
     workspace_limit: bytes of block staging per batch (default 1 GiB; at least one block goes through at a time).
     Returns (DeviceArray (H, W), info): read_geotiff's keys plus predictor, dtype, window (row0, col0, H, W) and geometry (the
@@ -621,7 +641,10 @@ def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=Non
     workspace_limit = int(workspace_limit)
     if workspace_limit < 1:
         raise ValueError("workspace_limit must be positive")
+    if inflate not in ("device", "host"):
+        raise ValueError(f"read_geotiff_resident: inflate {inflate!r}: 'device' or 'host'")
     gf = open_geotiff(path)
+    on_device = gf.compression == 5 or (gf.compression != 1 and inflate == "device")   # the streams themselves are uploaded
     if window_bound is None:
         geometry = None if isinstance(gf._geometry, Exception) else gf._geometry
     else:
@@ -634,7 +657,7 @@ def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=Non
     out = DeviceArray((H, W), ctx)
     itemsize = gf.dtype.itemsize
     with open(gf.path, "rb") as f:
-        for start, stop in _batches(gf, plan, workspace_limit):
+        for start, stop in _batches(gf, plan, workspace_limit, on_device):
             part = plan.blocks[start:stop]
             streams = []
             for b in part:
@@ -645,21 +668,21 @@ def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=Non
                 streams.append(s)
             table = np.zeros((len(part), 8), dtype=np.int64)
             table[:, 2:6] = part[:, BlockPlan.ROWS:BlockPlan.INDEX + 1]
-            if gf.compression == 5:
+            if on_device:
                 sizes = np.array([len(s) for s in streams], dtype=np.int64)
                 table[:, 0] = np.cumsum(sizes) - sizes
                 table[:, 1] = sizes
                 payload = np.frombuffer(b"".join(streams), dtype=np.uint8)
-                mode = 5
+                mode = 5 if gf.compression == 5 else 8
             else:
                 if gf.compression != 1:
-                    def inflate(k):
+                    def inflate_one(k):
                         try:
                             return zlib.decompress(streams[k])
                         except zlib.error as e:
                             raise _lib.DbmError(f"{gf.path}: block {part[k, BlockPlan.INDEX]}: malformed deflate stream ({e})") from None
                     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
-                        streams = list(pool.map(inflate, range(len(streams))))
+                        streams = list(pool.map(inflate_one, range(len(streams))))
                 want = part[:, BlockPlan.ROWS] * gf.block_w * itemsize
                 stride = -(-gf.block_h * gf.block_w * itemsize // 16) * 16
                 payload = np.zeros(len(part) * stride, dtype=np.uint8)

@@ -22,7 +22,7 @@
  *     the gradients and repeats forward + backward before updating (the step entry points clear them themselves).  Status 8:
  *     the same in a data-parallel run, where a local retry cannot keep the replicas identical -- fatal, abort the job.  Status 10
  *     (dbm_grid_tension_surface only): the solve did not converge within max_iter; the output holds the last iterate.  Status 11
- *     (dbm_tiff_decode only): a block's LZW stream is malformed.  Status 12 (dbm_tiff_encode only): a block's LZW stream did not fit
+ *     (dbm_tiff_decode only): a block's LZW or deflate stream is malformed.  Status 12 (dbm_tiff_encode only): a block's LZW stream did not fit
  *     its slot (the guard of the device encoder; it cannot occur with the slot the call allocates);
  *   - tensors are NCHW float32, C-contiguous; weights OIHW, exactly the arrays stored by
  *     chainer.serializers.save_npz (key layout: SURVEY.md Appendix B);
@@ -530,15 +530,18 @@ int dbm_generator_step(dbm_model* g, dbm_model* d, int N, int H, int W, const fl
  * dbm_lzw_encode_tiles: TIFF 6.0 LZW of `ntiles` tiles of `tile_bytes` bytes each (host memory, tile t at
  * tiles + t * tile_bytes) into out + t * out_stride (out_stride >= tile_bytes * 3 / 2 + 64 is always enough),
  * encoded sizes in out_sizes[t]; tiles are spread over `nthreads` host threads.  dbm_lzw_decode: one stream back
- * (round-trip check).  Host functions: no GPU, no context.  The TIFF container is written by the host shim
- * (deepbedmap_amd/geotiff.py). */
+ * (round-trip check).  dbm_inflate: one zlib stream (RFC 1950 around RFC 1951, dbm_tiff_decode's compression 8) decoded on the host
+ * by the device decoder's own loop run with one lane; *out_bytes = the decoded size; non-zero on everything that decoder reports (a
+ * malformed stream, more than cap bytes of output).  Host functions: no GPU, no context.  The TIFF container is written by the host
+ * shim (deepbedmap_amd/geotiff.py). */
 int dbm_f32_to_i16(dbm_ctx* ctx, const float* src_dev, void* dst_dev, size_t n);
 int dbm_lzw_encode_tiles(const void* tiles, size_t tile_bytes, int ntiles, void* out, size_t out_stride, size_t* out_sizes,
                          int nthreads);
 int dbm_lzw_decode(const void* src, size_t nbytes, void* dst, size_t cap, size_t* out_bytes);
+int dbm_inflate(const void* src, size_t nbytes, void* dst, size_t cap, size_t* out_bytes);
 
 /* ---- opening rasters: GeoTIFF blocks decoded on the device (replaces the rasterio / GDAL reads of data_prep.py:668, :845-877 and
- * deepbedmap.py:164-204; header parsing, the block plan, file reads and inflate stay with the host shim deepbedmap_amd/geotiff.py) ----
+ * deepbedmap.py:164-204; header parsing, the block plan and file reads stay with the host shim deepbedmap_amd/geotiff.py) ----
  * dbm_tiff_decode turns n_blocks blocks (strips or tiles) of one-sample pixels into their places of the float32 plane out_dev (out_h,
  * out_w), ALWAYS a device pointer.  streams_host (streams_bytes bytes, HOST, uploaded once per call) holds the blocks' bytes;
  * blocks_host (HOST) has 8 int64 per block: {offset of its bytes in streams_host, their count, rows the block holds (1..block_h: the
@@ -547,6 +550,10 @@ int dbm_lzw_decode(const void* src, size_t nbytes, void* dst, size_t cap, size_t
  * in error messages), 0, 0}.  A block row has block_w samples.
  * compression 5: the bytes are a TIFF 6.0 LZW stream (MSB-first codes, 9..12 bits, early change, ClearCode 256, EndOfInformation 257:
  * what dbm_lzw_decode reads), decoded by one wavefront per block; a stream may end without EndOfInformation if the block is complete.
+ * compression 8: the bytes are a zlib stream (RFC 1950: CM 8, CINFO <= 7, header check, no preset dictionary; RFC 1951 inside: stored,
+ * fixed and dynamic blocks; the Adler-32 of the decoded bytes behind it, bytes after that ignored), accepted and refused as zlib's
+ * `uncompress` does it, decoded by one wavefront per block; no alignment or length condition, as for 5.  TIFF Compression 32946 is
+ * the same codec: pass 8.
  * compression 1: the bytes ARE the decoded block (uncompressed files; deflate inflated by the caller), offset a multiple of 8, count
  * >= rows * block_w * bytes.
  * predictor (TIFF tag 317) 1: none; 2: every row is a running sum of its samples, wrapping in the sample's width (float samples:
@@ -554,11 +561,16 @@ int dbm_lzw_decode(const void* src, size_t nbytes, void* dst, size_t cap, size_t
  * (block_w bytes) holds byte k of every sample, most significant first.
  * sample_type 0 uint8, 1 int16, 2 uint16, 3 int32, 4 float32, 5 float64, little endian; converted as numpy.astype(float32) does
  * (float32 samples keep their bits, NaN payloads included).
- * The call allocates its workspace (streams_bytes + 68 per block; for LZW also block_w * block_h * bytes, rounded up to 16, per
+ * The call allocates its workspace (streams_bytes + 68 per block; for LZW and deflate also block_w * block_h * bytes, rounded up to 16, per
  * block), frees it on every path and synchronises the context's stream; the caller bounds the workspace by batching.
  * Status 11: an LZW stream is malformed (a first code above 255, a code above the next free one, more output than the block holds) or
- * does not decode to rows * block_w * bytes bytes; the message names the block's id and nothing of this call has been written.
- * Refused (status 1, nothing launched): compression not 1 or 5, sample_type outside 0..5, predictor not 1, 2 or 3 (3: float samples
+ * does not decode to rows * block_w * bytes bytes; or a deflate stream is malformed (a bad zlib header or a preset dictionary, block
+ * type 3, a stored block whose NLEN is not ~LEN or that is longer than the stream, HLIT > 286 or HDIST > 30, a repeat code with no
+ * previous length or past the last one, no end-of-block code, an over-subscribed or incomplete set of code lengths -- but a single
+ * code of length 1 and no distance code at all pass, as in zlib --, a bit pattern that is no code, symbols 286 / 287, distance codes
+ * 30 / 31, a distance beyond what has been written, more output than the block holds, a stream that ends early, an Adler-32 that does
+ * not match) or does not decode to that size; the message names the block's id and nothing of this call has been written.
+ * Refused (status 1, nothing launched): compression not 1, 5 or 8, sample_type outside 0..5, predictor not 1, 2 or 3 (3: float samples
  * only), block_w or block_h < 1, a block of 2^31 bytes or more, n_blocks * block_h >= 2^31, an empty plane, NULL pointers with
  * n_blocks > 0, bytes outside streams_host, rows outside 1..block_h, decoded bytes misaligned or short.  n_blocks = 0 succeeds. */
 int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host, int n_blocks, int compression,
