@@ -75,14 +75,12 @@ __device__ __forceinline__ void build_geometry(TileGeometry& g, const float* __r
       const int p = (int)(P - (long)n * plane);
       const int a = p / W, b = p - a * W;
       const float* on = off + (long)n * offsn;
-      const DeformGeom q = deform_geom(on[(long)t * plane + p], on[(long)(9 + t) * plane + p], a, b, t / 3, t % 3, H, W, 1);
-      const int o1 = deform_corner(q.v0, q.u0, H, W, 1), o2 = deform_corner(q.v0, q.u0 + 1, H, W, 1);
-      const int o3 = deform_corner(q.v0 + 1, q.u0, H, W, 1), o4 = deform_corner(q.v0 + 1, q.u0 + 1, H, W, 1);
+      const DeformTap s = deform_tap(on[(long)t * plane + p], on[(long)(9 + t) * plane + p], a, b, t / 3, t % 3, H, W);
       const int base = n * plane;
-      if (o1 >= 0) { id.x = base + o1; wg.x = q.wu1 * q.wv1; }
-      if (o2 >= 0) { id.y = base + o2; wg.y = q.wu0 * q.wv1; }
-      if (o3 >= 0) { id.z = base + o3; wg.z = q.wu1 * q.wv0; }
-      if (o4 >= 0) { id.w = base + o4; wg.w = q.wu0 * q.wv0; }
+      if (s.o1 >= 0) { id.x = base + s.o1; wg.x = s.w1(); }
+      if (s.o2 >= 0) { id.y = base + s.o2; wg.y = s.w2(); }
+      if (s.o3 >= 0) { id.z = base + s.o3; wg.z = s.w3(); }
+      if (s.o4 >= 0) { id.w = base + s.o4; wg.w = s.w4(); }
       if (abl) id = make_int4(base, base, base, base);   // (libdbm_measure.so only: every gather hits one cache-resident pixel)
     }
     g.idx[e] = id;
@@ -1335,17 +1333,15 @@ __device__ __forceinline__ void build_geometry_bwd(TileGeometryBwd& g, const flo
       const int p = (int)(P - (long)n * plane);
       const int a = p / W, b = p - a * W;
       const float* on = off + (long)n * offsn;
-      const DeformGeom q = deform_geom(on[(long)t * plane + p], on[(long)(9 + t) * plane + p], a, b, t / 3, t % 3, H, W, 1);
-      const int o1 = deform_corner(q.v0, q.u0, H, W, 1), o2 = deform_corner(q.v0, q.u0 + 1, H, W, 1);
-      const int o3 = deform_corner(q.v0 + 1, q.u0, H, W, 1), o4 = deform_corner(q.v0 + 1, q.u0 + 1, H, W, 1);
+      const DeformTap s = deform_tap(on[(long)t * plane + p], on[(long)(9 + t) * plane + p], a, b, t / 3, t % 3, H, W);
       const int base = n * plane;
-      if (o1 >= 0) { id.x = base + o1; fl |= 1; }
-      if (o2 >= 0) { id.y = base + o2; fl |= 2; }
-      if (o3 >= 0) { id.z = base + o3; fl |= 4; }
-      if (o4 >= 0) { id.w = base + o4; fl |= 8; }
-      if (q.mu) fl |= 16;
-      if (q.mv) fl |= 32;
-      wg = make_float4(q.wu0, q.wu1, q.wv0, q.wv1);
+      if (s.o1 >= 0) { id.x = base + s.o1; fl |= 1; }
+      if (s.o2 >= 0) { id.y = base + s.o2; fl |= 2; }
+      if (s.o3 >= 0) { id.z = base + s.o3; fl |= 4; }
+      if (s.o4 >= 0) { id.w = base + s.o4; fl |= 8; }
+      if (s.g.mu) fl |= 16;
+      if (s.g.mv) fl |= 32;
+      wg = make_float4(s.g.wu0, s.g.wu1, s.g.wv0, s.g.wv1);
     }
     g.idx[e] = id;
     g.wuv[e] = wg;
@@ -1355,18 +1351,18 @@ __device__ __forceinline__ void build_geometry_bwd(TileGeometryBwd& g, const flo
 
 __device__ __forceinline__ float4 mask4(const float4& v, bool ok) { return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f); }
 
-// d sample / d u and d sample / d v of the four channels of a quad (deform_goff_kernel's expressions)
+// d sample / d u and d sample / d v of the four channels of a quad
 __device__ __forceinline__ void coord_grads(const float4& wuv, const float4& x1, const float4& x2, const float4& x3, const float4& x4,
                                             float4& du, float4& dv) {
   const float wu0 = wuv.x, wu1 = wuv.y, wv0 = wuv.z, wv1 = wuv.w;
-  du.x = -wv1 * x1.x + wv1 * x2.x - wv0 * x3.x + wv0 * x4.x;
-  du.y = -wv1 * x1.y + wv1 * x2.y - wv0 * x3.y + wv0 * x4.y;
-  du.z = -wv1 * x1.z + wv1 * x2.z - wv0 * x3.z + wv0 * x4.z;
-  du.w = -wv1 * x1.w + wv1 * x2.w - wv0 * x3.w + wv0 * x4.w;
-  dv.x = -wu1 * x1.x - wu0 * x2.x + wu1 * x3.x + wu0 * x4.x;
-  dv.y = -wu1 * x1.y - wu0 * x2.y + wu1 * x3.y + wu0 * x4.y;
-  dv.z = -wu1 * x1.z - wu0 * x2.z + wu1 * x3.z + wu0 * x4.z;
-  dv.w = -wu1 * x1.w - wu0 * x2.w + wu1 * x3.w + wu0 * x4.w;
+  du.x = deform_du(wv0, wv1, x1.x, x2.x, x3.x, x4.x);
+  du.y = deform_du(wv0, wv1, x1.y, x2.y, x3.y, x4.y);
+  du.z = deform_du(wv0, wv1, x1.z, x2.z, x3.z, x4.z);
+  du.w = deform_du(wv0, wv1, x1.w, x2.w, x3.w, x4.w);
+  dv.x = deform_dv(wu0, wu1, x1.x, x2.x, x3.x, x4.x);
+  dv.y = deform_dv(wu0, wu1, x1.y, x2.y, x3.y, x4.y);
+  dv.z = deform_dv(wu0, wu1, x1.z, x2.z, x3.z, x4.z);
+  dv.w = deform_dv(wu0, wu1, x1.w, x2.w, x3.w, x4.w);
 }
 
 __device__ __forceinline__ float quad_sum16(float v) {  // over the sixteen channel quads of a position (lanes q = lane & 15)
@@ -1629,14 +1625,12 @@ __global__ __launch_bounds__(256) void deform1_goff_kernel(const float* __restri
   const int p = (int)(P - (long)n * plane);
   const int a = p / W, b = p - a * W;
   const float* on = off + (long)n * offsn + p;
-  const DeformGeom g = deform_geom(on[(long)t * plane], on[(long)(9 + t) * plane], a, b, t / 3, t % 3, H, W, 1);
-  const int o1 = deform_corner(g.v0, g.u0, H, W, 1), o2 = deform_corner(g.v0, g.u0 + 1, H, W, 1);
-  const int o3 = deform_corner(g.v0 + 1, g.u0, H, W, 1), o4 = deform_corner(g.v0 + 1, g.u0 + 1, H, W, 1);
+  const DeformTap s = deform_tap(on[(long)t * plane], on[(long)(9 + t) * plane], a, b, t / 3, t % 3, H, W);
+  const DeformGeom& g = s.g;
   const float* zt = z + ((long)n * 9 + t) * plane;
-  const float z1 = o1 >= 0 ? zt[o1] : 0.f, z2 = o2 >= 0 ? zt[o2] : 0.f, z3 = o3 >= 0 ? zt[o3] : 0.f, z4 = o4 >= 0 ? zt[o4] : 0.f;
-  // (coord_grads' expressions on the premultiplied corners)
-  const float du = -g.wv1 * z1 + g.wv1 * z2 - g.wv0 * z3 + g.wv0 * z4;
-  const float dv = -g.wu1 * z1 - g.wu0 * z2 + g.wu1 * z3 + g.wu0 * z4;
+  const float z1 = s.o1 >= 0 ? zt[s.o1] : 0.f, z2 = s.o2 >= 0 ? zt[s.o2] : 0.f, z3 = s.o3 >= 0 ? zt[s.o3] : 0.f, z4 = s.o4 >= 0 ? zt[s.o4] : 0.f;
+  float du, dv;   // (on the premultiplied corners)
+  deform_coord_grads(g, z1, z2, z3, z4, du, dv);
   const float gv = gy[P];
   float* gn = goff + (long)n * offsn + p;
   gn[(long)t * plane] = g.mu ? gv * du : 0.f;

@@ -1,4 +1,4 @@
-// Launchers of the non-GEMM kernels (misc.hip, norm_loss.hip).
+// Launchers of the non-GEMM kernels (misc.hip, deform_sampler.hip, norm_loss.hip).
 #pragma once
 #include <cstdlib>
 #include "dbm_internal.h"
@@ -37,6 +37,7 @@ bool input_block_rows_ok(int H, int W);
 void launch_input_block_rows(const InputBlockLaunch& a, int H, int W, hipStream_t s);
 void launch_im2col(const float* x, float* col, int N, int Cin, int Hin, int Win, int KH, int KW, int stride, int OH, int OW,
                    int KP, hipStream_t s);
+// the sampler, its backward, the CSR sampling lists and their gathers, the 576 -> 1 GEMV: deform_sampler.hip
 void launch_deform_sample(const float* x, const float* off, float* col, int N, int C, int H, int W, long offsn, hipStream_t s);
 void launch_deform_backward(const float* x, const float* off, const float* gcol, const float* w1o, const float* gy,
                             float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s, float* ws);

@@ -14,8 +14,9 @@ integer coordinate, where the offset gradient is a one-sided difference whose si
 denormalise round trip decides -- a kernel whose coordinate arithmetic is not the reference's sequence of single float32 operations
 passes under normal(0, 1) (3.4e-6) and is off by O(1) there (tests/test_deform_cases_host.py shows it on the CPU).
 
-Not reachable through the entry point: deform_backward_csr_kernel<8, 1024, true> needs C % 16 != 0, the entry point demands
-C % 32 == 0.
+The kernels under test beside the fused ones live in csrc/deform_sampler.hip.  Its deterministic forms take sixteen channels per
+workgroup (launch_deform_backward checks C % 16 == 0; the entry point demands C % 32 == 0): the eight-channel deterministic
+instantiations, which no call could reach, are gone.
 
 A mask mutant is NOT among the things these cases can catch: with pad = 1 a clipped coordinate has both of its corners in the zero
 padding, so the coordinate-gradient masks never change a value (tests/test_deform_cases_host.py asserts that a non-strict mask gives
