@@ -5,7 +5,7 @@
 //   - region: min / max of x and y over the rows whose x, y[, z] are all finite, lane -> wave -> workgroup -> one finishing workgroup
 //     (min and max are exact in any order; the launch depends on n only), outward to multiples of the increment;
 //   - block medians: row -> block index, integer histogram, exclusive scan of the H W counts and of the non-empty flags (three kernels:
-//     workgroup sums, one workgroup over the sums, rescan), rows scattered block-contiguously with integer atomics (the order INSIDE a
+//     workgroup sums, one workgroup over the sums, rescan: data_prims.h), rows scattered block-contiguously with integer atomics (the order INSIDE a
 //     block is arbitrary and never visible: every block is then sorted or selected from), medians per size class of population k:
 //       k <= DBM_BLOCKMEDIAN_SUB8 : 8 lanes per block, 32 blocks per workgroup     } rank by counting across the lanes of a
 //       k <= DBM_BLOCKMEDIAN_SUB32: 32 lanes per block, 8 blocks per workgroup     } sub-group (k shuffles per column): no LDS,
@@ -15,6 +15,7 @@
 //     on the order-preserving 64-bit image of the doubles (a total order: -0.0 before +0.0, ties by lane), so the result is a function
 //     of the multiset of rows.  No float atomics anywhere.
 #include "model.h"
+#include "data_layouts.h"
 #include <cmath>
 
 // NumPy rounds every quotient, sum and product: the block assignment may not be contracted into fused multiply-adds
@@ -28,10 +29,7 @@ constexpr int SCAN_ITEMS = 8;            // consecutive counts per lane of the s
 constexpr int SCAN_TILE = PTS_THREADS * SCAN_ITEMS;
 typedef unsigned long long u64;
 
-inline int stride_blocks(long n) {
-  const long b = (n + PTS_THREADS - 1) / PTS_THREADS;
-  return (int)(b < 1 ? 1 : (b > PTS_MAX_BLOCKS ? PTS_MAX_BLOCKS : b));
-}
+inline int stride_blocks(long n) { return grid_stride_blocks(n, PTS_THREADS, PTS_MAX_BLOCKS); }
 
 // ---- projection ----
 __global__ __launch_bounds__(PTS_THREADS) void polar_stereographic_kernel(ProjLaunch a) {
@@ -63,27 +61,8 @@ struct Box {
   long long cnt;
 };
 
-__device__ inline void box_merge(Box& a, const Box& b) {
-  a.xmin = fmin(a.xmin, b.xmin);
-  a.xmax = fmax(a.xmax, b.xmax);
-  a.ymin = fmin(a.ymin, b.ymin);
-  a.ymax = fmax(a.ymax, b.ymax);
-  a.cnt += b.cnt;
-}
-
-// lanes (fixed shuffle tree), then the workgroup's waves in order; the result is valid in thread 0
-__device__ Box box_block(Box r) {
-  __shared__ Box sh[PTS_THREADS / 64];
-  for (int off = 32; off > 0; off >>= 1) {
-    const Box o = {__shfl_down(r.xmin, off, 64), __shfl_down(r.xmax, off, 64), __shfl_down(r.ymin, off, 64), __shfl_down(r.ymax, off, 64),
-                   __shfl_down(r.cnt, off, 64)};
-    if ((threadIdx.x & 63) < off) box_merge(r, o);
-  }
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = r;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < PTS_THREADS / 64; ++w) box_merge(r, sh[w]);
-  return r;
+__device__ inline Box box_merge(const Box& a, const Box& b) {
+  return {fmin(a.xmin, b.xmin), fmax(a.xmax, b.xmax), fmin(a.ymin, b.ymin), fmax(a.ymax, b.ymax), a.cnt + b.cnt};
 }
 
 __global__ __launch_bounds__(PTS_THREADS) void region_kernel(const double* __restrict__ pts, long n, int ncol, Box* part) {
@@ -100,16 +79,14 @@ __global__ __launch_bounds__(PTS_THREADS) void region_kernel(const double* __res
       m.cnt += 1;
     }
   }
-  m = box_block(m);
+  m = block_reduce<PTS_THREADS>(m, box_merge);
   if (threadIdx.x == 0) part[blockIdx.x] = m;
 }
 
-// one workgroup: thread k folds the partials k, k + 256, ..., then the same tree; region = the box moved outward to multiples of inc
+// one workgroup folds the partials (fold_partials); region = the box moved outward to multiples of inc
 __global__ __launch_bounds__(PTS_THREADS) void region_finish_kernel(const Box* __restrict__ part, int blocks, double inc, double* region,
                                                                     long long* count) {
-  Box r = {INFINITY, -INFINITY, INFINITY, -INFINITY, 0};
-  for (int b = threadIdx.x; b < blocks; b += PTS_THREADS) box_merge(r, part[b]);
-  r = box_block(r);
+  const Box r = fold_partials<PTS_THREADS>(blocks, Box{INFINITY, -INFINITY, INFINITY, -INFINITY, 0}, [part](long b) { return part[b]; }, box_merge);
   if (threadIdx.x != 0) return;
   const double nan = __builtin_nan("");
   const bool any = r.cnt > 0;
@@ -153,61 +130,27 @@ struct Pair {  // (points, non-empty blocks)
   unsigned s, f;
 };
 
-// exclusive scan of one Pair per thread over the workgroup; *total = the workgroup's sum (every thread)
-__device__ Pair block_exscan(Pair v, Pair* total) {
-  __shared__ Pair wsum[PTS_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  Pair inc = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned s = __shfl_up(inc.s, off, 64), f = __shfl_up(inc.f, off, 64);
-    if (lane >= off) { inc.s += s; inc.f += f; }
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  Pair base = {0u, 0u}, tot = {0u, 0u};
-  for (int w = 0; w < PTS_THREADS / 64; ++w) {
-    if (w < wave) { base.s += wsum[w].s; base.f += wsum[w].f; }
-    tot.s += wsum[w].s; tot.f += wsum[w].f;
-  }
-  __syncthreads();   // (wsum is free for the next call)
-  *total = tot;
-  return {base.s + inc.s - v.s, base.f + inc.f - v.f};
-}
+__device__ inline Pair operator+(Pair x, Pair y) { return {x.s + y.s, x.f + y.f}; }
+__device__ inline Pair operator-(Pair x, Pair y) { return {x.s - y.s, x.f - y.f}; }
 
-__device__ inline Pair tile_items(const unsigned* __restrict__ cnt, long hw, long first, unsigned* k) {
-  Pair v = {0u, 0u};
-#pragma unroll
-  for (int j = 0; j < SCAN_ITEMS; ++j) {
-    k[j] = first + j < hw ? cnt[first + j] : 0u;
-    v.s += k[j];
-    v.f += k[j] != 0u;
-  }
-  return v;
+// the calling thread's SCAN_ITEMS consecutive counts of the tile into k; their (sum, number that are not zero)
+__device__ inline Pair tile_counts(const BlockMedianLaunch& a, unsigned* k) {
+  return scan_tile_items<PTS_THREADS, SCAN_ITEMS, Pair>(a.cnt, a.H * a.W, k, [](unsigned c) { return Pair{c, c != 0u ? 1u : 0u}; });
 }
 
 __global__ __launch_bounds__(PTS_THREADS) void bm_tile_sums_kernel(BlockMedianLaunch a) {
   unsigned k[SCAN_ITEMS];
   Pair tot;
-  block_exscan(tile_items(a.cnt, a.H * a.W, (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_ITEMS, k), &tot);
+  block_exscan<PTS_THREADS>(tile_counts(a, k), &tot);
   if (threadIdx.x == 0) a.part[blockIdx.x] = make_uint2(tot.s, tot.f);
 }
 
 // one workgroup: part[t] <- exclusive scan; totals[0] = non-empty blocks, off[H W] = points used, class counters cleared
 __global__ __launch_bounds__(PTS_THREADS) void bm_scan_sums_kernel(BlockMedianLaunch a, long tiles) {
-  Pair carry = {0u, 0u};
-  Pair* part = (Pair*)a.part;
-  for (long t0 = 0; t0 < tiles; t0 += PTS_THREADS) {
-    const long t = t0 + threadIdx.x;
-    const Pair v = t < tiles ? part[t] : Pair{0u, 0u};
-    Pair tot;
-    const Pair ex = block_exscan(v, &tot);
-    if (t < tiles) part[t] = {carry.s + ex.s, carry.f + ex.f};
-    carry.s += tot.s;
-    carry.f += tot.f;
-  }
+  const Pair sum = scan_parts<PTS_THREADS>((Pair*)a.part, tiles);
   if (threadIdx.x == 0) {
-    a.totals[0] = carry.f;
-    a.off[a.H * a.W] = carry.s;
+    a.totals[0] = sum.f;
+    a.off[a.H * a.W] = sum.s;
   }
   if (threadIdx.x >= 1 && threadIdx.x <= DBM_BLOCKMEDIAN_CLASSES) a.totals[threadIdx.x] = 0u;
 }
@@ -219,14 +162,10 @@ __device__ inline int size_class(unsigned k) {
 // off[b], rowof[b] for every block; non-empty blocks appended to their size class's list (one atomic per wave and class: the order of
 // a list is arbitrary, what is computed per block is not)
 __global__ __launch_bounds__(PTS_THREADS) void bm_offsets_kernel(BlockMedianLaunch a) {
-  const long hw = a.H * a.W, first = (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_ITEMS;
+  const long hw = a.H * a.W, first = scan_tile_first<PTS_THREADS, SCAN_ITEMS>();
   unsigned k[SCAN_ITEMS];
   Pair tot;
-  Pair ex = block_exscan(tile_items(a.cnt, hw, first, k), &tot);
-  const Pair base = ((const Pair*)a.part)[blockIdx.x];
-  ex.s += base.s;
-  ex.f += base.f;
-  const int lane = threadIdx.x & 63;
+  Pair ex = block_exscan<PTS_THREADS>(tile_counts(a, k), &tot) + ((const Pair*)a.part)[blockIdx.x];
 #pragma unroll
   for (int j = 0; j < SCAN_ITEMS; ++j) {
     const long b = first + j;
@@ -238,13 +177,8 @@ __global__ __launch_bounds__(PTS_THREADS) void bm_offsets_kernel(BlockMedianLaun
     ex.f += k[j] != 0u;
     const int cls = b < hw ? size_class(k[j]) : -1;
     for (int c = 0; c < DBM_BLOCKMEDIAN_CLASSES; ++c) {
-      const u64 mask = __ballot(cls == c);
-      if (mask == 0ull) continue;
-      const int leader = __ffsll((long long)mask) - 1;
-      unsigned at = 0u;
-      if (lane == leader) at = atomicAdd(&a.totals[1 + c], (unsigned)__popcll(mask));
-      at = __shfl(at, leader, 64);
-      if (cls == c) a.lists[c][at + (unsigned)__popcll(mask & ((1ull << lane) - 1ull))] = (unsigned)b;
+      const unsigned at = wave_append(cls == c, &a.totals[1 + c]);
+      if (cls == c) a.lists[c][at] = (unsigned)b;
     }
   }
 }
@@ -377,7 +311,6 @@ __global__ __launch_bounds__(PTS_THREADS) void bm_global_kernel(BlockMedianLaunc
   }
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline long scan_tiles(long hw) { return (hw + SCAN_TILE - 1) / SCAN_TILE; }
 inline size_t list_capacity(int c, long n, long hw) {   // blocks that can hold more than `floor` points each
   const long floor_k[DBM_BLOCKMEDIAN_CLASSES] = {1, DBM_BLOCKMEDIAN_SUB8 + 1, DBM_BLOCKMEDIAN_SUB32 + 1, DBM_BLOCKMEDIAN_WAVE + 1, DBM_BLOCKMEDIAN_LDS + 1};
@@ -405,28 +338,22 @@ void launch_points_region(const double* pts, long n, int ncol, double inc, void*
   DBM_HIP(hipGetLastError());
 }
 
-size_t blockmedian_workspace(long n, long hw) {
-  size_t b = align256(4 * (size_t)n) * 2;                       // blk, perm
-  b += align256(4 * (size_t)hw) * 2 + align256(4 * (size_t)(hw + 1));   // cnt, rowof, off
-  b += align256(8 * (size_t)scan_tiles(hw));                    // part
-  b += align256(4 * (1 + DBM_BLOCKMEDIAN_CLASSES));             // totals
-  for (int c = 0; c < DBM_BLOCKMEDIAN_CLASSES; ++c) b += align256(4 * list_capacity(c, n, hw));
-  return b;
+// the one layout of the block medians' workspace
+size_t blockmedian_layout(BlockMedianLaunch& a, long n, long hw, Carver c) {
+  a.blk = c.take<int>((size_t)n);
+  a.perm = c.take<unsigned>((size_t)n);
+  a.cnt = c.take<unsigned>((size_t)hw);
+  a.rowof = c.take<unsigned>((size_t)hw);
+  a.off = c.take<unsigned>((size_t)(hw + 1));
+  a.part = c.take<uint2>((size_t)scan_tiles(hw));
+  a.totals = c.take<unsigned>(1 + DBM_BLOCKMEDIAN_CLASSES);
+  for (int k = 0; k < DBM_BLOCKMEDIAN_CLASSES; ++k) a.lists[k] = c.take<unsigned>(list_capacity(k, n, hw));
+  return c.bytes();
 }
 
-void blockmedian_carve(BlockMedianLaunch& a, void* ws) {
-  const long hw = a.H * a.W;
-  char* p = (char*)ws;
-  auto take = [&p](size_t bytes) { char* q = p; p += align256(bytes); return q; };
-  a.blk = (int*)take(4 * (size_t)a.n);
-  a.perm = (unsigned*)take(4 * (size_t)a.n);
-  a.cnt = (unsigned*)take(4 * (size_t)hw);
-  a.rowof = (unsigned*)take(4 * (size_t)hw);
-  a.off = (unsigned*)take(4 * (size_t)(hw + 1));
-  a.part = (uint2*)take(8 * (size_t)scan_tiles(hw));
-  a.totals = (unsigned*)take(4 * (1 + DBM_BLOCKMEDIAN_CLASSES));
-  for (int c = 0; c < DBM_BLOCKMEDIAN_CLASSES; ++c) a.lists[c] = (unsigned*)take(4 * list_capacity(c, a.n, hw));
-}
+size_t blockmedian_workspace(long n, long hw) { BlockMedianLaunch a; return blockmedian_layout(a, n, hw, Carver(nullptr)); }
+
+void blockmedian_carve(BlockMedianLaunch& a, void* ws) { blockmedian_layout(a, a.n, a.H * a.W, Carver(ws)); }
 
 void launch_blockmedian_count(const BlockMedianLaunch& a, hipStream_t s) {
   const long hw = a.H * a.W, tiles = scan_tiles(hw);

@@ -9,7 +9,7 @@
 //              every node.  The same pass counts, per node tile of DBM_POLY_TILE^2 and per band of tile rows, the entries binning would
 //              make, flags non-finite coordinates (the call is then refused before anything is written) and coordinates beyond 2^480
 //              ("wild": the margins below assume no overflow, so such a call runs every edge against every node without shortcuts).
-//   bin      : exclusive scan of the counts (three kernels, the scan shapes of points.hip), then the lists are filled by tile / band.
+//   bin      : exclusive scan of the counts (three kernels, the scan of data_prims.h), then the lists are filled by tile / band.
 //   classify : one 256-thread workgroup per tile, one node per thread.  DBM_POLY_CHUNK edges at a time are staged into LDS by 16-byte
 //              loads (an edge is two of them; lanes 2k, 2k + 1 read the two halves of one edge) and every lane then reads the same LDS
 //              address per edge (a broadcast: no bank conflict).  Proximity first; a wavefront whose nodes are all near has its answer
@@ -26,6 +26,7 @@
 // lies within a few 2^-53 M of [min(xa, xb), max(xa, xb)] whenever the row straddles the edge (|y - ya| <= |ey| after rounding, because
 // rounding is monotone), so the same m decides nodes that far outside the span.
 #include "model.h"
+#include "data_layouts.h"
 #include <cmath>
 
 // the restatement rounds every difference, product, quotient and sum: nothing may be contracted into fused multiply-adds
@@ -51,10 +52,7 @@ struct Span {   // a closed box, or the rows / columns an edge may touch
   double x0, x1, y0, y1;
 };
 
-inline int stride_blocks(long n) {
-  const long b = (n + POLY_THREADS - 1) / POLY_THREADS;
-  return (int)(b < 1 ? 1 : (b > POLY_MAX_BLOCKS ? POLY_MAX_BLOCKS : b));
-}
+inline int stride_blocks(long n) { return grid_stride_blocks(n, POLY_THREADS, POLY_MAX_BLOCKS); }
 
 __device__ inline double node(double o, double d, long i) { return o + (double)i * d; }   // one product, one sum, each rounded
 
@@ -123,17 +121,6 @@ __device__ inline void parity_bands(const PolyLaunch& a, const Edge& e, F f) {
   }
 }
 
-// append to a list: one atomic per wavefront
-__device__ inline void list_append(bool keep, unsigned* list, u64* total, unsigned value) {
-  const u64 mask = __ballot(keep);
-  if (mask == 0ull) return;
-  const int lane = threadIdx.x & 63, leader = __ffsll((long long)mask) - 1;
-  u64 at = 0ull;
-  if (lane == leader) at = atomicAdd(total, (u64)__popcll(mask));
-  at = __shfl(at, leader, 64);
-  if (keep) list[at + (u64)__popcll(mask & ((1ull << lane) - 1ull))] = value;
-}
-
 // totals: [0] proximity list, [1] parity list, [2] non-finite edges, [3] wild edges, [4] / [5] entries the tile / band bins would hold
 __global__ __launch_bounds__(POLY_THREADS) void poly_cull_kernel(PolyLaunch a) {
   const long stride = (long)gridDim.x * POLY_THREADS;
@@ -158,67 +145,34 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_cull_kernel(PolyLaunch a) {
         if (keepB) parity_bands(a, e, [&](long t) { atomicAdd(&a.cnt[bands0 + t], 1u); ++binB; });
       }
     }
-    list_append(keepP, a.listP, &a.totals[0], (unsigned)i);
-    list_append(keepB, a.listB, &a.totals[1], (unsigned)i);
+    const u64 atP = wave_append(keepP, &a.totals[0]), atB = wave_append(keepB, &a.totals[1]);
+    if (keepP) a.listP[atP] = (unsigned)i;
+    if (keepB) a.listB[atB] = (unsigned)i;
   }
   if (binP) atomicAdd(&a.totals[4], binP);
   if (binB) atomicAdd(&a.totals[5], binB);
 }
 
 // ---- exclusive scan of cnt[0 .. nbins) into off (and cursor), off[nbins] = the sum ----
-__device__ unsigned block_exscan(unsigned v, unsigned* total) {
-  __shared__ unsigned wsum[POLY_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned inc = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned s = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += s;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  unsigned base = 0u, tot = 0u;
-  for (int w = 0; w < POLY_THREADS / 64; ++w) {
-    if (w < wave) base += wsum[w];
-    tot += wsum[w];
-  }
-  __syncthreads();   // (wsum is free for the next call)
-  *total = tot;
-  return base + inc - v;
-}
-
-__device__ inline unsigned scan_items(const unsigned* __restrict__ cnt, long n, long first, unsigned* k) {
-  unsigned v = 0u;
-#pragma unroll
-  for (int j = 0; j < SCAN_ITEMS; ++j) {
-    k[j] = first + j < n ? cnt[first + j] : 0u;
-    v += k[j];
-  }
-  return v;
+__device__ inline unsigned tile_counts(const PolyLaunch& a, unsigned* k) {
+  return scan_tile_items<POLY_THREADS, SCAN_ITEMS, unsigned>(a.cnt, a.nbins, k, [](unsigned c) { return c; });
 }
 
 __global__ __launch_bounds__(POLY_THREADS) void poly_scan_sums_kernel(PolyLaunch a) {
   unsigned k[SCAN_ITEMS], tot;
-  block_exscan(scan_items(a.cnt, a.nbins, (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_ITEMS, k), &tot);
+  block_exscan<POLY_THREADS>(tile_counts(a, k), &tot);
   if (threadIdx.x == 0) a.part[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(POLY_THREADS) void poly_scan_parts_kernel(PolyLaunch a, long tiles) {
-  unsigned carry = 0u;
-  for (long t0 = 0; t0 < tiles; t0 += POLY_THREADS) {
-    const long t = t0 + threadIdx.x;
-    const unsigned v = t < tiles ? a.part[t] : 0u;
-    unsigned tot;
-    const unsigned ex = block_exscan(v, &tot);
-    if (t < tiles) a.part[t] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) a.off[a.nbins] = carry;
+  const unsigned sum = scan_parts<POLY_THREADS>(a.part, tiles);
+  if (threadIdx.x == 0) a.off[a.nbins] = sum;
 }
 
 __global__ __launch_bounds__(POLY_THREADS) void poly_scan_offsets_kernel(PolyLaunch a) {
-  const long first = (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_ITEMS;
+  const long first = scan_tile_first<POLY_THREADS, SCAN_ITEMS>();
   unsigned k[SCAN_ITEMS], tot;
-  unsigned ex = block_exscan(scan_items(a.cnt, a.nbins, first, k), &tot) + a.part[blockIdx.x];
+  unsigned ex = block_exscan<POLY_THREADS>(tile_counts(a, k), &tot) + a.part[blockIdx.x];
 #pragma unroll
   for (int j = 0; j < SCAN_ITEMS; ++j) {
     if (first + j < a.nbins) {
@@ -335,7 +289,6 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_classify_kernel(PolyLaunch 
   if (a.grid && !in) a.grid[at] = __builtin_nanf("");
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline long scan_tiles(long n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 
 }  // namespace
@@ -354,27 +307,22 @@ void polygon_geometry(PolyLaunch& a) {
   a.identity = !(a.gmag <= WILD) ? 1 : 0;
 }
 
-size_t polygon_workspace(const PolyLaunch& a, bool stage_edges_too) {
-  size_t b = align256(sizeof(u64) * 8);                               // totals
-  b += align256(4 * (size_t)a.n) * 2;                                 // listP, listB
-  b += align256(4 * (size_t)a.nbins) * 2 + align256(4 * (size_t)(a.nbins + 1));   // cnt, cursor, off
-  b += align256(4 * (size_t)scan_tiles(a.nbins));                     // part
-  if (stage_edges_too) b += align256(32 * (size_t)a.n);
-  return b;
+// the one layout of the workspace; *staged = room for a host table of edges (32 bytes each) if asked for, else null
+size_t polygon_layout(PolyLaunch& a, bool stage_edges_too, double** staged, Carver c) {
+  a.totals = c.take<u64>(8);
+  a.listP = c.take<unsigned>((size_t)a.n);
+  a.listB = c.take<unsigned>((size_t)a.n);
+  a.cnt = c.take<unsigned>((size_t)a.nbins);
+  a.cursor = c.take<unsigned>((size_t)a.nbins);
+  a.off = c.take<unsigned>((size_t)(a.nbins + 1));
+  a.part = c.take<unsigned>((size_t)scan_tiles(a.nbins));
+  *staged = stage_edges_too ? c.take<double>(4 * (size_t)a.n) : nullptr;
+  return c.bytes();
 }
 
-double* polygon_carve(PolyLaunch& a, void* ws, bool stage_edges_too) {
-  char* p = (char*)ws;
-  auto take = [&p](size_t bytes) { char* q = p; p += align256(bytes); return q; };
-  a.totals = (u64*)take(sizeof(u64) * 8);
-  a.listP = (unsigned*)take(4 * (size_t)a.n);
-  a.listB = (unsigned*)take(4 * (size_t)a.n);
-  a.cnt = (unsigned*)take(4 * (size_t)a.nbins);
-  a.cursor = (unsigned*)take(4 * (size_t)a.nbins);
-  a.off = (unsigned*)take(4 * (size_t)(a.nbins + 1));
-  a.part = (unsigned*)take(4 * (size_t)scan_tiles(a.nbins));
-  return stage_edges_too ? (double*)take(32 * (size_t)a.n) : nullptr;
-}
+size_t polygon_workspace(const PolyLaunch& a, bool stage_edges_too) { PolyLaunch b = a; double* e; return polygon_layout(b, stage_edges_too, &e, Carver(nullptr)); }
+
+double* polygon_carve(PolyLaunch& a, void* ws, bool stage_edges_too) { double* e; polygon_layout(a, stage_edges_too, &e, Carver(ws)); return e; }
 
 void launch_polygon_cull(const PolyLaunch& a, hipStream_t s) {
   DBM_HIP(hipMemsetAsync(a.totals, 0, sizeof(u64) * 8, s));

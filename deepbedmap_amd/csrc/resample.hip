@@ -24,6 +24,7 @@
 //   shifted by one of them (the centre node, else the first valid node in row-major order), so that nothing cancels and a constant window
 //   gives exactly 0.
 #include "model.h"
+#include "data_prims.h"
 #include <cmath>
 
 namespace {
@@ -75,45 +76,32 @@ __device__ inline double mirror_coordinate(double c, long n) {
   return c;
 }
 
+struct MinMax {
+  double mn, mx;
+};
+__device__ inline MinMax minmax_merge(const MinMax& a, const MinMax& b) { return {fmin(a.mn, b.mn), fmax(a.mx, b.mx)}; }
+
 __global__ __launch_bounds__(RS_THREADS) void minmax_kernel(Src src, long total, double* part) {
-  __shared__ double smn[RS_THREADS / 64], smx[RS_THREADS / 64];
-  double mn = INFINITY, mx = -INFINITY;
+  MinMax m = {INFINITY, -INFINITY};
   const long stride = (long)gridDim.x * RS_THREADS;
   for (long i = (long)blockIdx.x * RS_THREADS + threadIdx.x; i < total; i += stride) {
     const double v = src.at(i);
-    mn = fmin(mn, v);
-    mx = fmax(mx, v);
+    m.mn = fmin(m.mn, v);
+    m.mx = fmax(m.mx, v);
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    mn = fmin(mn, __shfl_down(mn, off, 64));
-    mx = fmax(mx, __shfl_down(mx, off, 64));
-  }
-  if ((threadIdx.x & 63) == 0) { smn[threadIdx.x >> 6] = mn; smx[threadIdx.x >> 6] = mx; }
-  __syncthreads();
+  m = block_reduce<RS_THREADS>(m, minmax_merge);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < RS_THREADS / 64; ++w) { mn = fmin(mn, smn[w]); mx = fmax(mx, smx[w]); }
-    part[2 * (long)blockIdx.x] = mn;
-    part[2 * (long)blockIdx.x + 1] = mx;
+    part[2 * (long)blockIdx.x] = m.mn;
+    part[2 * (long)blockIdx.x + 1] = m.mx;
   }
 }
 
 __global__ __launch_bounds__(RS_THREADS) void minmax_finish_kernel(const double* part, int blocks, double* out) {
-  __shared__ double smn[RS_THREADS / 64], smx[RS_THREADS / 64];
-  double mn = INFINITY, mx = -INFINITY;
-  for (int b = threadIdx.x; b < blocks; b += RS_THREADS) {
-    mn = fmin(mn, part[2 * b]);
-    mx = fmax(mx, part[2 * b + 1]);
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    mn = fmin(mn, __shfl_down(mn, off, 64));
-    mx = fmax(mx, __shfl_down(mx, off, 64));
-  }
-  if ((threadIdx.x & 63) == 0) { smn[threadIdx.x >> 6] = mn; smx[threadIdx.x >> 6] = mx; }
-  __syncthreads();
+  const MinMax m = fold_partials<RS_THREADS>(blocks, MinMax{INFINITY, -INFINITY}, [part](long b) { return MinMax{part[2 * b], part[2 * b + 1]}; },
+                                             minmax_merge);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < RS_THREADS / 64; ++w) { mn = fmin(mn, smn[w]); mx = fmax(mx, smx[w]); }
-    out[0] = mn;
-    out[1] = mx;
+    out[0] = m.mn;
+    out[1] = m.mx;
   }
 }
 

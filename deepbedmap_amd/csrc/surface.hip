@@ -17,6 +17,7 @@
 // Every kernel returns at once when `done` is up, so the host may enqueue 32 iterations before it reads the state back.  No float
 // atomics; launch shapes depend on H and W only: the same bytes from call to call.
 #include "model.h"
+#include "data_layouts.h"
 #include <cmath>
 
 namespace {
@@ -45,20 +46,15 @@ __device__ inline double load_agent(const double* p) {
                                                            __HIP_MEMORY_SCOPE_AGENT));
 }
 
-// sums of a and b over the workgroup: lanes (fixed shuffle tree), then the waves in order; valid in thread 0
+// two sums that travel through one reduction tree (block_reduce: valid in thread 0)
+struct Sum2 {
+  double a, b;
+};
+__device__ inline Sum2 sum2_merge(const Sum2& x, const Sum2& y) { return {x.a + y.a, x.b + y.b}; }
 __device__ inline void block_sum2(double& a, double& b) {
-  __shared__ double sh[2][SURF_THREADS / 64];
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_down(a, off, 64);
-    b += __shfl_down(b, off, 64);
-  }
-  __syncthreads();   // (the words may still be read from a previous call)
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = a; sh[1][threadIdx.x >> 6] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = sh[0][0]; b = sh[1][0];
-    for (int w = 1; w < SURF_THREADS / 64; ++w) { a += sh[0][w]; b += sh[1][w]; }
-  }
+  const Sum2 r = block_reduce<SURF_THREADS, true>(Sum2{a, b}, sum2_merge);
+  a = r.a;
+  b = r.b;
 }
 
 // thread 0 has stored this workgroup's partials (store_agent); true in every thread of the workgroup that arrives last
@@ -73,14 +69,12 @@ __device__ inline bool arrive_last(unsigned* ticket, unsigned nblocks) {
   return last != 0u;
 }
 
-// the last workgroup: thread k folds the partials k, k + 256, ... (stride 2: two sums per workgroup) in order, then the fixed tree
-__device__ inline void fold_partials(const double* part, unsigned nblocks, double& a, double& b) {
-  a = 0.0; b = 0.0;
-  for (unsigned k = threadIdx.x; k < nblocks; k += SURF_THREADS) {
-    a += load_agent(part + 2 * (size_t)k);
-    b += load_agent(part + 2 * (size_t)k + 1);
-  }
-  block_sum2(a, b);
+// the last workgroup folds the two sums of every workgroup (fold_partials), read past the caches
+__device__ inline void fold_sums(const double* part, unsigned nblocks, double& a, double& b) {
+  const Sum2 r = fold_partials<SURF_THREADS, true>(nblocks, Sum2{0.0, 0.0}, [part](long k) { return Sum2{load_agent(part + 2 * k), load_agent(part + 2 * k + 1)}; },
+                                             sum2_merge);
+  a = r.a;
+  b = r.b;
 }
 
 // diagonal of A at node (r, c): the squared coefficients of the differences that exist and contain the node
@@ -184,7 +178,7 @@ __global__ __launch_bounds__(SURF_THREADS) void surface_operator_kernel(const do
   }
   if (!arrive_last(&st->ticket[0], gridDim.x)) return;
   double pap, zero;
-  fold_partials(part, gridDim.x, pap, zero);
+  fold_sums(part, gridDim.x, pap, zero);
   if (threadIdx.x == 0) {
     st->pap = pap;
     st->alpha = pap > 0.0 ? st->rz / pap : 0.0;
@@ -219,7 +213,7 @@ __global__ __launch_bounds__(SURF_THREADS) void surface_update_kernel(double* __
     store_agent(part + 2 * (size_t)blockIdx.x + 1, rr);
   }
   if (!arrive_last(&st->ticket[1], gridDim.x)) return;
-  fold_partials(part, gridDim.x, rz, rr);
+  fold_sums(part, gridDim.x, rz, rr);
   if (threadIdx.x != 0) return;
   if (start) {
     st->bb = rr;
@@ -279,37 +273,37 @@ __global__ __launch_bounds__(SURF_THREADS) void surface_mask_kernel(const float*
   }
 }
 
-int flat_blocks(long n) {
-  const long b = (n + SURF_THREADS - 1) / SURF_THREADS;
-  return (int)(b < 1 ? 1 : (b > SURF_MAX_BLOCKS ? SURF_MAX_BLOCKS : b));
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+int flat_blocks(long n) { return grid_stride_blocks(n, SURF_THREADS, SURF_MAX_BLOCKS); }
 
 }  // namespace
 
 static long surface_tiles(long H, long W) { return ((H + SURF_TR - 1) / SURF_TR) * ((W + SURF_TC - 1) / SURF_TC); }
 
-size_t surface_workspace(long H, long W) {
-  const size_t n = (size_t)H * (size_t)W;
-  const size_t parts = 2 * sizeof(double) * (size_t)(surface_tiles(H, W) > SURF_MAX_BLOCKS ? surface_tiles(H, W) : SURF_MAX_BLOCKS);
-  return align256(sizeof(SurfState)) + align256(parts) + 4 * align256(n * sizeof(double)) + align256(n);
+// the one layout of the workspace.  part: two sums per workgroup of whichever launch has more of them, the operator's tiles or the
+// elementwise kernels' SURF_MAX_BLOCKS
+size_t surface_layout(SurfaceArrays& v, long H, long W, Carver c) {
+  const size_t n = (size_t)H * (size_t)W, tiles = (size_t)surface_tiles(H, W);
+  v.state = c.take<SurfState>(1);
+  v.part = c.take<double>(2 * (tiles > SURF_MAX_BLOCKS ? tiles : (size_t)SURF_MAX_BLOCKS));
+  v.x = c.take<double>(n);
+  v.r = c.take<double>(n);
+  v.p = c.take<double>(n);
+  v.ap = c.take<double>(n);
+  v.mask = c.take<unsigned char>(n);
+  return c.bytes();
 }
+
+size_t surface_workspace(long H, long W) { SurfaceArrays v; return surface_layout(v, H, W, Carver(nullptr)); }
 
 bool surface_solve(const SurfaceLaunch& a, void* ws, hipStream_t s, double info[4]) {
   const long H = a.H, W = a.W, n = H * W;
   const long tiles = surface_tiles(H, W);
   const unsigned ntx = (unsigned)((W + SURF_TC - 1) / SURF_TC);
-  const size_t parts = 2 * sizeof(double) * (size_t)(tiles > SURF_MAX_BLOCKS ? tiles : SURF_MAX_BLOCKS);
-  const size_t plane = align256((size_t)n * sizeof(double));
-  char* q = (char*)ws;
-  SurfState* st = (SurfState*)q;  q += align256(sizeof(SurfState));
-  double* part = (double*)q;      q += align256(parts);
-  double* x = (double*)q;         q += plane;
-  double* r = (double*)q;         q += plane;
-  double* p = (double*)q;         q += plane;
-  double* ap = (double*)q;        q += plane;
-  unsigned char* mask = (unsigned char*)q;
+  SurfaceArrays v;
+  surface_layout(v, H, W, Carver(ws));
+  SurfState* st = (SurfState*)v.state;
+  double *part = v.part, *x = v.x, *r = v.r, *p = v.p, *ap = v.ap;
+  unsigned char* mask = v.mask;
   const int fb = flat_blocks(n);
   const dim3 blk(SURF_THREADS);
   SurfState host;

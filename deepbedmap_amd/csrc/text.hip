@@ -3,8 +3,8 @@
 //   - structure pass: a workgroup stages one tile of DBM_TEXT_TILE_BYTES of text in LDS with 16-byte loads (lane i loads bytes 16 i ..
 //     16 i + 15 of a 4 KiB slice: consecutive lanes, consecutive addresses) and leaves a newline bit per byte beside it; thread t owns the 64
 //     bytes 64 t .. 64 t + 63 of the tile and every line that STARTS there.  Per tile: lines started, and how many of them are not
-//     blank.  One workgroup scans the tiles' sums (the three-kernel scan of points.hip -- workgroup sums, one workgroup over the sums,
-//     rescan -- with 64-bit counters: a file above 4 GiB can hold more than 2^32 lines);
+//     blank.  One workgroup scans the tiles' sums (the three-kernel scan of data_prims.h -- workgroup sums, one workgroup over the
+//     sums, rescan -- with 64-bit counters: a file above 4 GiB can hold more than 2^32 lines);
 //   - parse pass: the same staging; the rescan gives every line its index among the non-blank lines, the first skip + 1 of them are
 //     left alone, line skip + 1 + k is candidate row k.  Its thread walks it out of LDS (out of global memory past the tile's end: a line
 //     belongs to the tile it starts in, however long it is), converts the used fields and writes them to row k of a scratch table,
@@ -16,9 +16,14 @@
 // double(w) / 10^-e, ONE IEEE operation on two exactly representable operands, hence correctly rounded.  Everything else that matches
 // the grammar is left to the host (flag bit 1), never guessed.  All byte offsets are 64-bit.
 #include "model.h"
+#include "data_layouts.h"
 
 // one rounding per operation: no fused multiply-add may appear in the conversion
 #pragma clang fp contract(off)
+
+// (in TextPair's own namespace, where the scan templates look for them)
+__device__ inline TextPair operator+(TextPair x, TextPair y) { return {x.a + y.a, x.b + y.b}; }
+__device__ inline TextPair operator-(TextPair x, TextPair y) { return {x.a - y.a, x.b - y.b}; }
 
 namespace {
 
@@ -37,42 +42,12 @@ __device__ const double P10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7
 
 typedef TextPair Pair64;
 
-// exclusive scan of one Pair64 per thread over the workgroup; *total = the workgroup's sum (every thread): points.hip's block_exscan
-__device__ Pair64 block_exscan64(Pair64 v, Pair64* total) {
-  __shared__ Pair64 wsum[TXT_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  Pair64 inc = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const u64 a = __shfl_up(inc.a, off, 64), b = __shfl_up(inc.b, off, 64);
-    if (lane >= off) { inc.a += a; inc.b += b; }
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  Pair64 base = {0ull, 0ull}, tot = {0ull, 0ull};
-  for (int w = 0; w < TXT_THREADS / 64; ++w) {
-    if (w < wave) { base.a += wsum[w].a; base.b += wsum[w].b; }
-    tot.a += wsum[w].a; tot.b += wsum[w].b;
-  }
-  __syncthreads();   // (wsum is free for the next call)
-  *total = tot;
-  return {base.a + inc.a - v.a, base.b + inc.b - v.b};
-}
-
 // one workgroup: part[t] <- exclusive scan over t; out[0], out[1] = the sums
 __global__ __launch_bounds__(TXT_THREADS) void text_scan_sums_kernel(Pair64* part, long n, u64* out) {
-  Pair64 carry = {0ull, 0ull};
-  for (long t0 = 0; t0 < n; t0 += TXT_THREADS) {
-    const long t = t0 + threadIdx.x;
-    const Pair64 v = t < n ? part[t] : Pair64{0ull, 0ull};
-    Pair64 tot;
-    const Pair64 ex = block_exscan64(v, &tot);
-    if (t < n) part[t] = {carry.a + ex.a, carry.b + ex.b};
-    carry.a += tot.a;
-    carry.b += tot.b;
-  }
+  const Pair64 sum = scan_parts<TXT_THREADS>(part, n);
   if (threadIdx.x == 0) {
-    out[0] = carry.a;
-    out[1] = carry.b;
+    out[0] = sum.a;
+    out[1] = sum.b;
   }
 }
 
@@ -162,7 +137,7 @@ __global__ __launch_bounds__(TXT_THREADS) void text_structure_kernel(TextLaunch 
   stage_tile(a, base, L);
   u64 ink;
   Pair64 tot;
-  block_exscan64(owned_lines(a, L, base, owned_starts(a, L, base), &ink), &tot);
+  block_exscan<TXT_THREADS>(owned_lines(a, L, base, owned_starts(a, L, base), &ink), &tot);
   if (threadIdx.x == 0) a.tiles[blockIdx.x] = tot;
 }
 
@@ -340,7 +315,7 @@ __global__ __launch_bounds__(TXT_THREADS) void text_parse_kernel(TextLaunch a) {
   const u64 starts = owned_starts(a, L, base);
   u64 ink;
   Pair64 tot;
-  const Pair64 ex = block_exscan64(owned_lines(a, L, base, starts, &ink), &tot);
+  const Pair64 ex = block_exscan<TXT_THREADS>(owned_lines(a, L, base, starts, &ink), &tot);
   u64 rank = a.tiles[blockIdx.x].b + ex.b;   // non-blank lines in front of this thread's
   const u64 first = base + (u64)(TXT_OWN * (int)threadIdx.x);
   for (u64 rest = ink; rest; rest &= rest - 1ull) {
@@ -351,33 +326,25 @@ __global__ __launch_bounds__(TXT_THREADS) void text_parse_kernel(TextLaunch a) {
 }
 
 // ---- compaction ----
-__device__ inline Pair64 flag_items(const unsigned char* __restrict__ flags, u64 n, u64 first, unsigned char* k) {
-  Pair64 v = {0ull, 0ull};
-#pragma unroll
-  for (int j = 0; j < TXT_SCAN_ITEMS; ++j) {
-    k[j] = first + j < n ? flags[first + j] : (unsigned char)0;
-    v.a += k[j] & 1;
-    v.b += (k[j] >> 1) & 1;
-  }
-  return v;
+// the calling thread's TXT_SCAN_ITEMS consecutive flag bytes into k; how many are (kept, left to the host)
+__device__ inline Pair64 flag_counts(const TextLaunch& a, unsigned char* k) {
+  return scan_tile_items<TXT_THREADS, TXT_SCAN_ITEMS, Pair64>(a.flags, (long)a.ncand, k,
+                                                             [](unsigned char f) { return Pair64{f & 1ull, (f >> 1) & 1ull}; });
 }
 
 __global__ __launch_bounds__(TXT_THREADS) void text_flag_sums_kernel(TextLaunch a) {
   unsigned char k[TXT_SCAN_ITEMS];
   Pair64 tot;
-  block_exscan64(flag_items(a.flags, a.ncand, (u64)blockIdx.x * TXT_SCAN_TILE + (u64)threadIdx.x * TXT_SCAN_ITEMS, k), &tot);
+  block_exscan<TXT_THREADS>(flag_counts(a, k), &tot);
   if (threadIdx.x == 0) a.parts[blockIdx.x] = tot;
 }
 
 // kept candidates to their final rows (file order); candidates that need the host to repair[2 j] = byte offset, [2 j + 1] = final row
 __global__ __launch_bounds__(TXT_THREADS) void text_compact_kernel(TextLaunch a) {
-  const u64 first = (u64)blockIdx.x * TXT_SCAN_TILE + (u64)threadIdx.x * TXT_SCAN_ITEMS;
+  const u64 first = (u64)scan_tile_first<TXT_THREADS, TXT_SCAN_ITEMS>();
   unsigned char k[TXT_SCAN_ITEMS];
   Pair64 tot;
-  Pair64 ex = block_exscan64(flag_items(a.flags, a.ncand, first, k), &tot);
-  const Pair64 before = a.parts[blockIdx.x];
-  ex.a += before.a;
-  ex.b += before.b;
+  Pair64 ex = block_exscan<TXT_THREADS>(flag_counts(a, k), &tot) + a.parts[blockIdx.x];
 #pragma unroll
   for (int j = 0; j < TXT_SCAN_ITEMS; ++j) {
     if (k[j] & 1) {
@@ -407,33 +374,30 @@ __global__ __launch_bounds__(TXT_THREADS) void text_columns_kernel(ColumnsLaunch
   }
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 long text_tiles(size_t nbytes) { return (long)((nbytes + TXT_TILE - 1) / TXT_TILE); }
 long text_scan_tiles(size_t ncand) { return (long)((ncand + TXT_SCAN_TILE - 1) / TXT_SCAN_TILE); }
 
-size_t text_structure_workspace(size_t nbytes) { return align256(sizeof(Pair64) * (size_t)text_tiles(nbytes)) + 256; }
-
-void text_structure_carve(TextLaunch& a, void* ws) {
-  a.tiles = (TextPair*)ws;
-  a.totals = (unsigned long long*)((char*)ws + align256(sizeof(Pair64) * (size_t)text_tiles(a.len)));
-  a.first_error = a.totals + 2;
+// the one layout of each workspace.  totals: 5 counters (first_error is totals[2]) in a 256-byte slot of their own
+size_t text_structure_layout(TextLaunch& a, size_t nbytes, Carver c) {
+  a.tiles = c.take<TextPair>((size_t)text_tiles(nbytes));
+  a.totals = c.take<unsigned long long>(5);
+  a.first_error = a.totals ? a.totals + 2 : nullptr;
+  return c.bytes();
+}
+size_t text_parse_layout(TextLaunch& a, size_t ncand, int nuse, Carver c) {
+  a.rows = c.take<double>(ncand * (size_t)nuse);
+  a.offs = c.take<unsigned long long>(ncand);
+  a.flags = c.take<unsigned char>(ncand);
+  a.parts = c.take<TextPair>((size_t)text_scan_tiles(ncand));
+  return c.bytes();
 }
 
-size_t text_parse_workspace(size_t ncand, int nuse) {
-  return align256(8 * ncand * (size_t)nuse) + align256(8 * ncand) + align256(ncand) + align256(sizeof(Pair64) * (size_t)text_scan_tiles(ncand));
-}
-
-void text_parse_carve(TextLaunch& a, void* ws) {
-  char* p = (char*)ws;
-  auto take = [&p](size_t bytes) { char* q = p; p += align256(bytes); return q; };
-  a.rows = (double*)take(8 * (size_t)a.ncand * (size_t)a.nuse);
-  a.offs = (unsigned long long*)take(8 * (size_t)a.ncand);
-  a.flags = (unsigned char*)take((size_t)a.ncand);
-  a.parts = (TextPair*)take(sizeof(Pair64) * (size_t)text_scan_tiles(a.ncand));
-}
+size_t text_structure_workspace(size_t nbytes) { TextLaunch a; return text_structure_layout(a, nbytes, Carver(nullptr)); }
+void text_structure_carve(TextLaunch& a, void* ws) { text_structure_layout(a, a.len, Carver(ws)); }
+size_t text_parse_workspace(size_t ncand, int nuse) { TextLaunch a; return text_parse_layout(a, ncand, nuse, Carver(nullptr)); }
+void text_parse_carve(TextLaunch& a, void* ws) { text_parse_layout(a, a.ncand, a.nuse, Carver(ws)); }
 
 // totals[0], [1] = lines, non-blank lines; the tiles' entries become the counts in front of each tile; totals[2] = no error yet
 void launch_text_structure(const TextLaunch& a, hipStream_t s) {
@@ -461,7 +425,6 @@ void launch_text_compact(const TextLaunch& a, hipStream_t s) {
 
 void launch_text_columns(const ColumnsLaunch& a, hipStream_t s) {
   if (a.n == 0) return;
-  const unsigned long long blocks = (a.n + TXT_THREADS - 1) / TXT_THREADS;
-  hipLaunchKernelGGL(text_columns_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(TXT_THREADS), 0, s, a);
+  hipLaunchKernelGGL(text_columns_kernel, dim3(grid_stride_blocks((long)a.n, TXT_THREADS, 4096)), dim3(TXT_THREADS), 0, s, a);
   DBM_HIP(hipGetLastError());
 }

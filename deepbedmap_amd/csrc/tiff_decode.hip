@@ -21,17 +21,11 @@
 //     gathered into little-endian samples), convert to float32 as numpy.astype does, write at the block's place in the output plane;
 //     samples outside the plane (tile padding, the part of a block outside the window) are dropped.
 #include "model.h"
+#include "data_prims.h"
 
 namespace {
 
 constexpr int ROW_THREADS = 256;
-
-__host__ __device__ inline void lanes_fence() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  // the lanes of one wave hand bytes to each other through memory: order the wave's own stores before its later loads
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#endif
-}
 
 // Decodes src[0, n) into dst[0, cap).  Returns the decoded size, or (size_t)-1 on the conditions lzw_decode_one returns it: a first code
 // above 255, a code above `next`, more output than cap.  A stream that ends without EndOfInformation is not an error here (the caller
@@ -122,37 +116,26 @@ __device__ inline void store_le(uint8_t* p, int w, unsigned long long v) {
 
 // workgroup idx -> (block b, row r of the block).  Rows of a block are independent: the predictors run along rows only.
 __global__ __launch_bounds__(ROW_THREADS) void tiff_rows_kernel(TiffDecodeLaunch a) {
-  __shared__ unsigned long long wsum[ROW_THREADS / 64];
   const long b = (long)blockIdx.x / a.block_h, r = (long)blockIdx.x - b * a.block_h;
   const long* e = a.blocks + 8 * b;
   const long orow = e[3] + r;
   if (r >= e[2] || orow < 0 || orow >= a.out_h) return;   // (uniform in the workgroup)
   uint8_t* row = (a.lzw ? a.stage + b * a.block_stride : a.stage + e[0]) + r * (long)a.block_w * a.bytes;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   if (a.predictor != 1) {
     const int w = a.predictor == 2 ? a.bytes : 1;                        // element width of the running sum
     const long count = a.predictor == 2 ? a.block_w : (long)a.block_w * a.bytes;
     unsigned long long carry = 0;
     for (long i0 = 0; i0 < count; i0 += ROW_THREADS) {
       const long i = i0 + tid;
-      unsigned long long v = i < count ? load_le(row + i * w, w) : 0ull;
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-      }
-      if (lane == 63) wsum[wave] = v;
-      __syncthreads();
-      unsigned long long before = carry, total = 0;
-      for (int k = 0; k < ROW_THREADS / 64; ++k) {
-        if (k < wave) before += wsum[k];
-        total += wsum[k];
-      }
-      if (i < count) store_le(row + i * w, w, v + before);   // (the store keeps the low 8 w bits: the sum wraps in the sample's width)
+      const unsigned long long v = i < count ? load_le(row + i * w, w) : 0ull;
+      unsigned long long total;
+      const unsigned long long before = carry + block_exscan<ROW_THREADS>(v, &total);
+      if (i < count) store_le(row + i * w, w, before + v);   // (the store keeps the low 8 w bits: the sum wraps in the sample's width)
       carry += total;
-      __syncthreads();
     }
+    __syncthreads();   // the row's bytes are visible to the whole workgroup (the scan's own barriers come before its round's stores)
   }
-  // (the last __syncthreads of the scan makes the row's bytes visible to the whole workgroup)
   const long ocol0 = e[4];
   uint32_t* out = (uint32_t*)a.out + orow * a.out_w;
   for (long c = tid; c < a.block_w; c += ROW_THREADS) {

@@ -28,19 +28,13 @@
 // (c) tiff_pack_kernel -- the streams from their slots (stride = capacity = block_bytes * 3 / 2 + 64, the host encoder's bound) to the
 //     even-aligned offsets the host computed from the downloaded sizes; one D2H copy then brings them over.
 #include "model.h"
+#include "data_prims.h"
 
 namespace {
 
 constexpr int ROW_THREADS = 256;
 constexpr uint32_t LZW_SLOTS = 8192, LZW_ROWS = LZW_SLOTS / 64, LZW_EMPTY = 0xFFFFFFFFu;
 constexpr int PACK_PARTS = 16;
-
-__host__ __device__ inline void lanes_fence() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  // the lanes of one wave hand table words to each other through LDS: order the wave's own stores before its later loads
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#endif
-}
 
 // ---- lane primitives: the only code that differs between the device and the host twin ----
 // One row of the table (64 slots) against `key`: true and the entry's code if a slot holds the key; else `empty` = index in the row of

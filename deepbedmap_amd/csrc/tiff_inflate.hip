@@ -47,15 +47,9 @@
 // inflate_lanes is __host__ __device__: with (lane, lanes) = (0, 1) it is the host twin (dbm_inflate) that tools/inflate_twin_check.cpp
 // runs against zlib and tests/test_inflate_host.py against zlib and a plain restatement.
 #include "model.h"
+#include "data_prims.h"
 
 namespace {
-
-__host__ __device__ inline void lanes_fence() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  // the lanes of one wave hand bytes to each other through memory (LDS and global): order the wave's own stores before its later loads
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#endif
-}
 
 // a value that is the same in every lane, as a scalar
 __host__ __device__ inline uint32_t uni(uint32_t v) {

@@ -10,6 +10,7 @@
 //   - NaN nodes: with V the non-NaN stencil nodes and wsum their weight sum, the result is sum_V w z / wsum if wsum + 1e-9 >= threshold,
 //     else NaN (no division when every node is valid).
 #include "model.h"
+#include "data_prims.h"
 #include <cmath>
 
 namespace {
@@ -45,27 +46,6 @@ __device__ inline Moments moments_merge(const Moments& a, const Moments& b) {  /
   r.mn = fmin(a.mn, b.mn);
   r.mx = fmax(a.mx, b.mx);
   return r;
-}
-
-__device__ inline Moments moments_shfl_down(const Moments& a, int off) {
-  return {__shfl_down(a.n, off, 64), __shfl_down(a.mean, off, 64), __shfl_down(a.m2, off, 64),
-          __shfl_down(a.ss, off, 64), __shfl_down(a.mn, off, 64), __shfl_down(a.mx, off, 64)};
-}
-
-// lanes (fixed shuffle tree), then the workgroup's waves in order; the result is valid in thread 0
-__device__ Moments moments_block(Moments m) {
-  __shared__ Moments sh[TRACK_THREADS / 64];
-  for (int off = 32; off > 0; off >>= 1) {
-    const Moments o = moments_shfl_down(m, off);
-    if ((threadIdx.x & 63) < off) m = moments_merge(m, o);
-  }
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = sh[0];
-    for (int w = 1; w < TRACK_THREADS / 64; ++w) m = moments_merge(m, sh[w]);
-  }
-  return m;
 }
 
 // value of the (possibly ghost) node (rr, cc), rr in [-2, H+1], cc in [-2, W+1]; H, W >= 2
@@ -166,22 +146,19 @@ __global__ __launch_bounds__(TRACK_THREADS) void grid_track_kernel(TrackLaunch a
     }
   }
   if (!a.part) return;
-  m = moments_block(m);
+  m = block_reduce<TRACK_THREADS>(m, moments_merge);
   if (threadIdx.x == 0) {
     double* o = a.part + 6 * (long)blockIdx.x;
     o[0] = m.n; o[1] = m.mean; o[2] = m.m2; o[3] = m.ss; o[4] = m.mn; o[5] = m.mx;
   }
 }
 
-// one workgroup: thread k folds the partials k, k + 256, ... in order, then the fixed tree; stats = count, mean, std (ddof 1),
-// min, max, rmse
+// one workgroup folds the partials in order (fold_partials); stats = count, mean, std (ddof 1), min, max, rmse
 __global__ __launch_bounds__(TRACK_THREADS) void grid_track_finish_kernel(const double* __restrict__ part, int blocks, double* stats) {
-  Moments m = moments_empty();
-  for (int b = threadIdx.x; b < blocks; b += TRACK_THREADS) {
-    const double* q = part + 6 * (long)b;
-    m = moments_merge(m, Moments{q[0], q[1], q[2], q[3], q[4], q[5]});
-  }
-  m = moments_block(m);
+  const Moments m = fold_partials<TRACK_THREADS>(blocks, moments_empty(), [part](long b) {
+    const double* q = part + 6 * b;
+    return Moments{q[0], q[1], q[2], q[3], q[4], q[5]};
+  }, moments_merge);
   if (threadIdx.x != 0) return;
   const double nan = __builtin_nan("");
   stats[0] = m.n;
@@ -203,10 +180,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void grid_to_pixel_kernel(TrackLaunc
 
 }  // namespace
 
-int grid_track_blocks(long n) {
-  const long b = (n + TRACK_THREADS - 1) / TRACK_THREADS;
-  return (int)(b < 1 ? 1 : (b > TRACK_MAX_BLOCKS ? TRACK_MAX_BLOCKS : b));
-}
+int grid_track_blocks(long n) { return grid_stride_blocks(n, TRACK_THREADS, TRACK_MAX_BLOCKS); }
 
 void launch_grid_track(const TrackLaunch& a, double* stats, hipStream_t s) {
   const int blocks = grid_track_blocks(a.n);

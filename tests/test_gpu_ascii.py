@@ -235,6 +235,31 @@ def test_dropping_keeps_file_order_and_is_deterministic(dbm):
     assert agree(dbm, every, ",", 0, names, names).shape == (0, 4)
 
 
+def test_compaction_past_one_round_of_the_tile_scan(dbm):
+    """256 * 2048 + 1 candidates: 257 scan tiles of the flag bytes, so the one-workgroup pass over the tiles' sums takes a second round
+    and the compaction's rescan adds a base that round produced (candidate 524 288, alone in the last tile, is a host-repair row: both
+    of its bases, rows kept and rows for the host, come from there).  Against the table built from k directly."""
+    n = 256 * 2048 + 1
+    repair = {100001: ("0.1234567890123456789012345", "1.5e-30", "9007199254740993"),     # too many digits, exponent beyond -22,
+              300000: ("-0.9876543210987654321098765", "2.25e-300", "18014398509481985"),  # mantissa above 2^53
+              n - 1: ("0.5000000000000000000000001", "7.125e-23", "9007199254740995")}
+    assert all(k % 7 for k in repair)
+    lines = ["NaN,1,2\n" if k % 7 == 0 else f"{k}.5,{-k},1e3\n" for k in range(n)]
+    for k, fields in repair.items():
+        lines[k] = ",".join(fields) + "\n"
+    data = ("a,b,c\n" + "".join(lines)).encode()
+    k = np.arange(n, dtype=np.int64)
+    want = np.stack([k + 0.5, (-k).astype(np.float64), np.full(n, 1e3)], axis=1)
+    for at, fields in repair.items():
+        want[at] = [float(f) for f in fields]
+    want = want[k % 7 != 0]
+    got, cols = dbm.read_text_table(data, dbm.TextReader(",", 0, ABC, ABC))
+    assert list(cols) == ABC and got.shape == want.shape, (cols, got.shape, want.shape)
+    assert same_bits(got, want)
+    again, _ = dbm.read_text_table(data, dbm.TextReader(",", 0, ABC, ABC))
+    assert same_bits(got, again)
+
+
 # ---- errors ----
 def test_errors_name_the_first_line_in_the_file(dbm, T):
     good = b"1.5,2.5,junk\n"
