@@ -148,6 +148,10 @@ SIGNATURES = {
     "dbm_op_deform_conv2d": [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 5,
     "dbm_op_deform_conv2d_form": [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 6,
     "dbm_op_deform_conv2d_backward": [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int] * 5,
+    "dbm_op_batchnorm_train": [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int] * 4 + [C.POINTER(C.c_int)],
+    "dbm_op_batchnorm_train_backward": [C.c_void_p] + [C.c_void_p] * 9 + [C.c_int] * 4 + [C.POINTER(C.c_int)],
+    "dbm_op_disc_head": [C.c_void_p] + [C.c_void_p] * 7 + [C.c_int],
+    "dbm_op_disc_head_backward": [C.c_void_p] + [C.c_void_p] * 10 + [C.c_int, C.POINTER(C.c_int)],
 }
 
 _lib = None

@@ -1539,4 +1539,68 @@ int dbm_op_deform_conv2d_backward(dbm_ctx* ctx, const float* x, const float* off
   DBM_API_END
 }
 
+// Training-mode BatchNorm + LeakyReLU exactly as the discriminator launches it (discriminator.hip: eps 1e-5, decay 0.9, slope 0.2, the
+// context's time-out word as `hold`): which of the six kernel forms runs is launch_bn_train_fwd's own choice, reported through form_out
+// (a BnForm; -1 with sync: the sync_batch_stats kernels at world = 1, no all-reduce).
+int dbm_op_batchnorm_train(dbm_ctx* ctx, const float* z, const float* gamma, const float* beta, float* avg_mean, float* avg_var, float* y,
+                           float* mean, float* inv_std, int N, int C, int plane, int sync, int* form_out) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(N >= 1 && C >= 1 && plane >= 1, "batchnorm op: N, C, plane >= 1");
+  hipStream_t s = ctx->stream;
+  if (sync) {
+    ScopedBuf buf;
+    buf.ensure(3 * (size_t)C);
+    launch_bn_sync_stats(z, buf.p, N, C, plane, s);
+    launch_bn_sync_fwd_apply(z, y, gamma, beta, buf.p, mean, inv_std, avg_mean, avg_var, N, C, plane, 1, 1e-5f, 0.9f, 0.2f, s, ctx->dev_err_flag);
+    DBM_HIP(hipStreamSynchronize(s));
+  } else {
+    launch_bn_train_fwd(z, y, gamma, beta, mean, inv_std, avg_mean, avg_var, N, C, plane, 1e-5f, 0.9f, 0.2f, s, ctx->dev_err_flag);
+    DBM_HIP(hipStreamSynchronize(s));
+  }
+  if (form_out) *form_out = sync ? -1 : (int)bn_train_form(N, C, plane);
+  DBM_API_END
+}
+
+int dbm_op_batchnorm_train_backward(dbm_ctx* ctx, const float* z, const float* gh, const float* gamma, const float* beta, const float* mean,
+                                    const float* inv_std, float* gz, float* ggamma, float* gbeta, int N, int C, int plane, int sync,
+                                    int* form_out) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(N >= 1 && C >= 1 && plane >= 1, "batchnorm op: N, C, plane >= 1");
+  hipStream_t s = ctx->stream;
+  if (sync) {
+    ScopedBuf buf;
+    buf.ensure(2 * (size_t)C);
+    launch_bn_sync_bwd_sums(z, gh, gamma, beta, mean, inv_std, buf.p, ggamma, gbeta, N, C, plane, 0.2f, s);
+    launch_bn_sync_bwd_apply(z, gh, gamma, beta, mean, inv_std, buf.p, gz, N, C, plane, 1, 0.2f, s);
+    DBM_HIP(hipStreamSynchronize(s));
+  } else {
+    launch_bn_train_bwd(z, gh, gamma, beta, mean, inv_std, gz, ggamma, gbeta, nullptr, N, C, plane, 0.2f, s);
+    DBM_HIP(hipStreamSynchronize(s));
+  }
+  if (form_out) *form_out = sync ? -1 : (int)bn_train_form(N, C, plane);
+  DBM_API_END
+}
+
+// The discriminator's head, 512 -> 100 -> 1, through the launches Discriminator::forward / ::backward use.
+int dbm_op_disc_head(dbm_ctx* ctx, const float* x, const float* W1, const float* b1, const float* W2, const float* b2, float* l1,
+                     float* logits, int N) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(N >= 1, "disc head op: N >= 1");
+  launch_disc_head_fwd(x, W1, b1, W2, b2, l1, logits, N, 512, 100, 0.2f, ctx->stream);
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  DBM_API_END
+}
+
+int dbm_op_disc_head_backward(dbm_ctx* ctx, const float* x, const float* W1, const float* W2, const float* glogits, const float* l1, float* gx,
+                              float* gW1, float* gb1, float* gW2, float* gb2, int N, int* fused_out) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(N >= 1, "disc head op: N >= 1");
+  ScopedBuf g_l1;
+  g_l1.ensure((size_t)N * 100);
+  const bool fused = disc_head_backward(x, W1, W2, glogits, l1, g_l1.p, gx, gW1, gb1, gW2, gb2, N, 512, 100, 0.2f, ctx->stream);
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  if (fused_out) *fused_out = fused ? 1 : 0;
+  DBM_API_END
+}
+
 }  // extern "C"

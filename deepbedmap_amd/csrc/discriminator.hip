@@ -218,12 +218,8 @@ void Discriminator::backward(int slot, const float* glogits, bool join, bool mer
   float* gh = g_h[slot][0].p;
   float* gh_next = g_h[slot][1].p;
   if (!skip_deep) {
-  if (disc_head_bwd_fused_ok(N, 100)) {  // both linear layers' backward as ONE launch (round 6: bitwise the two linear_bwd launches)
-    launch_disc_head_bwd(c.h[9].p, P(T_l1W), P(T_l2W), glogits, c.l1.p, gh, G(T_l1W), G(T_l1b), G(T_l2W), G(T_l2b), N, 512, 100, SLOPE, s);
-  } else {
-    launch_linear_bwd(c.l1.p, P(T_l2W), glogits, nullptr, g_l1[slot].p, G(T_l2W), G(T_l2b), N, 100, 1, SLOPE, s);
-    launch_linear_bwd(c.h[9].p, P(T_l1W), g_l1[slot].p, c.l1.p, gh, G(T_l1W), G(T_l1b), N, 512, 100, SLOPE, s);
-  }
+  disc_head_backward(c.h[9].p, P(T_l1W), P(T_l2W), glogits, c.l1.p, g_l1[slot].p, gh, G(T_l1W), G(T_l1b), G(T_l2W), G(T_l2b), N, 512, 100,
+                     SLOPE, s);
   }
   for (int i = 9; i >= 1; --i) {
     const IgLayer& L = layers[L_conv[i]];

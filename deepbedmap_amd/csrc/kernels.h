@@ -87,6 +87,17 @@ void launch_sumpool2(const float* g, const float* mask, float* out, long nc, int
 // ---- norm_loss.hip ----
 // BatchNorm (training): per-channel batch statistics of z [N,C,plane]; writes mean/inv_std, updates running stats,
 // then y = lrelu(gamma*(z-mean)*inv_std + beta).
+// The six kernel forms of training-mode BatchNorm; bn_train_form is the ONE selector (both launchers and dbm_op_batchnorm_train*'s
+// form_out go through it; its only inputs are bn_reg_slots / bn_flat_slots and the plane >= 64 && C <= 256 split of the general kernels).
+enum BnForm {
+  BN_FORM_REG2 = 0,   // bn_train_*_reg_kernel<2>: <= 64 images, planes of 64..128 positions, <= 256 channels
+  BN_FORM_REG6 = 1,   // bn_train_*_reg_kernel<6>: ... planes of 129..384 positions
+  BN_FORM_FLAT1 = 2,  // bn_train_*_flat_kernel<1>: N * plane <= 256 (planes < 64 positions or > 256 channels)
+  BN_FORM_FLAT4 = 3,  // bn_train_*_flat_kernel<4>: N * plane <= 1024
+  BN_FORM_WIDE = 4,   // bn_train_*_kernel<1024>: planes >= 64 positions, <= 256 channels (register-cached for <= 64 images of <= 512 positions)
+  BN_FORM_GENERAL = 5 // bn_train_*_kernel<256>: everything else
+};
+BnForm bn_train_form(int N, int C, int plane);
 void launch_bn_train_fwd(const float* z, float* y, const float* gamma, const float* beta, float* mean, float* inv_std,
                          float* avg_mean, float* avg_var, int N, int C, int plane, float eps, float decay, float slope,
                          hipStream_t s, const int* hold = nullptr);  // hold: device word; non-zero = no running-average update
@@ -112,6 +123,11 @@ void launch_disc_head_fwd(const float* x, const float* W1, const float* b1, cons
 bool disc_head_bwd_fused_ok(int N, int O);
 void launch_disc_head_bwd(const float* x, const float* W1, const float* W2, const float* glogits, const float* l1, float* gx, float* gW1,
                           float* gb1, float* gW2, float* gb2, int N, int K, int O, float slope, hipStream_t s);
+// The head's backward sequence (Discriminator::backward and dbm_op_disc_head_backward both run THIS): the fused launch if its masked
+// gradient fits the LDS, else linear_2's then linear_1's launch_linear_bwd through g_l1 (N x O floats of scratch, read by nothing else).
+// Returns whether the fused form ran.
+bool disc_head_backward(const float* x, const float* W1, const float* W2, const float* glogits, const float* l1, float* g_l1, float* gx,
+                        float* gW1, float* gb1, float* gW2, float* gb2, int N, int K, int O, float slope, hipStream_t s);
 
 // RaGAN discriminator loss (srgan_train.py:960-1009) on N real + N fake logits.
 // out[0] = loss, out[1] = binary accuracy (train_eval_discriminator :1156-1158); g_real/g_fake may be null.

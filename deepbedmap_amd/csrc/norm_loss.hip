@@ -347,25 +347,35 @@ static int bn_reg_slots(int N, int C, int plane) {
   return plane <= 128 ? 2 : plane <= 384 ? 6 : 0;
 }
 
+BnForm bn_train_form(int N, int C, int plane) {
+  const int cp = bn_reg_slots(N, C, plane);
+  if (cp == 2) return BN_FORM_REG2;
+  if (cp == 6) return BN_FORM_REG6;
+  const int k = bn_flat_slots(N, C, plane);
+  if (k == 1) return BN_FORM_FLAT1;
+  if (k == 4) return BN_FORM_FLAT4;
+  return plane >= 64 && C <= 256 ? BN_FORM_WIDE : BN_FORM_GENERAL;
+}
+
 void launch_bn_train_fwd(const float* z, float* y, const float* gamma, const float* beta, float* mean, float* inv_std,
                          float* avg_mean, float* avg_var, int N, int C, int plane, float eps, float decay, float slope,
                          hipStream_t s, const int* hold) {
   if (dbm_abl_skip() & 1) return;  // (libdbm_measure.so only)
   // (round 5 A/B: 256-thread workgroups everywhere -- easier to place beside other kernels -- cost 8.69-8.71 against 7.91 ms per step)
-  const int cp = bn_reg_slots(N, C, plane);
-  if (cp == 2)
+  const BnForm form = bn_train_form(N, C, plane);
+  if (form == BN_FORM_REG2)
     hipLaunchKernelGGL(bn_train_fwd_reg_kernel<2>, dim3(C), dim3(1024), 0, s, z, y, gamma, beta, mean, inv_std, avg_mean, avg_var, N, C,
                        plane, eps, decay, slope, hold);
-  else if (cp == 6)
+  else if (form == BN_FORM_REG6)
     hipLaunchKernelGGL(bn_train_fwd_reg_kernel<6>, dim3(C), dim3(1024), 0, s, z, y, gamma, beta, mean, inv_std, avg_mean, avg_var, N, C,
                        plane, eps, decay, slope, hold);
-  else if (bn_flat_slots(N, C, plane) == 1)
+  else if (form == BN_FORM_FLAT1)
     hipLaunchKernelGGL(bn_train_fwd_flat_kernel<1>, dim3(C), dim3(256), 0, s, z, y, gamma, beta, mean, inv_std, avg_mean, avg_var, N, C,
                        plane, eps, decay, slope, hold);
-  else if (bn_flat_slots(N, C, plane) == 4)
+  else if (form == BN_FORM_FLAT4)
     hipLaunchKernelGGL(bn_train_fwd_flat_kernel<4>, dim3(C), dim3(256), 0, s, z, y, gamma, beta, mean, inv_std, avg_mean, avg_var, N, C,
                        plane, eps, decay, slope, hold);
-  else if (plane >= 64 && C <= 256)
+  else if (form == BN_FORM_WIDE)
     hipLaunchKernelGGL(bn_train_fwd_kernel<1024>, dim3(C), dim3(1024), 0, s, z, y, gamma, beta, mean, inv_std, avg_mean,
                        avg_var, N, C, plane, eps, decay, slope, hold);
   else
@@ -481,20 +491,20 @@ void launch_bn_train_bwd(const float* z, const float* gh, const float* gamma, co
                          int plane, float slope, hipStream_t s) {
   if (dbm_abl_skip() & 1) return;  // (libdbm_measure.so only)
   (void)scratch;
-  const int cp = bn_reg_slots(N, C, plane);
-  if (cp == 2)
+  const BnForm form = bn_train_form(N, C, plane);
+  if (form == BN_FORM_REG2)
     hipLaunchKernelGGL(bn_train_bwd_reg_kernel<2>, dim3(C), dim3(1024), 0, s, z, gh, gamma, beta, mean, inv_std, gz, ggamma, gbeta, N, C,
                        plane, slope);
-  else if (cp == 6)
+  else if (form == BN_FORM_REG6)
     hipLaunchKernelGGL(bn_train_bwd_reg_kernel<6>, dim3(C), dim3(1024), 0, s, z, gh, gamma, beta, mean, inv_std, gz, ggamma, gbeta, N, C,
                        plane, slope);
-  else if (bn_flat_slots(N, C, plane) == 1)
+  else if (form == BN_FORM_FLAT1)
     hipLaunchKernelGGL(bn_train_bwd_flat_kernel<1>, dim3(C), dim3(256), 0, s, z, gh, gamma, beta, mean, inv_std, gz, ggamma, gbeta, N, C,
                        plane, slope);
-  else if (bn_flat_slots(N, C, plane) == 4)
+  else if (form == BN_FORM_FLAT4)
     hipLaunchKernelGGL(bn_train_bwd_flat_kernel<4>, dim3(C), dim3(256), 0, s, z, gh, gamma, beta, mean, inv_std, gz, ggamma, gbeta, N, C,
                        plane, slope);
-  else if (plane >= 64 && C <= 256)
+  else if (form == BN_FORM_WIDE)
     hipLaunchKernelGGL(bn_train_bwd_kernel<1024>, dim3(C), dim3(1024), 0, s, z, gh, gamma, beta, mean, inv_std, gz, ggamma,
                        gbeta, N, C, plane, slope);
   else
@@ -787,6 +797,17 @@ void launch_disc_head_bwd(const float* x, const float* W1, const float* W2, cons
   hipLaunchKernelGGL(disc_head_bwd_kernel, dim3((total + 255) / 256), dim3(256), sizeof(float) * (size_t)N * O, s, x, W1, W2, glogits, l1, gx,
                      gW1, gb1, gW2, gb2, N, K, O, slope);
   DBM_HIP(hipGetLastError());
+}
+
+bool disc_head_backward(const float* x, const float* W1, const float* W2, const float* glogits, const float* l1, float* g_l1, float* gx,
+                        float* gW1, float* gb1, float* gW2, float* gb2, int N, int K, int O, float slope, hipStream_t s) {
+  if (disc_head_bwd_fused_ok(N, O)) {  // both linear layers' backward as ONE launch (round 6: bitwise the two linear_bwd launches)
+    launch_disc_head_bwd(x, W1, W2, glogits, l1, gx, gW1, gb1, gW2, gb2, N, K, O, slope, s);
+    return true;
+  }
+  launch_linear_bwd(l1, W2, glogits, nullptr, g_l1, gW2, gb2, N, O, 1, slope, s);  // linear_2, then linear_1 (through its LeakyReLU)
+  launch_linear_bwd(x, W1, g_l1, l1, gx, gW1, gb1, N, K, O, slope, s);
+  return false;
 }
 
 // ----------------------------------------------------------------------------------------------

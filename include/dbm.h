@@ -648,6 +648,26 @@ int dbm_op_deform_conv2d_form(dbm_ctx* ctx, const float* x, const float* off, co
                               int W, int O, int form, int lrelu);
 int dbm_op_deform_conv2d_backward(dbm_ctx* ctx, const float* x, const float* off, const float* w, const float* gy,
                                   float* gx, float* goff, float* gw, float* gb, int N, int C, int H, int W, int O);
+/* L.BatchNormalization (training mode, eps 1e-5, decay 0.9) + F.leaky_relu(0.2) as the discriminator runs them (srgan_train.py:636-644,
+ * 664-689): z (N,C,plane) -> y, per-channel mean / inv_std (C) overwritten; avg_mean / avg_var (C) updated in place with the unbiased
+ * correction m / max(m - 1, 1), m = N * plane.  The kernel form is the model's own launch choice for (N, C, plane); *form_out (HOST, may
+ * be NULL) receives it: 0 reg<2>, 1 reg<6>, 2 flat<1>, 3 flat<4>, 4 the 1024-thread general kernel, 5 the 256-thread general kernel.
+ * sync = 1: the sync_batch_stats kernels (local statistics, then apply) at world = 1 without an all-reduce; *form_out = -1. */
+int dbm_op_batchnorm_train(dbm_ctx* ctx, const float* z, const float* gamma, const float* beta, float* avg_mean, float* avg_var, float* y,
+                           float* mean, float* inv_std, int N, int C, int plane, int sync, int* form_out);
+/* ... and their backward pass: gh = d loss / d y -> gz (overwritten); ggamma / gbeta (C) are ACCUMULATED (atomicAdd).  mean / inv_std:
+ * what the forward pass wrote. */
+int dbm_op_batchnorm_train_backward(dbm_ctx* ctx, const float* z, const float* gh, const float* gamma, const float* beta, const float* mean,
+                                    const float* inv_std, float* gz, float* ggamma, float* gbeta, int N, int C, int plane, int sync,
+                                    int* form_out);
+/* linear_1 (512 -> 100) -> LeakyReLU -> linear_2 (100 -> 1), the discriminator's head (srgan_train.py:646-647, 693-696): x (N,512),
+ * W1 (100,512), b1 (100), W2 (1,100), b2 (1) -> l1 (N,100) after the LeakyReLU, logits (N) */
+int dbm_op_disc_head(dbm_ctx* ctx, const float* x, const float* W1, const float* b1, const float* W2, const float* b2, float* l1,
+                     float* logits, int N);
+/* ... and its backward pass from glogits (N): gx (N,512) overwritten; gW1, gb1, gW2, gb2 ACCUMULATED.  The model's own sequence: one fused
+ * launch while 4 * N * 100 bytes fit 48 KiB of LDS, else one launch per linear layer; *fused_out (HOST, may be NULL) = 1 / 0. */
+int dbm_op_disc_head_backward(dbm_ctx* ctx, const float* x, const float* W1, const float* W2, const float* glogits, const float* l1, float* gx,
+                              float* gW1, float* gb1, float* gW2, float* gb2, int N, int* fused_out);
 
 /* ---- reading survey text tables: the `pandas.read_csv` + `dropna` of ascii_to_xyz (data_prep.py:298-305) ----
  * text: nbytes bytes of one file, host or (DBM_DEVICE_PTRS) device, a device pointer 16-byte aligned; offsets are 64-bit, files above

@@ -1,4 +1,4 @@
-"""-m gpu: every HIP kernel family against the NumPy oracle through the C ABI (op-level entry points).
+"""-m gpu: the convolution kernel families against the NumPy oracle through the C ABI (BatchNorm, dense head, loss, Adam: test_gpu_norm_ops.py).
 
 Tolerance: fp32, `max|a-b| / max|b| <= 1e-4` (BASELINE.json north_star); the MFMA kernels accumulate
 in fp32 in a different order than BLAS, so results are compared with that tolerance, not bitwise.

@@ -178,7 +178,7 @@ def test_schedule_switches_of_round5_change_no_number(tmp_path, env):
             # the bulk agrees to rounding.  The discriminator's parameters are NOT compared here: its gradients pass through nine
             # training-mode batch normalisations over 12 x 1 x 1 .. 12 x 18 x 18 values (and biases in front of them have an exactly
             # zero gradient: Adam normalises their rounding noise to full steps) -- a summation-order change moves them by whole steps
-            # in this tiny configuration; their kernels' parity is tests/test_gpu_ops.py's and the model suites'.
+            # in this tiny configuration; their kernels' parity is tests/test_gpu_norm_ops.py's and the model suites'.
             err = np.abs(a.astype(np.float64) - b)
             assert err.max() <= 2e-2, (k, err.max())
             assert np.median(err) <= 2e-4 * max(np.abs(b).max(), 1e-30) + 1e-7, (k, np.median(err), err.max())
