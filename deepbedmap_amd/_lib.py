@@ -28,6 +28,29 @@ ONE_GEN_FORWARD = 16  # dbm_train_iteration: one generator forward per minibatch
 c_float_p = C.POINTER(C.c_float)
 c_void_pp = C.POINTER(C.c_void_p)
 
+
+
+class ConvLaunch(C.Structure):
+    """dbm_conv_launch (include/dbm.h): one forward / data-gradient launch with every epilogue field a model can set."""
+    _fields_ = [("dgrad", C.c_int), ("N", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("O", C.c_int), ("k", C.c_int),
+                ("stride", C.c_int), ("pad", C.c_int), ("ups", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p),
+                ("x", C.c_void_p), ("xsn", C.c_int64), ("y", C.c_void_p), ("ysn", C.c_int64), ("act", C.c_int), ("s1", C.c_float),
+                ("r1", C.c_void_p), ("r1sn", C.c_int64), ("r1_nch", C.c_int), ("r1s", C.c_float),
+                ("r2", C.c_void_p), ("r2sn", C.c_int64), ("s2", C.c_float), ("accumulate", C.c_int),
+                ("mask", C.c_void_p), ("masksn", C.c_int64), ("mask_c0", C.c_int), ("ch_scale", C.c_void_p), ("yt", C.c_void_p)]
+
+
+CONV_REPORT_INTS = 41  # launches, then ten ints per launch (at most four)
+CONV_REPORT_FIELDS = ("family", "cfg", "waves", "npb", "row", "ksplit", "nosplit", "nphase", "mt2", "yt")
+
+
+class WgradDesc(C.Structure):
+    """dbm_wgrad_desc (include/dbm.h): one weight gradient of a dbm_op_conv2d_wgrad_batch call."""
+    _fields_ = [("x", C.c_void_p), ("xsn", C.c_int64), ("dy", C.c_void_p), ("dysn", C.c_int64), ("N", C.c_int), ("C", C.c_int),
+                ("H", C.c_int), ("W", C.c_int), ("O", C.c_int), ("k", C.c_int), ("stride", C.c_int), ("pad", C.c_int), ("ups", C.c_int),
+                ("scale", C.c_float), ("gW", C.c_void_p), ("gb", C.c_void_p)]
+
+
 # name -> (argtypes) ; every function returns int except dbm_last_error
 # void allreduce_sum(void* user, float* dev, int n): the sync_batch_stats hook (dbm_set_sync_batch_stats)
 ALLREDUCE_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)
@@ -143,6 +166,8 @@ SIGNATURES = {
                             C.c_void_p, C.c_void_p, c_float_p, C.c_int, C.c_int, C.c_void_p],
     "dbm_op_conv2d": [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] * 10,
     "dbm_op_conv2d_backward": [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int] * 9,
+    "dbm_op_conv2d_launch": [C.c_void_p, C.POINTER(ConvLaunch), C.POINTER(C.c_int)],
+    "dbm_op_conv2d_wgrad_batch": [C.c_void_p, C.POINTER(WgradDesc), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "dbm_op_conv2d_cl16": [C.c_void_p] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p] + [C.c_int] * 6,
     "dbm_op_conv2d_cl16x3": [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] * 7,
     "dbm_op_deform_conv2d": [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 5,

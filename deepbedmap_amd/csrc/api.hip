@@ -1376,6 +1376,94 @@ int dbm_op_conv2d_backward(dbm_ctx* ctx, const float* x, const float* w, const f
   DBM_API_END
 }
 
+// One forward or data-gradient launch exactly as the models make it: fwd_desc / dgrad_desc + run_dgrad, every epilogue field, strided
+// operands; the launcher's choice comes back in `report` (include/dbm.h).
+int dbm_op_conv2d_launch(dbm_ctx* ctx, const dbm_conv_launch* a, int* report) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(a != nullptr && a->x && a->y && a->w, "conv launch op: x, y and w are required");
+  DBM_CHECK(a->C % 32 == 0 && a->C >= 32, "conv launch op: C must be a multiple of 32 (the implicit-GEMM kernels)");
+  DBM_CHECK(a->N >= 1 && a->O >= 1 && a->H >= 1 && a->W >= 1 && (a->ups == 0 || a->ups == 1), "conv launch op: bad geometry");
+  const int Cout = a->dgrad ? a->C : a->O;
+  DBM_CHECK(!a->r1 || (a->r1_nch >= 0 && a->r1_nch <= Cout), "conv launch op: r1_nch outside the output channels");
+  DBM_CHECK(!a->mask || (a->mask_c0 >= 0 && a->mask_c0 <= Cout), "conv launch op: mask_c0 outside the output channels");
+  dbm_model holder;
+  const bool has_bias = !a->dgrad && a->bias != nullptr;
+  IgLayer L = make_temp_layer(ctx, a->w, a->O, a->C, a->k, a->stride, a->pad, holder, has_bias);
+  if (has_bias) DBM_HIP(hipMemcpyAsync(holder.P(L.bi), a->bias, sizeof(float) * a->O, hipMemcpyDeviceToDevice, ctx->stream));
+  auto epilogue = [&](ConvDesc& d) {
+    d.act = a->act; d.s1 = a->s1;
+    d.r1 = a->r1; d.r1sn = a->r1sn; d.r1_nch = a->r1_nch; d.r1s = a->r1s;
+    d.r2 = a->r2; d.r2sn = a->r2sn; d.s2 = a->s2;
+    d.accumulate = a->accumulate;
+    d.mask = a->mask; d.masksn = a->masksn; d.mask_c0 = a->mask_c0;
+    d.ch_scale = a->ch_scale;
+  };
+  std::vector<ConvLaunchReport> reps;
+  if (!a->dgrad) {
+    ConvDesc d = holder.fwd_desc(L, a->x, a->xsn, a->H, a->W, a->ups, a->y, a->ysn, a->N);
+    epilogue(d);
+    d.yt = a->yt;
+    if (d.yt && !conv_tile_writes_yt(d)) d.yt = nullptr;   // (as Generator::forward asks before it hands the twin out)
+    ConvLaunchReport r;
+    launch_igemm_conv(d, ctx->stream, &r);
+    reps.push_back(r);
+  } else {
+    DBM_CHECK(a->ups == 0 && a->bias == nullptr && a->ch_scale == nullptr && a->yt == nullptr,
+              "conv launch op: a data gradient has no folded resize, bias, channel scale or channels-last twin");
+    holder.ensure_packed_bwd();
+    ConvDesc d = dbm_model::dgrad_desc(a->x, a->xsn, a->y, a->ysn, a->N);
+    epilogue(d);
+    holder.run_dgrad(L, d, a->H, a->W, nullptr, &reps);
+  }
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  if (report) {
+    report[0] = (int)reps.size();
+    for (size_t i = 0; i < reps.size() && i < 4; ++i) {
+      const ConvLaunchReport& r = reps[i];
+      const int v[10] = {r.family, r.cfg, r.waves, r.npb, r.row, r.ksplit, r.nosplit, r.nphase, r.mt2, r.yt};
+      memcpy(report + 1 + 10 * i, v, sizeof(v));
+    }
+  }
+  DBM_API_END
+}
+
+// L weight gradients as ONE WgradBatch (the training step's form).  The batch is kept between calls with the same descriptors, as
+// the step keeps its batches between iterations: a call that only switches the mode goes through WgradBatch::launch's re-plan.
+int dbm_op_conv2d_wgrad_batch(dbm_ctx* ctx, const dbm_wgrad_desc* descs, int L, int cleared_target, int* cat_out, int* S_out) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(descs != nullptr && L >= 1, "wgrad batch op: no descriptors");
+  static WgradBatch* batch = nullptr;
+  static std::vector<dbm_wgrad_desc> key;
+  const bool same = batch && (int)key.size() == L && memcmp(key.data(), descs, sizeof(dbm_wgrad_desc) * (size_t)L) == 0;
+  if (!same) {
+    if (!batch) batch = new WgradBatch;
+    batch->reset();
+    key.assign(descs, descs + L);
+    for (int i = 0; i < L; ++i) {
+      const dbm_wgrad_desc& q = descs[i];
+      DBM_CHECK(q.x && q.dy && q.gW && q.C % 32 == 0 && q.C >= 32 && q.N >= 1 && (q.ups == 0 || q.ups == 1),
+                "wgrad batch op: x, dy, gW are required; C must be a multiple of 32");
+      const int Hl = q.H << q.ups, Wl = q.W << q.ups;
+      const int OH = (Hl + 2 * q.pad - q.k) / q.stride + 1, OW = (Wl + 2 * q.pad - q.k) / q.stride + 1;
+      DBM_CHECK(OH >= 1 && OW >= 1, "wgrad batch op: empty output plane");
+      WgradDesc wd;
+      memset(&wd, 0, sizeof(wd));
+      wd.x = q.x; wd.xsn = q.xsn; wd.xsc = q.H * q.W; wd.Cin = q.C; wd.Hin = q.H; wd.Win = q.W; wd.ups = q.ups;
+      wd.dy = q.dy; wd.dysn = q.dysn; wd.dysc = OH * OW; wd.Cout = q.O; wd.OH = OH; wd.OW = OW;
+      wd.KH = wd.KW = q.k; wd.stride = q.stride; wd.pad = q.pad; wd.N = q.N; wd.scale = q.scale; wd.gW = q.gW; wd.gb = q.gb;
+      batch->add(wd);
+    }
+  }
+  batch->cleared_target = cleared_target != 0;
+  batch->launch(ctx->stream);
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < L; ++i) {
+    if (cat_out) cat_out[i] = batch->desc_cat[i];
+    if (S_out) S_out[i] = batch->desc_S[i];
+  }
+  DBM_API_END
+}
+
 // 3x3 / stride 1 / pad 1 convolution through the channels-last bf16 kernel of the sweep's trunk (conv_cl16.hip), for the parity
 // tests: x (N, C, H, W) fp32 is rounded to bf16 NHWC, y = [lrelu](s1 * (conv + b) + r1), fp32 out.  All DEVICE pointers.
 int dbm_op_conv2d_cl16(dbm_ctx* ctx, const float* x, const float* w, const float* b, const float* r1, float s1, float* y, int N,

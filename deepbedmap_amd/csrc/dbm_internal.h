@@ -122,7 +122,19 @@ struct ConvDesc {
   unsigned phPlaneM[4], phOwM[4];
 };
 
-void launch_igemm_conv(const ConvDesc& d, hipStream_t s);
+// What launch_igemm_conv chose for a descriptor (op-level tests: dbm_op_conv2d_launch), written where the launcher decides.
+struct ConvLaunchReport {
+  int family;   // 0 igemm_conv_kernel, 1 igemm_pm_kernel, 2 conv_tile_kernel
+  int cfg;      // conv_tile configuration 1..6 (else 0)
+  int waves;    // wavefronts per workgroup
+  int npb;      // igemm_conv_kernel's NPB: 0 streaming, 6 register-resident, -1 tap-skip, -2 bf16, -4 two tiles per wavefront
+  int row;      // igemm_conv_kernel's ROW (one 12-byte load per kernel row)
+  int ksplit;   // cross-workgroup K split (1: none)
+  int nosplit, nphase;
+  int mt2;      // two output-channel tiles per wavefront (igemm_conv NPB -4, igemm_pm <T, true>)
+  int yt;       // the channels-last twin d.yt is written
+};
+void launch_igemm_conv(const ConvDesc& d, hipStream_t s, ConvLaunchReport* rep = nullptr);
 // the LDS-tiled form for the mid-size training planes (conv_tile.hip); launch_igemm_conv dispatches to it
 int conv_tile_plan(ConvDesc& d, long* wgs);
 void conv_tile_launch(const ConvDesc& d, int cfg, hipStream_t s);
@@ -211,6 +223,11 @@ struct WgradPlan {
   float* pairW;
   long pair_stride;   // floats per buffer: Cout * Cin * T, then Cout
   int pair_n, pair_direct;
+  // Several descriptors of one launch that add into the SAME gradient (the real- and the fake-batch graph of the discriminator): all of
+  // them go through pair buffers (also a single slice, never pair_direct), the first one's fold job adds every member's buffer sum
+  // -- this plan's, then plans[pair_next]'s, ... -- and updates the gradient ONCE per element: g + (a + b), whatever g holds and
+  // whoever finishes first.  (Two fold jobs adding a and b with atomics gave (g + a) + b or (g + b) + a: reproducible only for g = 0.)
+  int pair_next;      // next plan of the same category that shares this gradient (-1: none)
 };
 extern bool g_wgrad_deterministic;  // dbm_set_deterministic: weight gradients are folded without fp32 atomics
 // fills p, returns the dynamic LDS bytes it needs (0: not eligible for the wave-task form)
@@ -240,6 +257,8 @@ struct WgradBatch {
   int n_tiny = 0, tiny_wgs = 0, tiny_rowlen = 4;
   double tiny_flops = 0.0, tiny_bytes = 0.0;
   std::vector<int> tiny_owner;
+  // per descriptor, what build() chose: the category (-1: wgrad_s2tiny_kernel, else 0 .. NCAT - 1) and the plan's K slices S (tiny: 1)
+  std::vector<int> desc_cat, desc_S;
   void add(const WgradDesc& d) { if (!built) descs.push_back(d); }
   void build();
   void launch(hipStream_t s);

@@ -311,6 +311,10 @@ void Generator::forward(GenWorkspace& ws, int N, int H, int W, const float* x, c
   auto cn0 = [&](int c) { return (long)(((long)c * N) / nsplit); };          // first image of range c
   auto cnc = [&](int c) { return (int)(cn0(c + 1) - cn0(c)); };                // images in range c
   auto cstream = [&](int c) { return c == 0 ? s : ctx->chain[c - 1]; };
+  // the trunk's per-layer images are rebuilt on `s` BEFORE the ranges fork from it: queued behind the fork (as it was until the
+  // wide-plane forward of tests/test_gpu_model.py came out 6e-3 off in its second image), only range 0 is ordered behind the repack
+  // and the other ranges' first dense block can read images that are still being written
+  if (!fused && !cl16) ensure_packed_lazy();
   for (int c = 1; c < nsplit; ++c) ctx->fork(s, cstream(c), c);
   // ---- pre-residual conv + LeakyReLU -> cat[0][:, :64]  (:541-542) ----
   if (pre_x3) {
@@ -397,7 +401,6 @@ void Generator::forward(GenWorkspace& ws, int N, int H, int W, const float* x, c
     }
     for (int c = 1; c < nsplit; ++c) ctx->fork(s, cstream(c), c);  // the post-residual conv's ranges continue behind it
   }
-  if (!fused && !cl16) ensure_packed_lazy();
   for (int j = 0; j < ((fused || cl16) ? 0 : nrdb); ++j) {
     for (int c = 0; c < nsplit; ++c) {  // one dense block per range at a time: fewer stream switches on the host
       for (int k = 0; k < 5; ++k) {

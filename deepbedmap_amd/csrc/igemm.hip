@@ -730,21 +730,25 @@ constexpr int IGEMM_NPB = 6;  // channel pairs a wavefront may hold entirely in 
 
 
 template <int T, int WAVES, bool ROW>
-static void launch_twr(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2) {
+static void launch_twr(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2, ConvLaunchReport* rep) {
+  if (rep) { rep->waves = WAVES; rep->row = ROW ? 1 : 0; rep->npb = 0; }
   if (d.wp16) {
     if constexpr (!ROW || T == 9) {
       if constexpr (WAVES == 4) {
         if (d.nosplit) {  // (decided by the launcher: bf16 on large grids, no cross-workgroup split)
+          if (rep) rep->npb = -2;
           hipLaunchKernelGGL((igemm_conv_kernel<T, WAVES, -2, ROW, true>), grid, dim3(64 * WAVES), 0, s, d);
           return;
         }
       }
+      if (rep) rep->npb = -2;
       hipLaunchKernelGGL((igemm_conv_kernel<T, WAVES, -2, ROW>), grid, dim3(64 * WAVES), WAVES * 4096, s, d);
       return;
     }
   }
   if constexpr (WAVES == 4) {
     if (mt2) {  // two output tiles per wavefront: grid.y counts 64-channel groups
+      if (rep) rep->npb = -4;
       hipLaunchKernelGGL((igemm_conv_kernel<T, WAVES, -4, ROW>), grid, dim3(64 * WAVES), WAVES * 4096, s, d);
       return;
     }
@@ -752,6 +756,7 @@ static void launch_twr(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2) {
   const int npairs = d.Cin / (d.ksplit > 1 ? d.ksplit : 1) / WAVES / 2;
   if constexpr (T <= 9 && WAVES >= 8) {
     if (npairs <= IGEMM_NPB) {
+      if (rep) rep->npb = IGEMM_NPB;
       hipLaunchKernelGGL((igemm_conv_kernel<T, WAVES, IGEMM_NPB, ROW>), grid, dim3(64 * WAVES), WAVES * 4096, s, d);
       return;
     }
@@ -759,6 +764,7 @@ static void launch_twr(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2) {
   if constexpr ((T == 16 || T == 4) && !ROW) {
     // most taps of a 4x4 window (of a 2x2 phase window of its data gradient) fall outside such planes: the tap-skipping variant
     if (igemm_tap_skip(d)) {
+      if (rep) rep->npb = -1;
       hipLaunchKernelGGL((igemm_conv_kernel<T, WAVES, -1, ROW>), grid, dim3(64 * WAVES), WAVES * 4096, s, d);
       return;
     }
@@ -767,25 +773,25 @@ static void launch_twr(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2) {
 }
 
 template <int T, int WAVES>
-static void launch_tw(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2) {
+static void launch_tw(const ConvDesc& d, dim3 grid, hipStream_t s, bool mt2, ConvLaunchReport* rep) {
   if constexpr (T == 9) {
     // row-contiguous taps: 3x3, unit stride, no folded resize, taps ordered (dy, dx) with dx = -1,0,1 or 1,0,-1
     const bool row = d.sin == 1 && d.ups == 0 && d.dy[0] == d.dy[1] && d.dy[1] == d.dy[2] && d.dx[1] == 0 &&
                      d.dx[0] == -d.dx[2] && (d.dx[0] == 1 || d.dx[0] == -1) && d.dy[3] == d.dy[5] && d.dy[6] == d.dy[8] &&
                      d.dx[3] == d.dx[0] && d.dx[6] == d.dx[0] && d.dx[4] == 0 && d.dx[7] == 0;
     if (row) {
-      launch_twr<T, WAVES, true>(d, grid, s, mt2);
+      launch_twr<T, WAVES, true>(d, grid, s, mt2, rep);
       return;
     }
   }
-  launch_twr<T, WAVES, false>(d, grid, s, mt2);
+  launch_twr<T, WAVES, false>(d, grid, s, mt2, rep);
 }
 
 template <int T>
-static void launch_t(const ConvDesc& d, dim3 grid, int waves, hipStream_t s, bool mt2) {
-  if (waves == 16) launch_tw<T, 16>(d, grid, s, false);
-  else if (waves == 8) launch_tw<T, 8>(d, grid, s, false);
-  else launch_tw<T, 4>(d, grid, s, mt2);
+static void launch_t(const ConvDesc& d, dim3 grid, int waves, hipStream_t s, bool mt2, ConvLaunchReport* rep) {
+  if (waves == 16) launch_tw<T, 16>(d, grid, s, false, rep);
+  else if (waves == 8) launch_tw<T, 8>(d, grid, s, false, rep);
+  else launch_tw<T, 4>(d, grid, s, mt2, rep);
 }
 
 // Workspace of the cross-workgroup split-K (partial tiles + arrival counters), one per launch stream: launches on one
@@ -810,9 +816,10 @@ static unsigned igemm_magic(unsigned long long dv) {  // floor(2^32 / dv), satur
   return (unsigned)(m > 0xffffffffULL ? 0xffffffffULL : m);
 }
 
-void launch_igemm_conv(const ConvDesc& d_in, hipStream_t s) {
+void launch_igemm_conv(const ConvDesc& d_in, hipStream_t s, ConvLaunchReport* rep) {
   if (dbm_abl_skip() & 512) return;  // (libdbm_measure.so only)
   ConvDesc d = d_in;
+  if (rep) memset(rep, 0, sizeof(*rep));
   d.ksplit = 1;
   const int nph = d.nphase > 1 ? d.nphase : 1;
   long total = (long)d.N * d.OHl * d.OWl;   // positions of the (widest) phase
@@ -867,6 +874,7 @@ void launch_igemm_conv(const ConvDesc& d_in, hipStream_t s) {
           g_profiler.begin(s, 0, 2.0 * flop_positions * d.Cout * d.Cin * d.T, bytes, tag, (long)grid.x * grid.y * grid.z);
         }
         const size_t lds = 4 * 4096;
+        if (rep) { rep->family = 1; rep->waves = 4; rep->ksplit = d.ksplit; rep->nphase = nph; rep->mt2 = mt2 ? 1 : 0; }
         if (d.T == 9) {
           if (mt2) hipLaunchKernelGGL((igemm_pm_kernel<9, true>), grid, dim3(256), lds, s, d);
           else hipLaunchKernelGGL((igemm_pm_kernel<9, false>), grid, dim3(256), lds, s, d);
@@ -895,6 +903,7 @@ void launch_igemm_conv(const ConvDesc& d_in, hipStream_t s) {
         snprintf(tag, sizeof(tag), "c%d>%d_k%d_%dx%d%s", d.Cin, d.Cout, d.T, d.Hin, d.Win, d.ups ? "u" : "");
         g_profiler.begin(s, 0, 2.0 * flop_positions * d.Cout * d.Cin * d.T, bytes, tag, wgs);
       }
+      if (rep) { rep->family = 2; rep->cfg = cfg; rep->waves = 4; rep->ksplit = 1; rep->nphase = nph; rep->yt = d.yt ? 1 : 0; }
       conv_tile_launch(d, cfg, s);
       if (g_profiler.enabled) g_profiler.end(s);
       return;
@@ -962,11 +971,12 @@ void launch_igemm_conv(const ConvDesc& d_in, hipStream_t s) {
     g_profiler.begin(s, 0, 2.0 * flop_positions * d.Cout * d.Cin * d.T, bytes, tag, (long)grid.x * grid.y * grid.z);
   }
   switch (d.T) {
-    case 1: launch_t<1>(d, grid, waves, s, mt2); break;
-    case 4: launch_t<4>(d, grid, waves, s, mt2); break;
-    case 9: launch_t<9>(d, grid, waves, s, mt2); break;
-    default: launch_t<16>(d, grid, waves, s, mt2); break;
+    case 1: launch_t<1>(d, grid, waves, s, mt2, rep); break;
+    case 4: launch_t<4>(d, grid, waves, s, mt2, rep); break;
+    case 9: launch_t<9>(d, grid, waves, s, mt2, rep); break;
+    default: launch_t<16>(d, grid, waves, s, mt2, rep); break;
   }
+  if (rep) { rep->family = 0; rep->ksplit = d.ksplit; rep->nosplit = d.nosplit; rep->nphase = nph; rep->mt2 = rep->npb == -4 ? 1 : 0; }
   if (g_profiler.enabled) g_profiler.end(s);
   DBM_HIP(hipGetLastError());
 }

@@ -201,7 +201,9 @@ struct dbm_model {
   ConvDesc fwd_desc(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, float* y, long ysn, int N) const;
   // run_dgrad's `base` for the gradient dy (image stride dysn) -> gx (gxsn): zeroed, s1 = s2 = 1; the caller adds accumulate / mask* / r1*
   static ConvDesc dgrad_desc(const float* dy, long dysn, float* gx, long gxsn, int N);
-  void run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_fwd, hipStream_t s = nullptr) const;
+  // reps (op-level tests): one report per launch made, in launch order
+  void run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_fwd, hipStream_t s = nullptr,
+                 std::vector<ConvLaunchReport>* reps = nullptr) const;
   // weight gradient of layer L into its own gradient tensors; run_wgrad queues it on `batch` (launched later, all layers at once) or runs
   // it immediately
   WgradDesc wgrad_desc(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, const float* dy, long dysn, int OH, int OW,

@@ -338,8 +338,13 @@ ConvDesc dbm_model::dgrad_desc(const float* dy, long dysn, float* gx, long gxsn,
 // Data gradient of layer L.  `base` carries the gradient input (x, xsn = dY and its image stride), the output
 // (y, ysn) and every epilogue field; geometry and weights are filled here.  Hin_fwd/Win_fwd: forward INPUT dims
 // (after upsample), i.e. the dims of the gradient being produced.
-void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_fwd, hipStream_t s) const {
+void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_fwd, hipStream_t s, std::vector<ConvLaunchReport>* reps) const {
   if (!s) s = ctx->stream;
+  auto launch = [&](const ConvDesc& d) {
+    ConvLaunchReport r;
+    launch_igemm_conv(d, s, reps ? &r : nullptr);
+    if (reps) reps->push_back(r);
+  };
   DBM_CHECK(!bwd_dirty, "run_dgrad: the data-gradient weight images are stale (ensure_packed_bwd was not called)");
   const int OH = (Hin_fwd + 2 * L.pad - L.Kview) / L.stride + 1, OW = (Win_fwd + 2 * L.pad - L.Kview) / L.stride + 1;
   base.xsc = OH * OW; base.Cin = L.OP; base.Hin = OH; base.Win = OW; base.ups = 0;
@@ -356,7 +361,7 @@ void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_
     base.T = L.Tb;
     for (int t = 0; t < L.Tb; ++t) { base.dy[t] = L.bdy[0][t]; base.dx[t] = L.bdx[0][t]; }
     base.wp = L.wb[0];
-    launch_igemm_conv(base, s);
+    launch(base);
   } else {
     // the four phases (py, px) of the stride-2 gradient -- output positions (2a + py, 2b + px), 2x2 taps each -- as ONE launch
     // (blockIdx.z = phase); planes that lack a phase (a single row or column) fall back to one launch per phase
@@ -370,7 +375,7 @@ void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_
         base.phwp[ph] = L.wb[ph];
       }
       base.OHl = base.phOH[0]; base.OWl = base.phOW[0]; base.oy0 = 0; base.ox0 = 0; base.wp = L.wb[0];
-      launch_igemm_conv(base, s);
+      launch(base);
       return;
     }
     for (int ph = 0; ph < 4; ++ph) {
@@ -380,7 +385,7 @@ void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_
       base.oy0 = py; base.ox0 = px;
       for (int t = 0; t < 4; ++t) { base.dy[t] = L.bdy[ph][t]; base.dx[t] = L.bdx[ph][t]; }
       base.wp = L.wb[ph];
-      launch_igemm_conv(base, s);
+      launch(base);
     }
   }
 }

@@ -1307,6 +1307,14 @@ __global__ __launch_bounds__(256) void wgrad_pair_fold_kernel(const WgradPlan* _
     for (int u = 0; u < 8; ++u) v += k0 + u < n ? t[u] : 0.f;   // (buffer order: the sum is the one the sequential loop formed)
   }
   for (int k = 0; k < n; ++k) p.pairW[(long)k * p.pair_stride + i] = 0.f;
+  // the other descriptors that add into this gradient (WgradPlan::pair_next): each one's buffer sum, in plan order
+  for (int nx = p.pair_next; nx >= 0; nx = plans[nx].pair_next) {
+    const WgradPlan& q = plans[nx];
+    float w = 0.f;
+    for (int k = 0; k < q.pair_n; ++k) w += q.pairW[(long)k * q.pair_stride + i];
+    for (int k = 0; k < q.pair_n; ++k) q.pairW[(long)k * q.pair_stride + i] = 0.f;
+    v += w;
+  }
   if (i < wsize) atomicAdd(p.d.gW + i, v);
   else if (p.d.gb) atomicAdd(p.d.gb + (i - wsize), v);
 }
@@ -1517,6 +1525,8 @@ void WgradBatch::reset() {
   n_tiny = tiny_wgs = 0;
   tiny_flops = 0.0;
   tiny_owner.clear();
+  desc_cat.clear();
+  desc_S.clear();
   for (int g = 0; g < NCAT; ++g) {
     if (d_plans[g]) (void)hipFree(d_plans[g]);
     if (d_starts[g]) (void)hipFree(d_starts[g]);
@@ -1601,6 +1611,8 @@ void WgradBatch::build() {
     else if (T == 9) cat[i] = wgrad_plan(descs[i], p, 0, 2) != 0 ? 3 : dm >= 0 ? 6 + dm : wgrad_plan(descs[i], p, 0, 3) != 0 ? 4 : 1;
     else cat[i] = dm >= 0 ? 6 + dm : wgrad_plan(descs[i], p, 0, 3) != 0 ? 5 : 2;
   }
+  desc_cat = cat;
+  desc_S.assign(descs.size(), 1);
   for (int g = 0; g < NCAT; ++g) {
     std::vector<WgradPlan> plans;
     std::vector<int> starts;
@@ -1657,7 +1669,7 @@ void WgradBatch::build() {
                                                                                     : wgrad_plan(d, p, g >= 3 ? 0 : level, MODE[g], S_fixed));
         p.zeros = device_zeros();
         p.partial = nullptr; p.partial_b = nullptr; p.fold_start = 0;
-        p.pairW = nullptr; p.pair_n = 0; p.pair_direct = 0; p.pair_stride = 0;
+        p.pairW = nullptr; p.pair_n = 0; p.pair_direct = 0; p.pair_stride = 0; p.pair_next = -1;
         p.fold_slots = p.fold_cts = p.fold_ctmul = p.fold_tpw = 0;
         starts.push_back(total);
         total += p.wg_count;
@@ -1675,34 +1687,57 @@ void WgradBatch::build() {
     fold_wgs[g] = 0;
     if (g_wgrad_deterministic && !plans.empty()) {
       // pair buffers: slices 2k, 2k + 1 -> buffer k (pair 0 straight to the gradient when it is known to be zero)
+      // plans that add into one gradient (same tensor, same geometry): chained behind the first one (WgradPlan::pair_next)
+      const int np = (int)plans.size();
+      std::vector<int> first(np), shared(np, 0);
+      for (int i = 0; i < np; ++i) {
+        first[i] = i;
+        for (int j = 0; j < i; ++j) {
+          const WgradDesc &a = plans[j].d, &b = plans[i].d;
+          if (a.gW == b.gW && a.gb == b.gb && a.Cout == b.Cout && a.Cin == b.Cin && a.KH == b.KH && a.KW == b.KW) { first[i] = first[j]; break; }
+        }
+        if (first[i] != i) shared[i] = shared[first[i]] = 1;
+      }
+      auto buffers = [&](int i) {   // pair buffers of plan i
+        const int npair = (plans[i].S + 1) / 2;
+        if (shared[i]) return npair;
+        return plans[i].S > 1 ? std::max(0, npair - (cleared_target ? 1 : 0)) : 0;
+      };
       size_t floats = 0;
       int fw = 0;
-      for (auto& pl : plans) {
-        const int npair = (pl.S + 1) / 2, direct = cleared_target ? 1 : 0;
+      for (int i = 0; i < np; ++i) {
+        const WgradPlan& pl = plans[i];
         const long stride = (((long)pl.d.Cout * pl.d.Cin * pl.d.KH * pl.d.KW + pl.d.Cout) + 3) & ~3L;
-        if (pl.S > 1 && npair - direct > 0) floats += (size_t)(npair - direct) * stride;
+        floats += (size_t)buffers(i) * stride;
       }
       if (d_partial[g]) (void)hipFree(d_partial[g]);
       DBM_HIP(hipMalloc((void**)&d_partial[g], (floats + 4) * sizeof(float)));
       DBM_HIP(hipMemset(d_partial[g], 0, (floats + 4) * sizeof(float)));
       float* base = d_partial[g];
-      for (auto& pl : plans) {
+      for (int i = 0; i < np; ++i) {
+        WgradPlan& pl = plans[i];
         pl.fold_start = fw;
         fstarts.push_back(fw);
-        pl.pairW = nullptr; pl.pair_n = 0; pl.pair_direct = 0; pl.pair_stride = 0;
-        if (pl.S <= 1) continue;
-        const int npair = (pl.S + 1) / 2, direct = cleared_target ? 1 : 0;
-        if (npair - direct <= 0) continue;  // two slices onto a cleared gradient: plain atomics commute
+        pl.pairW = nullptr; pl.pair_n = 0; pl.pair_direct = 0; pl.pair_stride = 0; pl.pair_next = -1;
+        const int nb = buffers(i);
+        if (nb <= 0) continue;  // one slice, or two slices onto a cleared gradient: plain atomics commute
         // (the stride is the exact tensor size + bias; the arena offset is rounded up to four floats)
         pl.pair_stride = (long)pl.d.Cout * pl.d.Cin * pl.d.KH * pl.d.KW + pl.d.Cout;
-        pl.pairW = base; pl.pair_n = npair - direct; pl.pair_direct = direct;
+        pl.pairW = base; pl.pair_n = nb; pl.pair_direct = shared[i] ? 0 : (cleared_target ? 1 : 0);
         base += (size_t)pl.pair_n * ((pl.pair_stride + 3) & ~3L);
+        if (shared[i]) {
+          for (int j = i + 1; j < np; ++j)
+            if (first[j] == first[i]) { pl.pair_next = j; break; }
+          if (first[i] != i) continue;  // folded by the first plan of its gradient: no fold workgroups of its own
+        }
         fw += (int)((pl.pair_stride + 255) / 256);
       }
       fold_wgs[g] = fw;
       for (int v : fstarts) starts.push_back(v);  // the fold table rides behind the launch table
     }
     starts.insert(starts.begin() + (long)plans.size(), total);  // (prefix table of the launch: plans.size() + 1 entries)
+    for (size_t i = 0, k = 0; i < descs.size(); ++i)
+      if (cat[i] == g) desc_S[i] = plans[k++].S;
     nplans[g] = (int)plans.size();
     total_wg[g] = total;
     lds[g] = maxlds;

@@ -624,6 +624,52 @@ int dbm_op_conv2d(dbm_ctx* ctx, const float* x, const float* w, const float* b, 
 /* data gradient (gx, may be NULL) and weight/bias gradient (gw, gb accumulated; may be NULL) of the same layer */
 int dbm_op_conv2d_backward(dbm_ctx* ctx, const float* x, const float* w, const float* gy, float* gx, float* gw,
                            float* gb, int N, int C, int H, int W, int O, int k, int stride, int pad, int upsample2);
+/* One forward or data-gradient launch of the same layer exactly as the models make it (fwd_desc / dgrad_desc + run_dgrad with every
+ * epilogue field, strided operands); all DEVICE pointers.  With acc = the convolution sum for output channel c:
+ *   v = (acc * ch_scale[c] + bias[c]) * s1 + (c < r1_nch ? r1s * r1 : 0);  if (r2) v = s2 * v + r2;  if (accumulate) v += y;
+ *   if (act) v = lrelu_0.2(v);  if (mask && c >= mask_c0) v *= (mask >= 0 ? 1 : 0.2)
+ * r1, r2, mask are addressed like y (same channel plane, same position) with their own image strides.  The layer is (O, C, k, k),
+ * stride, pad, on an H x W input plane (ups = 1: x holds H x W, the layer sees the nearest x2 resize).
+ *   dgrad = 0: x (N, >= C, H, W) with image stride xsn -> y (N, >= O, OH, OW) with image stride ysn; bias (O) or NULL; yt (N * OH * OW, 64) or
+ *              NULL is handed to the launch only where the model would (conv_tile_writes_yt).
+ *   dgrad = 1: x = dy (N, >= 32 * ceil(O / 32) channel planes, OH, OW; planes >= O hold zeros) -> y = gx (N, >= C, H, W); ups, bias,
+ *              ch_scale, yt must be 0 / NULL.  A stride-2 layer is the four-phase launch, or one launch per phase on a plane one pixel wide.
+ * report (HOST, may be NULL, 41 ints): report[0] = launches made (1, or up to 4), then ten ints per launch:
+ *   family (0 igemm_conv_kernel, 1 igemm_pm_kernel, 2 conv_tile_kernel), conv_tile cfg (1..6, else 0), wavefronts per workgroup,
+ *   NPB (0 streaming, 6 register-resident, -1 tap-skip, -2 bf16, -4 two tiles), ROW, ksplit, nosplit, nphase, two output tiles per
+ *   wavefront, yt written. */
+typedef struct dbm_conv_launch {
+  int dgrad;
+  int N, C, H, W, O, k, stride, pad, ups;
+  const float* w;      /* OIHW (O, C, k, k), contiguous */
+  const float* bias;
+  const float* x; int64_t xsn;
+  float* y; int64_t ysn;
+  int act; float s1;
+  const float* r1; int64_t r1sn; int r1_nch; float r1s;
+  const float* r2; int64_t r2sn; float s2;
+  int accumulate;
+  const float* mask; int64_t masksn; int mask_c0;
+  const float* ch_scale;
+  float* yt;
+} dbm_conv_launch;
+int dbm_op_conv2d_launch(dbm_ctx* ctx, const dbm_conv_launch* args, int* report);
+/* L weight gradients as ONE batch, the training step's form: gW (O, C, k, k) += scale * sum dy * x, gb (O, or NULL) += scale * sum dy, for
+ * x (N, >= C, H, W) with image stride xsn (ups = 1: the layer sees its nearest x2 resize) and dy (N, >= O, OH, OW) with image stride dysn.
+ * Two descriptors may name the same gW / gb (the real and the fake graph).  cleared_target = 1: the caller guarantees every gW / gb is
+ * zero and receives nothing else.  dbm_set_deterministic selects the folding; a call with the descriptors of the previous call reuses
+ * its batch (a mode switch re-plans it).  cat_out / S_out (HOST, L ints each, may be NULL): per descriptor the kernel category (-1
+ * wgrad_s2tiny_kernel; 0 1x1, 1 3x3 and 2 4x4 workgroup form; 3 3x3 wave LDS-DMA; 4 / 5 3x3 / 4x4 row-band LDS-DMA; 6 / 7 / 8 direct
+ * form 3x3 / 3x3 on a resized input / 4x4 stride 2; 9 1x1 on large planes) and its number of K slices. */
+typedef struct dbm_wgrad_desc {
+  const float* x; int64_t xsn;
+  const float* dy; int64_t dysn;
+  int N, C, H, W, O, k, stride, pad, ups;
+  float scale;
+  float* gW;
+  float* gb;
+} dbm_wgrad_desc;
+int dbm_op_conv2d_wgrad_batch(dbm_ctx* ctx, const dbm_wgrad_desc* descs, int L, int cleared_target, int* cat_out, int* S_out);
 /* the same L.Convolution2D (3x3, stride 1, pad 1: the RRDB trunk's layers, srgan_train.py:292-331) on the channels-last
  * bf16 kernel of the area sweep (conv_cl16.hip): x is rounded to bf16, fp32 accumulation, y = [lrelu](s1 * (conv + b) + r1)
  * with r1 (N,64,H,W) or NULL; C % 32 == 0, O = 32 or 64 */
