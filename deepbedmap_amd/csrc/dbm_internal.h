@@ -175,66 +175,13 @@ struct PackJob {
 };
 void launch_pack_jobs(const PackJob* d_jobs, int njobs, int total_blocks, hipStream_t s);
 
-// wgrad (wgrad.hip): gW[o][c][ky][kx] (+)= scale * sum_{n,a,b} dy[n][o][a][b] * x[n][c][(a*stride+ky-pad)>>ups][...]
-struct WgradDesc {
-  const float* x;   // input activations
-  long xsn; int xsc; int Cin; int Hin, Win; int ups;
-  const float* dy;  // output gradients
-  long dysn; int dysc; int Cout; int OH, OW;
-  int KH, KW, stride, pad;
-  int N;
-  float scale;
-  float* gW;        // canonical OIHW, accumulated with atomicAdd
-  float* gb;        // may be null; accumulated with atomicAdd
-};
+// wgrad (wgrad.hip).  WgradDesc, WgradPlan, the form table and the planner are host-only C++ in wgrad_plan.h.
+#include "wgrad_plan.h"
 void launch_wgrad(const WgradDesc& d, hipStream_t s);  // single layer, synchronous (tests / op-level API)
-
-struct WgradPlan {
-  WgradDesc d;
-  int groups, coutTiles, S;  // workgroups = groups (input-channel groups) x coutTiles x S (K splits)
-  int wg_count;
-  int G;        // 32-channel input tiles per workgroup (= active wavefronts)
-  int IB, R;    // band = IB images x R output rows
-  int nbr;      // row-bands per image
-  int BP, BPp;  // positions per band, padded to even
-  int YS;       // LDS row stride of the dy slab (odd)
-  int Rin, Wst; // staged logical input patch rows / cols per image
-  int ImgS;     // Rin*Wst
-  int XS;       // LDS channel stride of the patch (odd)
-  int nbands;
-  // whole-image bands of plain (not upsampled) planes: both operands are contiguous per image and are staged with
-  // 16-byte loads; `fast` = 0 falls back to the per-element gather
-  int fast;
-  unsigned planeM, winM;  // ceil(2^32 / (Hin*Win)), ceil(2^32 / Win): exact quotients for the sizes staged here
-  unsigned oplaneM;       // ceil(2^32 / (OH*OW))
-  int wave_task;          // 0: wgrad_kernel (workgroup form), 2: wgrad_wave_dma_kernel, 3: wgrad_band_dma_kernel,
-                          // 4: wgrad_direct_kernel (Wst = segments per output row, nbands = segments, S = K slices)
-  const float* zeros;     // >= 4 bytes of device zeros (out-of-image rows of the row-band DMA form)
-  // Slot partials: partial[slice][cout tile][group][wave][tap][16][64] in accumulator order, partial_b[slice][cout tile][32].  The
-  // planner always leaves them null (deterministic mode folds through the pair buffers below); the kernels' epilogue for them is kept
-  // because removing it changes the code hipcc emits for the LDS-DMA weight-gradient kernels.
-  float* partial;
-  float* partial_b;
-  int fold_start;         // first workgroup of this layer in the fold launch
-  int fold_slots, fold_cts, fold_ctmul, fold_tpw;   // (slot partials: which input tile / taps a wavefront slot owns)
-  // Pair buffers (deterministic folding, no fp32 atomics on the K split): K slices 2k and 2k + 1 add with atomics into buffer k, which is
-  // zero and has gW's own layout (+ Cout bias floats): two contributions commute bit for bit.  pair_direct: pair 0 goes
-  // straight to gW / gb (the gradient is known to be zero).  wgrad_pair_fold_kernel adds the buffers in order, clears them.
-  float* pairW;
-  long pair_stride;   // floats per buffer: Cout * Cin * T, then Cout
-  int pair_n, pair_direct;
-  // Several descriptors of one launch that add into the SAME gradient (the real- and the fake-batch graph of the discriminator): all of
-  // them go through pair buffers (also a single slice, never pair_direct), the first one's fold job adds every member's buffer sum
-  // -- this plan's, then plans[pair_next]'s, ... -- and updates the gradient ONCE per element: g + (a + b), whatever g holds and
-  // whoever finishes first.  (Two fold jobs adding a and b with atomics gave (g + a) + b or (g + b) + a: reproducible only for g = 0.)
-  int pair_next;      // next plan of the same category that shares this gradient (-1: none)
-};
 extern bool g_wgrad_deterministic;  // dbm_set_deterministic: weight gradients are folded without fp32 atomics
-// fills p, returns the dynamic LDS bytes it needs (0: not eligible for the wave-task form)
-size_t wgrad_plan(const WgradDesc& d, WgradPlan& p, int level = 0, int wave_task = 0, int S_fixed = 0);
 
 // All weight gradients of one backward pass: collected as descriptors, planned and uploaded once per
-// workspace shape, then launched as one kernel per kernel size (1x1, 3x3, 4x4).
+// workspace shape, then launched as one kernel per form.
 struct WgradBatch {
   std::vector<WgradDesc> descs;
   bool built = false;
@@ -243,20 +190,18 @@ struct WgradBatch {
   // training step: cleargrads, then one backward pass).  Two K slices may then fold with atomics even in deterministic
   // mode: (0 + a) + b == (0 + b) + a bit for bit -- no partial tiles, no fold kernel for those layers.
   bool cleared_target = false, built_cleared = false;
-  static const int NCAT = 10;  // see WgradBatch::build
+  static const int NCAT = WGRAD_NCAT;  // rows of the form table (wgrad_plan.h)
+  // what build() uploaded per form: plans, the launch's prefix table with the fold's behind it, the pair-buffer arena
   WgradPlan* d_plans[NCAT] = {};
   int* d_starts[NCAT] = {};
-  int nplans[NCAT] = {}, total_wg[NCAT] = {};
+  float* d_arena[NCAT] = {};
+  int nplans[NCAT] = {}, total_wg[NCAT] = {}, fold_wgs[NCAT] = {};
   size_t lds[NCAT] = {};
-  float* d_partial[NCAT] = {};   // pair buffers of the atomic-free folding (per category)
-  int fold_wgs[NCAT] = {};
-  double flops[NCAT] = {};
-  double abytes[NCAT] = {};      // algorithmic bytes of a category's launch: every layer's x, dy and gW once
-  // 4x4 stride-2 layers on tiny planes (wgrad_s2tiny_kernel): their own plan table, outside the categories
-  void* d_tiny = nullptr;
+  double flops[NCAT] = {}, abytes[NCAT] = {};
+  // layers on tiny planes (wgrad_s2tiny_kernel): their own plan table, outside the form table
+  TinyPlan* d_tiny = nullptr;
   int n_tiny = 0, tiny_wgs = 0, tiny_rowlen = 4;
   double tiny_flops = 0.0, tiny_bytes = 0.0;
-  std::vector<int> tiny_owner;
   // per descriptor, what build() chose: the category (-1: wgrad_s2tiny_kernel, else 0 .. NCAT - 1) and the plan's K slices S (tiny: 1)
   std::vector<int> desc_cat, desc_S;
   void add(const WgradDesc& d) { if (!built) descs.push_back(d); }

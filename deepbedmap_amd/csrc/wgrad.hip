@@ -14,7 +14,7 @@
 // group, output tile, K split); all weight gradients of a group of layers with the same kernel
 // form go out in a single launch (they do not depend on each other).
 //
-// Three kernel forms (WgradBatch::build picks per layer):
+// Kernel forms (the planner, wgrad_plan.h, picks one per layer from its form table):
 //   wgrad_wave_dma_kernel   3x3 / stride 1 on small planes (the 9x9 trunk): whole-image bands, LDS-DMA staging,
 //                           two wavefronts = two input tiles sharing one dy slab
 //   wgrad_band_dma_kernel   3x3 / 4x4, any stride / folded resize, on large planes: row bands, dword LDS-DMA
@@ -41,7 +41,7 @@ __device__ unsigned long long g_dbg[4 * 8192];
 bool g_wgrad_deterministic = true;  // the reference trains with cudnn_deterministic = True (srgan_train.py:69)
 
 // Deterministic mode: K slices 2k and 2k + 1 add into pair buffer k (WgradPlan::pairW), wgrad_pair_fold_kernel sums the buffers in
-// order.  (The slot-partial epilogue below -- WgradPlan::partial -- is never selected by the planner; see WgradPlan.)
+// order.
 // gradient targets of K slice bz: gW / gb themselves, or a pair buffer
 __device__ __forceinline__ void pair_targets(const WgradPlan& p, int bz, float*& gW, float*& gb) {
   gW = p.d.gW; gb = p.d.gb;
@@ -54,6 +54,7 @@ __device__ __forceinline__ void pair_targets(const WgradPlan& p, int bz, float*&
   }
 }
 
+// Slot-partial epilogue (WgradPlan::partial): never selected by the planner, kept because the kernels measured slower without it (see WgradPlan)
 template <int TPW>
 __device__ __forceinline__ void store_partial(const WgradPlan& p, int bz, int by, int grp, int slot, int lane, float scale,
                                               const f32x16 (&acc)[TPW]) {
@@ -62,6 +63,56 @@ __device__ __forceinline__ void store_partial(const WgradPlan& p, int bz, int by
   for (int t = 0; t < TPW; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) dst[(t * 16 + r) * 64] = scale * acc[t][r];
+}
+
+// which plan does workgroup `wg` belong to?  (binary search in a prefix table: the launch's `starts` or the fold's)
+__device__ __forceinline__ int plan_of(const int* __restrict__ starts, int nplans, int wg) {
+  int lo = 0, hi = nplans - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (starts[mid] <= wg) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Fold of the accumulators into gW[o][c][t] (t fastest).  A lane owns (o, c) pairs with a stride of T floats between lanes, so
+// direct atomics would touch a different cache line per lane; instead the wavefronts of one input tile transpose 8 output rows
+// at a time through LDS (`tw`: 8 x 32 T floats; this wavefront writes taps tg * TPW ..) and issue the atomics over consecutive
+// addresses, elements e0, e0 + STRIDE, ... per thread.  BLOCK: the wavefronts that share `tw` meet at a workgroup barrier, else
+// the area is this wavefront's own.  SUM4 (direct form): the four wavefronts hold K sub-slices of ONE tile in four areas behind
+// `rd`, summed on the way out; then e0 / STRIDE span the workgroup and every thread skips the taps of the other tap half.
+// Used by wgrad_kernel and wgrad_direct_kernel.  The two LDS-DMA kernels keep their own copy of this text (and of the plan lookup and
+// of their K-loop step `half`): on the shared helpers wgrad_band_dma_kernel<16,8> measured slower than the parent's own run-to-run
+// range (profiles/r7/wgrad_forms_refactor.txt, 4b).
+template <int T, int TPW, bool BLOCK, int STRIDE, bool SUM4>
+__device__ __forceinline__ void fold_rows(const f32x16 (&acc)[TPW], float* tw, const float* rd, const WgradDesc& d, float* gWt, int cout0,
+                                          int cin_w, int tg, int j, int kh, int e0, bool active) {
+  constexpr int ROWF = 32 * T;  // floats of one output row of a 32-channel input tile
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (active) {
+#pragma unroll
+      for (int t = 0; t < TPW; ++t)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr)
+          tw[(rr + 4 * kh) * ROWF + j * T + tg * TPW + t] = SUM4 ? acc[t][4 * q + rr] : d.scale * acc[t][4 * q + rr];
+    }
+    if (BLOCK) __syncthreads(); else __builtin_amdgcn_wave_barrier();
+    if (active) {
+      for (int e = e0; e < 8 * ROWF; e += STRIDE) {
+        const int rl = e / ROWF;
+        const int rem = e - rl * ROWF;
+        const int o = cout0 + 8 * q + rl;
+        const int c = rem / T;
+        if (SUM4 && T != TPW && ((rem - c * T) / TPW) != tg) continue;
+        if (o < d.Cout && cin_w + c < d.Cin) {
+          const float v = SUM4 ? d.scale * (((rd[e] + rd[8 * ROWF + e]) + rd[2 * 8 * ROWF + e]) + rd[3 * 8 * ROWF + e]) : rd[e];
+          atomicAdd(gWt + ((long)o * d.Cin + cin_w) * T + rem, v);
+        }
+      }
+    }
+    if (BLOCK) __syncthreads(); else __builtin_amdgcn_wave_barrier();
+  }
 }
 
 // TPW = taps per wavefront.  3x3 / 1x1: every wavefront keeps all T accumulators (TPW = T, 4 wavefronts, 256
@@ -74,13 +125,8 @@ __global__ __launch_bounds__(256 * (T / TPW), 2) void wgrad_kernel(const WgradPl
   constexpr int NW = 4 * TG;        // wavefronts per workgroup
   constexpr int NT = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  // ---- which layer does this workgroup belong to? (binary search in the prefix table) ----
-  int lo = 0, hi = nplans - 1;
   const int wg = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (starts[mid] <= wg) lo = mid; else hi = mid - 1;
-  }
+  const int lo = plan_of(starts, nplans, wg);
   const WgradPlan& p = plans[lo];
   const WgradDesc& d = p.d;
   int local = wg - starts[lo];
@@ -311,41 +357,18 @@ __global__ __launch_bounds__(256 * (T / TPW), 2) void wgrad_kernel(const WgradPl
     }
   }
 
-  // ---- fold the partial sums into gW[o][c][t] (t fastest).  A lane owns (o, c) pairs with a stride of T floats
-  // between lanes, so direct atomics would touch a different cache line per lane; instead the wavefronts of one
-  // input tile transpose 8 output rows at a time through LDS and issue the atomics over consecutive addresses. ----
   if (p.partial) {
     if (wave_active) store_partial<TPW>(p, bz, by, bx, wave, lane, d.scale, acc);
     if (d.gb && bx == 0 && tid < 256 && (tid & 7) == 0) p.partial_b[((long)bz * p.coutTiles + by) * 32 + (tid >> 3)] = d.scale * bsum;
     return;
   }
+  // ---- fold the partial sums into gW (fold_rows): one transpose area per input tile ----
   float *gWt, *gbt;
   pair_targets(p, bz, gWt, gbt);
   __syncthreads();  // staging buffers are dead: reuse the LDS
   {
-    constexpr int ROWF = 32 * T;  // floats of one output row of a 32-channel input tile
-    float* tw = lds + ct * (8 * ROWF);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (wave_active) {
-#pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr)
-            tw[(rr + 4 * kh) * ROWF + j * T + tg * TPW + t] = d.scale * acc[t][4 * q + rr];
-      }
-      __syncthreads();
-      if (wave_active) {
-        for (int e = tg * 64 + lane; e < 8 * ROWF; e += 64 * TG) {
-          const int rl = e / ROWF;
-          const int rem = e - rl * ROWF;
-          const int o = cout0 + 8 * q + rl;
-          const int c = cin_w + rem / T;
-          if (o < d.Cout && c < d.Cin) atomicAdd(gWt + ((long)o * d.Cin + cin_w) * T + rem, tw[e]);
-        }
-      }
-      __syncthreads();
-    }
+    float* tw = lds + ct * (8 * 32 * T);
+    fold_rows<T, TPW, true, 64 * TG, false>(acc, tw, tw, d, gWt, cout0, cin_w, tg, j, kh, tg * 64 + lane, wave_active);
   }
   if (d.gb && bx == 0 && tid < 256 && (tid & 7) == 0 && cout0 + (tid >> 3) < d.Cout)
     atomicAdd(gbt + cout0 + (tid >> 3), d.scale * bsum);
@@ -824,12 +847,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_direct_kernel(const WgradPlan* _
   constexpr int NR = MODE == 2 ? 2 : 3;                       // kernel rows per wavefront
   constexpr int NB = MODE == 0 ? 6 : (MODE == 1 ? 4 : 10);     // floats per kernel row and lane
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  int lo = 0, hi = nplans - 1;
   const int wg = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (starts[mid] <= wg) lo = mid; else hi = mid - 1;
-  }
+  const int lo = plan_of(starts, nplans, wg);
   const WgradPlan& p = plans[lo];
   const WgradDesc& d = p.d;
   int local = wg - starts[lo];
@@ -957,28 +976,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_direct_kernel(const WgradPlan* _
   // ---- four K sub-slices -> one contribution: 8 output rows at a time through LDS, atomics over consecutive addresses ----
   float *gWt, *gbt;
   pair_targets(p, bz, gWt, gbt);
-  constexpr int ROWF = 32 * T;
-  float* tw = lds + wave * (8 * ROWF);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-#pragma unroll
-    for (int t = 0; t < TPW; ++t)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) tw[(rr + 4 * kh) * ROWF + j * T + tg * TPW + t] = acc[t][4 * q + rr];
-    __syncthreads();
-    for (int e = tid; e < 8 * ROWF; e += 256) {
-      const int rl = e / ROWF;
-      const int rem = e - rl * ROWF;
-      const int c = rem / T, t = rem - c * T;
-      if (TG > 1 && (t / TPW) != tg) continue;
-      const int o = cout0 + 8 * q + rl;
-      if (o < d.Cout && cin_w + c < d.Cin) {
-        const float v = ((lds[e] + lds[8 * ROWF + e]) + lds[2 * 8 * ROWF + e]) + lds[3 * 8 * ROWF + e];
-        atomicAdd(gWt + ((long)o * d.Cin + cin_w) * T + rem, d.scale * v);
-      }
-    }
-    __syncthreads();
-  }
+  fold_rows<T, TPW, true, 256, true>(acc, lds + wave * (8 * 32 * T), lds, d, gWt, cout0, cin_w, tg, j, kh, tid, true);
   if (want_bias) {
     bsum += __shfl_xor(bsum, 32, 64);
     if (kh == 0) lds[wave * 32 + j] = bsum;
@@ -1004,12 +1002,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_1x1_kernel(const WgradPlan* __re
   constexpr int BP = 32, BS = 36;             // positions per band, LDS row stride
   constexpr int ROWS = 64 + 128;              // dy rows, then x rows
   extern __shared__ __attribute__((aligned(16))) float lds[];   // 2 x ROWS x BS
-  int lo = 0, hi = nplans - 1;
   const int wg = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (starts[mid] <= wg) lo = mid; else hi = mid - 1;
-  }
+  const int lo = plan_of(starts, nplans, wg);
   const WgradPlan& p = plans[lo];
   const WgradDesc& d = p.d;
   int local = wg - starts[lo];
@@ -1130,19 +1124,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_1x1_kernel(const WgradPlan* __re
 // the other, into the same accumulators: the gradient leaves with a plain read-modify-write of elements nobody else
 // touches -- no atomics, no partial buffers, bitwise reproducible.
 // ---------------------------------------------------------------------------------------------------------------
-struct TinyPlan {
-  const float* x[2];    // input activations of the (up to two) graphs; x[1] == null: one graph
-  const float* dy[2];
-  float* gW;
-  long xsn, dysn;
-  int N, Cin, Cout, Hin, Win, OH, OW;
-  float scale;
-  int wg_start, ctiles;  // workgroups of this layer: (Cout / 16) * ctiles, ctiles = Cin / 16
-  int K;                 // 4: 4x4 stride 2 pad 1;  3: 3x3 stride 1 pad 1 (round 3: conv_layer6 / 8 of the discriminator)
-};
-
 struct __attribute__((packed, aligned(4))) f32x4u4 { float v[4]; };
-constexpr int TINY_MAXK = 2048;  // K entries (images x valid output positions) a kernel row may have: 64 KB of LDS tables
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -1270,20 +1252,11 @@ __global__ __launch_bounds__(256) void wgrad_s2tiny_kernel(const TinyPlan* __res
   else if (ky < 3) tiny_body<3, 1>(p, local, tbl + ky * rowlen, ky, lane);
 }
 
-static bool s2tiny_eligible(const WgradDesc& d) {
-  const bool k4 = d.KH == 4 && d.KW == 4 && d.stride == 2;
-  const bool k3 = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.Hin == d.OH && d.Win == d.OW;
-  return (k4 || k3) && d.pad == 1 && d.ups == 0 && d.OW <= 4 && d.OH <= 4 && d.gb == nullptr &&
-         d.Cin % 32 == 0 && d.Cout % 32 == 0 && d.xsc == d.Hin * d.Win && d.dysc == d.OH * d.OW && d.Win >= 2 &&
-         (long)d.N * d.OH * d.OW + 4 <= TINY_MAXK && (long)d.N * d.xsn < (1L << 31) && (long)d.N * d.dysn < (1L << 27);
-}
-
-static inline int odd_up(int v) { return v | 1; }
-
 // The other deterministic folding (pair buffers, see WgradPlan::pairW): gW += buffers in order, the buffers are cleared for
 // the next launch.  Elementwise and coalesced: the buffers have gW's layout.
 __global__ __launch_bounds__(256) void wgrad_pair_fold_kernel(const WgradPlan* __restrict__ plans, const int* __restrict__ fstarts,
                                                               int nplans) {
+  // (its own copy of plan_of: on the helper this kernel measured 9.12 -> 9.27 us, profiles/r7/wgrad_forms_refactor.txt)
   int lo = 0, hi = nplans - 1;
   const int wg = blockIdx.x;
   while (lo < hi) {
@@ -1319,203 +1292,16 @@ __global__ __launch_bounds__(256) void wgrad_pair_fold_kernel(const WgradPlan* _
   else if (p.d.gb) atomicAdd(p.d.gb + (i - wsize), v);
 }
 
-static size_t band_plan(const WgradDesc& d, WgradPlan& p, int S_fixed) {
-  // row-band LDS-DMA form (wgrad_band_dma_kernel): the largest band of R output rows whose slabs fit half a CU's LDS
-  const int T = d.KH * d.KW;
-  if (!(T == 9 || T == 16) || d.KH != d.KW) return 0;
-  const int tiles = (d.Cin + 31) / 32;
-  p.groups = T == 9 ? (tiles + 1) / 2 : tiles;
-  p.G = T == 9 ? 2 : 1;
-  p.coutTiles = (d.Cout + 31) / 32;
-  const int nx = T == 9 ? 2 : 1;
-  const int Wl = d.Win << d.ups, Wf = Wl + 1;
-  auto floats = [&](int R) {
-    const int Rin = (R - 1) * d.stride + d.KH;
-    const int bpp = (R * d.OW + 1) & ~1;
-    return 32L * odd_up(bpp) + 4 + (long)nx * 32 * odd_up(Rin * Wf) + bpp + 8;
-  };
-  auto fits = [&](int R) {
-    const int Rin = (R - 1) * d.stride + d.KH;
-    return Rin * Wf <= 512 && R * d.OW <= 512 && floats(R) <= 19400 && (R * d.stride + d.KH) * Wf < 32768;
-  };
-  if (!fits(1) || d.OH * d.OW < 64) return 0;  // tiny planes: several images per band (workgroup / trunk forms)
-  int R = 1;
-  while (R < d.OH && fits(R + 1)) ++R;
-  // equal bands: the smallest R with the same number of bands per image
-  const int nbr = (d.OH + R - 1) / R;
-  R = (d.OH + nbr - 1) / nbr;
-  p.IB = 1; p.R = R; p.nbr = nbr;
-  p.BP = R * d.OW;
-  p.BPp = (p.BP + 1) & ~1;
-  p.YS = odd_up(p.BPp);
-  p.Rin = (R - 1) * d.stride + d.KH;
-  p.Wst = Wf;
-  p.ImgS = p.Rin * Wf;
-  p.XS = odd_up(p.ImgS);
-  p.nbands = d.N * nbr;
-  int S = S_fixed > 0 ? S_fixed : 1;
-  if (S > p.nbands) S = p.nbands;
-  p.S = S;
-  p.wg_count = p.groups * p.coutTiles * S;
-  p.fast = 0; p.planeM = p.winM = p.oplaneM = 0;
-  const size_t stage = sizeof(float) * (size_t)floats(R);
-  return std::max(stage, sizeof(float) * 2 * 8 * 32 * (size_t)9);
-}
 
-// direct form (wgrad_direct_kernel): mode 0 / 1 / 2 or -1 if the layer is not eligible
-static int direct_mode(const WgradDesc& d) {
-  const int T = d.KH * d.KW;
-  const int Hl = d.Hin << d.ups, Wl = d.Win << d.ups;
-  if (d.KH != d.KW || d.pad != 1 || d.OW < 16 || d.xsc != d.Hin * d.Win || d.dysc != d.OH * d.OW) return -1;
-  if (T == 9 && d.stride == 1 && d.OH == Hl && d.OW == Wl) return d.ups ? 1 : 0;
-  if (T == 16 && d.stride == 2 && d.ups == 0 && 2 * d.OH == Hl && 2 * d.OW == Wl) return 2;
-  return -1;
-}
-
-// segs_per_wg: K segments (8 positions each) one workgroup (four wavefronts) works through
-static size_t direct_plan(const WgradDesc& d, WgradPlan& p, long segs_per_wg) {
-  const int mode = direct_mode(d);
-  DBM_CHECK(mode >= 0, "wgrad: layer not eligible for the direct form");
-  const int T = d.KH * d.KW;
-  p.d = d;
-  p.wave_task = 4;
-  p.zeros = nullptr;
-  p.groups = (d.Cin + 31) / 32;
-  p.G = 1;
-  p.coutTiles = (d.Cout + 31) / 32;
-  p.Wst = (d.OW + 7) / 8;
-  const long nseg = (long)d.N * d.OH * p.Wst;
-  DBM_CHECK(nseg < (1L << 30), "wgrad: too many positions");
-  p.nbands = (int)nseg;
-  long S = (nseg + segs_per_wg - 1) / segs_per_wg;
-  if (S < 1) S = 1;
-  p.S = (int)S;
-  p.wg_count = p.groups * p.coutTiles * (mode == 2 ? 2 : 1) * p.S;
-  p.IB = 1; p.R = 1; p.nbr = d.OH; p.BP = p.BPp = 8; p.YS = p.XS = 0; p.Rin = 0; p.ImgS = 0;
-  p.fast = 0; p.planeM = p.winM = p.oplaneM = 0;
-  return sizeof(float) * 4 * 8 * 32 * (size_t)T;  // four transpose areas of 8 output rows
-}
-
-// 1x1 layers on large contiguous planes (wgrad_1x1_kernel)
-static bool gemm1x1_eligible(const WgradDesc& d) {
-  const int plane = d.OH * d.OW;
-  return d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0 && d.ups == 0 && d.Hin == d.OH && d.Win == d.OW && plane >= 256 &&
-         plane % 4 == 0 && d.xsc == plane && d.dysc == plane && d.xsn % 4 == 0 && d.dysn % 4 == 0 &&
-         ((uintptr_t)d.x % 16) == 0 && ((uintptr_t)d.dy % 16) == 0;
-}
-
-static size_t gemm1x1_plan(const WgradDesc& d, WgradPlan& p, long bands_per_wg) {
-  p.d = d;
-  p.wave_task = 5;
-  p.zeros = nullptr;
-  p.groups = (d.Cin + 127) / 128;
-  p.G = 4;
-  p.coutTiles = (d.Cout + 63) / 64;
-  const int plane = d.OH * d.OW;
-  p.nbr = (plane + 31) / 32;
-  p.nbands = d.N * p.nbr;
-  long S = (p.nbands + bands_per_wg - 1) / bands_per_wg;
-  if (S < 1) S = 1;
-  p.S = (int)S;
-  p.wg_count = p.groups * p.coutTiles * p.S;
-  p.IB = 1; p.R = 1; p.BP = p.BPp = 32; p.YS = p.XS = 36; p.Rin = 0; p.ImgS = 0; p.Wst = 0;
-  p.fast = 0; p.planeM = p.winM = p.oplaneM = 0;
-  return sizeof(float) * 2 * (64 + 128) * 36;
-}
-
-size_t wgrad_plan(const WgradDesc& d, WgradPlan& p, int level, int wave_task, int S_fixed) {
-  const int T = d.KH * d.KW;
-  DBM_CHECK(T == 1 || T == 9 || T == 16, "wgrad: supported kernels are 1x1, 3x3, 4x4");
-  DBM_CHECK(d.OW < 4096 && d.OH < 4096, "wgrad: image too large");
-  p.d = d;
-  p.wave_task = wave_task;
-  p.zeros = nullptr;
-  if (wave_task == 3) return band_plan(d, p, S_fixed);
-  const bool dma = wave_task == 2;
-  if (dma && !(T == 9 && d.stride == 1 && d.pad == 1 && d.OH == d.Hin && d.OW == d.Win && (d.OH + 2) * (d.OW + 1) <= 128)) return 0;
-  const int tiles = (d.Cin + 31) / 32;
-  p.groups = dma ? (tiles + 1) / 2 : (tiles + 3) / 4;
-  p.G = dma ? 2 : (tiles + p.groups - 1) / p.groups;
-  p.coutTiles = (d.Cout + 31) / 32;
-  // band selection: whole images if small, else row bands of one image
-  const int Wst = (d.OW - 1) * d.stride + d.KW;
-  // floats; workgroup form: <= 79 KB lets two workgroups share a CU's 160 KB; dma: four two-wavefront groups per CU
-  const long budget = dma ? 10000 : (T <= 9) ? 19800 : 25000;
-  auto cost = [&](int IB, int R) {
-    const int Rin = (R - 1) * d.stride + d.KH;
-    const long bpp = (IB * R * d.OW + 1) & ~1;
-    if (dma) return 32L * IB * d.OH * d.OW + 4 + 64L * IB * (d.OH + 2) * (d.OW + 1) + bpp + 8;
-    return (long)p.G * 32 * odd_up(IB * Rin * Wst) + 32L * odd_up((int)bpp) + 2 * bpp + (long)IB * Rin * Wst;
-  };
-  int IB = 1, R = d.OH;
-  if (cost(1, d.OH) <= budget) {
-    while (IB * 2 <= d.N && IB * 2 <= 128 && IB * 2 * d.OH * d.OW <= (324 >> std::max(level, 0)) && cost(IB * 2, d.OH) <= budget) IB *= 2;
-  } else {
-    if (dma) return 0;
-    while (R > 1 && cost(1, R) > budget) --R;
-  }
-  DBM_CHECK(cost(IB, R) <= 38000, "wgrad: band does not fit in LDS");
-  p.IB = IB; p.R = R;
-  p.nbr = (d.OH + R - 1) / R;
-  p.BP = IB * R * d.OW;
-  p.BPp = (p.BP + 1) & ~1;
-  p.YS = odd_up(p.BPp);
-  p.Rin = (R - 1) * d.stride + d.KH;
-  p.Wst = Wst;
-  p.ImgS = p.Rin * p.Wst;
-  p.XS = odd_up(IB * p.ImgS);
-  DBM_CHECK(p.Rin < 4096 && p.Wst < 4096, "wgrad: patch too large");
-  const int imgGroups = (d.N + IB - 1) / IB;
-  p.nbands = imgGroups * p.nbr;
-  // K split: enough positions per workgroup that the closing atomics stay a small fraction of the MFMA work
-  // (~8 images of the 9x9 trunk per workgroup; `level` > 0 halves that, and the band, per step: used by batches
-  // that would otherwise leave most of the chip idle)
-  const long positions = (long)d.N * d.OH * d.OW;
-  const long per_wg = level >= 0 ? std::max(1L, 648L >> level) : (648L << -level);
-  int S = (int)((positions + per_wg - 1) / per_wg);
-  if (S_fixed > 0) S = S_fixed;
-  if (S > p.nbands) S = p.nbands;
-  if (S < 1) S = 1;
-  p.S = S;
-  p.wg_count = p.groups * p.coutTiles * S;
-  auto magic = [](unsigned dv) { return (unsigned)((0x100000000ULL + dv - 1) / dv); };
-  const int plane = d.Hin * d.Win, oplane = d.OH * d.OW;
-  p.planeM = magic((unsigned)plane);
-  p.winM = magic((unsigned)d.Win);
-  p.oplaneM = magic((unsigned)oplane);
-  // contiguous 16-byte staging: whole-image bands of plain planes, every per-image run 16-byte aligned and a
-  // multiple of four floats (all channel counts of a run: full tiles / groups and the ragged last one)
-  const int chx = p.G * 32;
-  const int tail_ci = d.Cin - (p.groups - 1) * chx, tail_co = d.Cout - (p.coutTiles - 1) * 32;
-  auto mult4 = [](long v) { return (v % 4) == 0; };
-  // (d.Win > 1: the multiply-high constants ceil(2^32 / dv) do not exist for dv = 1 -- a plane one pixel wide, e.g. the 1x1
-  // view of the input block's k6 s2 branch on 3 x 3 tiles, got every sample of a run decoded to channel 0; found by the
-  // randomised-geometry tests of round 3)
-  p.fast = d.Win > 1 && p.nbr == 1 && d.ups == 0 && d.xsc == plane && d.dysc == oplane && mult4(d.xsn) && mult4(d.dysn) &&
-           ((uintptr_t)d.x % 16) == 0 && ((uintptr_t)d.dy % 16) == 0 && mult4(32L * oplane) && mult4((long)chx * plane) &&
-           mult4((long)std::min(32, tail_co) * oplane) && mult4((long)std::min(chx, tail_ci) * plane) &&
-           (long)chx * plane < (1L << 20) && 32L * oplane < (1L << 20) && plane < 4096 && oplane < 4096;
-  if (dma) {
-    if (!p.fast || (long)IB * 32 * oplane >= 65536 || (long)IB * 32 * (d.OH + 2) * (d.OW + 1) >= 32768) return 0;
-    p.ImgS = (d.OH + 2) * (d.OW + 1);
-    const size_t stage = sizeof(float) * ((size_t)32 * IB * oplane + 4 + (size_t)64 * IB * p.ImgS + (size_t)p.BPp + 8);
-    return std::max(stage, sizeof(float) * 2 * 8 * 32 * (size_t)T);
-  }
-  const size_t stage = sizeof(float) * ((size_t)32 * p.YS + 2 * (size_t)p.BPp + (size_t)IB * p.ImgS + (size_t)p.G * 32 * p.XS);
-  const size_t epilogue = sizeof(float) * 4 * 8 * 32 * (size_t)T;  // per-wavefront transpose areas
-  return std::max(stage, epilogue);
-}
-
-template <int T, int TPW>
-static void launch_T(const WgradPlan* plans, const int* starts, int nplans, int total_wg, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    DBM_HIP(hipFuncSetAttribute((const void*)wgrad_kernel<T, TPW>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((wgrad_kernel<T, TPW>), dim3(total_wg), dim3(256 * (T / TPW)), lds, s, plans, starts, nplans);
-  DBM_HIP(hipGetLastError());
-}
+// ---------------------------------------------------------------------------------------------------------------
+// Host side.  wgrad_plan.h decides (forms, band shapes, K splits, pair-buffer layout); build() allocates and uploads what it decided,
+// launch() walks the form table.
+// ---------------------------------------------------------------------------------------------------------------
+typedef void (*WgradKernel)(const WgradPlan*, const int*, int);
+#define WGRAD_KERNEL_ROW(cat, tag, T, kernel, threads, lds_attr, plan, ksplit, kparam) kernel,
+static const WgradKernel kWgradKernels[WGRAD_NCAT] = {WGRAD_FORMS(WGRAD_KERNEL_ROW)};  // the table's kernel column
+#undef WGRAD_KERNEL_ROW
+static_assert(WgradBatch::NCAT == WGRAD_NCAT, "one launch per row of the form table");
 
 void WgradBatch::reset() {
   descs.clear();
@@ -1524,18 +1310,16 @@ void WgradBatch::reset() {
   d_tiny = nullptr;
   n_tiny = tiny_wgs = 0;
   tiny_flops = 0.0;
-  tiny_owner.clear();
   desc_cat.clear();
   desc_S.clear();
   for (int g = 0; g < NCAT; ++g) {
     if (d_plans[g]) (void)hipFree(d_plans[g]);
     if (d_starts[g]) (void)hipFree(d_starts[g]);
-    if (d_partial[g]) (void)hipFree(d_partial[g]);
-    d_partial[g] = nullptr;
-    fold_wgs[g] = 0;
+    if (d_arena[g]) (void)hipFree(d_arena[g]);
     d_plans[g] = nullptr;
     d_starts[g] = nullptr;
-    nplans[g] = total_wg[g] = 0;
+    d_arena[g] = nullptr;
+    nplans[g] = total_wg[g] = fold_wgs[g] = 0;
     lds[g] = 0;
     flops[g] = 0.0;
   }
@@ -1551,226 +1335,40 @@ static const float* device_zeros() {
   return z;
 }
 
+template <class V>
+static void upload(V** dst, const std::vector<V>& v) {
+  DBM_HIP(hipMalloc((void**)dst, v.size() * sizeof(V)));
+  DBM_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice));
+}
+
 void WgradBatch::build() {
-  // categories: 0 = 1x1, 1 = 3x3 workgroup form, 2 = 4x4 workgroup form, 3 = 3x3 trunk LDS-DMA tasks (whole-image bands
-  // of small planes), 4 = 3x3 row-band LDS-DMA, 5 = 4x4 row-band LDS-DMA, 6 / 7 / 8 = direct form (3x3, 3x3 on a
-  // nearest-x2 input, 4x4 stride 2)
-  // 9 = 1x1 on large contiguous planes (LDS-staged GEMM, wgrad_1x1_kernel)
-  static const int TT[NCAT] = {1, 9, 16, 9, 9, 16, 9, 9, 16, 1};
-  static const int MODE[NCAT] = {0, 0, 0, 2, 3, 3, 4, 4, 4, 5};
-  std::vector<int> cat(descs.size());
-  // ---- 4x4 stride-2 layers on tiny planes: their own kernel (wgrad_s2tiny_kernel), outside the category tables.  Two
-  // descriptors with the same gradient (the real- and the fake-batch graph of the discriminator) share a plan. ----
-  {
-    std::vector<TinyPlan> tp;
-    std::vector<int> owner(descs.size(), -1);
-    int wgs = 0;
-    double fl = 0.0, tiny_bytes_acc = 0.0;
-    for (size_t i = 0; i < descs.size(); ++i) {
-      if (owner[i] >= 0) continue;
-      const WgradDesc& d = descs[i];
-      // the descriptors that add to this gradient: all of them must qualify, at most two, same geometry
-      std::vector<size_t> grp;
-      bool ok = true;
-      for (size_t k = 0; k < descs.size(); ++k) {
-        if (descs[k].gW != d.gW) continue;
-        const WgradDesc& f = descs[k];
-        grp.push_back(k);
-        ok = ok && s2tiny_eligible(f) && f.KH == d.KH && f.N == d.N && f.Cin == d.Cin && f.Cout == d.Cout && f.Hin == d.Hin && f.Win == d.Win &&
-             f.OH == d.OH && f.OW == d.OW && f.xsn == d.xsn && f.dysn == d.dysn && f.scale == d.scale;
-      }
-      if (!ok || grp.size() > 2 || grp[0] != i) continue;
-      TinyPlan q;
-      memset(&q, 0, sizeof(q));
-      for (size_t u = 0; u < grp.size(); ++u) { q.x[u] = descs[grp[u]].x; q.dy[u] = descs[grp[u]].dy; owner[grp[u]] = (int)tp.size(); }
-      q.gW = d.gW; q.xsn = d.xsn; q.dysn = d.dysn;
-      q.N = d.N; q.Cin = d.Cin; q.Cout = d.Cout; q.Hin = d.Hin; q.Win = d.Win; q.OH = d.OH; q.OW = d.OW; q.scale = d.scale;
-      q.ctiles = d.Cin / 16; q.wg_start = wgs; q.K = d.KH;
-      wgs += (d.Cout / 16) * q.ctiles;
-      tp.push_back(q);
-      fl += 2.0 * (double)grp.size() * d.N * d.OH * d.OW * d.Cout * d.Cin * (d.KH * d.KW);
-      tiny_bytes_acc += 4.0 * ((double)grp.size() * d.N * ((double)d.Cin * d.Hin * d.Win + (double)d.Cout * d.OH * d.OW) + (double)d.Cout * d.Cin * (d.KH * d.KW));
-    }
-    n_tiny = (int)tp.size(); tiny_wgs = wgs; tiny_flops = fl; tiny_bytes = tiny_bytes_acc;
-    tiny_rowlen = 4;
-    for (const TinyPlan& q : tp) tiny_rowlen = std::max(tiny_rowlen, ((q.N * q.OH * q.OW + 3) / 4) * 4);
-    tiny_owner = owner;
-    if (d_tiny) { (void)hipFree(d_tiny); d_tiny = nullptr; }
-    if (n_tiny) {
-      DBM_HIP(hipMalloc((void**)&d_tiny, tp.size() * sizeof(TinyPlan)));
-      DBM_HIP(hipMemcpy(d_tiny, tp.data(), tp.size() * sizeof(TinyPlan), hipMemcpyHostToDevice));
-    }
-  }
-  for (size_t i = 0; i < descs.size(); ++i) {
-    if (tiny_owner[i] >= 0) { cat[i] = -1; continue; }
-    const int T = descs[i].KH * descs[i].KW;
-    WgradPlan p;
-    // (the workgroup forms, categories 0 / 1 / 2, serve every layer the other forms refuse)
-    const int dm = direct_mode(descs[i]);
-    if (T == 1) cat[i] = gemm1x1_eligible(descs[i]) ? 9 : 0;
-    else if (T == 9) cat[i] = wgrad_plan(descs[i], p, 0, 2) != 0 ? 3 : dm >= 0 ? 6 + dm : wgrad_plan(descs[i], p, 0, 3) != 0 ? 4 : 1;
-    else cat[i] = dm >= 0 ? 6 + dm : wgrad_plan(descs[i], p, 0, 3) != 0 ? 5 : 2;
-  }
-  desc_cat = cat;
-  desc_S.assign(descs.size(), 1);
+  WgradLayout L = wgrad_layout(descs, g_wgrad_deterministic, cleared_target);
+  desc_cat = L.desc_cat;
+  desc_S = L.desc_S;
+  n_tiny = (int)L.tiny.size(); tiny_wgs = L.tiny_wgs; tiny_rowlen = L.tiny_rowlen;
+  tiny_flops = L.tiny_flops; tiny_bytes = L.tiny_bytes;
+  if (n_tiny) upload(&d_tiny, L.tiny);
   for (int g = 0; g < NCAT; ++g) {
-    std::vector<WgradPlan> plans;
-    std::vector<int> starts;
-    int total = 0;
-    size_t maxlds = 0;
-    double fl = 0.0, by = 0.0;
-    // LDS-DMA forms: the K split is chosen so that the launch is ONE round of equally long two-wavefront groups
-    // (four per CU for the trunk form; two or four per CU for row bands, by their LDS footprint)
-    int S_fixed = 0;
-    long segs_per_wg = 0;
-    if (g == 9) {
-      long work = 0;
-      for (size_t i = 0; i < descs.size(); ++i) {
-        if (cat[i] != g) continue;
-        const WgradDesc& d = descs[i];
-        work += (long)((d.Cin + 127) / 128) * ((d.Cout + 63) / 64) * d.N * ((d.OH * d.OW + 31) / 32);
-      }
-      segs_per_wg = std::max(8L, (work + 511) / 512);   // bands of 32 positions per workgroup
-    } else if (g >= 6) {
-      // direct form: equally long workgroups, about two per CU over the whole launch (a workgroup's K range should stay
-      // long enough that its closing atomics are a small fraction: >= 64 segments = 512 positions)
-      long work = 0;
-      for (size_t i = 0; i < descs.size(); ++i) {
-        if (cat[i] != g) continue;
-        const WgradDesc& d = descs[i];
-        work += (long)((d.Cin + 31) / 32) * ((d.Cout + 31) / 32) * (g == 8 ? 2 : 1) * d.N * d.OH * ((d.OW + 7) / 8);
-      }
-      segs_per_wg = std::max(64L, (work + 511) / 512);
-    } else if (g >= 3) {
-      long units = 0;
-      size_t need = 0;
-      for (size_t i = 0; i < descs.size(); ++i) {
-        if (cat[i] != g) continue;
-        WgradPlan p;
-        need = std::max(need, wgrad_plan(descs[i], p, 0, MODE[g], 1));
-        units += (long)p.groups * p.coutTiles;
-      }
-      // (few-layer launches -- the discriminator's conv_layer4: 16 units -- take a coarser K split: 256 workgroups of four images
-      // instead of 1024 of one, a quarter of the partial tiles to write and fold: 116 -> 90 us standalone, round 3)
-      int slots = need > 40 * 1024 ? 512 : 1024;
-      // (<= 32 units: in data-parallel runs the trunk's launches are cut into four groups of 126 units each -- those keep the fine split)
-      if (g == 3 && units > 0 && units <= 32) slots = std::min(slots, 256);  // (the row-band forms lose: 164 -> 204 us)
-      if (units > 0) S_fixed = (int)std::max(1L, slots / units);
+    WgradFormLayout& F = L.form[g];
+    nplans[g] = (int)F.plans.size();
+    total_wg[g] = F.total_wg; fold_wgs[g] = F.fold_wgs;
+    lds[g] = F.lds; flops[g] = F.flops; abytes[g] = F.abytes;
+    if (F.plans.empty()) continue;
+    if (F.arena_floats) {  // pair buffers: zero between launches (the fold kernel clears what it read)
+      DBM_HIP(hipMalloc((void**)&d_arena[g], F.arena_floats * sizeof(float)));
+      DBM_HIP(hipMemset(d_arena[g], 0, F.arena_floats * sizeof(float)));
     }
-    // workgroup forms: a launch should offer about two workgroups per CU; small batches split their position axis finer
-    for (int level = 0; level < 4; ++level) {
-      plans.clear(); starts.clear();
-      total = 0; maxlds = 0; fl = 0.0;
-      for (size_t i = 0; i < descs.size(); ++i) {
-        if (cat[i] != g) continue;
-        const WgradDesc& d = descs[i];
-        WgradPlan p;
-        maxlds = std::max(maxlds, g == 9 ? gemm1x1_plan(d, p, segs_per_wg) : g >= 6 ? direct_plan(d, p, segs_per_wg)
-                                                                                    : wgrad_plan(d, p, g >= 3 ? 0 : level, MODE[g], S_fixed));
-        p.zeros = device_zeros();
-        p.partial = nullptr; p.partial_b = nullptr; p.fold_start = 0;
-        p.pairW = nullptr; p.pair_n = 0; p.pair_direct = 0; p.pair_stride = 0; p.pair_next = -1;
-        p.fold_slots = p.fold_cts = p.fold_ctmul = p.fold_tpw = 0;
-        starts.push_back(total);
-        total += p.wg_count;
-        plans.push_back(p);
-        fl += 2.0 * (double)d.N * d.OH * d.OW * d.Cout * d.Cin * TT[g];
-        by += 4.0 * ((double)d.N * ((double)d.Cin * d.Hin * d.Win + (double)d.Cout * d.OH * d.OW) + (double)d.Cout * d.Cin * TT[g]);
-      }
-      // (deterministic mode: no finer K split than necessary -- every extra slice is a pair buffer to write and fold --
-      // but a launch of a few dozen workgroups, e.g. the 4x4 layers of the deep discriminator, is split as well)
-      // (256 since round 5 -- the input block's GEMM-shaped launch, 144 workgroups at 128, ends the iteration behind the trunk's launch:
-      //  62.6 -> 46 us; 7.61-7.64 against 7.62-7.68 ms per step, 448: 7.64-7.67, 64: 7.68-7.71)
-      if (total >= 448 || plans.empty() || g >= 3 || (g_wgrad_deterministic && total >= 256)) break;
+    for (size_t i = 0; i < F.plans.size(); ++i) {
+      F.plans[i].zeros = device_zeros();
+      if (F.pair_off[i] >= 0) F.plans[i].pairW = d_arena[g] + F.pair_off[i];
     }
-    std::vector<int> fstarts;
-    fold_wgs[g] = 0;
-    if (g_wgrad_deterministic && !plans.empty()) {
-      // pair buffers: slices 2k, 2k + 1 -> buffer k (pair 0 straight to the gradient when it is known to be zero)
-      // plans that add into one gradient (same tensor, same geometry): chained behind the first one (WgradPlan::pair_next)
-      const int np = (int)plans.size();
-      std::vector<int> first(np), shared(np, 0);
-      for (int i = 0; i < np; ++i) {
-        first[i] = i;
-        for (int j = 0; j < i; ++j) {
-          const WgradDesc &a = plans[j].d, &b = plans[i].d;
-          if (a.gW == b.gW && a.gb == b.gb && a.Cout == b.Cout && a.Cin == b.Cin && a.KH == b.KH && a.KW == b.KW) { first[i] = first[j]; break; }
-        }
-        if (first[i] != i) shared[i] = shared[first[i]] = 1;
-      }
-      auto buffers = [&](int i) {   // pair buffers of plan i
-        const int npair = (plans[i].S + 1) / 2;
-        if (shared[i]) return npair;
-        return plans[i].S > 1 ? std::max(0, npair - (cleared_target ? 1 : 0)) : 0;
-      };
-      size_t floats = 0;
-      int fw = 0;
-      for (int i = 0; i < np; ++i) {
-        const WgradPlan& pl = plans[i];
-        const long stride = (((long)pl.d.Cout * pl.d.Cin * pl.d.KH * pl.d.KW + pl.d.Cout) + 3) & ~3L;
-        floats += (size_t)buffers(i) * stride;
-      }
-      if (d_partial[g]) (void)hipFree(d_partial[g]);
-      DBM_HIP(hipMalloc((void**)&d_partial[g], (floats + 4) * sizeof(float)));
-      DBM_HIP(hipMemset(d_partial[g], 0, (floats + 4) * sizeof(float)));
-      float* base = d_partial[g];
-      for (int i = 0; i < np; ++i) {
-        WgradPlan& pl = plans[i];
-        pl.fold_start = fw;
-        fstarts.push_back(fw);
-        pl.pairW = nullptr; pl.pair_n = 0; pl.pair_direct = 0; pl.pair_stride = 0; pl.pair_next = -1;
-        const int nb = buffers(i);
-        if (nb <= 0) continue;  // one slice, or two slices onto a cleared gradient: plain atomics commute
-        // (the stride is the exact tensor size + bias; the arena offset is rounded up to four floats)
-        pl.pair_stride = (long)pl.d.Cout * pl.d.Cin * pl.d.KH * pl.d.KW + pl.d.Cout;
-        pl.pairW = base; pl.pair_n = nb; pl.pair_direct = shared[i] ? 0 : (cleared_target ? 1 : 0);
-        base += (size_t)pl.pair_n * ((pl.pair_stride + 3) & ~3L);
-        if (shared[i]) {
-          for (int j = i + 1; j < np; ++j)
-            if (first[j] == first[i]) { pl.pair_next = j; break; }
-          if (first[i] != i) continue;  // folded by the first plan of its gradient: no fold workgroups of its own
-        }
-        fw += (int)((pl.pair_stride + 255) / 256);
-      }
-      fold_wgs[g] = fw;
-      for (int v : fstarts) starts.push_back(v);  // the fold table rides behind the launch table
-    }
-    starts.insert(starts.begin() + (long)plans.size(), total);  // (prefix table of the launch: plans.size() + 1 entries)
-    for (size_t i = 0, k = 0; i < descs.size(); ++i)
-      if (cat[i] == g) desc_S[i] = plans[k++].S;
-    nplans[g] = (int)plans.size();
-    total_wg[g] = total;
-    lds[g] = maxlds;
-    flops[g] = fl;
-    abytes[g] = by;
-    if (plans.empty()) continue;
-    DBM_HIP(hipMalloc((void**)&d_plans[g], plans.size() * sizeof(WgradPlan)));
-    DBM_HIP(hipMalloc((void**)&d_starts[g], starts.size() * sizeof(int)));
-    DBM_HIP(hipMemcpy(d_plans[g], plans.data(), plans.size() * sizeof(WgradPlan), hipMemcpyHostToDevice));
-    DBM_HIP(hipMemcpy(d_starts[g], starts.data(), starts.size() * sizeof(int), hipMemcpyHostToDevice));
+    upload(&d_plans[g], F.plans);
+    upload(&d_starts[g], F.starts);
   }
   DBM_HIP(hipDeviceSynchronize());
   built = true;
   built_deterministic = g_wgrad_deterministic;
   built_cleared = cleared_target;
-}
-
-template <typename K>
-static void launch_dma(K kernel, const WgradPlan* plans, const int* starts, int nplans, int total_wg, size_t lds, hipStream_t s,
-                       int threads = 128) {
-  static bool attr_set = false;
-  if (!attr_set) {  // (one flag for the three kernels: they share this instantiation's signature)
-    DBM_HIP(hipFuncSetAttribute((const void*)wgrad_wave_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    DBM_HIP(hipFuncSetAttribute((const void*)wgrad_band_dma_kernel<9, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    DBM_HIP(hipFuncSetAttribute((const void*)wgrad_band_dma_kernel<16, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    DBM_HIP(hipFuncSetAttribute((const void*)wgrad_direct_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
-    DBM_HIP(hipFuncSetAttribute((const void*)wgrad_direct_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
-    DBM_HIP(hipFuncSetAttribute((const void*)wgrad_direct_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
-    DBM_HIP(hipFuncSetAttribute((const void*)wgrad_1x1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(total_wg), dim3(threads), lds, s, plans, starts, nplans);
-  DBM_HIP(hipGetLastError());
 }
 
 void WgradBatch::launch(hipStream_t s) {
@@ -1792,23 +1390,20 @@ void WgradBatch::launch(hipStream_t s) {
   }
   for (int g = 0; g < NCAT; ++g) {
     if (nplans[g] == 0) continue;
+    const WgradForm& f = kWgradForms[g];
     if (g_profiler.enabled) {
-      static const char* const cat_name[NCAT] = {"wgrad<1,1>", "wgrad<9,9>", "wgrad<16,8>", "wave_dma", "band_dma<9,9>", "band_dma<16,8>",
-                                                 "direct<0>", "direct<1>", "direct<2>", "wgrad_1x1"};
       char tag[40];
-      snprintf(tag, sizeof(tag), "%s_x%d", cat_name[g], nplans[g]);
+      snprintf(tag, sizeof(tag), "%s_x%d", f.tag, nplans[g]);
       g_profiler.begin(s, 1, flops[g], abytes[g], tag, total_wg[g]);
     }
-    if (g == 0) launch_T<1, 1>(d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s);
-    else if (g == 1) launch_T<9, 9>(d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s);
-    else if (g == 2) launch_T<16, 8>(d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s);
-    else if (g == 3) launch_dma(wgrad_wave_dma_kernel, d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s);
-    else if (g == 4) launch_dma(wgrad_band_dma_kernel<9, 9>, d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s);
-    else if (g == 5) launch_dma(wgrad_band_dma_kernel<16, 8>, d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s);
-    else if (g == 6) launch_dma(wgrad_direct_kernel<0>, d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s, 256);
-    else if (g == 7) launch_dma(wgrad_direct_kernel<1>, d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s, 256);
-    else if (g == 8) launch_dma(wgrad_direct_kernel<2>, d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s, 256);
-    else launch_dma(wgrad_1x1_kernel, d_plans[g], d_starts[g], nplans[g], total_wg[g], lds[g], s, 256);
+    static bool attr_set[NCAT] = {};
+    if (!attr_set[g]) {
+      DBM_HIP(hipFuncSetAttribute((const void*)kWgradKernels[g], hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_attr));
+      attr_set[g] = true;
+    }
+    hipLaunchKernelGGL(kWgradKernels[g], dim3(total_wg[g]), dim3(f.threads), lds[g], s, (const WgradPlan*)d_plans[g], (const int*)d_starts[g],
+                       nplans[g]);
+    DBM_HIP(hipGetLastError());
     if (fold_wgs[g]) {
       static const bool abl_fold = (dbm_abl_skip() & 8) != 0;  // (libdbm_measure.so only)
       if (!abl_fold)
