@@ -15,8 +15,9 @@ from .training import (  # noqa: F401
     save_model_weights_and_architecture, split_dataset_random, train_epochs, train_eval_discriminator, train_eval_generator, train_iteration, train_minibatch, trainer,
 )
 from .parallel import DataParallel, shard_batch, shard_slice  # noqa: F401
-from .evaluation import DevicePoints, GridGeometry, TrackStats, get_deepbedmap_test_result, grdtrack, make_test_area_score  # noqa: F401
-from .comparison import compare_on_tracks, cubic_bedmap, rescale, standard_deviation_2d  # noqa: F401
+from .evaluation import (DevicePoints, GridGeometry, TrackDescription, TrackStats, describe_errors, error_histogram,  # noqa: F401
+                         get_deepbedmap_test_result, grdtrack, make_test_area_score)
+from .comparison import compare_on_tracks, cubic_bedmap, describe_on_tracks, rescale, standard_deviation_2d  # noqa: F401
 from .gridding import block_geometry, block_shape, blockmedian, blockmedian_grid, get_region, parse_region, region_of, reproject  # noqa: F401
 from .gridding import mask_far_from_data, tension_surface, to_pixel_registration, xyz_to_grid  # noqa: F401
 from .ascii_table import TextReader, ascii_to_xyz, parse_pipeline, read_text_table  # noqa: F401

@@ -129,6 +129,10 @@ SIGNATURES = {
     "dbm_ssim": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int],
     "dbm_grid_track": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                        C.c_double, C.c_void_p, C.c_void_p, C.c_int],
+    "dbm_track_error_quantiles": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_int],
+    "dbm_track_error_histogram": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_int],
     "dbm_grid_tile": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.POINTER(C.c_double), C.c_void_p, C.c_long, C.c_int, C.c_double,
                       C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
     "dbm_grid_filled_windows": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],

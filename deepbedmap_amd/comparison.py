@@ -10,7 +10,7 @@ releases; the reference's pinned 0.15 interpolates differently).  No CPU fallbac
 """
 import numpy as np
 
-from .evaluation import grdtrack
+from .evaluation import describe_errors, distribution_arguments, grdtrack
 from .resident import DeviceArray, DevicePoints, GridGeometry, devptr, plane_shape, points_table, resident_plane
 from .resident import to_device  # noqa: F401  (re-exported)
 
@@ -90,11 +90,9 @@ def cubic_bedmap(X_tile, ctx=None):
     return out
 
 
-def compare_on_tracks(points, grids, interpolation="bicubic", threshold=0.5, ctx=None):
-    """The table of deepbedmap.py:550-574, 622-626: every product grid sampled at the same survey points (x, y, z) and its
-    along-track error summarised.  grids: {name: (grid, GridGeometry)}, grid a NumPy array or a DeviceArray (read in place);
-    points: array / DataFrame (uploaded once) or DevicePoints.  Returns {name: TrackStats}; the reference's headline number is
-    result["deepbedmap3"].rmse - result["cubicbedmap"].rmse."""
+def _grids_and_points(who, points, grids, ctx):
+    """[(name, grid, GridGeometry)] of a {name: (grid, GridGeometry)} mapping, and the points (x, y, z) as DevicePoints: a host table is
+    uploaded once, to the context of the first resident grid"""
     if not hasattr(grids, "items"):
         raise TypeError("grids must map a name to (grid, GridGeometry)")
     entries = []
@@ -104,11 +102,33 @@ def compare_on_tracks(points, grids, interpolation="bicubic", threshold=0.5, ctx
         plane_shape(entry[0])
         entries.append((name, entry[0], entry[1]))
     if (points.ncol if isinstance(points, DevicePoints) else points_table(points).shape[1]) != 3:
-        raise ValueError("compare_on_tracks: the points need a z column")
+        raise ValueError(f"{who}: the points need a z column")
     if not isinstance(points, DevicePoints):
         for _, g, _ in entries:
             if ctx is None and isinstance(g, DeviceArray):
                 ctx = g.ctx
         points = DevicePoints(points, ctx)   # uploaded once, sampled by every grid
+    return entries, points
+
+
+def compare_on_tracks(points, grids, interpolation="bicubic", threshold=0.5, ctx=None):
+    """The table of deepbedmap.py:550-574, 622-626: every product grid sampled at the same survey points (x, y, z) and its
+    along-track error summarised.  grids: {name: (grid, GridGeometry)}, grid a NumPy array or a DeviceArray (read in place);
+    points: array / DataFrame (uploaded once) or DevicePoints.  Returns {name: TrackStats}; the reference's headline number is
+    result["deepbedmap3"].rmse - result["cubicbedmap"].rmse.  The quartile rows of the table and the histograms: describe_on_tracks."""
+    entries, points = _grids_and_points("compare_on_tracks", points, grids, ctx)
     return {name: grdtrack(points, g, geom, interpolation=interpolation, threshold=threshold, return_values=False, ctx=points.ctx)[1]
+            for name, g, geom in entries}
+
+
+def describe_on_tracks(points, grids, interpolation="bicubic", threshold=0.5, percentiles=(0.25, 0.5, 0.75), bins=None, range=None,
+                       ctx=None):
+    """compare_on_tracks with the whole table of deepbedmap.py:550-563 -- `describe()`'s eight rows per grid -- and, with `bins`, the
+    error histograms of deepbedmap.py:575-608 (`hist(column="error", bins=25)`; range None: each grid's own (min, max), as pandas
+    plots them).  The points are uploaded once for all grids; z_interpolated never leaves the device.  Returns {name:
+    TrackDescription}; `.as_dict()` is `describe()`, `.histogram` (counts, edges) or None."""
+    distribution_arguments(percentiles, bins, range)
+    entries, points = _grids_and_points("describe_on_tracks", points, grids, ctx)
+    return {name: describe_errors(points, g, geom, interpolation=interpolation, threshold=threshold, percentiles=percentiles,
+                                  ctx=points.ctx, bins=bins, range=range)
             for name, g, geom in entries}

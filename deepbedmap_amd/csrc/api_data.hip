@@ -48,6 +48,61 @@ int dbm_grid_track(dbm_ctx* ctx, const float* grid_dev, long H, long W, const do
   DBM_API_END
 }
 
+// ---- the distribution of the along-track errors (track_dist.hip) ----
+// what the two calls share: the table checks, and the host form's points in stage[0], z_interpolated in stage[1]
+static TrackErrors track_errors(dbm_ctx* ctx, const char* who, const double* points, const double* z_interpolated, size_t n, bool dev) {
+  DBM_CHECK(n == 0 || (points != nullptr && z_interpolated != nullptr), std::string(who) + ": NULL points or z_interpolated");
+  DBM_CHECK(n < ((size_t)1 << 40), std::string(who) + ": n must stay below 2^40 points");
+  TrackErrors a;
+  a.points = dev || n == 0 ? points : stage_table(ctx, 0, points, 3 * n);
+  a.z_interp = dev || n == 0 ? z_interpolated : stage_table(ctx, 1, z_interpolated, n);
+  a.n = (long)n;
+  return a;
+}
+
+// the result of the host form leaves through stage[2]; the stream is drained for it, and before a workspace of the call's own is freed
+static void track_result(dbm_ctx* ctx, void* out, const void* dresult, size_t bytes, bool dev, bool own_workspace) {
+  if (!dev) DBM_HIP(hipMemcpyAsync(out, dresult, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (!dev || own_workspace) DBM_HIP(hipStreamSynchronize(ctx->stream));
+}
+
+int dbm_track_error_quantiles(dbm_ctx* ctx, const double* points, const double* z_interpolated, size_t n, const double* probabilities,
+                              int count, double* quantiles_out, void* workspace_dev, int flags) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && probabilities != nullptr && quantiles_out != nullptr, "dbm_track_error_quantiles: NULL argument");
+  const bool dev = device_ptrs(flags);
+  if (dev) note_device_write(ctx);
+  DBM_CHECK(count >= 1 && count <= DBM_TRACK_MAX_QUANTILES, "dbm_track_error_quantiles: 1..16 probabilities per call");
+  for (int k = 0; k < count; ++k)
+    DBM_CHECK(probabilities[k] >= 0.0 && probabilities[k] <= 1.0, "dbm_track_error_quantiles: the probabilities must lie in [0, 1]");
+  const TrackErrors a = track_errors(ctx, "dbm_track_error_quantiles", points, z_interpolated, n, dev);
+  ScopedBuf own;
+  void* ws = workspace_dev ? workspace_dev : own.as<char>(track_quantiles_workspace());
+  double* dout = dev ? quantiles_out : stage_table(ctx, 2, nullptr, (size_t)count);
+  launch_track_error_quantiles(a, probabilities, count, dout, ws, ctx->stream);
+  track_result(ctx, quantiles_out, dout, sizeof(double) * (size_t)count, dev, workspace_dev == nullptr);
+  DBM_API_END
+}
+
+int dbm_track_error_histogram(dbm_ctx* ctx, const double* points, const double* z_interpolated, size_t n, const double* edges, int bins,
+                              int64_t* counts_out, void* workspace_dev, int flags) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && edges != nullptr && counts_out != nullptr, "dbm_track_error_histogram: NULL argument");
+  const bool dev = device_ptrs(flags);
+  if (dev) note_device_write(ctx);
+  DBM_CHECK(bins >= 1 && bins <= DBM_TRACK_MAX_BINS, "dbm_track_error_histogram: 1..4096 bins");
+  for (int k = 0; k <= bins; ++k)
+    DBM_CHECK(std::isfinite(edges[k]) && (k == 0 || edges[k] >= edges[k - 1]), "dbm_track_error_histogram: the edges must be finite and must not decrease");
+  DBM_CHECK(edges[0] < edges[bins], "dbm_track_error_histogram: the range is empty (edges[0] >= edges[bins])");
+  const TrackErrors a = track_errors(ctx, "dbm_track_error_histogram", points, z_interpolated, n, dev);
+  ScopedBuf own;
+  void* ws = workspace_dev ? workspace_dev : own.as<char>(track_histogram_workspace(bins));
+  long long* dout = dev ? (long long*)counts_out : (long long*)stage_table(ctx, 2, nullptr, (size_t)bins);
+  launch_track_error_histogram(a, edges, bins, dout, ws, ctx->stream);
+  track_result(ctx, counts_out, dout, sizeof(int64_t) * (size_t)bins, dev, workspace_dev == nullptr);
+  DBM_API_END
+}
+
 int dbm_grid_tile(dbm_ctx* ctx, const float* grid_dev, long H, long W, const double geom[4], const void* windows_host, long n, int mode,
                   double resolution, int out_h, int out_w, const double* nodata, const float* gapfiller, int fill_nan, float* out_dev,
                   size_t window_stride, int* counts_dev) {

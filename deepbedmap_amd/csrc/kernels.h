@@ -279,6 +279,20 @@ struct TrackLaunch {
 int grid_track_blocks(long n);   // workgroups of the sampling launch (depends on n only): partials needed
 void launch_grid_track(const TrackLaunch& a, double* stats, hipStream_t s);
 
+// The errors of one dbm_grid_track call (track_dist.hip; dbm_track_error_quantiles, dbm_track_error_histogram): e_i = z_interp[i] -
+// points[3 i + 2], finite ones only, -0.0 as +0.0.  Quantiles: `count` probabilities (host) -> out (device), NumPy's method="linear" on
+// exact order statistics (radix select, 8 passes over the points whatever `count`).  Histogram: np.histogram's uniform-bin rule with
+// the caller's bins + 1 edges (host, copied into ws) -> counts (device, int64).  ws: track_*_workspace() bytes, 256-byte aligned.
+struct TrackErrors {
+  const double* points;
+  const double* z_interp;
+  long n;
+};
+size_t track_quantiles_workspace();
+size_t track_histogram_workspace(int bins);
+void launch_track_error_quantiles(const TrackErrors& a, const double* probs, int count, double* out, void* ws, hipStream_t s);
+void launch_track_error_histogram(const TrackErrors& a, const double* edges_host, int bins, long long* counts, void* ws, hipStream_t s);
+
 // Gridline -> pixel registration (track.hip; dbm_grid_to_pixel, `grdsample -T`): out (H - 1, W - 1) = the bicubic interpolant of
 // launch_grid_track (same weights, ghost nodes, NaN / threshold rule) at the cell centres (c + 1/2, r + 1/2), rounded to float32 once
 void launch_grid_to_pixel(const float* in, long H, long W, double threshold, float* out, hipStream_t s);

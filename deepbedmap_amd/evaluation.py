@@ -5,8 +5,10 @@ along-track error to its RMSE: `rmse_test`, the number that picks the keep-best 
 and is the Optuna objective (:1721).  Here the grid is sampled on the GPU (dbm_grid_track, include/dbm.h) where it
 lives -- a DeviceArray canvas of `predict_tiled_resident(download=False)` is read in place -- with GMT's three standard
 interpolants (`grdtrack -nn / -nl / -nc`, NaN threshold +t 0.5), and the errors are reduced there too (count, mean,
-std, min, max, rmse; deterministic).  Semantics: DESIGN.md "Track sampling".  No CPU fallback: without a GPU every
-call raises DbmError.
+std, min, max, rmse; deterministic).  Semantics: DESIGN.md "Track sampling".  The rest of the reference's error table and
+its error histogram (deepbedmap.py:550-563, 575-608) -- the quartiles of `describe()`, `hist(bins=25)` -- come from
+`describe_errors` and `error_histogram`, which read z_interpolated where dbm_grid_track left it (dbm_track_error_quantiles,
+dbm_track_error_histogram; DESIGN.md "Error distribution").  No CPU fallback: without a GPU every call raises DbmError.
 """
 import dataclasses
 
@@ -18,12 +20,14 @@ from .resident import (REGISTRATIONS, DeviceArray, DevicePoints, GridGeometry, d
 from .srgan import using_config
 
 INTERPOLATIONS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+MAX_QUANTILES, MAX_BINS, DIST_WORKSPACE = 16, 4096, 69632   # DBM_TRACK_MAX_QUANTILES, _MAX_BINS, _DIST_WORKSPACE (include/dbm.h)
 
 
 @dataclasses.dataclass(frozen=True)
 class TrackStats:
-    """Summary of the finite along-track errors e = z_interpolated - z (`DataFrame.describe()` columns, std with ddof 1) and
-    rmse = sqrt(sum e^2 / count).  count 0: every other value NaN; std NaN for count < 2.  All NaN without a z column."""
+    """Summary of the finite along-track errors e = z_interpolated - z: the count, mean, std (ddof 1), min and max rows of
+    `DataFrame.describe()`, and rmse = sqrt(sum e^2 / count).  The 25 %, 50 % and 75 % rows are in `TrackDescription`
+    (`describe_errors`).  count 0: every other value NaN; std NaN for count < 2.  All NaN without a z column."""
     count: int
     mean: float
     std: float
@@ -34,6 +38,30 @@ class TrackStats:
     @classmethod
     def from_array(cls, s):
         return cls(int(s[0]), float(s[1]), float(s[2]), float(s[3]), float(s[4]), float(s[5]))
+
+
+def percentile_label(p):
+    """0.25 -> "25%", 0.125 -> "12.5%": the row labels of `describe()`"""
+    return f"{round(100.0 * float(p), 9):g}%"
+
+
+@dataclasses.dataclass(frozen=True)
+class TrackDescription:
+    """The error table of deepbedmap.py:550-563 for one grid: `stats` (TrackStats) and `quantiles[k]` = the `percentiles[k]` quantile
+    of the finite errors (`np.quantile(e, p, method="linear")`, what `describe()` computes; NaN for count 0).  `histogram`: (counts
+    int64, edges float64) when bins were asked for, else None."""
+    stats: TrackStats
+    percentiles: tuple
+    quantiles: tuple
+    histogram: tuple = dataclasses.field(default=None, compare=False)
+
+    def as_dict(self):
+        """`describe()`'s rows in its order: count, mean, std, min, the percentiles (ascending, "25%" ...), max"""
+        d = {"count": self.stats.count, "mean": self.stats.mean, "std": self.stats.std, "min": self.stats.min}
+        for p, q in sorted(zip(self.percentiles, self.quantiles), key=lambda pq: pq[0]):
+            d[percentile_label(p)] = q
+        d["max"] = self.stats.max
+        return d
 
 
 _NO_STATS = TrackStats(0, float("nan"), float("nan"), float("nan"), float("nan"), float("nan"))
@@ -57,6 +85,11 @@ def grdtrack(points, grid, geometry, interpolation="bicubic", threshold=0.5, ret
     points: (n, 2) / (n, 3) array or DataFrame of x, y[, z], or DevicePoints (already resident); grid: NumPy array or
     DeviceArray of shape (H, W), (1, H, W) or (1, 1, H, W) (a DeviceArray is read in place); geometry: GridGeometry.
     Returns (z_interpolated float64 (n,) or None, TrackStats; the statistics are NaN without a z column)."""
+    return _grdtrack(points, grid, geometry, interpolation, threshold, return_values, ctx)
+
+
+def _grdtrack(points, grid, geometry, interpolation, threshold, return_values, ctx, resident_values=False):
+    """grdtrack; resident_values: a DevicePoints' z_interpolated is written to `points.outputs()[0]` also when it is not returned"""
     H, W = plane_shape(grid)
     _check(interpolation, threshold, H, W)
     if not isinstance(geometry, GridGeometry):
@@ -72,7 +105,7 @@ def grdtrack(points, grid, geometry, interpolation="bicubic", threshold=0.5, ret
             raise ValueError("grdtrack: the points and the grid live on different contexts")
         n, ncol = dpts.n, dpts.ncol
         zdev, sdev = dpts.outputs()
-        src, zout, sout, flags = dpts, (zdev if return_values else None), sdev, _lib.DEVICE_PTRS
+        src, zout, sout, flags = dpts, (zdev if return_values or resident_values else None), sdev, _lib.DEVICE_PTRS
     else:
         n, ncol = pts.shape
         z = np.empty(n if return_values else 0, dtype=np.float64)
@@ -83,6 +116,92 @@ def grdtrack(points, grid, geometry, interpolation="bicubic", threshold=0.5, ret
         z = ctx.download(zdev, np.float64, n if return_values else 0)
         ctx.download(sdev, out=stats)
     return (z if return_values else None), (TrackStats.from_array(stats) if ncol == 3 else _NO_STATS)
+
+
+def _probabilities(percentiles):
+    q = np.atleast_1d(np.asarray(percentiles, dtype=np.float64))
+    if q.ndim != 1 or not 1 <= q.size <= MAX_QUANTILES:
+        raise ValueError(f"percentiles: 1..{MAX_QUANTILES} probabilities, got shape {q.shape}")
+    if not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError(f"percentiles must lie in [0, 1], got {percentiles!r}")
+    return np.ascontiguousarray(q)
+
+
+def _bins(bins):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)):
+        raise TypeError(f"bins must be an integer (uniform bins), got {bins!r}")
+    if not 1 <= bins <= MAX_BINS:
+        raise ValueError(f"bins must lie in 1..{MAX_BINS}, got {bins}")
+    return int(bins)
+
+
+def histogram_edges(stats, bins, range=None):
+    """The bins + 1 edges `np.histogram(e, bins, range)` uses for errors with the extremes of `stats` (NumPy's own rule, by
+    NumPy: range None -> (min, max), (0, 1) for count 0; first == last -> -+ 0.5; then np.linspace)."""
+    seen = np.array([stats.min, stats.max] if stats.count > 0 else [], dtype=np.float64)
+    return np.histogram_bin_edges(seen, bins=_bins(bins), range=range).astype(np.float64, copy=False)
+
+
+def distribution_arguments(percentiles, bins=None, range=None):
+    """The probabilities as a float64 array; ValueError / TypeError for percentiles, bins or a range that will not do"""
+    q = _probabilities(percentiles)
+    if bins is not None:
+        histogram_edges(_NO_STATS, bins, range)
+    return q
+
+
+def _sampled(who, points, grid, geometry, interpolation, threshold, ctx):
+    """grdtrack on a DevicePoints (a host table is uploaded once, to the grid's context), z_interpolated left on the device"""
+    if not isinstance(points, DevicePoints):
+        points = DevicePoints(points, ctx or (grid.ctx if isinstance(grid, DeviceArray) else None))
+    if points.ncol != 3:
+        raise ValueError(f"{who}: the points need a z column")
+    _, stats = _grdtrack(points, grid, geometry, interpolation, threshold, False, ctx, resident_values=True)
+    return points, stats
+
+
+def _quantiles(dpts, q):
+    ctx, out = dpts.ctx, np.empty(q.size, dtype=np.float64)
+    with ctx.scratch(DIST_WORKSPACE + out.nbytes) as ws:   # the workspace, then the result
+        ctx.call("dbm_track_error_quantiles", devptr(dpts), devptr(dpts.outputs()[0]), dpts.n, f64ptr(q), q.size,
+                 devptr(ws + DIST_WORKSPACE), devptr(ws), _lib.DEVICE_PTRS)
+        ctx.download(ws + DIST_WORKSPACE, out=out)
+    return tuple(float(v) for v in out)
+
+
+def _histogram(dpts, edges):
+    ctx, out = dpts.ctx, np.empty(edges.size - 1, dtype=np.int64)
+    with ctx.scratch(DIST_WORKSPACE + out.nbytes) as ws:
+        ctx.call("dbm_track_error_histogram", devptr(dpts), devptr(dpts.outputs()[0]), dpts.n, f64ptr(edges), out.size,
+                 devptr(ws + DIST_WORKSPACE), devptr(ws), _lib.DEVICE_PTRS)
+        ctx.download(ws + DIST_WORKSPACE, out=out)
+    return out
+
+
+def describe_errors(points, grid, geometry, interpolation="bicubic", threshold=0.5, percentiles=(0.25, 0.5, 0.75), ctx=None, bins=None,
+                    range=None):
+    """The error table of deepbedmap.py:550-563 for one grid, on the GPU: `grdtrack` at the points (x, y, z), then
+    `(z_interpolated - z).describe(percentiles)` of the finite errors -- TrackStats plus exact quantiles (NumPy's / pandas' linear
+    rule on exact order statistics, dbm_track_error_quantiles).  points: array / DataFrame (uploaded once) or DevicePoints;
+    z_interpolated stays on the device and only the table comes back.  percentiles: 1..16 probabilities in [0, 1].  With `bins`,
+    the description also carries `error_histogram`'s (counts, edges) of the same sampling.  Returns TrackDescription."""
+    q = distribution_arguments(percentiles, bins, range)   # (argument errors before any work)
+    dpts, stats = _sampled("describe_errors", points, grid, geometry, interpolation, threshold, ctx)
+    hist = None
+    if bins is not None:
+        edges = histogram_edges(stats, bins, range)
+        hist = (_histogram(dpts, edges), edges)
+    return TrackDescription(stats, tuple(float(v) for v in q), _quantiles(dpts, q), hist)
+
+
+def error_histogram(points, grid, geometry, bins=25, range=None, interpolation="bicubic", threshold=0.5, ctx=None):
+    """`df.hist(column="error", bins=25)`'s numbers (deepbedmap.py:575-608) on the GPU: `np.histogram(e, bins=bins, range=range)` of
+    the finite errors e = z_interpolated - z of `grdtrack` at the points.  bins: 1..4096 uniform bins; range None: the errors'
+    (min, max), from the statistics of the same sampling.  Returns (counts int64 (bins,), edges float64 (bins + 1,))."""
+    distribution_arguments((0.5,), bins, range)   # (argument errors before any work)
+    dpts, stats = _sampled("error_histogram", points, grid, geometry, interpolation, threshold, ctx)
+    edges = histogram_edges(stats, bins, range)
+    return _histogram(dpts, edges), edges
 
 
 def _forward(model, X_tile, W1_tile, W2_tile, W3_tile, dtype):

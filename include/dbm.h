@@ -86,6 +86,16 @@ enum {
   DBM_TEXT_MAX_NA_BYTES = 16,
   DBM_TEXT_MAX_COLUMNS = 8
 };
+/* dbm_track_error_*: the most probabilities of one quantile call, the most bins of one histogram, the bytes of device workspace either
+ * call fits in, and the threads and the most workgroups of their passes over the points (track_dist.hip).  Listed here so that tests
+ * can put n on both sides of a workgroup's share and of one grid-stride round. */
+enum {
+  DBM_TRACK_MAX_QUANTILES = 16,
+  DBM_TRACK_MAX_BINS = 4096,
+  DBM_TRACK_DIST_WORKSPACE = 69632,
+  DBM_TRACK_DIST_THREADS = 256,
+  DBM_TRACK_DIST_BLOCKS = 1024
+};
 
 /* ---- context ---- */
 int dbm_init(int hip_device, dbm_ctx** out);      /* replaces model.to_gpu(): srgan_train.py:1038-1040, deepbedmap.py:659 */
@@ -294,6 +304,38 @@ int dbm_ssim_ex(dbm_ctx* ctx, const float* y_pred, const float* y_true, int N, i
  * dx or dy zero or not finite. */
 int dbm_grid_track(dbm_ctx* ctx, const float* grid_dev, long H, long W, const double geom[5], const double* points, size_t n,
                    int ncol, int interp, double threshold, double* z_out, double* stats, int flags);
+
+/* ---- the rest of the error table and the error histogram (deepbedmap.py:550-563, the 25 %, 50 % and 75 % rows of `df.describe()` of
+ * error = z_interpolated - z; deepbedmap.py:575-608, `df.hist(column="error", bins=25)`) ----
+ * Both calls take the points table -- C-contiguous float64 (n, 3) x, y, z -- and the z_interpolated column (n doubles) that
+ * dbm_grid_track wrote for it, and work on e_i = z_interpolated_i - z_i, formed on the fly in float64.  An error takes part iff it is
+ * finite (the set dbm_grid_track reduces; m of them) and -0.0 counts as +0.0.  flags: DBM_DEVICE_PTRS = points, z_interpolated and the
+ * result are device pointers (asynchronous); otherwise host pointers, staged, and the call synchronises.  probabilities and edges are
+ * ALWAYS host pointers (read before the call returns).  workspace_dev: DBM_TRACK_DIST_WORKSPACE bytes of device memory, 256-byte
+ * aligned, the call's own until its work on the stream is done; NULL: the call allocates and frees it, which synchronises.  Only
+ * integer atomics carry counts between lanes and workgroups (no float atomics): every result is exact, the same bytes from call to
+ * call and under any permutation of the points.
+ *
+ * dbm_track_error_quantiles: quantiles_out[k] = `np.quantile(e, probabilities[k], method="linear")` of the m finite errors (what
+ * `Series.describe()` and `Series.quantile` compute), count in 1..DBM_TRACK_MAX_QUANTILES probabilities in any order, duplicates
+ * allowed.  Exact order statistics by a device-wide radix select -- no sort: errors map to order-preserving 64-bit keys, eight digit
+ * passes read the points once each (however many probabilities are asked) and count, per wanted rank, the next digit of the keys that
+ * share the rank's prefix; one workgroup narrows the prefixes between the passes; no host round trip.  Then h = (m - 1) q, j = floor(h),
+ * g = h - j; a, b = the order statistics j and j + 1 (both the maximum if h >= m - 1); d = b - a; the result is a + d g, or
+ * b - d (1 - g) where g >= 0.5, every product and sum rounded on its own (no fused multiply-add).  m = 0: NaN.
+ *
+ * dbm_track_error_histogram: counts_out (bins int64) = `np.histogram(e, bins=bins, range=(edges[0], edges[bins]))[0]` for the
+ * bins + 1 edges the caller computed (`np.linspace(first, last, bins + 1)`), by NumPy's uniform-bin rule: keep first <= e <= last;
+ * i = (long)(((e - first) / (last - first)) * bins), an IEEE division; i == bins: i - 1; e < edges[i]: i - 1; e >= edges[i + 1] and
+ * i != bins - 1: i + 1 (the last bin includes its right edge).
+ *
+ * Refused (status 1, nothing launched or written): NULL pointers with n > 0, NULL probabilities / edges / result, n >= 2^40, count
+ * outside 1..DBM_TRACK_MAX_QUANTILES, a probability that is NaN or outside [0, 1], bins outside 1..DBM_TRACK_MAX_BINS, edges that are
+ * not finite, that decrease, or with edges[0] >= edges[bins]. */
+int dbm_track_error_quantiles(dbm_ctx* ctx, const double* points, const double* z_interpolated, size_t n, const double* probabilities,
+                              int count, double* quantiles_out, void* workspace_dev, int flags);
+int dbm_track_error_histogram(dbm_ctx* ctx, const double* points, const double* z_interpolated, size_t n, const double* edges, int bins,
+                              int64_t* counts_out, void* workspace_dev, int flags);
 
 /* ---- tiling: `selective_tile` (data_prep.py:622-741: every raster cut and bilinearly geo-registered to a list of windows; the
  * training set data_prep.py:757-771, 880-911 and the inputs of an area deepbedmap.py:132-213 are built from it) ----
