@@ -51,6 +51,20 @@ class WgradDesc(C.Structure):
                 ("scale", C.c_float), ("gW", C.c_void_p), ("gb", C.c_void_p)]
 
 
+class TrunkForward(C.Structure):
+    """dbm_trunk_forward (include/dbm.h): the persistent trunk forward at op level; every pointer is a HOST pointer."""
+    _fields_ = [("nrdb", C.c_int), ("N", C.c_int), ("rs", C.c_float), ("imgs_per_launch", C.c_int), ("only_launch", C.c_int),
+                ("epoch0", C.c_int), ("keep", C.c_int), ("tile", C.c_int), ("helper", C.c_int), ("agent_stores", C.c_int),
+                ("w", c_void_pp), ("b", c_void_pp), ("cat", c_void_pp), ("out", C.c_void_p)]
+
+
+class TrunkBackward(C.Structure):
+    """dbm_trunk_backward (include/dbm.h): the trunk's data-gradient chain at op level; every pointer is a HOST pointer."""
+    _fields_ = [("nrdb", C.c_int), ("N", C.c_int), ("rs", C.c_float), ("imgs_per_launch", C.c_int), ("only_launch", C.c_int),
+                ("epoch0", C.c_int), ("agent_stores", C.c_int), ("nlaunch", C.c_int), ("j0", C.POINTER(C.c_int)), ("j1", C.POINTER(C.c_int)),
+                ("w", c_void_pp), ("gin", C.c_void_p), ("gin_sn", C.c_int64), ("cat", c_void_pp), ("g_a3", C.c_void_p), ("dA", c_void_pp)]
+
+
 # name -> (argtypes) ; every function returns int except dbm_last_error
 # void allreduce_sum(void* user, float* dev, int n): the sync_batch_stats hook (dbm_set_sync_batch_stats)
 ALLREDUCE_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)
@@ -172,6 +186,8 @@ SIGNATURES = {
     "dbm_op_conv2d_backward": [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int] * 9,
     "dbm_op_conv2d_launch": [C.c_void_p, C.POINTER(ConvLaunch), C.POINTER(C.c_int)],
     "dbm_op_conv2d_wgrad_batch": [C.c_void_p, C.POINTER(WgradDesc), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "dbm_op_trunk_forward": [C.c_void_p, C.POINTER(TrunkForward), C.POINTER(C.c_int), C.c_int],
+    "dbm_op_trunk_backward": [C.c_void_p, C.POINTER(TrunkBackward), C.POINTER(C.c_int), C.c_int],
     "dbm_op_conv2d_cl16": [C.c_void_p] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p] + [C.c_int] * 6,
     "dbm_op_conv2d_cl16x3": [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] * 7,
     "dbm_op_deform_conv2d": [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 5,

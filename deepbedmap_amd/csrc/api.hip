@@ -1464,6 +1464,187 @@ int dbm_op_conv2d_wgrad_batch(dbm_ctx* ctx, const dbm_wgrad_desc* descs, int L, 
   DBM_API_END
 }
 
+// ---- the persistent trunk kernels at op level (include/dbm.h) ----
+// One inbox and one launch counter for both ops, for the life of the process: successive calls meet each other's granules, as the
+// passes of a generator's workspace do.  The counter starts in the middle of the 20-bit range, so that a process crosses the wrap
+// only where a caller asks for it (epoch0).
+static unsigned long long* g_op_trunk_inbox = nullptr;
+static int g_op_trunk_epoch = 0x80000;
+static const int TRUNK_PLANE = 81;
+static const float TRUNK_SLOPE = 0.2f;
+
+static unsigned long long* op_trunk_inbox() {
+  if (!g_op_trunk_inbox) {
+    DBM_HIP(hipMalloc((void**)&g_op_trunk_inbox, trunk_fused_inbox_bytes(64)));
+    DBM_HIP(hipMemset(g_op_trunk_inbox, 0, trunk_fused_inbox_bytes(64)));
+    DBM_HIP(hipDeviceSynchronize());
+  }
+  return g_op_trunk_inbox;
+}
+
+// floats of dense block layer k's (0..4) OIHW weight tensor / bias
+static size_t trunk_w_floats(int k) { return (size_t)(k < 4 ? 32 : 64) * (64 + 32 * k) * 9; }
+static size_t trunk_b_floats(int k) { return k < 4 ? 32 : 64; }
+
+// the nrdb * 5 host tensors of `host` (sizes by layer) into one device arena; their device addresses as a device table
+static const float** upload_trunk_tensors(dbm_ctx* ctx, const float* const* host, int nrdb, bool bias, ScopedBuf& arena, ScopedBuf& table) {
+  size_t total = 0;
+  for (int i = 0; i < nrdb * 5; ++i) total += bias ? trunk_b_floats(i % 5) : trunk_w_floats(i % 5);
+  arena.ensure(total);
+  std::vector<const float*> ptrs(nrdb * 5);
+  size_t off = 0;
+  for (int i = 0; i < nrdb * 5; ++i) {
+    const size_t n = bias ? trunk_b_floats(i % 5) : trunk_w_floats(i % 5);
+    DBM_CHECK(host[i] != nullptr, "trunk op: a weight / bias pointer is null");
+    DBM_HIP(hipMemcpyAsync(arena.p + off, host[i], n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    ptrs[i] = arena.p + off;
+    off += n;
+  }
+  const float** d = table.as<const float*>(ptrs.size());
+  DBM_HIP(hipMemcpyAsync((void*)d, ptrs.data(), ptrs.size() * sizeof(float*), hipMemcpyHostToDevice, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));  // (ptrs is a local)
+  return d;
+}
+
+static void check_trunk_op(const dbm_ctx* ctx, int nrdb, int N, int ipl, int only_launch) {
+  DBM_CHECK(nrdb >= 3 && nrdb % 3 == 0, "trunk op: nrdb must be a positive multiple of 3");
+  DBM_CHECK(nrdb + 1 <= TRUNK_FUSED_MAXCAT, "trunk op: too many dense blocks for the persistent kernels");
+  DBM_CHECK(N >= 1 && ipl >= 1 && ipl <= ctx->trunk_imgs, "trunk op: imgs_per_launch outside 1 .. the context's images per persistent launch");
+  DBM_CHECK(only_launch < (N + ipl - 1) / ipl, "trunk op: only_launch past the last launch");
+}
+
+// after the synchronisation: a bounded spin that ran out fails the call (the word is lowered again: no model is involved)
+static void finish_trunk_op(dbm_ctx* ctx, const std::vector<TrunkLaunchReport>& reps, int* report, int report_cap) {
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  const bool gave_up = ctx->dev_err && *(volatile int*)ctx->dev_err;
+  if (gave_up) {
+    *(volatile int*)ctx->dev_err = 0;
+    if (ctx->dev_err_flag) DBM_HIP(hipMemset(ctx->dev_err_flag, 0, sizeof(int)));
+    DBM_HIP(hipDeviceSynchronize());
+  }
+  if (report && report_cap >= 1) {
+    report[0] = (int)reps.size();
+    for (size_t i = 0; i < reps.size() && 2 + 2 * (int)i < report_cap; ++i) {
+      report[1 + 2 * i] = reps[i].form;
+      report[2 + 2 * i] = reps[i].grid;
+    }
+  }
+  if (gave_up) throw DbmError(7, "trunk op: a persistent kernel gave up waiting for a neighbouring workgroup");
+}
+
+int dbm_op_trunk_forward(dbm_ctx* ctx, const dbm_trunk_forward* a, int* report, int report_cap) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(a != nullptr && a->w && a->b && a->cat && a->cat[0], "trunk forward op: w, b and cat[0] are required");
+  check_trunk_op(ctx, a->nrdb, a->N, a->imgs_per_launch, a->only_launch);
+  DBM_CHECK(a->tile == 27 || a->tile == 32, "trunk forward op: tile must be 27 or 32");
+  DBM_CHECK(!a->helper || a->tile == 27, "trunk forward op: the helper form has 27-position tiles");
+  DBM_CHECK(a->keep || a->out, "trunk forward op: out is required without keep");
+  const int nrdb = a->nrdb, N = a->N, nbuf = a->keep ? nrdb + 1 : 2;
+  const size_t catn = (size_t)N * 192 * TRUNK_PLANE;
+  std::vector<float*> host(nbuf);
+  for (int i = 0; i < nbuf; ++i) {
+    host[i] = a->keep ? a->cat[i] : (i == 0 ? a->cat[0] : a->out);
+    DBM_CHECK(host[i] != nullptr, "trunk forward op: a concat buffer is null");
+  }
+  ScopedBuf warena, barena, wtab, btab, wstream, bstream, bufs;
+  const float** d_w = upload_trunk_tensors(ctx, a->w, nrdb, false, warena, wtab);
+  const float** d_b = upload_trunk_tensors(ctx, a->b, nrdb, true, barena, btab);
+  wstream.ensure(trunk_fused_stream_floats(nrdb));   // (zeroed: the read-ahead pad behind the last block)
+  bstream.ensure((size_t)nrdb * 192);
+  launch_pack_trunk_fused(d_w, d_b, wstream.p, bstream.p, nrdb, ctx->stream);
+  bufs.ensure(catn * nbuf);
+  std::vector<float*> dev(nbuf);
+  for (int i = 0; i < nbuf; ++i) {
+    dev[i] = bufs.p + catn * i;
+    DBM_HIP(hipMemcpyAsync(dev[i], host[i], catn * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  unsigned long long* inbox = op_trunk_inbox();
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  std::vector<TrunkLaunchReport> reps;
+  int epoch = a->epoch0 >= 0 ? a->epoch0 - 1 : g_op_trunk_epoch;
+  const int IMGS = a->imgs_per_launch;
+  for (int i0 = 0; i0 < N; i0 += IMGS) {  // (Generator::forward's loop)
+    if (a->only_launch >= 0 && i0 / IMGS != a->only_launch) continue;
+    TrunkFusedLaunch L;
+    L.wstream = wstream.p; L.bstream = bstream.p; L.in = dev[0];
+    L.cat = a->keep ? dev.data() : nullptr; L.out = a->keep ? dev[nrdb] : dev[1];
+    L.inbox = inbox; L.err = ctx->dev_err_d; L.err_dev = ctx->dev_err_flag;
+    L.nrdb = nrdb; L.nimg = std::min(IMGS, N - i0); L.img0 = i0; L.epoch = ++epoch;
+    L.rs = a->rs; L.slope = TRUNK_SLOPE;
+    L.tile = a->tile; L.helper = a->helper ? 1 : 0; L.local_st = a->agent_stores ? 0 : 1;
+    TrunkLaunchReport r;
+    ctx->persist_begin(ctx->stream);
+    launch_trunk_fused(L, ctx->stream, &r);
+    ctx->persist_end(ctx->stream);
+    reps.push_back(r);
+  }
+  g_op_trunk_epoch = epoch;
+  for (int i = 0; i < nbuf; ++i) DBM_HIP(hipMemcpyAsync(host[i], dev[i], catn * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  finish_trunk_op(ctx, reps, report, report_cap);
+  DBM_API_END
+}
+
+int dbm_op_trunk_backward(dbm_ctx* ctx, const dbm_trunk_backward* a, int* report, int report_cap) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(a != nullptr && a->w && a->cat && a->dA && a->gin && a->g_a3 && a->j0 && a->j1, "trunk backward op: a required pointer is null");
+  check_trunk_op(ctx, a->nrdb, a->N, a->imgs_per_launch, a->only_launch);
+  const int nrdb = a->nrdb, N = a->N;
+  DBM_CHECK(a->gin_sn == 64 * TRUNK_PLANE || a->gin_sn == 192 * TRUNK_PLANE, "trunk backward op: gin's image stride is 64 * 81 or 192 * 81");
+  DBM_CHECK(a->nlaunch >= 1, "trunk backward op: no launches");
+  for (int i = 0; i < a->nlaunch; ++i) {
+    DBM_CHECK(a->j0[i] >= 0 && a->j0[i] % 3 == 0 && a->j1[i] % 3 == 0 && a->j0[i] < a->j1[i] && a->j1[i] <= nrdb,
+              "trunk backward op: launches cover whole RRDBs");
+    DBM_CHECK(i == 0 || a->j1[i] == a->j0[i - 1], "trunk backward op: a launch starts where the one before ended");
+  }
+  const size_t catn = (size_t)N * 192 * TRUNK_PLANE;
+  ScopedBuf warena, wtab, wstream, bufs, gin, ga3;
+  const float** d_w = upload_trunk_tensors(ctx, a->w, nrdb, false, warena, wtab);
+  wstream.ensure(trunk_fused_bwd_stream_floats(nrdb));
+  launch_pack_trunk_fused_bwd(d_w, wstream.p, nrdb, ctx->stream);
+  bufs.ensure(catn * 2 * nrdb);
+  gin.ensure((size_t)N * a->gin_sn);
+  ga3.ensure((size_t)N * 64 * TRUNK_PLANE);
+  std::vector<float*> dAp(nrdb);
+  std::vector<const float*> catp(nrdb);
+  for (int j = 0; j < nrdb; ++j) {
+    DBM_CHECK(a->cat[j] && a->dA[j], "trunk backward op: a concat buffer is null");
+    float* c = bufs.p + catn * j;
+    dAp[j] = bufs.p + catn * (nrdb + j);
+    catp[j] = c;
+    DBM_HIP(hipMemcpyAsync(c, a->cat[j], catn * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    DBM_HIP(hipMemcpyAsync(dAp[j], a->dA[j], catn * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  DBM_HIP(hipMemcpyAsync(gin.p, a->gin, (size_t)N * a->gin_sn * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  DBM_HIP(hipMemcpyAsync(ga3.p, a->g_a3, (size_t)N * 64 * TRUNK_PLANE * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  unsigned long long* inbox = op_trunk_inbox();
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  std::vector<TrunkLaunchReport> reps;
+  int epoch = a->epoch0 >= 0 ? a->epoch0 - 1 : g_op_trunk_epoch;
+  const int IMGS = a->imgs_per_launch;
+  for (int g = 0; g < a->nlaunch; ++g) {  // (Generator::backward's loops: groups from the top down, image chunks inside)
+    for (int i0 = 0; i0 < N; i0 += IMGS) {
+      if (a->only_launch >= 0 && i0 / IMGS != a->only_launch) continue;
+      TrunkFusedBwdLaunch L;
+      L.wstream = wstream.p;
+      L.gin = g == 0 ? gin.p : dAp[a->j1[g]]; L.gin_sn = g == 0 ? (long)a->gin_sn : 192L * TRUNK_PLANE;
+      L.dA = dAp.data(); L.cat = catp.data(); L.g_a3 = ga3.p;
+      L.inbox = inbox; L.err = ctx->dev_err_d; L.err_dev = ctx->dev_err_flag;
+      L.nrdb = nrdb; L.j0 = a->j0[g]; L.j1 = a->j1[g]; L.nimg = std::min(IMGS, N - i0); L.img0 = i0; L.epoch = ++epoch;
+      L.rs = a->rs; L.slope = TRUNK_SLOPE;
+      L.local_st = a->agent_stores ? 0 : 1;
+      TrunkLaunchReport r;
+      ctx->persist_begin(ctx->stream);
+      launch_trunk_fused_bwd(L, ctx->stream, &r);
+      ctx->persist_end(ctx->stream);
+      reps.push_back(r);
+    }
+  }
+  g_op_trunk_epoch = epoch;
+  for (int j = 0; j < nrdb; ++j) DBM_HIP(hipMemcpyAsync(a->dA[j], dAp[j], catn * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  finish_trunk_op(ctx, reps, report, report_cap);
+  DBM_API_END
+}
+
 // 3x3 / stride 1 / pad 1 convolution through the channels-last bf16 kernel of the sweep's trunk (conv_cl16.hip), for the parity
 // tests: x (N, C, H, W) fp32 is rounded to bf16 NHWC, y = [lrelu](s1 * (conv + b) + r1), fp32 out.  All DEVICE pointers.
 int dbm_op_conv2d_cl16(dbm_ctx* ctx, const float* x, const float* w, const float* b, const float* r1, float s1, float* y, int N,

@@ -172,12 +172,23 @@ struct TrunkFusedLaunch {
   int nrdb, nimg, img0, epoch;
   float rs, slope;
   int no_helper = 0;     // 1: never the four-workgroups-per-image form (data-parallel runs: RCCL's kernels need compute units too)
+  // Overrides of what the launcher otherwise takes from the environment / the process state (op-level tests: dbm_op_trunk_forward).
+  // The defaults mean "as ever"; host side only, the kernels' arguments are the same.
+  int tile = 0;          // 27 or 32: the tile form (0: DBM_TRUNK_TP)
+  int helper = -1;       // 1 / 0: ask for / never the helper form, whatever the pass keeps (-1: DBM_TRUNK_HELPER's mask); still TP = 27
+                         // only, and only while four workgroups per image fit the device
+  int local_st = -1;     // 1 / 0: same-XCD exchange stores may stay in the L2 / agent scope only (-1: trunk_local_stores())
+};
+// What launch_trunk_fused / launch_trunk_fused_bwd launched (op-level tests), written where the launcher decides.
+struct TrunkLaunchReport {
+  int form;              // 0 TP = 27, 1 TP = 27 with a helper workgroup per image, 2 TP = 32, 3 the data-gradient chain
+  int grid;              // workgroups launched
 };
 size_t trunk_fused_stream_floats(int nrdb);
 size_t trunk_fused_inbox_bytes(int nimg);
 void launch_pack_trunk_fused(const float* const* d_wsrc, const float* const* d_bsrc, float* wstream, float* bstream, int nrdb,
                              hipStream_t s);
-void launch_trunk_fused(const TrunkFusedLaunch& L, hipStream_t s);
+void launch_trunk_fused(const TrunkFusedLaunch& L, hipStream_t s, TrunkLaunchReport* rep = nullptr);
 
 // ---- fused data-gradient chain of the RRDB trunk on 9x9 planes (trunk_fused_bwd.hip) ----
 struct TrunkFusedBwdLaunch {
@@ -193,13 +204,14 @@ struct TrunkFusedBwdLaunch {
   int nrdb, j0, j1;          // dense blocks j1 - 1 ... j0 (both multiples of 3)
   int nimg, img0, epoch;
   float rs, slope;
+  int local_st = -1;         // 1 / 0: as TrunkFusedLaunch::local_st (-1: trunk_local_stores())
 };
 size_t trunk_fused_xcc_offset(int nimg_alloc);  // granules in front of the XCC_ID table at the end of an inbox buffer
 int trunk_local_stores();                       // same-XCD exchange stores stay in the L2 (until the first time-out)
 extern bool g_trunk_local_off;                  // ... until a persistent kernel has timed out once in this process
 size_t trunk_fused_bwd_stream_floats(int nrdb);
 void launch_pack_trunk_fused_bwd(const float* const* d_wsrc, float* wstream, int nrdb, hipStream_t s);
-void launch_trunk_fused_bwd(const TrunkFusedBwdLaunch& L, hipStream_t s);
+void launch_trunk_fused_bwd(const TrunkFusedBwdLaunch& L, hipStream_t s, TrunkLaunchReport* rep = nullptr);
 
 // ---- sync_batch_stats (norm_loss.hip): BatchNorm / RaGAN statistics over the global batch of a data-parallel run ----
 void launch_bn_sync_stats(const float* z, float* buf, int N, int C, int plane, hipStream_t s);

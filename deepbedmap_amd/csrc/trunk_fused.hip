@@ -828,7 +828,7 @@ void launch_pack_trunk_fused(const float* const* d_wsrc, const float* const* d_b
   DBM_HIP(hipGetLastError());
 }
 
-void launch_trunk_fused(const TrunkFusedLaunch& L, hipStream_t s) {
+void launch_trunk_fused(const TrunkFusedLaunch& L, hipStream_t s, TrunkLaunchReport* rep) {
   // DBM_TRUNK_TP=27 (default): three whole rows per tile (three workgroups per image, 27 of 32 MFMA columns); 32: tiles of 32
   // consecutive positions across rows and images (5184 positions of 64 images = 162 workgroups, every column works; measured
   // 5 % slower per pass: only the centre tap can run ahead of the halo, 255 VGPRs).
@@ -836,8 +836,11 @@ void launch_trunk_fused(const TrunkFusedLaunch& L, hipStream_t s) {
   // per 64-image pass).  Bit 0: in passes that keep nothing (inference, the D-step's fakes), bit 1: in retained passes.
   // Default 1: the G-step's retained forward runs underneath the discriminator's passes, which need the 64 CUs it leaves
   // (measured: 8.82 ms per step without helpers, 8.75 with bit 0, 9.2 with both).
-  static const int TP = getenv("DBM_TRUNK_TP") ? atoi(getenv("DBM_TRUNK_TP")) : 27;
-  static const int helper_mask = getenv("DBM_TRUNK_HELPER") ? atoi(getenv("DBM_TRUNK_HELPER")) : 1;
+  static const int env_TP = getenv("DBM_TRUNK_TP") ? atoi(getenv("DBM_TRUNK_TP")) : 27;
+  static const int env_helper_mask = getenv("DBM_TRUNK_HELPER") ? atoi(getenv("DBM_TRUNK_HELPER")) : 1;
+  // (TrunkFusedLaunch::tile / helper: the op-level tests name the form themselves)
+  const int TP = L.tile ? L.tile : env_TP;
+  const int helper_mask = L.helper < 0 ? env_helper_mask : (L.helper ? 3 : 0);
   static const int n_cus = [] {
     int dev = 0;
     hipDeviceProp_t prop;
@@ -846,7 +849,7 @@ void launch_trunk_fused(const TrunkFusedLaunch& L, hipStream_t s) {
   }();
   // (four workgroups per image, all resident at once, one per CU: only if the device has that many)
   const bool helper = TP == 27 && (helper_mask & (L.cat ? 2 : 1)) != 0 && 4 * L.nimg <= n_cus && !L.no_helper;
-  DBM_CHECK(TP == 27 || TP == 32, "DBM_TRUNK_TP must be 27 or 32");
+  DBM_CHECK(TP == 27 || TP == 32, "DBM_TRUNK_TP (TrunkFusedLaunch::tile) must be 27 or 32");
   static bool attr = false;
   if (!attr) {
     DBM_HIP(hipFuncSetAttribute((const void*)trunk_fused_kernel<27, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -867,7 +870,7 @@ void launch_trunk_fused(const TrunkFusedLaunch& L, hipStream_t s) {
   a.ntiles = (L.nimg * 81 + TP - 1) / TP;
   a.tpx = TP == 27 ? 3 * ((L.nimg + 7) / 8) : (a.ntiles + 7) / 8;
   a.off_xcc = (unsigned)trunk_fused_xcc_offset(64);
-  a.local_st = trunk_local_stores();
+  a.local_st = L.local_st < 0 ? trunk_local_stores() : (L.local_st != 0);
   a.off_hb = (unsigned)(3 * L.nimg * 2 * 2 * 64 * HS);
   a.off_bh = a.off_hb + (unsigned)(L.nimg * 2 * 5 * 32 * 81);
   const double flop = 2.0 * 19408896.0 * L.nrdb * L.nimg;  // 19 408 896 MAC per dense block and tile
@@ -886,6 +889,10 @@ void launch_trunk_fused(const TrunkFusedLaunch& L, hipStream_t s) {
   DBM_HIP(hipMemsetAsync(d_ts, 0, sizeof(long long) * 512 * NWAVE * 8, s));
   a.tstamp = d_ts;
 #endif
+  if (rep) {
+    rep->form = helper ? 1 : TP == 27 ? 0 : 2;
+    rep->grid = helper ? 32 * ((L.nimg + 7) / 8) : 8 * a.tpx;
+  }
   if (helper)
     hipLaunchKernelGGL((trunk_fused_kernel<27, true>), dim3(32 * ((L.nimg + 7) / 8)), dim3(NTHREADS), LDS_HELPER, s, a);
   else if (TP == 27)

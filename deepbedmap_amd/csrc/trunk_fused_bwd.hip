@@ -564,7 +564,7 @@ void launch_pack_trunk_fused_bwd(const float* const* d_wsrc, float* wstream, int
   DBM_HIP(hipGetLastError());
 }
 
-void launch_trunk_fused_bwd(const TrunkFusedBwdLaunch& L, hipStream_t s) {
+void launch_trunk_fused_bwd(const TrunkFusedBwdLaunch& L, hipStream_t s, TrunkLaunchReport* rep) {
   static bool attr = false;
   if (!attr) {
     DBM_HIP(hipFuncSetAttribute((const void*)trunk_fused_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
@@ -585,8 +585,9 @@ void launch_trunk_fused_bwd(const TrunkFusedBwdLaunch& L, hipStream_t s) {
   a.abl = abl;
 #endif
   a.off_xcc = (unsigned)trunk_fused_xcc_offset(64);
-  a.local_st = trunk_local_stores();
+  a.local_st = L.local_st < 0 ? trunk_local_stores() : (L.local_st != 0);
   const int grid = ((L.nimg + 7) / 8) * 24;
+  if (rep) { rep->form = 3; rep->grid = grid; }
   if (g_profiler.enabled) {
     // algorithmic bytes: the flipped weights of the launch's dense blocks once; per image the incoming gradient (64 channels),
     // every block's stored concatenation (192: the LeakyReLU masks) in, every block's conv-output gradients dA (192) out

@@ -712,6 +712,59 @@ typedef struct dbm_wgrad_desc {
   float* gb;
 } dbm_wgrad_desc;
 int dbm_op_conv2d_wgrad_batch(dbm_ctx* ctx, const dbm_wgrad_desc* descs, int L, int cleared_target, int* cat_out, int* S_out);
+/* The persistent trunk kernels (trunk_fused.hip, trunk_fused_bwd.hip) through the models' own path: the weight streams are packed from
+ * plain OIHW tensors (launch_pack_trunk_fused / launch_pack_trunk_fused_bwd), the launch loop is Generator::forward's / backward's, chunk
+ * by chunk between persist_begin / persist_end, with the context's error words.  All pointers are HOST pointers: every buffer goes up
+ * whole and comes back whole, so what a launch did not write comes back as the caller left it.  Planes are 9 x 9; a concat buffer is
+ * (N, 192, 81): channels 0..63 the dense block's input, 64..191 conv_layer1..4's outputs.
+ *   nrdb: dense blocks, a multiple of 3 with nrdb + 1 <= 64 (TRUNK_FUSED_MAXCAT; anything else is refused, nothing launched)
+ *   w, b: tables of nrdb * 5 pointers, dense block j's conv_layer(k + 1) at [5 j + k]: (32, 64 + 32 k, 3, 3) / (32), conv_layer5 (64, 192, 3, 3) / (64)
+ *   imgs_per_launch: 1 .. the context's images per persistent launch (min(64, CUs / 3)); launch c covers images [c * imgs_per_launch, ...)
+ *   only_launch: >= 0 runs that chunk's launch(es) alone (the other images are not touched), -1 all
+ *   epoch0: the first launch's epoch, the following launches count up from it (the kernels use its low 20 bits); negative: the op's own
+ *           counter goes on.  The two ops share ONE inbox of trunk_fused_inbox_bytes(64) bytes (zeroed once per process) and that counter,
+ *           as a generator's workspace does.
+ *   agent_stores: 1 = exchange stores at agent scope only (what the kernels do after a time-out), 0 = same-XCD stores may stay in the L2
+ * report (HOST, report_cap ints, may be NULL): report[0] = launches made, then per launch {form, workgroups}: form 0 = 27-position tiles,
+ *   1 = the same with a helper workgroup per image, 2 = 32-position tiles, 3 = the data-gradient chain.  The launcher takes the helper
+ *   form only while four workgroups per image fit the device; the report says what ran.
+ * A call returns status 7 when a bounded spin ran out (the error word was raised); the op lowers the word again and touches no model.
+ *
+ * dbm_op_trunk_forward (srgan_train.py:333-360, :393-404, :546): cat[0][:, 0:64] is the trunk input.  keep = 1: cat is a table of nrdb + 1
+ *   buffers, every layer's output is stored (cat[j][:, 64:192], cat[j + 1][:, 0:64]); keep = 0: cat[0] only, the trunk's output goes to
+ *   out[:, 0:64] (N, 192, 81).  tile: 27 or 32; helper: 1 asks for the helper form (tile 27 only). */
+typedef struct dbm_trunk_forward {
+  int nrdb, N;
+  float rs;
+  int imgs_per_launch, only_launch, epoch0;
+  int keep, tile, helper, agent_stores;
+  const float* const* w;
+  const float* const* b;
+  float* const* cat;
+  float* out;
+} dbm_trunk_forward;
+int dbm_op_trunk_forward(dbm_ctx* ctx, const dbm_trunk_forward* args, int* report, int report_cap);
+/* dbm_op_trunk_backward: the data-gradient chain, nlaunch launches (j0[i], j1[i]) from the top of the trunk down, each over whole RRDBs
+ *   (multiples of 3, j0 < j1 <= nrdb), each starting where the one before ended (j1[i] = j0[i - 1]).  The first launch's incoming
+ *   gradient is gin (N images of gin_sn floats, 64 * 81 or 192 * 81, channels 0..63 are read); a later one reads dA[j1][:, 0:64].  cat and
+ *   dA are tables of nrdb buffers (N, 192, 81): cat[j] supplies the LeakyReLU masks (value >= 0: derivative 1), dA[j] receives block j's
+ *   concat gradient -- channels 64..191 the gradients of conv_layer1..4's outputs in front of their LeakyReLU, channels 0..63 the gradient of
+ *   the block's input.  g_a3 (N, 64, 81) is added at block 0, whose channels 0..63 then pass cat[0]'s mask. */
+typedef struct dbm_trunk_backward {
+  int nrdb, N;
+  float rs;
+  int imgs_per_launch, only_launch, epoch0;
+  int agent_stores;
+  int nlaunch;
+  const int* j0;
+  const int* j1;
+  const float* const* w;
+  const float* gin; int64_t gin_sn;
+  const float* const* cat;
+  const float* g_a3;
+  float* const* dA;
+} dbm_trunk_backward;
+int dbm_op_trunk_backward(dbm_ctx* ctx, const dbm_trunk_backward* args, int* report, int report_cap);
 /* the same L.Convolution2D (3x3, stride 1, pad 1: the RRDB trunk's layers, srgan_train.py:292-331) on the channels-last
  * bf16 kernel of the area sweep (conv_cl16.hip): x is rounded to bf16, fp32 accumulation, y = [lrelu](s1 * (conv + b) + r1)
  * with r1 (N,64,H,W) or NULL; C % 32 == 0, O = 32 or 64 */
