@@ -21,8 +21,8 @@ from .comparison import compare_on_tracks, cubic_bedmap, describe_on_tracks, res
 from .gridding import block_geometry, block_shape, blockmedian, blockmedian_grid, get_region, parse_region, region_of, reproject  # noqa: F401
 from .gridding import mask_far_from_data, tension_surface, to_pixel_registration, xyz_to_grid  # noqa: F401
 from .ascii_table import TextReader, ascii_to_xyz, parse_pipeline, read_text_table  # noqa: F401
-from .geotiff import (canvas_to_int16, open_geotiff, read_geotiff, read_geotiff_resident, save_array_to_grid,  # noqa: F401
-                      write_geotiff_resident)
+from .geotiff import (build_overviews, canvas_to_int16, open_geotiff, overview_pyramid, overview_shapes, read_geotiff,  # noqa: F401
+                      read_geotiff_resident, save_array_to_grid, write_geotiff_resident)
 from .tiling import Raster, fill_gaps, get_deepbedmap_model_inputs, get_window_bounds, selective_tile, tile_training_set  # noqa: F401
 from .polygons import (Polygons, mask_outside, polygon_mask, read_polygons, read_tiles_geojson, select_tiles,  # noqa: F401
                        tiles_to_geojson)

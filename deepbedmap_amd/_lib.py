@@ -156,6 +156,7 @@ SIGNATURES = {
                         C.c_long, C.c_long],
     "dbm_tiff_encode": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int,
                         C.c_void_p, C.c_size_t, C.c_void_p],
+    "dbm_grid_overviews": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p],
     "dbm_grid_rescale": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "dbm_grid_rolling_std": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_void_p],
     "dbm_points_polar_stereographic": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int],

@@ -341,6 +341,34 @@ int dbm_tiff_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sa
   DBM_API_END
 }
 
+// ---- the overview pyramid of a plane (pyramid.hip) ----
+int dbm_grid_overviews(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sample_type, const double* nodata, int levels,
+                       float* out_dev) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_grid_overviews: NULL context");
+  note_device_write(ctx);
+  DBM_CHECK(plane_dev != nullptr, "dbm_grid_overviews: NULL plane");
+  DBM_CHECK(nodata != nullptr, "dbm_grid_overviews: NULL nodata");
+  check_plane("dbm_grid_overviews", H, W, 1, "H W must stay below 2^31 samples", "empty plane");
+  DBM_CHECK(sample_type == 1 || sample_type == 4, "dbm_grid_overviews: sample_type must be 1 (int16, by cast) or 4 (float32)");
+  DBM_CHECK(sample_type == 4 || std::isfinite(*nodata), "dbm_grid_overviews: the nodata value of an int16 file must be finite");
+  const int admits = pyramid_max_levels(H, W);
+  DBM_CHECK(levels >= 0 && levels <= admits, "dbm_grid_overviews: levels must lie in 0.." + std::to_string(admits) + " for a plane of " +
+                                                 std::to_string(H) + " x " + std::to_string(W));
+  if (levels == 0) return 0;
+  DBM_CHECK(out_dev != nullptr, "dbm_grid_overviews: NULL output");
+  DBM_CHECK((const void*)plane_dev != (const void*)out_dev, "dbm_grid_overviews: the output must not be the input");
+  PyramidLaunch a;
+  a.plane = plane_dev;
+  a.H = H; a.W = W;
+  a.sample_type = sample_type;
+  a.nodata = sample_type == 1 ? (float)std::trunc(*nodata) : (float)*nodata;   // int(nodata) / float32(nodata)
+  a.levels = levels;
+  a.out = out_dev;
+  launch_grid_overviews(a, ctx->stream);
+  DBM_API_END
+}
+
 int dbm_grid_rescale(dbm_ctx* ctx, const float* in_dev, long H, long W, long out_h, long out_w, int order, int anti_aliasing, int clip,
                      int input_cast, float* out_dev) {
   DBM_API_BEGIN(ctx)

@@ -397,6 +397,20 @@ void launch_tiff_pack(const uint8_t* src, size_t src_stride, const unsigned long
 // with dbm_lzw_encode_tiles)
 size_t tiff_lzw_encode_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
 
+// The overview pyramid of a plane (pyramid.hip; dbm_grid_overviews): `levels` nodata-aware halvings of the plane as a file of
+// sample_type holds it, written back to back to out as float32 planes of (H + 1) / 2 x (W + 1) / 2, ... -- three levels per launch.
+// nodata: float32(nodata) for float32 files, float(int(nodata)) for int16 files.  pyramid_max_levels: the halvings down to 1 x 1.
+struct PyramidLaunch {
+  const float* plane;
+  long H, W;
+  int sample_type;             // 1 int16 (level 0 by dbm_cast_i16, results rounded to even), 4 float32
+  float nodata;
+  int levels;
+  float* out;
+};
+int pyramid_max_levels(long H, long W);
+void launch_grid_overviews(const PyramidLaunch& a, hipStream_t s);
+
 // Fully filled windows of a raster (tile.hip; dbm_grid_filled_windows): flags[uly * nx + ulx] = 1 iff no node of rows [uly step, uly step
 // + size) x columns [ulx step, ulx step + size) is NaN, rows counted from the north (flip_rows: raster row 0 is the south edge), columns
 // from the west (flip_cols).  rowany: rows * nx bytes of scratch.  filled_windows_geometry fills ny, nx, rows, nw, nseg from H, W,

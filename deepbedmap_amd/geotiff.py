@@ -9,7 +9,10 @@ from libdbm (dbm_lzw_encode_tiles: TIFF 6.0 LZW, host threads over tiles) and th
 from the GPU (dbm_f32_to_i16: NumPy's astype semantics, NaN frame -> 0).  `read_geotiff` decodes the file again
 (bit-exact round trip; the tests also decode it with Pillow / libtiff).  `write_geotiff_resident` writes the same file from a plane in
 HBM without downloading it: cast, tile cutting, predictor 2 and LZW run on the GPU (dbm_tiff_encode), only the streams
-cross PCIe; both writers share the tags (`_image_tags`) and the container (`_write_container`).
+cross PCIe; both writers share the tags (`_image_tags`) and the container (`_write_container`).  `overviews=` on either writer puts
+reduced-resolution images behind the first one, as `gdaladdo -r average` would: each level is the nodata-aware 2 x 2 mean of the one
+before (`overview_pyramid`, the NumPy statement; dbm_grid_overviews builds the levels next to a resident canvas), and `overview=k` on
+the readers selects one ("Overviews").
 
 Reading rasters as GDAL and libtiff write them (reference data_prep.py:668, :845-877; deepbedmap.py:164-204, through rasterio): the
 second half of this file -- `open_geotiff` (header, geometry, block plan, refusals: host), `read_geotiff_resident` (the blocks decoded on
@@ -130,19 +133,24 @@ def _compression_of(compression, who):
     raise ValueError(f"{who}: unsupported compression {compression!r} (none, lzw)")
 
 
-def _image_tags(H, W, dt, comp, predictor, tiled, th, tw, window_bound, nodataval, epsg, bigtiff):
-    """The image directory both writers share: (tag, type, values) with _OFFSETS / _COUNTS where the block tables go."""
+def _image_tags(H, W, dt, comp, predictor, tiled, th, tw, window_bound, nodataval, epsg, bigtiff, overview=False):
+    """The image directory both writers share: (tag, type, values) with _OFFSETS / _COUNTS where the block tables go.  overview: the
+    directory of a reduced-resolution image behind the first one, as GDAL lays it out: NewSubfileType (254) = 1 and no georeference
+    tags (window_bound and epsg are not looked at)."""
     sample_format = {"f": 3, "i": 2, "u": 1}[dt.kind]
-    minx, miny, maxx, maxy = (float(v) for v in window_bound)
-    px, py = (maxx - minx) / W, (maxy - miny) / H  # rasterio.transform.from_bounds
     nodata = (repr(int(nodataval)) if float(nodataval).is_integer() else repr(float(nodataval))).encode() + b"\0"
-    geokeys = [1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 3072, 0, 1, epsg]  # projected, PixelIsArea, ProjectedCSType
     off_t = 16 if bigtiff else 4  # LONG8 / LONG
     tags = [
         (256, 4, [W]), (257, 4, [H]), (258, 3, [8 * dt.itemsize]), (259, 3, [comp]), (262, 3, [1]), (277, 3, [1]),
-        (284, 3, [1]), (339, 3, [sample_format]),
-        (33550, 12, [px, py, 0.0]), (33922, 12, [0.0, 0.0, 0.0, minx, maxy, 0.0]), (34735, 3, geokeys), (42113, 2, [nodata]),
+        (284, 3, [1]), (339, 3, [sample_format]), (42113, 2, [nodata]),
     ]
+    if overview:
+        tags += [(254, 4, [1])]
+    else:
+        minx, miny, maxx, maxy = (float(v) for v in window_bound)
+        px, py = (maxx - minx) / W, (maxy - miny) / H  # rasterio.transform.from_bounds
+        geokeys = [1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 3072, 0, 1, epsg]  # projected, PixelIsArea, ProjectedCSType
+        tags += [(33550, 12, [px, py, 0.0]), (33922, 12, [0.0, 0.0, 0.0, minx, maxy, 0.0]), (34735, 3, geokeys)]
     if predictor != 1:
         tags += [(317, 3, [predictor])]
     if tiled:
@@ -152,20 +160,25 @@ def _image_tags(H, W, dt, comp, predictor, tiled, th, tw, window_bound, nodatava
     return tags
 
 
-def _write_container(path, bigtiff, tags, streams):
+def _write_container(path, bigtiff, tags, streams, overviews=()):
     """The file both writers share: the header, then the streams (any iterable of bytes-like objects, taken one at a time) at even
-    offsets, then the image directory with its tags sorted and the values that do not fit an entry behind it."""
-    tags = sorted(tags, key=lambda t: t[0])
+    offsets, then the image directory with its tags sorted and the values that do not fit an entry behind it.  overviews: the images
+    behind the first one, a list of (tags, streams): the streams of image 0, 1, ... follow one another, then the directories in the
+    same order, each at an even offset and chained through its next-IFD offset, the last one 0."""
+    images = [(tags, streams)] + list(overviews)
     with open(path, "wb") as f:
-        # header, then the pixel data, then the IFD (offsets known by then)
+        # header, then the pixel data, then the IFDs (offsets known by then)
         f.write(struct.pack("<2sHHHQ", b"II", 43, 8, 0, 0) if bigtiff else struct.pack("<2sHI", b"II", 42, 0))
-        offsets, counts = [], []
-        for s in streams:
-            if f.tell() % 2:
-                f.write(b"\0")
-            offsets.append(f.tell())
-            counts.append(len(s))
-            f.write(s)
+        tables = []
+        for _, image_streams in images:
+            offsets, counts = [], []
+            for s in image_streams:
+                if f.tell() % 2:
+                    f.write(b"\0")
+                offsets.append(f.tell())
+                counts.append(len(s))
+                f.write(s)
+            tables.append((offsets, counts))
         if f.tell() % 2:
             f.write(b"\0")
 
@@ -175,30 +188,38 @@ def _write_container(path, bigtiff, tags, streams):
                 return vals[0]
             return struct.pack("<%d%s" % (len(vals), fmt), *vals)
 
-        entries, extra = [], b""
         inline = 8 if bigtiff else 4
-        ifd_pos = f.tell()
-        ntags = len(tags)
-        ifd_size = (8 + 20 * ntags + 8) if bigtiff else (2 + 12 * ntags + 4)
-        extra_pos = ifd_pos + ifd_size
-        for tag, typ, vals in tags:
-            if vals is _OFFSETS:
-                vals = offsets
-            elif vals is _COUNTS:
-                vals = counts
-            data = payload(typ, vals)
-            count = len(data) if typ == 2 else len(vals)
-            if len(data) <= inline:
-                field = data + b"\0" * (inline - len(data))
-            else:
-                if (extra_pos + len(extra)) % 2:
-                    extra += b"\0"
-                field = struct.pack("<Q" if bigtiff else "<I", extra_pos + len(extra))
-                extra += data
-            entries.append(struct.pack("<HHQ" if bigtiff else "<HHI", tag, typ, count) + field)
-        f.write(struct.pack("<Q" if bigtiff else "<H", ntags) + b"".join(entries) + struct.pack("<Q" if bigtiff else "<I", 0) + extra)
+        first_ifd = ifd_pos = f.tell()
+        for k, (image_tags, _) in enumerate(images):
+            image_tags = sorted(image_tags, key=lambda t: t[0])
+            offsets, counts = tables[k]
+            entries, extra = [], b""
+            ntags = len(image_tags)
+            ifd_size = (8 + 20 * ntags + 8) if bigtiff else (2 + 12 * ntags + 4)
+            extra_pos = ifd_pos + ifd_size
+            for tag, typ, vals in image_tags:
+                if vals is _OFFSETS:
+                    vals = offsets
+                elif vals is _COUNTS:
+                    vals = counts
+                data = payload(typ, vals)
+                count = len(data) if typ == 2 else len(vals)
+                if len(data) <= inline:
+                    field = data + b"\0" * (inline - len(data))
+                else:
+                    if (extra_pos + len(extra)) % 2:
+                        extra += b"\0"
+                    field = struct.pack("<Q" if bigtiff else "<I", extra_pos + len(extra))
+                    extra += data
+                entries.append(struct.pack("<HHQ" if bigtiff else "<HHI", tag, typ, count) + field)
+            last = k == len(images) - 1
+            if not last and (extra_pos + len(extra)) % 2:
+                extra += b"\0"
+            next_ifd = 0 if last else extra_pos + len(extra)
+            f.write(struct.pack("<Q" if bigtiff else "<H", ntags) + b"".join(entries) + struct.pack("<Q" if bigtiff else "<I", next_ifd) + extra)
+            ifd_pos = next_ifd
         f.seek(8 if bigtiff else 4)
-        f.write(struct.pack("<Q" if bigtiff else "<I", ifd_pos))
+        f.write(struct.pack("<Q" if bigtiff else "<I", first_ifd))
     return path
 
 
@@ -211,14 +232,158 @@ def _difference_blocks(blocks):
     return d.view(blocks.dtype)
 
 
+def overview_shapes(H, W, levels, who="overview_shapes", name="levels"):
+    """The shapes [(H_1, W_1), ..., (H_levels, W_levels)] of the overviews of an (H, W) image: every level halves the one before,
+    H' = ceil(H / 2), W' = ceil(W / 2).  levels: an int >= 0, or "auto": down to the first level whose larger side is at most TILE
+    (256; none for an image that small).  A level beyond the first 1 x 1 level, or anything else, raises a ValueError that names the
+    argument (`name` of `who`) and the number of levels the image admits."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"{who}: an image of {H} x {W} has no overviews")
+    shapes, h, w = [], H, W
+    while h > 1 or w > 1:
+        h, w = -(-h // 2), -(-w // 2)
+        shapes.append((h, w))
+    if isinstance(levels, str) and levels == "auto":
+        n = 0
+        while max((H, W) if n == 0 else shapes[n - 1]) > TILE:
+            n += 1
+        return shapes[:n]
+    if isinstance(levels, (bool, np.bool_)) or not isinstance(levels, (int, np.integer)) or levels < 0:
+        raise ValueError(f"{who}: {name} {levels!r}: an int >= 0 or 'auto' (an image of {H} x {W} admits {len(shapes)} levels)")
+    if levels > len(shapes):
+        raise ValueError(f"{who}: {name} {levels!r}: an image of {H} x {W} admits {len(shapes)} levels (the last one is 1 x 1)")
+    return shapes[:int(levels)]
+
+
+def _halved(a, nodata):
+    """One level of `overview_pyramid`: a float32 (H, W) -> (the means, float32 (ceil(H / 2), ceil(W / 2)); where a window holds no valid
+    sample); `nodata` marks invalid samples besides NaN."""
+    H, W = a.shape
+    h, w = -(-H // 2), -(-W // 2)
+    zero = np.float32(0.0)
+    x = np.full((2 * h, 2 * w), zero, dtype=np.float32)   # samples that do not exist: +0.0, not counted
+    ok = np.zeros((2 * h, 2 * w), dtype=bool)
+    ok[:H, :W] = ~(np.isnan(a) | (a == nodata))
+    x[:H, :W] = a
+    x = np.where(ok, x, zero)
+    s = (x[0::2, 0::2] + x[0::2, 1::2]) + (x[1::2, 0::2] + x[1::2, 1::2])
+    n = (ok[0::2, 0::2].astype(np.float32) + ok[0::2, 1::2].astype(np.float32)) + (ok[1::2, 0::2].astype(np.float32)
+                                                                                  + ok[1::2, 1::2].astype(np.float32))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = s / n
+    return m, n == 0
+
+
+def overview_pyramid(band, levels, nodataval):
+    """The overviews of the image `band` (H, W), int16 or float32 as the file holds it: the NumPy statement of the definition in
+    DESIGN.md 6j ("Overviews"), float32 throughout, that dbm_grid_overviews computes bit for bit.  Level k + 1 is made from level k
+    alone: pixel (r, c) is s / float32(n), s = (a00 + a01) + (a10 + a11) over the samples of rows 2r, 2r + 1 and columns 2c, 2c + 1
+    with +0.0 for those that do not exist or are invalid (float32: NaN or equal to float32(nodataval); int16: equal to
+    int(nodataval)), n the number of the others; n == 0 gives the nodata value; int16 levels are `np.rint` of that (ties to even)
+    and the next level is made from the rounded samples.  Returns the list of the levels 1 .. levels in band's dtype
+    (levels: `overview_shapes`)."""
+    band = np.asarray(band)
+    if band.ndim != 2 or band.dtype not in (np.dtype(np.int16), np.dtype(np.float32)):
+        raise ValueError(f"overview_pyramid: band must be an int16 or float32 (H, W) array, not {band.dtype.name} {band.shape}")
+    shapes = overview_shapes(band.shape[0], band.shape[1], levels, "overview_pyramid")
+    integer = band.dtype.kind == "i"
+    nodata = np.float32(int(nodataval)) if integer else np.float32(nodataval)
+    out, a = [], band.astype(np.float32)
+    for shape in shapes:
+        m, empty = _halved(a, nodata)
+        with np.errstate(invalid="ignore"):
+            a = np.where(empty, nodata, np.rint(m) + np.float32(0.0) if integer else m).astype(np.float32)   # (+ 0.0: the int16 0 is +0.0)
+        assert a.shape == shape
+        with np.errstate(invalid="ignore"):
+            out.append(a.astype(band.dtype))
+    return out
+
+
+def build_overviews(array, levels, dtype=np.float32, nodataval=-2000):
+    """The overviews a writer puts behind `array` with `overviews=levels`, without writing a file (`overview_pyramid`'s
+    definition; levels: `overview_shapes`).  A float32 DeviceArray (H, W) or (1, H, W): one dbm_grid_overviews call, the levels
+    returned as float32 DeviceArrays (H_k, W_k) that share one allocation -- dtype int16: level 0 is the cast of the plane and the
+    samples are the rounded values as floats.  A NumPy array: the levels as NumPy arrays of `dtype`, from the array cast to it."""
+    who = "build_overviews"
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.int16), np.dtype(np.float32)):
+        raise ValueError(f"{who}: dtype {dt.name}: int16 (by cast) and float32 have overviews")
+    if not isinstance(array, DeviceArray):
+        band = np.asarray(array)
+        if not (band.ndim == 2 or (band.ndim == 3 and band.shape[0] == 1)):
+            raise ValueError(f"{who}: array must be (1, H, W) or (H, W); got {band.shape}")
+        band = band.reshape(band.shape[-2:])
+        with np.errstate(invalid="ignore"):
+            return overview_pyramid(band.astype(dt), levels, nodataval)
+    shape = tuple(array.shape)
+    if array.dtype != np.float32 or not (len(shape) == 2 or (len(shape) == 3 and shape[0] == 1)) or shape[-2] < 1 or shape[-1] < 1:
+        raise ValueError(f"{who}: array must be a float32 DeviceArray of (1, H, W) or (H, W) and not empty; got {array.dtype.name} {shape}")
+    shapes = overview_shapes(shape[-2], shape[-1], levels, who)
+    if dt == np.int16:
+        _finite_nodata(nodataval, who)
+    return _device_pyramid(array, shape[-2], shape[-1], 1 if dt == np.int16 else 4, nodataval, shapes)
+
+
+def _finite_nodata(nodataval, who):
+    """int(nodataval) marks the invalid samples of an int16 file: NaN and inf have none (refused before any device work)."""
+    try:
+        int(nodataval)
+    except (ValueError, OverflowError):
+        raise ValueError(f"{who}: nodataval {nodataval!r}: the overviews of an int16 file need a finite value") from None
+
+
+def _device_pyramid(array, H, W, sample_type, nodataval, shapes):
+    """dbm_grid_overviews of the resident plane `array` into ONE DeviceArray; returns the levels as views of it."""
+    if not shapes:
+        return []
+    ctx = array.ctx
+    pyramid = DeviceArray((sum(h * w for h, w in shapes),), ctx)
+    ctx.call("dbm_grid_overviews", devptr(array), H, W, sample_type, C.byref(C.c_double(float(nodataval))), len(shapes), devptr(pyramid))
+    pyramid.written()
+    levels, at = [], 0
+    for h, w in shapes:
+        levels.append(DeviceArray((h, w), ctx, ptr=pyramid.ptr + 4 * at, owner=pyramid))
+        at += h * w
+    return levels
+
+
+def _host_blocks(band, dt, comp, predictor, tiled, nthreads):
+    """One image of `save_array_to_grid`: (th, tw, the list of its blocks' streams)."""
+    H, W = band.shape
+    th, tw = (TILE, TILE) if tiled else (min(TILE, H), W)
+    blocks, ny, nx = _tiles_of(band, th, tw)
+    if predictor == 2:
+        blocks = _difference_blocks(blocks)
+    raw = blocks.reshape(len(blocks), -1).view(np.uint8)
+    # strips: the last one holds only the rows that exist (TIFF 6.0: StripByteCounts of H % RowsPerStrip rows, what GDAL
+    # writes); tiles are always whole (zero padded)
+    last_rows = H - (ny - 1) * th
+    short_last = (not tiled) and last_rows < th
+    if comp == 5:
+        if short_last:
+            streams = lzw_encode_tiles(raw[:-1], nthreads) if ny > 1 else []
+            streams += lzw_encode_tiles(np.ascontiguousarray(raw[-1:, :last_rows * tw * dt.itemsize]), nthreads)
+        else:
+            streams = lzw_encode_tiles(raw, nthreads)
+    else:
+        streams = [r.tobytes() for r in raw]
+        if short_last:
+            streams[-1] = streams[-1][:last_rows * tw * dt.itemsize]
+    return th, tw, streams
+
+
 def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=EPSG_ANTARCTIC_POLAR_STEREOGRAPHIC, dtype=None,
-                       nodataval=-2000, tiled=False, compression="none", bigtiff=True, nthreads=None, predictor=1):
+                       nodataval=-2000, tiled=False, compression="none", bigtiff=True, nthreads=None, predictor=1, overviews=0):
     """data_prep.py:779-834 without rasterio: writes `{outfilepath}.tif` and returns its path.
 
     window_bound = (minx, miny, maxx, maxy); array is CHW with one channel (a NumPy array, or a DeviceArray canvas when
     dtype is int16); compression "none" or "lzw" (rasterio.enums.Compression values); tiled=False writes one strip per
     row block of 256 rows.  predictor=2 (with "lzw"; libtiff's predictors are part of its codecs, so "none" writes the samples
-    as they are and no tag): every block row is differenced on the host before it is encoded, and Predictor (317) = 2 is written."""
+    as they are and no tag): every block row is differenced on the host before it is encoded, and Predictor (317) = 2 is written.
+    overviews (int16 and float32 files): the number of reduced-resolution images written behind the first one, or "auto"
+    (`overview_shapes`); each halves the one before (`overview_pyramid`: `gdaladdo -r average` in spirit) and is cut, differenced
+    and compressed as the first one is.  0: the file is byte for byte what it always was."""
     if save_netcdf:
         raise NotImplementedError("NetCDF output (xarray) is outside this framework; convert the GeoTIFF with GDAL")
     assert len(array.shape) == 3 and array.shape[0] == 1  # one band, CHW (data_prep.py:800-801)
@@ -239,31 +404,22 @@ def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=
     comp = _compression_of(compression, "save_array_to_grid")
     if comp == 1:
         predictor = 1
-    th, tw = (TILE, TILE) if tiled else (min(TILE, H), W)
-    blocks, ny, nx = _tiles_of(band, th, tw)
-    if predictor == 2:
-        blocks = _difference_blocks(blocks)
-    raw = blocks.reshape(len(blocks), -1).view(np.uint8)
-    # strips: the last one holds only the rows that exist (TIFF 6.0: StripByteCounts of H % RowsPerStrip rows, what GDAL
-    # writes); tiles are always whole (zero padded)
-    last_rows = H - (ny - 1) * th
-    short_last = (not tiled) and last_rows < th
-    if comp == 5:
-        if short_last:
-            streams = lzw_encode_tiles(raw[:-1], nthreads) if ny > 1 else []
-            streams += lzw_encode_tiles(np.ascontiguousarray(raw[-1:, :last_rows * tw * dt.itemsize]), nthreads)
-        else:
-            streams = lzw_encode_tiles(raw, nthreads)
-    else:
-        streams = [r.tobytes() for r in raw]
-        if short_last:
-            streams[-1] = streams[-1][:last_rows * tw * dt.itemsize]
+    shapes = overview_shapes(H, W, overviews, "save_array_to_grid", "overviews")
+    if shapes and dt not in (np.dtype(np.int16), np.dtype(np.float32)):
+        raise ValueError(f"save_array_to_grid: overviews of {dt.name} samples: int16 and float32 files have them")
+    th, tw, streams = _host_blocks(band, dt, comp, predictor, tiled, nthreads)
     tags = _image_tags(H, W, dt, comp, predictor, tiled, th, tw, window_bound, nodataval, epsg, bigtiff)
-    return _write_container(f"{outfilepath}.tif", bigtiff, tags, streams)
+    images = []
+    for level in overview_pyramid(band, len(shapes), nodataval) if shapes else ():
+        h, w = level.shape
+        level = np.ascontiguousarray(level.astype(dt.newbyteorder("<"), copy=False))
+        lh, lw, level_streams = _host_blocks(level, dt, comp, predictor, tiled, nthreads)
+        images.append((_image_tags(h, w, dt, comp, predictor, tiled, lh, lw, None, nodataval, None, bigtiff, overview=True), level_streams))
+    return _write_container(f"{outfilepath}.tif", bigtiff, tags, streams, images)
 
 
 def write_geotiff_resident(outfilepath, window_bound, array, dtype=None, nodataval=-2000, tiled=True, compression="lzw", predictor=1,
-                           bigtiff=True, crs=EPSG_ANTARCTIC_POLAR_STEREOGRAPHIC, workspace_limit=None):
+                           bigtiff=True, crs=EPSG_ANTARCTIC_POLAR_STEREOGRAPHIC, workspace_limit=None, overviews=0):
     """The mirror of `read_geotiff_resident`: writes `{outfilepath}.tif` from a plane that lives in HBM and returns its path.  The cast
     to int16 (NumPy's `astype`), the cutting of tiles or strips, predictor 2 and TIFF 6.0 LZW (one wavefront per block) run on the GPU
     (dbm_tiff_encode); only the encoded streams cross PCIe.  The file is byte for byte the one `save_array_to_grid` writes from the
@@ -271,8 +427,12 @@ def write_geotiff_resident(outfilepath, window_bound, array, dtype=None, nodatav
 
     array: a float32 DeviceArray of shape (1, H, W) or (H, W), or a resident Raster; dtype int16 or float32 (the default);
     compression "lzw" or "none" (the samples as they are: as in save_array_to_grid the predictor then has no effect); predictor 1 or
-    2.  workspace_limit: bytes of raw blocks plus stream slots per batch (default 1 GiB; one block always goes through).  Anything
-    else raises a ValueError that names the argument, before any device work."""
+    2.  workspace_limit: bytes of raw blocks plus stream slots per batch (default 1 GiB; one block always goes through).
+    overviews: the number of reduced-resolution images behind the first one, or "auto" (`overview_shapes`), as in save_array_to_grid:
+    one dbm_grid_overviews call builds them all next to the plane -- float32 planes one behind the other in one allocation of at most
+    a third of the plane's size (1/4 + 1/16 + ..., a little more at odd sizes); for int16 the canvas is cast while it is read, never
+    copied -- and every level then goes through the same batches as the first image.  Anything else raises a ValueError that names
+    the argument, before any device work."""
     who = "write_geotiff_resident"
     from .tiling import Raster
 
@@ -305,24 +465,30 @@ def write_geotiff_resident(outfilepath, window_bound, array, dtype=None, nodatav
     workspace_limit = int(workspace_limit)
     if workspace_limit < 1:
         raise ValueError(f"{who}: workspace_limit must be positive")
-    th, tw = (TILE, TILE) if tiled else (min(TILE, H), W)
-    block_bytes = th * tw * dt.itemsize
-    if block_bytes >= 1 << 31:
-        raise ValueError(f"{who}: array: blocks of {th} x {tw} samples hold 2^31 bytes or more")
-    ny, nx = -(-H // th), -(-W // tw)
-    nblocks = ny * nx
-    worst = block_bytes * 3 // 2 + 64 if comp == 5 else block_bytes   # a block's bytes in the download, before rounding up to even
-    per_batch = max(1, min(workspace_limit // (block_bytes + (worst if comp == 5 else 0)), ((1 << 31) - 1) // th, nblocks))
+    shapes = overview_shapes(H, W, overviews, who, "overviews")
+    if shapes and dt == np.int16:
+        _finite_nodata(nodataval, who)
     sample_type = 1 if dt == np.int16 else 4
     ctx = array.ctx
 
-    def streams():
+    def plan(h, w):
+        """Block shape, number of blocks, a block's worst case in the download, blocks per dbm_tiff_encode call of an (h, w) image."""
+        th, tw = (TILE, TILE) if tiled else (min(TILE, h), w)
+        block_bytes = th * tw * dt.itemsize
+        if block_bytes >= 1 << 31:
+            raise ValueError(f"{who}: array: blocks of {th} x {tw} samples hold 2^31 bytes or more")
+        nblocks = -(-h // th) * -(-w // tw)
+        worst = block_bytes * 3 // 2 + 64 if comp == 5 else block_bytes   # a block's bytes in the download, before rounding up to even
+        per_batch = max(1, min(workspace_limit // (block_bytes + (worst if comp == 5 else 0)), ((1 << 31) - 1) // th, nblocks))
+        return th, tw, nblocks, worst, per_batch
+
+    def streams(plane, h, w, th, tw, nblocks, worst, per_batch):
         out = np.empty(per_batch * ((worst + 1) & ~1), dtype=np.uint8)
         sizes = np.zeros(per_batch, dtype=np.uintp)
         view = memoryview(out)
         for first in range(0, nblocks, per_batch):
             n = min(per_batch, nblocks - first)
-            ctx.call("dbm_tiff_encode", devptr(array), H, W, sample_type, th, tw, 1 if tiled else 0, predictor, comp, first, n, devptr(out),
+            ctx.call("dbm_tiff_encode", devptr(plane), h, w, sample_type, th, tw, 1 if tiled else 0, predictor, comp, first, n, devptr(out),
                      out.size, devptr(sizes))
             pos = 0
             for k in range(n):
@@ -330,31 +496,53 @@ def write_geotiff_resident(outfilepath, window_bound, array, dtype=None, nodatav
                 yield view[pos:pos + size]
                 pos += (size + 1) & ~1
 
-    tags = _image_tags(H, W, dt, comp, predictor, bool(tiled), th, tw, window_bound, nodataval, epsg, bigtiff)
-    return _write_container(f"{outfilepath}.tif", bool(bigtiff), tags, streams())
+    plans = [plan(h, w) for h, w in [(H, W)] + shapes]   # (every refusal before any device work)
+    levels = _device_pyramid(array, H, W, sample_type, nodataval, shapes)
+    tags = _image_tags(H, W, dt, comp, predictor, bool(tiled), plans[0][0], plans[0][1], window_bound, nodataval, epsg, bigtiff)
+    images = [(_image_tags(h, w, dt, comp, predictor, bool(tiled), p[0], p[1], None, nodataval, None, bigtiff, overview=True),
+               streams(level, h, w, *p)) for (h, w), p, level in zip(shapes, plans[1:], levels)]
+    return _write_container(f"{outfilepath}.tif", bool(bigtiff), tags, streams(array, H, W, *plans[0]), images)
 
 
-def read_geotiff(path):
+def read_geotiff(path, overview=0):
     """Decodes a file written by save_array_to_grid or write_geotiff_resident.  Returns (array (1, H, W), info dict with the GeoTIFF
     tags).  Predictor 2 is undone in the package's own files, recognised by the directory its writers always write (ModelPixelScale,
     ModelTiepoint, GeoKeyDirectory and GDAL_NODATA all present).  In any other file the Predictor tag is ignored, as it always was
-    (tests/test_geotiff_open_host.py pins that): files of other writers are read by open_geotiff / read_geotiff_resident."""
+    (tests/test_geotiff_open_host.py pins that): files of other writers are read by open_geotiff / read_geotiff_resident.
+    overview = k > 0: the k-th reduced-resolution image behind the first one (a directory whose NewSubfileType (254) has bit 0 set and
+    bit 2, mask, clear) instead; its info holds its own tags, and the first directory's GDAL_NODATA where it has none."""
     with open(path, "rb") as f:
         buf = f.read()
     big = struct.unpack_from("<H", buf, 2)[0] == 43
     assert buf[:2] == b"II" and struct.unpack_from("<H", buf, 2)[0] in (42, 43)
-    ifd = struct.unpack_from("<Q", buf, 8)[0] if big else struct.unpack_from("<I", buf, 4)[0]
-    n = struct.unpack_from("<Q" if big else "<H", buf, ifd)[0]
-    pos = ifd + (8 if big else 2)
-    tags = {}
-    for _ in range(n):
-        tag, typ, count = struct.unpack_from("<HHQ" if big else "<HHI", buf, pos)
-        fmt, size = _TYPES[typ]
-        fpos = pos + (12 if big else 8)
-        if count * size > (8 if big else 4):
-            fpos = struct.unpack_from("<Q" if big else "<I", buf, fpos)[0]
-        tags[tag] = buf[fpos:fpos + count] if typ == 2 else list(struct.unpack_from("<%d%s" % (count, fmt), buf, fpos))
-        pos += 20 if big else 12
+
+    def directory(ifd):
+        n = struct.unpack_from("<Q" if big else "<H", buf, ifd)[0]
+        pos = ifd + (8 if big else 2)
+        tags = {}
+        for _ in range(n):
+            tag, typ, count = struct.unpack_from("<HHQ" if big else "<HHI", buf, pos)
+            fmt, size = _TYPES[typ]
+            fpos = pos + (12 if big else 8)
+            if count * size > (8 if big else 4):
+                fpos = struct.unpack_from("<Q" if big else "<I", buf, fpos)[0]
+            tags[tag] = buf[fpos:fpos + count] if typ == 2 else list(struct.unpack_from("<%d%s" % (count, fmt), buf, fpos))
+            pos += 20 if big else 12
+        return tags, struct.unpack_from("<Q" if big else "<I", buf, pos)[0]
+
+    tags, nxt = directory(struct.unpack_from("<Q", buf, 8)[0] if big else struct.unpack_from("<I", buf, 4)[0])
+    own = all(t in tags for t in (33550, 33922, 34735, 42113))   # the directory of _image_tags
+    if _overview_of(overview, "read_geotiff"):
+        base, found, seen = tags, 0, set()
+        while found < overview:
+            if nxt == 0:
+                raise ValueError(f"{path}: overview {overview} asked for, the file holds {found}")
+            if nxt in seen or nxt + (8 if big else 2) > len(buf):
+                raise ValueError(f"{path}: the image directory at offset {nxt} repeats or lies outside the file")
+            seen.add(nxt)
+            tags, nxt = directory(nxt)
+            found += tags.get(254, [0])[0] & 5 == 1
+        tags.setdefault(42113, base.get(42113, b""))
     W, H, bits, comp, fmtc = tags[256][0], tags[257][0], tags[258][0], tags[259][0], tags.get(339, [1])[0]
     dt = np.dtype({(16, 2): "<i2", (16, 1): "<u2", (32, 3): "<f4", (32, 2): "<i4", (8, 1): "u1", (64, 3): "<f8"}[(bits, fmtc)])
     if 322 in tags:
@@ -363,7 +551,6 @@ def read_geotiff(path):
         tw, th, offs, cnts = W, tags[278][0], tags[273], tags[279]
     ny, nx = (H + th - 1) // th, (W + tw - 1) // tw
     out = np.zeros((ny * th, nx * tw), dtype=dt)
-    own = all(t in tags for t in (33550, 33922, 34735, 42113))   # the directory of _image_tags
     predictor = tags.get(317, [1])[0] if own and comp == 5 else 1   # (without effect on uncompressed data)
     assert predictor in (1, 2), predictor
     for i, (o, c) in enumerate(zip(offs, cnts)):
@@ -405,10 +592,14 @@ class BlockPlan:
 
 
 class GeoTiffFile:
-    """The first image of a TIFF / BigTIFF file as `open_geotiff` accepts it (one sample per pixel, little endian)."""
+    """One image of a TIFF / BigTIFF file as `open_geotiff` accepts it (one sample per pixel, little endian): the first one, or with
+    `base` (the GeoTiffFile of the first one) its overview number `overview` >= 1 -- the same checks, and from the base what the
+    directory lacks: GDAL_NODATA, the geokeys and the geometry (the base's outer pixel-edge box divided into this image's pixels).
+    overview_count: the overviews behind the first image."""
 
-    def __init__(self, path, bigtiff, tags):
+    def __init__(self, path, bigtiff, tags, base=None, overview=0, overview_count=0):
         self.path, self.bigtiff, self.tags = path, bigtiff, tags
+        self.overview, self.overview_count = overview, overview_count
 
         def one(tag, default=None):
             v = tags.get(tag)
@@ -457,6 +648,23 @@ class GeoTiffFile:
         self.nodata = tags.get(42113, b"").split(b"\0")[0].decode("ascii", "replace").strip()
         self.pixel_scale, self.tiepoint, self.geokeys = tags.get(33550), tags.get(33922), tags.get(34735)
         self._geometry = self._parse_geometry()
+        if base is not None:
+            if 42113 not in tags:
+                self.nodata = base.nodata
+            if self.geokeys is None:
+                self.geokeys = base.geokeys
+            if isinstance(self._geometry, Exception):
+                self._geometry = self._overview_geometry(base)
+
+    def _overview_geometry(self, base):
+        """Pixel registration, x0 and y0 centres: the base's outer pixel-edge box is kept and divided into this image's W_k x H_k pixels --
+        dx_k = dx W / W_k, x0_k = (x0 - dx / 2) + dx_k / 2, likewise in y, in float64 and in this order.  (The base's error where it
+        has no georeference.)"""
+        g = base._geometry
+        if isinstance(g, Exception):
+            return g
+        dx, dy = g.dx * base.width / self.width, g.dy * base.height / self.height
+        return GridGeometry(x0=(g.x0 - g.dx / 2) + dx / 2, y0=(g.y0 - g.dy / 2) + dy / 2, dx=dx, dy=dy, registration="pixel")
 
     def _raster_type(self):
         """GTRasterTypeGeoKey (1025): 1 PixelIsArea (the default), 2 PixelIsPoint."""
@@ -561,8 +769,21 @@ def _read_tags(f, path):
         return f.read(n)
 
     cnt_fmt, cnt_size, entry_size, inline = ("<Q", 8, 20, 8) if big else ("<H", 2, 12, 4)
-    n = struct.unpack(cnt_fmt, at(ifd, cnt_size, "the first IFD"))[0]
-    table = at(ifd + cnt_size, n * entry_size, "the first IFD's entries")
+    directories, seen = [], set()
+    while ifd != 0 or not directories:
+        name = "the first IFD" if not directories else f"IFD {len(directories)}"
+        if ifd in seen:
+            raise ValueError(f"{path}: {name} at offset {ifd}: the chain of image directories comes back to this offset")
+        seen.add(ifd)
+        tags, ifd = _read_directory(at, ifd, name, big, cnt_fmt, cnt_size, entry_size, inline)
+        directories.append(tags)
+    return big, directories
+
+
+def _read_directory(at, ifd, name, big, cnt_fmt, cnt_size, entry_size, inline):
+    """The tags of the image directory at offset `ifd`, and the offset of the next one (0: none)."""
+    n = struct.unpack(cnt_fmt, at(ifd, cnt_size, name))[0]
+    table = at(ifd + cnt_size, n * entry_size + inline, f"{name}'s entries")
     tags = {}
     for k in range(n):
         tag, typ, count = struct.unpack_from("<HHQ" if big else "<HHI", table, k * entry_size)
@@ -581,18 +802,34 @@ def _read_tags(f, path):
                                                                    "q": "i8", "f": "f4", "d": "f8"}[fmt]))
         else:
             tags[tag] = list(struct.unpack("<" + fmt * count, data))
-    return big, tags
+    return tags, struct.unpack_from("<Q" if big else "<I", table, n * entry_size)[0]
 
 
-def open_geotiff(path):
-    """Parses the header and the first image directory of a TIFF / BigTIFF file as GDAL and libtiff write them: little endian,
+def _overview_of(overview, who):
+    if isinstance(overview, (bool, np.bool_)) or not isinstance(overview, (int, np.integer)) or overview < 0:
+        raise ValueError(f"{who}: overview {overview!r}: an int >= 0 (0: the first image)")
+    return int(overview)
+
+
+def open_geotiff(path, overview=0):
+    """Parses the header and the image directories of a TIFF / BigTIFF file as GDAL and libtiff write them: little endian,
     strips or tiles, one sample per pixel of uint8 / int16 / uint16 / int32 / float32 / float64, Compression 1 / 5 (LZW) / 8 or
     32946 (deflate), Predictor 1 / 2 / 3.  Everything else raises ValueError naming the tag and its value -- here, before any
-    device work.  Returns a GeoTiffFile."""
+    device work.  Returns the GeoTiffFile of the first image, or of its overview number `overview`: the later directories whose
+    NewSubfileType (254) has bit 0 (reduced resolution) set and bit 2 (mask) clear are the overviews 1, 2, ... in file order; masks
+    and anything else are skipped.  An overview passes the same checks, may be compressed and cut differently from the first
+    image, and takes GDAL_NODATA and the georeference from it where it has none.  More than the file holds: a ValueError that says
+    how many it has."""
     path = os.fspath(path)
+    overview = _overview_of(overview, "open_geotiff")
     with open(path, "rb") as f:
-        big, tags = _read_tags(f, path)
-        gf = GeoTiffFile(path, big, tags)
+        big, directories = _read_tags(f, path)
+        overviews = [t for t in directories[1:] if (t[254][0] if len(t.get(254, ())) else 0) & 5 == 1]
+        if overview > len(overviews):
+            raise ValueError(f"{path}: overview {overview} asked for, the file holds {len(overviews)}")
+        gf = GeoTiffFile(path, big, directories[0], overview_count=len(overviews))
+        if overview:
+            gf = GeoTiffFile(path, big, overviews[overview - 1], base=gf, overview=overview, overview_count=len(overviews))
         if gf.compression == 5:
             # old-style LZW (TIFF 5.0 writers: least significant bit first) starts with the bytes 00 01; TIFF 6.0 streams with ClearCode
             for o, c in zip(gf.offsets, gf.counts):
@@ -623,13 +860,15 @@ def _batches(gf, plan, limit, streams=None):
     return runs
 
 
-def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=None, inflate=INFLATE_DEFAULT):
+def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=None, inflate=INFLATE_DEFAULT, overview=0):
     """Decodes a GeoTIFF (`open_geotiff`'s dialect) into HBM: LZW, deflate, the predictors, the conversion to float32 (NumPy's `astype`)
     and the placement run on the GPU (dbm_tiff_decode), so only the compressed bytes cross PCIe.  inflate="host" inflates deflate
     streams with zlib on host threads and uploads the decoded blocks instead (DESIGN.md 6i has the measurements behind the default);
     files that are not deflate read the same either way.  window_bound = (minx, miny,
     maxx, maxy) reads the pixels whose centres lie in [minx, maxx) x (miny, maxy] and only the blocks that hold them.
     workspace_limit: bytes of block staging per batch (default 1 GiB; at least one block goes through at a time).
+    overview = k > 0 reads the file's k-th overview instead of its first image (`open_geotiff`): everything above, window_bound included,
+    then applies to that image, whose geometry is the first image's pixel-edge box divided into its own pixels.
     Returns (DeviceArray (H, W), info): read_geotiff's keys plus predictor, dtype, window (row0, col0, H, W) and geometry (the
     window's GridGeometry, None for a file without georeference)."""
     import dataclasses
@@ -643,7 +882,7 @@ def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=Non
         raise ValueError("workspace_limit must be positive")
     if inflate not in ("device", "host"):
         raise ValueError(f"read_geotiff_resident: inflate {inflate!r}: 'device' or 'host'")
-    gf = open_geotiff(path)
+    gf = open_geotiff(path, _overview_of(overview, "read_geotiff_resident"))
     on_device = gf.compression == 5 or (gf.compression != 1 and inflate == "device")   # the streams themselves are uploaded
     if window_bound is None:
         geometry = None if isinstance(gf._geometry, Exception) else gf._geometry

@@ -50,14 +50,15 @@ class Raster:
         return cls(array[0].astype(np.float32), geometry, nodata=nodata, ctx=ctx)
 
     @classmethod
-    def open(cls, path, window_bound=None, ctx=None):
+    def open(cls, path, window_bound=None, ctx=None, overview=0):
         """A GeoTIFF as GDAL and libtiff write them (`geotiff.open_geotiff`'s dialect), decoded on the GPU and resident from the
         start: the file's geometry (GTRasterTypeGeoKey honoured), shifted to the window (minx, miny, maxx, maxy) if one is given
-        -- only its blocks are read --, and its GDAL_NODATA.  A file without georeference raises ValueError."""
+        -- only its blocks are read --, and its GDAL_NODATA.  A file without georeference raises ValueError.  overview = k > 0: the
+        file's k-th reduced-resolution image instead of the first one, on the same extent."""
         from .geotiff import open_geotiff
 
-        open_geotiff(path).geometry   # (raises before any device work)
-        array, info = read_geotiff_resident(path, window_bound=window_bound, ctx=ctx)
+        open_geotiff(path, overview).geometry   # (raises before any device work)
+        array, info = read_geotiff_resident(path, window_bound=window_bound, ctx=ctx, overview=overview)
         try:
             nodata = float(info["nodata"]) if info["nodata"] else None
         except ValueError:

@@ -645,6 +645,22 @@ int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes
 int dbm_tiff_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sample_type, int block_h, int block_w, int tiled, int predictor,
                     int compression, long first, int n_blocks, void* out_host, size_t out_capacity, size_t* sizes_host);
 
+/* ---- the overviews of that file, built next to the canvas (deepbedmap.py:749-756 -> data_prep.py:779-834 write one full-resolution
+ * image; its readers then run `gdaladdo -r average`.  The directories and the container stay with deepbedmap_amd/geotiff.py) ----
+ * dbm_grid_overviews halves the float32 plane plane_dev (H, W) `levels` times and writes the levels back to back to out_dev as float32
+ * planes of ceil(H / 2) x ceil(W / 2), ceil(H / 4) x ceil(W / 4), ...; both are DEVICE pointers and the call only enqueues.
+ * sample_type (dbm_tiff_encode's) 1: level 0 is the int16 cast of the plane (the canvas itself is not touched), every result is rounded
+ * to even and stored as an exactly representable float, so that dbm_tiff_encode encodes a level unchanged; 4: float32.
+ * Level k + 1 is made from level k alone: pixel (r, c) is the mean of the samples of rows 2r, 2r + 1 and columns 2c, 2c + 1 that exist
+ * and are valid (float32: neither NaN nor float32(*nodata); int16: not int(*nodata)): s = (a00 + a01) + (a10 + a11) in float32 with
+ * +0.0f for the others, divided by their number n in one IEEE division; n == 0 gives float32(*nodata) / int(*nodata).  nodata is a HOST
+ * pointer to one value.  Three levels come out of one pass over memory; the results are those of one halving at a time, bit for bit.
+ * Refused (status 1, nothing launched): NULL pointers, an empty plane or H * W >= 2^31, sample_type not 1 or 4, a nodata value that is
+ * not finite with sample_type 1, levels < 0 or beyond the first 1 x 1 level (the message says how many the plane admits), out_dev ==
+ * plane_dev.  levels = 0 succeeds. */
+int dbm_grid_overviews(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sample_type, const double* nodata, int levels,
+                       float* out_dev);
+
 /* One minibatch of `trainer` (srgan_train.py:1286-1309) as ONE call: train_eval_discriminator (:1084-1166) with its
  * optimizer update, then train_eval_generator (:1170-1263) with its update; both optimizers must have been set up
  * (dbm_adam_setup).  Numerically the two step calls + two dbm_adam_update calls, bit for bit; scheduled as a whole: the
