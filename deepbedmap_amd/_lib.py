@@ -154,6 +154,8 @@ SIGNATURES = {
                            C.c_long, C.c_long, C.POINTER(C.c_double), C.c_void_p],
     "dbm_tiff_decode": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                         C.c_long, C.c_long],
+    "dbm_chunk_decode": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                         C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_long, C.c_long],
     "dbm_tiff_encode": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int,
                         C.c_void_p, C.c_size_t, C.c_void_p],
     "dbm_grid_overviews": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p],
@@ -208,7 +210,7 @@ class DbmError(RuntimeError):
     # optimizer updates queued since the event were skipped (`Context.timeout_info()`).  8: the same in a data-parallel
     # run -- fatal, the replicas have diverged.  9 (dbm_adam_update only): the gradients about to be applied come from a
     # void pass; nothing was applied -- repeat forward + backward, then update.  10 (dbm_grid_tension_surface only): the solve did not
-    # converge within max_iter; the output holds the last iterate.  11 (dbm_tiff_decode only): a block's LZW or deflate stream is malformed.
+    # converge within max_iter; the output holds the last iterate.  11 (dbm_tiff_decode, dbm_chunk_decode): a block's LZW or deflate stream is malformed.
     # 12 (dbm_tiff_encode only): a block's LZW stream did not fit its slot (the device encoder's guard; the message names the block).
     code = None
 

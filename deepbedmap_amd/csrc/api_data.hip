@@ -263,6 +263,90 @@ int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes
   DBM_API_END
 }
 
+// ---- netCDF chunks / row bands -> a float32 plane (nc_chunks.hip; deflate through tiff_inflate.hip) ----
+int dbm_chunk_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host, int n_blocks, int compression,
+                     int shuffle, int sample_type, int big_endian, int block_w, int block_h, int has_fill, uint64_t fill_bits, int has_scale,
+                     double scale, double offset, float* out_dev, long out_h, long out_w) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_chunk_decode: NULL context");
+  note_device_write(ctx);
+  DBM_CHECK(n_blocks >= 0, "dbm_chunk_decode: negative number of blocks");
+  DBM_CHECK(compression == 1 || compression == 8, "dbm_chunk_decode: compression must be 1 (decoded bytes) or 8 (zlib streams)");
+  DBM_CHECK(shuffle == 0 || shuffle == 1, "dbm_chunk_decode: shuffle must be 0 or 1");
+  DBM_CHECK(big_endian == 0 || big_endian == 1, "dbm_chunk_decode: big_endian must be 0 or 1");
+  DBM_CHECK(has_fill == 0 || has_fill == 1, "dbm_chunk_decode: has_fill must be 0 or 1");
+  DBM_CHECK(has_scale == 0 || has_scale == 1, "dbm_chunk_decode: has_scale must be 0 or 1");
+  DBM_CHECK(sample_type >= 0 && sample_type <= 6, "dbm_chunk_decode: sample_type must lie in 0..6");
+  static const int kBytes[7] = {1, 2, 2, 4, 4, 8, 1};
+  const int bytes = kBytes[sample_type];
+  DBM_CHECK(!has_fill || bytes == 8 || (fill_bits >> (8 * bytes)) == 0, "dbm_chunk_decode: fill_bits has bits beyond the sample's width");
+  DBM_CHECK(block_w >= 1 && block_h >= 1 && (long)block_w * block_h * bytes < (1L << 31), "dbm_chunk_decode: a block must hold 1..2^31 - 1 bytes");
+  DBM_CHECK(out_h >= 1 && out_w >= 1, "dbm_chunk_decode: empty output plane");
+  DBM_CHECK(n_blocks == 0 || (streams_host != nullptr && blocks_host != nullptr && out_dev != nullptr), "dbm_chunk_decode: NULL streams, blocks or output");
+  const unsigned groups = nc_chunks_groups_per_block(block_w, block_h);
+  DBM_CHECK((long)n_blocks * groups < (1L << 31), "dbm_chunk_decode: more than 2^31 workgroups in one call");
+  if (n_blocks == 0) return 0;
+  const bool staged = compression == 8;
+  const int64_t whole = (int64_t)block_w * block_h * bytes;
+  for (int b = 0; b < n_blocks; ++b) {
+    const int64_t* e = blocks_host + 8 * (size_t)b;
+    const std::string name = "dbm_chunk_decode: block " + std::to_string(e[5]);
+    DBM_CHECK(e[0] >= 0 && e[1] >= 0 && (uint64_t)e[0] + (uint64_t)e[1] <= (uint64_t)streams_bytes, name + ": its bytes lie outside the streams");
+    DBM_CHECK(e[2] >= 1 && e[2] <= block_h, name + ": its rows must lie in 1..block_h");
+    DBM_CHECK(e[6] == 1 || e[6] == -1, name + ": its row step must be +1 or -1");
+    // decoded bytes: a shuffled block is always whole (the byte planes are block_h * block_w apart); otherwise the rows held will do
+    DBM_CHECK(staged || (e[0] % 8 == 0 && e[1] >= (shuffle ? whole : e[2] * (int64_t)block_w * bytes)),
+              name + ": decoded bytes must be 8-byte aligned and complete");
+    DBM_CHECK(e[3] > -(1L << 40) && e[3] < (1L << 40) && e[4] > -(1L << 40) && e[4] < (1L << 40), name + ": placement out of range");
+  }
+  ChunkDecodeLaunch a;
+  a.n_blocks = n_blocks; a.staged = staged ? 1 : 0;
+  a.block_w = block_w; a.block_h = block_h; a.bytes = bytes; a.sample_type = sample_type;
+  a.shuffle = shuffle; a.big_endian = big_endian;
+  a.has_fill = has_fill; a.has_scale = has_scale; a.fill_bits = fill_bits; a.scale = scale; a.offset = offset;
+  a.groups_per_block = groups;
+  a.block_stride = (whole + 15) / 16 * 16;
+  a.out = out_dev; a.out_h = out_h; a.out_w = out_w;
+  ScopedBuf up, table, stage;   // this call's own, released on every path
+  const size_t table_bytes = (size_t)n_blocks * sizeof(int64_t[8]);
+  // the block table; for streams a second one behind it in which every block holds block_h rows (an HDF5 chunk is always stored
+  // whole: that is the size the inflater checks), then one status word per block
+  const size_t tables = staged ? 2 : 1;
+  uint8_t* up_p = up.as<uint8_t>(streams_bytes + 16);                  // (16 bytes of slack: the decoders load whole words)
+  uint8_t* table_p = table.as<uint8_t>(tables * table_bytes + (size_t)n_blocks * sizeof(int));
+  a.stage = up_p;
+  a.blocks = (const long*)table_p;
+  DBM_HIP(hipMemcpyAsync(up_p, streams_host, streams_bytes, hipMemcpyHostToDevice, ctx->stream));
+  DBM_HIP(hipMemcpyAsync(table_p, blocks_host, table_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (staged) {
+    std::vector<int64_t> whole_blocks(blocks_host, blocks_host + 8 * (size_t)n_blocks);
+    for (int b = 0; b < n_blocks; ++b) whole_blocks[8 * (size_t)b + 2] = block_h;
+    DBM_HIP(hipMemcpyAsync(table_p + table_bytes, whole_blocks.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
+    TiffDecodeLaunch t;
+    t.streams = up_p;
+    t.stage = stage.as<uint8_t>((size_t)n_blocks * (size_t)a.block_stride);
+    t.blocks = (const long*)(table_p + table_bytes);
+    t.status = (int*)(table_p + 2 * table_bytes);
+    t.n_blocks = n_blocks; t.lzw = 1;
+    t.block_stride = a.block_stride;
+    t.block_w = block_w; t.block_h = block_h; t.bytes = bytes; t.sample_type = 0; t.predictor = 1;
+    t.out = nullptr; t.out_h = 0; t.out_w = 0;
+    launch_tiff_inflate(t, ctx->stream);
+    std::vector<int> status((size_t)n_blocks);
+    DBM_HIP(hipMemcpyAsync(status.data(), t.status, sizeof(int) * (size_t)n_blocks, hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));   // (also: whole_blocks has been read)
+    for (int b = 0; b < n_blocks; ++b)
+      if (status[b] != 0)
+        throw DbmError(11, "dbm_chunk_decode: block " + std::to_string(blocks_host[8 * (size_t)b + 5]) +
+                               (status[b] == 1 ? ": malformed deflate stream" : ": the deflate stream does not decode to the block's size") +
+                               "; nothing of this call was written");
+    a.stage = t.stage;
+  }
+  launch_nc_chunks(a, ctx->stream);
+  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
+  DBM_API_END
+}
+
 // ---- a float32 plane -> GeoTIFF blocks (tiff_encode.hip) ----
 int dbm_tiff_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sample_type, int block_h, int block_w, int tiled, int predictor,
                     int compression, long first, int n_blocks, void* out_host, size_t out_capacity, size_t* sizes_host) {

@@ -362,6 +362,28 @@ size_t tiff_lzw_decode_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t c
 // inflate_lanes with one lane on the host: the decoded size or (size_t)-1 (dbm_inflate; tools/inflate_twin_check.cpp compares it with zlib)
 size_t tiff_inflate_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
 
+// Chunks of a netCDF variable -> a float32 plane (nc_chunks.hip; dbm_chunk_decode).  blocks: n_blocks x 8 int64 on the device = {offset
+// of the block's bytes in the upload, their count, rows held, output row of row 0, output column of column 0, id, row step (+1 / -1), 0}.
+// staged: the blocks were inflated (launch_tiff_inflate, through a TiffDecodeLaunch over the same upload) to stage + b * block_stride;
+// else the block's bytes lie at stage + offset (8-byte aligned).  Row r of a block lands on output row e[3] + e[6] * r.
+struct ChunkDecodeLaunch {
+  const uint8_t* stage;
+  const long* blocks;
+  int n_blocks, staged;
+  long block_stride;           // bytes between staged blocks, a multiple of 16, >= block_h * block_w * bytes
+  unsigned groups_per_block;   // nc_chunks_groups_per_block(block_w, block_h)
+  int block_w, block_h, bytes; // samples per block row, rows of a whole block, bytes per sample
+  int sample_type;             // TiffDecodeLaunch's 0..5, 6 int8
+  int shuffle, big_endian;     // HDF5 shuffle over the whole block; the samples' byte order
+  int has_fill, has_scale;
+  unsigned long long fill_bits;  // the fill in the sample's width
+  double scale, offset;
+  float* out;
+  long out_h, out_w;
+};
+unsigned nc_chunks_groups_per_block(int block_w, int block_h);
+void launch_nc_chunks(const ChunkDecodeLaunch& a, hipStream_t s);
+
 // numpy.ndarray.astype(int16) of a float32 on x86-64: truncation to int32 (cvttss2si: NaN and |x| >= 2^31 give INT32_MIN), then the low
 // 16 bits -- NaN (the canvas frame that no tile covers), +-inf and out-of-range values become 0.  The one cast of f32_to_i16_kernel
 // (tiff_lzw.hip) and tiff_blocks_kernel (tiff_encode.hip).

@@ -57,6 +57,13 @@ class Raster:
         file's k-th reduced-resolution image instead of the first one, on the same extent."""
         from .geotiff import open_geotiff
 
+        if isinstance(path, str) and path.startswith("netcdf:"):   # the reference's GDAL subdataset names (data_prep.py:889-900)
+            file, _, variable = path[len("netcdf:"):].rpartition(":")
+            if not file or not variable:
+                raise ValueError(f"{path}: a netCDF variable is named netcdf:FILE:VARIABLE")
+            if overview:
+                raise ValueError(f"{path}: overview {overview!r}: netCDF variables have no overviews")
+            return cls.open_netcdf(file, variable, window_bound=window_bound, ctx=ctx)
         open_geotiff(path, overview).geometry   # (raises before any device work)
         array, info = read_geotiff_resident(path, window_bound=window_bound, ctx=ctx, overview=overview)
         try:
@@ -66,6 +73,20 @@ class Raster:
         if nodata is not None and np.isinf(nodata):
             nodata = None   # (GDAL writes "inf" / "-inf" too; a Raster's nodata is finite or NaN)
         return cls(array, info["geometry"], nodata=nodata)
+
+    @classmethod
+    def open_netcdf(cls, path, variable=None, window_bound=None, ctx=None):
+        """A variable of a netCDF file (`netcdf.open_netcdf`'s dialect: netCDF-4 / HDF5 chunks with shuffle and deflate, classic
+        CDF-1 / CDF-2), its chunks placed on the GPU and resident from the start, north-up, masked and scaled by the module's value
+        rule; `variable` None: the file's only 2-D variable.  The geometry comes from the file's x / y coordinates (a file without
+        them raises ValueError), shifted to the window if one is given -- only its chunks are read.  nodata is NaN when the variable
+        has a fill (those samples ARE NaN), else None."""
+        from .netcdf import open_netcdf, read_netcdf_resident
+
+        if open_netcdf(path, variable).geometry is None:   # (raises before any device work)
+            raise ValueError(f"{path}: no georeference: the coordinate variables x and y are missing")
+        array, info = read_netcdf_resident(path, variable, window_bound=window_bound, ctx=ctx)
+        return cls(array, info["geometry"], nodata=None if info["fill"] is None else float("nan"))
 
     @property
     def shape(self):

@@ -558,7 +558,7 @@ int dbm_discriminator_step(dbm_model* g, dbm_model* d, int N, int H, int W, cons
  * (its bit 1); bit 2 (4) = consume the forward that step prefetched (its bit 2): the caller asserts that the five
  * arrays are the same, UNCHANGED, device arrays.  The library additionally checks pointers, shapes, the parameter
  * version and its own record of writes to device memory (dbm_memcpy_h2d, dbm_gather_rows, dbm_fill_f32,
- * dbm_memcpy2d_d2d, dbm_grid_tile, dbm_grid_filled_windows, dbm_grid_fill_gaps, dbm_tiff_decode, dbm_grid_rescale, dbm_grid_rolling_std, dbm_malloc, dbm_free); writes by anybody else (another library filling the same buffer in
+ * dbm_memcpy2d_d2d, dbm_grid_tile, dbm_grid_filled_windows, dbm_grid_fill_gaps, dbm_tiff_decode, dbm_chunk_decode, dbm_grid_rescale, dbm_grid_rolling_std, dbm_malloc, dbm_free); writes by anybody else (another library filling the same buffer in
  * place) are invisible to it, hence the explicit bit.  Without it the prefetched pass is discarded and the forward is
  * recomputed.  bit 4 (16) = see dbm_discriminator_step. */
 int dbm_generator_step(dbm_model* g, dbm_model* d, int N, int H, int W, const float* X, const float* W1,
@@ -617,6 +617,40 @@ int dbm_inflate(const void* src, size_t nbytes, void* dst, size_t cap, size_t* o
  * n_blocks > 0, bytes outside streams_host, rows outside 1..block_h, decoded bytes misaligned or short.  n_blocks = 0 succeeds. */
 int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host, int n_blocks, int compression,
                     int predictor, int sample_type, int block_w, int block_h, float* out_dev, long out_h, long out_w);
+
+/* ---- opening netCDF grids: chunks and row bands placed on the device (replaces the xarray / rasterio reads of netCDF files: the ice
+ * velocity `netcdf:misc/antarctic_ice_vel_phase_map_v01.nc:VX` / `:VY` of data_prep.py:889-900 and deepbedmap.py:176-191, the ground-truth
+ * grids of deepbedmap.py:74-78; the HDF5 / classic container, the chunk plan and file reads stay with the host shim
+ * deepbedmap_amd/netcdf.py) ----
+ * dbm_chunk_decode turns n_blocks blocks (HDF5 chunks, or row bands of contiguous / classic data: blocks with block_w == the variable's
+ * width) into their places of the float32 plane out_dev (out_h, out_w), ALWAYS a device pointer.  streams_host / streams_bytes /
+ * blocks_host as for dbm_tiff_decode, with a row step: 8 int64 per block, {offset of its bytes, their count, rows held (1..block_h),
+ * output row of the block's row 0, output column of its column 0, id (only named in error messages), row step (+1 or -1), 0}.  Row r
+ * of a block lands on output row e[3] + step * r (step -1: a file whose rows run south to north is returned north-up); samples outside
+ * [0, out_h) x [0, out_w) are dropped (the columns of edge chunks beyond the dataset, the part of a chunk outside a window); cells no
+ * block covers keep what they held.
+ * compression 8: the bytes are a zlib stream (dbm_tiff_decode's compression 8, the same decoder: one wavefront per block) that decodes
+ * to exactly block_h * block_w * bytes bytes -- an HDF5 chunk is always stored whole, whatever `rows held` says.  compression 1: the
+ * bytes ARE the block, offset a multiple of 8, count >= rows held * block_w * bytes (shuffle 1: >= block_h * block_w * bytes).
+ * shuffle 1: HDF5's shuffle filter over the WHOLE block of n = block_h * block_w elements is undone: byte k of element i lies at
+ * k * n + i.  big_endian 1: the samples are stored most significant byte first.
+ * sample_type: dbm_tiff_decode's 0 uint8, 1 int16, 2 uint16, 3 int32, 4 float32, 5 float64, and 6 int8.
+ * Values: has_fill 1: a sample that equals the fill (fill_bits: the fill's bits in the sample's width, native order, upper bits 0) BY
+ * VALUE in its stored type becomes NaN (floats: -0.0 equals 0.0, a NaN fill matches every NaN).  has_scale 1: every other sample
+ * becomes float32(float64(v) * scale + offset), two separately rounded float64 operations (never an FMA) and one rounding to float32;
+ * has_scale 0: numpy.astype(float32) (float32 samples keep their bits, NaN payloads included).
+ * The call allocates its workspace (streams_bytes + 68 per block; for compression 8 also 64 bytes and block_w * block_h * bytes,
+ * rounded up to 16, per block), frees it on every path and synchronises the context's stream; the caller bounds it by batching.
+ * Status 11: a zlib stream is malformed (dbm_tiff_decode's list) or does not decode to exactly block_h * block_w * bytes bytes; the
+ * message names the block's id and nothing of this call has been written.
+ * Refused (status 1, nothing launched): compression not 1 or 8, shuffle, big_endian, has_fill or has_scale not 0 or 1, sample_type
+ * outside 0..6, fill_bits wider than the sample, block_w or block_h < 1, a block of 2^31 bytes or more, 2^31 workgroups or more
+ * (n_blocks * ceil(block_h * block_w / 1024)), an empty plane, NULL pointers with n_blocks > 0, bytes outside streams_host, rows
+ * outside 1..block_h, a row step other than +1 / -1, decoded bytes misaligned or short, a placement beyond +-2^40.  n_blocks = 0
+ * succeeds. */
+int dbm_chunk_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host, int n_blocks, int compression,
+                     int shuffle, int sample_type, int big_endian, int block_w, int block_h, int has_fill, uint64_t fill_bits, int has_scale,
+                     double scale, double offset, float* out_dev, long out_h, long out_w);
 
 /* ---- writing the DEM from HBM: GeoTIFF blocks encoded on the device (deepbedmap.py:749-756: `save_array_to_grid(array=
  * Y_hat.astype(np.int16), dtype=np.int16, tiled=True, compression=lzw)` -> data_prep.py:779-834, a tiled LZW GeoTIFF written by rasterio
