@@ -204,6 +204,58 @@ int dbm_grid_fill_gaps(dbm_ctx* ctx, const float* fine_dev, long H, long W, cons
   DBM_API_END
 }
 
+// ---- block reads: the staging dbm_tiff_decode and dbm_chunk_decode share ----
+struct BlockStage {
+  ScopedBuf up, table, decoded;   // this call's own, released on every path
+  uint8_t* stage;                 // staged: block b at stage + b * block_stride; else its bytes at stage + offset
+  const long* blocks;
+  int staged;
+  long block_stride;
+};
+
+// Checks the table's common columns, uploads the streams and the table and, for compression 5 (LZW) or 8 (deflate), decodes the streams
+// into a staging area of their own; a block that does not decode throws status 11 before anything of the call is written.
+// whole_decoded: decoded bytes must be a whole block (shuffled chunks: the byte planes are block_h * block_w apart), else the rows held
+// will do.  whole_rows: StreamDecodeLaunch's.  The caller launches its row kernel on st and synchronises before st goes.
+static void stage_blocks(dbm_ctx* ctx, const std::string& who, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host,
+                         int n_blocks, int compression, int block_w, int block_h, int bytes, bool whole_decoded, int whole_rows, BlockStage& st) {
+  st.staged = compression != 1 ? 1 : 0;
+  const int64_t row_bytes = (int64_t)block_w * bytes;
+  for (int b = 0; b < n_blocks; ++b) {
+    const int64_t* e = blocks_host + 8 * (size_t)b;
+    const std::string name = who + ": block " + std::to_string(e[5]);
+    DBM_CHECK(e[0] >= 0 && e[1] >= 0 && (uint64_t)e[0] + (uint64_t)e[1] <= (uint64_t)streams_bytes, name + ": its bytes lie outside the streams");
+    DBM_CHECK(e[2] >= 1 && e[2] <= block_h, name + ": its rows must lie in 1..block_h");
+    DBM_CHECK(st.staged || (e[0] % 8 == 0 && e[1] >= (whole_decoded ? block_h : e[2]) * row_bytes),
+              name + ": decoded bytes must be 8-byte aligned and complete");
+    DBM_CHECK(e[3] > -(1L << 40) && e[3] < (1L << 40) && e[4] > -(1L << 40) && e[4] < (1L << 40), name + ": placement out of range");
+  }
+  st.block_stride = (block_h * row_bytes + 15) / 16 * 16;
+  const size_t table_bytes = (size_t)n_blocks * sizeof(int64_t[8]);   // the block table; one status word per block lies behind it
+  st.stage = st.up.as<uint8_t>(streams_bytes + 16);                   // (16 bytes of slack: the decoders load whole words)
+  st.blocks = (const long*)st.table.as<uint8_t>(table_bytes + (size_t)n_blocks * sizeof(int));
+  DBM_HIP(hipMemcpyAsync(st.up.p, streams_host, streams_bytes, hipMemcpyHostToDevice, ctx->stream));
+  DBM_HIP(hipMemcpyAsync(st.table.p, blocks_host, table_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (!st.staged) return;
+  StreamDecodeLaunch d;
+  d.streams = st.stage;
+  d.stage = st.stage = st.decoded.as<uint8_t>((size_t)n_blocks * (size_t)st.block_stride);
+  d.blocks = st.blocks;
+  d.status = (int*)((uint8_t*)st.table.p + table_bytes);
+  d.n_blocks = n_blocks; d.block_stride = st.block_stride; d.row_bytes = row_bytes; d.whole_rows = whole_rows;
+  const std::string codec = compression == 8 ? "deflate" : "LZW";
+  if (compression == 8) launch_block_inflate(d, ctx->stream);
+  else launch_block_lzw(d, ctx->stream);
+  std::vector<int> status((size_t)n_blocks);
+  DBM_HIP(hipMemcpyAsync(status.data(), d.status, sizeof(int) * (size_t)n_blocks, hipMemcpyDeviceToHost, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  for (int b = 0; b < n_blocks; ++b)
+    if (status[b] != 0)
+      throw DbmError(11, who + ": block " + std::to_string(blocks_host[8 * (size_t)b + 5]) +
+                             (status[b] == 1 ? ": malformed " + codec + " stream" : ": the " + codec + " stream does not decode to the block's size") +
+                             "; nothing of this call was written");
+}
+
 // ---- GeoTIFF blocks -> a float32 plane (tiff_decode.hip) ----
 int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes, const int64_t* blocks_host, int n_blocks, int compression,
                     int predictor, int sample_type, int block_w, int block_h, float* out_dev, long out_h, long out_w) {
@@ -213,51 +265,19 @@ int dbm_tiff_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_bytes
   DBM_CHECK(n_blocks >= 0, "dbm_tiff_decode: negative number of blocks");
   DBM_CHECK(compression == 1 || compression == 5 || compression == 8, "dbm_tiff_decode: compression must be 1 (decoded bytes), 5 (LZW) or 8 (deflate)");
   DBM_CHECK(sample_type >= 0 && sample_type <= 5, "dbm_tiff_decode: sample_type must lie in 0..5");
-  static const int kBytes[6] = {1, 2, 2, 4, 4, 8};
-  const int bytes = kBytes[sample_type];
+  const int bytes = block_sample_bytes(sample_type);
   DBM_CHECK(predictor == 1 || predictor == 2 || (predictor == 3 && sample_type >= 4), "dbm_tiff_decode: predictor must be 1, 2, or 3 with float samples");
   DBM_CHECK(block_w >= 1 && block_h >= 1 && (long)block_w * block_h * bytes < (1L << 31), "dbm_tiff_decode: a block must hold 1..2^31 - 1 bytes");
   DBM_CHECK(out_h >= 1 && out_w >= 1, "dbm_tiff_decode: empty output plane");
   DBM_CHECK(n_blocks == 0 || (streams_host != nullptr && blocks_host != nullptr && out_dev != nullptr), "dbm_tiff_decode: NULL streams, blocks or output");
   DBM_CHECK((long)n_blocks * block_h < (1L << 31), "dbm_tiff_decode: more than 2^31 block rows in one call");
   if (n_blocks == 0) return 0;
-  const bool lzw = compression != 1;   // the blocks are streams: decoded into a staging area of their own (LZW or deflate)
-  const char* codec = compression == 8 ? "deflate" : "LZW";
-  for (int b = 0; b < n_blocks; ++b) {
-    const int64_t* e = blocks_host + 8 * (size_t)b;
-    const std::string name = "dbm_tiff_decode: block " + std::to_string(e[5]);
-    DBM_CHECK(e[0] >= 0 && e[1] >= 0 && (uint64_t)e[0] + (uint64_t)e[1] <= (uint64_t)streams_bytes, name + ": its bytes lie outside the streams");
-    DBM_CHECK(e[2] >= 1 && e[2] <= block_h, name + ": its rows must lie in 1..block_h");
-    DBM_CHECK(lzw || (e[0] % 8 == 0 && e[1] >= e[2] * (int64_t)block_w * bytes), name + ": decoded bytes must be 8-byte aligned and complete");
-    DBM_CHECK(e[3] > -(1L << 40) && e[3] < (1L << 40) && e[4] > -(1L << 40) && e[4] < (1L << 40), name + ": placement out of range");
-  }
+  BlockStage st;
+  stage_blocks(ctx, "dbm_tiff_decode", streams_host, streams_bytes, blocks_host, n_blocks, compression, block_w, block_h, bytes, false, 0, st);
   TiffDecodeLaunch a;
-  a.n_blocks = n_blocks; a.lzw = lzw ? 1 : 0;
+  a.stage = st.stage; a.blocks = st.blocks; a.n_blocks = n_blocks; a.staged = st.staged; a.block_stride = st.block_stride;
   a.block_w = block_w; a.block_h = block_h; a.bytes = bytes; a.sample_type = sample_type; a.predictor = predictor;
-  a.block_stride = (((long)block_w * block_h * bytes) + 15) / 16 * 16;
   a.out = out_dev; a.out_h = out_h; a.out_w = out_w;
-  ScopedBuf up, table, stage;   // this call's own, released on every path
-  const size_t table_bytes = (size_t)n_blocks * sizeof(int64_t[8]);   // the block table; one status word per block lies behind it
-  a.stage = up.as<uint8_t>(streams_bytes + 16);                       // (16 bytes of slack: the decoders load whole words)
-  a.streams = a.stage;
-  a.blocks = (const long*)table.as<uint8_t>(table_bytes + (size_t)n_blocks * sizeof(int));
-  a.status = (int*)((uint8_t*)table.p + table_bytes);
-  DBM_HIP(hipMemcpyAsync(up.p, streams_host, streams_bytes, hipMemcpyHostToDevice, ctx->stream));
-  DBM_HIP(hipMemcpyAsync(table.p, blocks_host, table_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (lzw) {
-    a.stage = stage.as<uint8_t>((size_t)n_blocks * (size_t)a.block_stride);
-    if (compression == 8) launch_tiff_inflate(a, ctx->stream);
-    else launch_tiff_lzw(a, ctx->stream);
-    std::vector<int> status((size_t)n_blocks);
-    DBM_HIP(hipMemcpyAsync(status.data(), a.status, sizeof(int) * (size_t)n_blocks, hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < n_blocks; ++b)
-      if (status[b] != 0)
-        throw DbmError(11, "dbm_tiff_decode: block " + std::to_string(blocks_host[8 * (size_t)b + 5]) +
-                               (status[b] == 1 ? std::string(": malformed ") + codec + " stream"
-                                               : std::string(": the ") + codec + " stream does not decode to the block's size") +
-                               "; nothing of this call was written");
-  }
   launch_tiff_rows(a, ctx->stream);
   DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
   DBM_API_END
@@ -277,8 +297,7 @@ int dbm_chunk_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_byte
   DBM_CHECK(has_fill == 0 || has_fill == 1, "dbm_chunk_decode: has_fill must be 0 or 1");
   DBM_CHECK(has_scale == 0 || has_scale == 1, "dbm_chunk_decode: has_scale must be 0 or 1");
   DBM_CHECK(sample_type >= 0 && sample_type <= 6, "dbm_chunk_decode: sample_type must lie in 0..6");
-  static const int kBytes[7] = {1, 2, 2, 4, 4, 8, 1};
-  const int bytes = kBytes[sample_type];
+  const int bytes = block_sample_bytes(sample_type);
   DBM_CHECK(!has_fill || bytes == 8 || (fill_bits >> (8 * bytes)) == 0, "dbm_chunk_decode: fill_bits has bits beyond the sample's width");
   DBM_CHECK(block_w >= 1 && block_h >= 1 && (long)block_w * block_h * bytes < (1L << 31), "dbm_chunk_decode: a block must hold 1..2^31 - 1 bytes");
   DBM_CHECK(out_h >= 1 && out_w >= 1, "dbm_chunk_decode: empty output plane");
@@ -286,62 +305,20 @@ int dbm_chunk_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_byte
   const unsigned groups = nc_chunks_groups_per_block(block_w, block_h);
   DBM_CHECK((long)n_blocks * groups < (1L << 31), "dbm_chunk_decode: more than 2^31 workgroups in one call");
   if (n_blocks == 0) return 0;
-  const bool staged = compression == 8;
-  const int64_t whole = (int64_t)block_w * block_h * bytes;
   for (int b = 0; b < n_blocks; ++b) {
     const int64_t* e = blocks_host + 8 * (size_t)b;
-    const std::string name = "dbm_chunk_decode: block " + std::to_string(e[5]);
-    DBM_CHECK(e[0] >= 0 && e[1] >= 0 && (uint64_t)e[0] + (uint64_t)e[1] <= (uint64_t)streams_bytes, name + ": its bytes lie outside the streams");
-    DBM_CHECK(e[2] >= 1 && e[2] <= block_h, name + ": its rows must lie in 1..block_h");
-    DBM_CHECK(e[6] == 1 || e[6] == -1, name + ": its row step must be +1 or -1");
-    // decoded bytes: a shuffled block is always whole (the byte planes are block_h * block_w apart); otherwise the rows held will do
-    DBM_CHECK(staged || (e[0] % 8 == 0 && e[1] >= (shuffle ? whole : e[2] * (int64_t)block_w * bytes)),
-              name + ": decoded bytes must be 8-byte aligned and complete");
-    DBM_CHECK(e[3] > -(1L << 40) && e[3] < (1L << 40) && e[4] > -(1L << 40) && e[4] < (1L << 40), name + ": placement out of range");
+    DBM_CHECK(e[6] == 1 || e[6] == -1, "dbm_chunk_decode: block " + std::to_string(e[5]) + ": its row step must be +1 or -1");
   }
+  BlockStage st;   // (an HDF5 chunk is always stored whole: that is the size the inflater checks)
+  stage_blocks(ctx, "dbm_chunk_decode", streams_host, streams_bytes, blocks_host, n_blocks, compression, block_w, block_h, bytes, shuffle != 0,
+               block_h, st);
   ChunkDecodeLaunch a;
-  a.n_blocks = n_blocks; a.staged = staged ? 1 : 0;
+  a.stage = st.stage; a.blocks = st.blocks; a.n_blocks = n_blocks; a.staged = st.staged; a.block_stride = st.block_stride;
   a.block_w = block_w; a.block_h = block_h; a.bytes = bytes; a.sample_type = sample_type;
   a.shuffle = shuffle; a.big_endian = big_endian;
   a.has_fill = has_fill; a.has_scale = has_scale; a.fill_bits = fill_bits; a.scale = scale; a.offset = offset;
   a.groups_per_block = groups;
-  a.block_stride = (whole + 15) / 16 * 16;
   a.out = out_dev; a.out_h = out_h; a.out_w = out_w;
-  ScopedBuf up, table, stage;   // this call's own, released on every path
-  const size_t table_bytes = (size_t)n_blocks * sizeof(int64_t[8]);
-  // the block table; for streams a second one behind it in which every block holds block_h rows (an HDF5 chunk is always stored
-  // whole: that is the size the inflater checks), then one status word per block
-  const size_t tables = staged ? 2 : 1;
-  uint8_t* up_p = up.as<uint8_t>(streams_bytes + 16);                  // (16 bytes of slack: the decoders load whole words)
-  uint8_t* table_p = table.as<uint8_t>(tables * table_bytes + (size_t)n_blocks * sizeof(int));
-  a.stage = up_p;
-  a.blocks = (const long*)table_p;
-  DBM_HIP(hipMemcpyAsync(up_p, streams_host, streams_bytes, hipMemcpyHostToDevice, ctx->stream));
-  DBM_HIP(hipMemcpyAsync(table_p, blocks_host, table_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (staged) {
-    std::vector<int64_t> whole_blocks(blocks_host, blocks_host + 8 * (size_t)n_blocks);
-    for (int b = 0; b < n_blocks; ++b) whole_blocks[8 * (size_t)b + 2] = block_h;
-    DBM_HIP(hipMemcpyAsync(table_p + table_bytes, whole_blocks.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
-    TiffDecodeLaunch t;
-    t.streams = up_p;
-    t.stage = stage.as<uint8_t>((size_t)n_blocks * (size_t)a.block_stride);
-    t.blocks = (const long*)(table_p + table_bytes);
-    t.status = (int*)(table_p + 2 * table_bytes);
-    t.n_blocks = n_blocks; t.lzw = 1;
-    t.block_stride = a.block_stride;
-    t.block_w = block_w; t.block_h = block_h; t.bytes = bytes; t.sample_type = 0; t.predictor = 1;
-    t.out = nullptr; t.out_h = 0; t.out_w = 0;
-    launch_tiff_inflate(t, ctx->stream);
-    std::vector<int> status((size_t)n_blocks);
-    DBM_HIP(hipMemcpyAsync(status.data(), t.status, sizeof(int) * (size_t)n_blocks, hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipStreamSynchronize(ctx->stream));   // (also: whole_blocks has been read)
-    for (int b = 0; b < n_blocks; ++b)
-      if (status[b] != 0)
-        throw DbmError(11, "dbm_chunk_decode: block " + std::to_string(blocks_host[8 * (size_t)b + 5]) +
-                               (status[b] == 1 ? ": malformed deflate stream" : ": the deflate stream does not decode to the block's size") +
-                               "; nothing of this call was written");
-    a.stage = t.stage;
-  }
   launch_nc_chunks(a, ctx->stream);
   DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
   DBM_API_END

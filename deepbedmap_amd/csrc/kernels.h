@@ -335,37 +335,54 @@ void launch_grid_tile(const TileLaunch& a, hipStream_t s);
 void launch_grid_fill_gaps(const TileLaunch& a, const double window[4], const float* fine, int has_fine_nodata, float fine_nodata, float* out,
                            hipStream_t s);
 
-// GeoTIFF blocks -> a float32 plane (tiff_decode.hip; dbm_tiff_decode).  blocks: n_blocks x 8 int64 on the device = {offset of the
-// block's bytes in `streams`, their count, rows the block holds, output row of the block's row 0, output column of its column 0, id, 0, 0}.
-// lzw (set for both codecs: "the blocks are staged"): launch_tiff_lzw (TIFF 6.0 LZW) or launch_tiff_inflate (zlib streams,
-// tiff_inflate.hip) decodes streams + offset into stage + b * block_stride and writes status[b] (0 good, 1 malformed, 2 the decoded
-// size is not rows * block_w * bytes); launch_tiff_rows then reads from there.  Not lzw: stage == streams, the block's decoded bytes lie
-// at stage + offset (8-byte aligned).  launch_tiff_rows changes the decoded bytes in place (the predictor) and writes out (out_h, out_w).
-struct TiffDecodeLaunch {
+// Block reads (dbm_tiff_decode, dbm_chunk_decode).  blocks: n_blocks x 8 int64 on the device = {offset of the block's bytes in the
+// upload, their count, rows the block holds, output row of the block's row 0, output column of its column 0, id, row step (chunks:
+// +1 / -1; GeoTIFF: 0, not read), 0}.  sample_type: 0 uint8, 1 int16, 2 uint16, 3 int32, 4 float32, 5 float64, 6 int8 (chunks only).
+inline int block_sample_bytes(int sample_type) {
+  static const int kBytes[7] = {1, 2, 2, 4, 4, 8, 1};
+  return kBytes[sample_type];
+}
+
+// The stream decoders, one wavefront per block: launch_block_lzw (TIFF 6.0 LZW, tiff_decode.hip) or launch_block_inflate (zlib streams,
+// tiff_inflate.hip) decodes streams + offset into stage + b * block_stride and writes status[b]: 0 good, 1 malformed, 2 the decoded
+// size is not want = (whole_rows ? whole_rows : rows held) * row_bytes.  whole_rows: 0, or block_h where a block is always stored whole
+// (HDF5 chunks) however many rows it holds.
+struct StreamDecodeLaunch {
   const uint8_t* streams;
   uint8_t* stage;
   const long* blocks;
   int* status;
-  int n_blocks, lzw;
-  long block_stride;           // bytes between decoded blocks in stage (lzw), a multiple of 8, >= block_h * block_w * bytes
+  int n_blocks;
+  long block_stride;           // bytes between decoded blocks in stage, a multiple of 16, >= block_h * row_bytes
+  long row_bytes;              // block_w * bytes per sample
+  int whole_rows;
+};
+void launch_block_lzw(const StreamDecodeLaunch& a, hipStream_t s);
+void launch_block_inflate(const StreamDecodeLaunch& a, hipStream_t s);
+
+// GeoTIFF blocks -> a float32 plane (tiff_decode.hip; dbm_tiff_decode).  staged: the blocks were decoded to stage + b * block_stride;
+// else the block's decoded bytes lie at stage + offset (8-byte aligned).  launch_tiff_rows changes the decoded bytes in place (the
+// predictor) and writes out (out_h, out_w).
+struct TiffDecodeLaunch {
+  uint8_t* stage;
+  const long* blocks;
+  int n_blocks, staged;
+  long block_stride;           // bytes between staged blocks, a multiple of 16, >= block_h * block_w * bytes
   int block_w, block_h, bytes; // samples per block row, rows of a whole block, bytes per sample
-  int sample_type;             // 0 uint8, 1 int16, 2 uint16, 3 int32, 4 float32, 5 float64
+  int sample_type;             // 0..5
   int predictor;               // 1 none, 2 horizontal differencing, 3 floating point
   float* out;
   long out_h, out_w;
 };
-void launch_tiff_lzw(const TiffDecodeLaunch& a, hipStream_t s);
-void launch_tiff_inflate(const TiffDecodeLaunch& a, hipStream_t s);
 void launch_tiff_rows(const TiffDecodeLaunch& a, hipStream_t s);
 // lzw_decode_lanes with one lane on the host: the decoded size or (size_t)-1 (tools/lzw_twin_check.cpp compares it with dbm_lzw_decode)
 size_t tiff_lzw_decode_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
 // inflate_lanes with one lane on the host: the decoded size or (size_t)-1 (dbm_inflate; tools/inflate_twin_check.cpp compares it with zlib)
 size_t tiff_inflate_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
 
-// Chunks of a netCDF variable -> a float32 plane (nc_chunks.hip; dbm_chunk_decode).  blocks: n_blocks x 8 int64 on the device = {offset
-// of the block's bytes in the upload, their count, rows held, output row of row 0, output column of column 0, id, row step (+1 / -1), 0}.
-// staged: the blocks were inflated (launch_tiff_inflate, through a TiffDecodeLaunch over the same upload) to stage + b * block_stride;
-// else the block's bytes lie at stage + offset (8-byte aligned).  Row r of a block lands on output row e[3] + e[6] * r.
+// Chunks of a netCDF variable -> a float32 plane (nc_chunks.hip; dbm_chunk_decode).  staged: the blocks were inflated to
+// stage + b * block_stride; else the block's bytes lie at stage + offset (8-byte aligned).  Row r of a block lands on output row
+// e[3] + e[6] * r.
 struct ChunkDecodeLaunch {
   const uint8_t* stage;
   const long* blocks;
@@ -373,7 +390,7 @@ struct ChunkDecodeLaunch {
   long block_stride;           // bytes between staged blocks, a multiple of 16, >= block_h * block_w * bytes
   unsigned groups_per_block;   // nc_chunks_groups_per_block(block_w, block_h)
   int block_w, block_h, bytes; // samples per block row, rows of a whole block, bytes per sample
-  int sample_type;             // TiffDecodeLaunch's 0..5, 6 int8
+  int sample_type;             // 0..6
   int shuffle, big_endian;     // HDF5 shuffle over the whole block; the samples' byte order
   int has_fill, has_scale;
   unsigned long long fill_bits;  // the fill in the sample's width

@@ -2,7 +2,7 @@
 // reading the streams -- is deepbedmap_amd/netcdf.py).  Replaces the reference's xarray / rasterio reads of netCDF grids
 // (data_prep.py:889-900, deepbedmap.py:74-78, :176-191).  DESIGN.md 6l.
 //
-// Deflated chunks are inflated by launch_tiff_inflate (tiff_inflate.hip, one wavefront per block) into the staging area, as for
+// Deflated chunks are inflated by launch_block_inflate (tiff_inflate.hip, one wavefront per block) into the staging area, as for
 // dbm_tiff_decode; uncompressed chunks and the row bands of contiguous / classic data are read where they were uploaded.  ONE kernel
 // then does everything else, one pass over the staged bytes:
 //   - HDF5's shuffle filter is undone while reading: with shuffle on, byte k (in memory order) of element i of the block lies at

@@ -87,12 +87,12 @@ __host__ __device__ inline size_t lzw_decode_lanes(const uint8_t* src, size_t n,
   return outn;
 }
 
-__global__ __launch_bounds__(64) void tiff_lzw_kernel(TiffDecodeLaunch a) {
+__global__ __launch_bounds__(64) void tiff_lzw_kernel(StreamDecodeLaunch a) {
   __shared__ uint32_t tpos[4096];
   __shared__ uint32_t tlen[4096];
   const long b = blockIdx.x;
   const long* e = a.blocks + 8 * b;
-  const size_t want = (size_t)e[2] * (size_t)a.block_w * (size_t)a.bytes;   // <= block_stride (checked by the caller)
+  const size_t want = (size_t)(a.whole_rows ? a.whole_rows : e[2]) * (size_t)a.row_bytes;   // <= block_stride (checked by the caller)
   const size_t got = lzw_decode_lanes(a.streams + e[0], (size_t)e[1], a.stage + b * a.block_stride, want, tpos, tlen, threadIdx.x, 64u);
   if (threadIdx.x == 0) a.status[b] = got == (size_t)-1 ? 1 : (got != want ? 2 : 0);
 }
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(ROW_THREADS) void tiff_rows_kernel(TiffDecodeLaunch
   const long* e = a.blocks + 8 * b;
   const long orow = e[3] + r;
   if (r >= e[2] || orow < 0 || orow >= a.out_h) return;   // (uniform in the workgroup)
-  uint8_t* row = (a.lzw ? a.stage + b * a.block_stride : a.stage + e[0]) + r * (long)a.block_w * a.bytes;
+  uint8_t* row = (a.staged ? a.stage + b * a.block_stride : a.stage + e[0]) + r * (long)a.block_w * a.bytes;
   const int tid = threadIdx.x;
   if (a.predictor != 1) {
     const int w = a.predictor == 2 ? a.bytes : 1;                        // element width of the running sum
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(ROW_THREADS) void tiff_rows_kernel(TiffDecodeLaunch
 
 }  // namespace
 
-void launch_tiff_lzw(const TiffDecodeLaunch& a, hipStream_t s) {
+void launch_block_lzw(const StreamDecodeLaunch& a, hipStream_t s) {
   if (a.n_blocks <= 0) return;
   hipLaunchKernelGGL(tiff_lzw_kernel, dim3((unsigned)a.n_blocks), dim3(64), 0, s, a);
   DBM_HIP(hipGetLastError());

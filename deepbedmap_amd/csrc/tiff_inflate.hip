@@ -433,18 +433,18 @@ __host__ __device__ inline size_t inflate_lanes(const uint8_t* src, size_t n, ui
   return outn;
 }
 
-__global__ __launch_bounds__(64) void tiff_inflate_kernel(TiffDecodeLaunch a) {
+__global__ __launch_bounds__(64) void tiff_inflate_kernel(StreamDecodeLaunch a) {
   __shared__ InflateTables t;
   const long b = blockIdx.x;
   const long* e = a.blocks + 8 * b;
-  const size_t want = (size_t)e[2] * (size_t)a.block_w * (size_t)a.bytes;   // <= block_stride (checked by the caller)
+  const size_t want = (size_t)(a.whole_rows ? a.whole_rows : e[2]) * (size_t)a.row_bytes;   // <= block_stride (checked by the caller)
   const size_t got = inflate_lanes(a.streams + e[0], (size_t)e[1], a.stage + b * a.block_stride, want, &t, threadIdx.x, 64u);
   if (threadIdx.x == 0) a.status[b] = got == (size_t)-1 ? 1 : (got != want ? 2 : 0);
 }
 
 }  // namespace
 
-void launch_tiff_inflate(const TiffDecodeLaunch& a, hipStream_t s) {
+void launch_block_inflate(const StreamDecodeLaunch& a, hipStream_t s) {
   if (a.n_blocks <= 0) return;
   hipLaunchKernelGGL(tiff_inflate_kernel, dim3((unsigned)a.n_blocks), dim3(64), 0, s, a);
   DBM_HIP(hipGetLastError());

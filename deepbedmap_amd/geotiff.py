@@ -25,7 +25,8 @@ import struct
 
 import numpy as np
 
-from . import _lib
+from . import _lib, block_reads
+from .block_reads import WORKSPACE_DEFAULT, BlockPlan
 from .resident import DeviceArray, GridGeometry, devptr
 
 TILE = 256  # GDAL's default block size for tiled=True
@@ -573,22 +574,7 @@ _FIELD_TYPES = {1: ("B", 1), 2: ("s", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8)
 # (BitsPerSample, SampleFormat) -> (NumPy dtype, dbm_tiff_decode's sample_type)
 _SAMPLES = {(8, 1): ("u1", 0), (16, 2): ("<i2", 1), (16, 1): ("<u2", 2), (32, 2): ("<i4", 3), (32, 3): ("<f4", 4), (64, 3): ("<f8", 5)}
 _COMPRESSIONS = {1: "none", 5: "lzw", 8: "deflate", 32946: "deflate"}
-WORKSPACE_DEFAULT = 1 << 30   # bytes of block staging per batch of read_geotiff_resident
 INFLATE_DEFAULT = "device"    # where read_geotiff_resident inflates deflate blocks (the measurement that decided it)
-
-
-class BlockPlan:
-    """What one (windowed) read takes from the file.  `window` = (row0, col0, H, W) in image pixels; `blocks` = int64 (n, 6), one row
-    per block that meets the window, in file order of the block index: file offset, byte count, rows the block holds (the last strip
-    is short; tiles are whole), row and column of the block's pixel (0, 0) in the OUTPUT plane (negative where the block starts
-    before the window), block index."""
-    OFFSET, BYTES, ROWS, OUT_ROW, OUT_COL, INDEX = range(6)
-
-    def __init__(self, window, blocks):
-        self.window, self.blocks = tuple(int(v) for v in window), blocks
-
-    def __len__(self):
-        return len(self.blocks)
 
 
 class GeoTiffFile:
@@ -706,21 +692,8 @@ class GeoTiffFile:
         return self.height, self.width
 
     def window(self, window_bound=None):
-        """(row0, col0, H, W): the pixels whose centres lie in [minx, maxx) x (miny, maxy] -- for bounds on pixel edges the
-        reference's `rasterio.windows.from_bounds(...).round_offsets()` --, clipped to the image.  None: the whole image."""
-        if window_bound is None:
-            return 0, 0, self.height, self.width
-        minx, miny, maxx, maxy = (float(v) for v in window_bound)
-        if not all(np.isfinite(v) for v in (minx, miny, maxx, maxy)):
-            raise ValueError("window_bound must be finite")
-        g = self.geometry
-        xc = np.arange(self.width, dtype=np.float64) * g.dx + g.x0    # (node coordinates as everywhere: multiply, then add)
-        yc = np.arange(self.height, dtype=np.float64) * g.dy + g.y0
-        cols = np.flatnonzero((xc >= minx) & (xc < maxx))
-        rows = np.flatnonzero((yc > miny) & (yc <= maxy))
-        if cols.size == 0 or rows.size == 0:
-            raise ValueError(f"{self.path}: window_bound {(minx, miny, maxx, maxy)} holds no pixel centre of the raster")
-        return int(rows[0]), int(cols[0]), int(rows[-1] - rows[0] + 1), int(cols[-1] - cols[0] + 1)
+        """(row0, col0, H, W): `block_reads.pixel_window` of this image.  None: the whole image."""
+        return block_reads.pixel_window(lambda: self.geometry, self.height, self.width, window_bound, self.path, "the raster")
 
     def plan(self, window_bound=None):
         """The blocks a read of `window_bound` (None: everything) needs: a BlockPlan."""
@@ -744,7 +717,7 @@ class GeoTiffFile:
             if b[BlockPlan.OFFSET] < 0 or b[BlockPlan.OFFSET] + b[BlockPlan.BYTES] > size:
                 raise ValueError(f"{self.path}: block {b[BlockPlan.INDEX]} (offset {b[BlockPlan.OFFSET]}, {b[BlockPlan.BYTES]} bytes) lies "
                                  f"outside the file ({size} bytes)")
-        return BlockPlan((row0, col0, H, W), blocks)
+        return BlockPlan((row0, col0, H, W), blocks, (self.block_h, self.block_w))
 
 
 def _read_tags(f, path):
@@ -844,20 +817,9 @@ def open_geotiff(path, overview=0):
 
 
 def _batches(gf, plan, limit, streams=None):
-    """Consecutive runs of the plan's blocks whose staging (stream + decoded block) stays within `limit` bytes; never an empty run.
-    streams: the blocks' streams are uploaded and decoded on the device (LZW always; deflate unless it is inflated on the host)."""
-    decoded = -(-gf.block_h * gf.block_w * gf.dtype.itemsize // 16) * 16
-    if streams is None:
-        streams = gf.compression == 5
-    runs, start, used = [], 0, 0
-    for k, b in enumerate(plan.blocks):
-        cost = decoded + (int(b[BlockPlan.BYTES]) if streams else 16)
-        if k > start and used + cost > limit:
-            runs.append((start, k))
-            start, used = k, 0
-        used += cost
-    runs.append((start, len(plan.blocks)))
-    return runs
+    """`block_reads.batches` of a plan; streams: the streams themselves are uploaded (None: as for LZW, which always is)."""
+    return block_reads.batches(plan.blocks[:, BlockPlan.BYTES], plan.decoded_bytes(gf.dtype.itemsize), limit,
+                               gf.compression == 5 if streams is None else streams)
 
 
 def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=None, inflate=INFLATE_DEFAULT, overview=0):
@@ -871,17 +833,7 @@ def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=Non
     then applies to that image, whose geometry is the first image's pixel-edge box divided into its own pixels.
     Returns (DeviceArray (H, W), info): read_geotiff's keys plus predictor, dtype, window (row0, col0, H, W) and geometry (the
     window's GridGeometry, None for a file without georeference)."""
-    import dataclasses
-    import zlib
-    from concurrent.futures import ThreadPoolExecutor
-
-    if workspace_limit is None:
-        workspace_limit = WORKSPACE_DEFAULT
-    workspace_limit = int(workspace_limit)
-    if workspace_limit < 1:
-        raise ValueError("workspace_limit must be positive")
-    if inflate not in ("device", "host"):
-        raise ValueError(f"read_geotiff_resident: inflate {inflate!r}: 'device' or 'host'")
+    workspace_limit = block_reads.read_options(workspace_limit, inflate, "read_geotiff_resident")
     gf = open_geotiff(path, _overview_of(overview, "read_geotiff_resident"))
     on_device = gf.compression == 5 or (gf.compression != 1 and inflate == "device")   # the streams themselves are uploaded
     if window_bound is None:
@@ -890,57 +842,23 @@ def read_geotiff_resident(path, window_bound=None, workspace_limit=None, ctx=Non
         geometry = gf.geometry
     plan = gf.plan(window_bound)
     row0, col0, H, W = plan.window
-    if geometry is not None:
-        geometry = dataclasses.replace(geometry, x0=col0 * geometry.dx + geometry.x0, y0=row0 * geometry.dy + geometry.y0)
     ctx = ctx or _lib.default_context()
     out = DeviceArray((H, W), ctx)
-    itemsize = gf.dtype.itemsize
+    mode = 1 if not on_device else 5 if gf.compression == 5 else 8
     with open(gf.path, "rb") as f:
-        for start, stop in _batches(gf, plan, workspace_limit, on_device):
-            part = plan.blocks[start:stop]
-            streams = []
-            for b in part:
-                f.seek(int(b[BlockPlan.OFFSET]))
-                s = f.read(int(b[BlockPlan.BYTES]))
-                if len(s) != b[BlockPlan.BYTES]:
-                    raise _lib.DbmError(f"{gf.path}: block {b[BlockPlan.INDEX]}: the file ends inside its {b[BlockPlan.BYTES]} bytes")
-                streams.append(s)
-            table = np.zeros((len(part), 8), dtype=np.int64)
-            table[:, 2:6] = part[:, BlockPlan.ROWS:BlockPlan.INDEX + 1]
-            if on_device:
-                sizes = np.array([len(s) for s in streams], dtype=np.int64)
-                table[:, 0] = np.cumsum(sizes) - sizes
-                table[:, 1] = sizes
-                payload = np.frombuffer(b"".join(streams), dtype=np.uint8)
-                mode = 5 if gf.compression == 5 else 8
-            else:
-                if gf.compression != 1:
-                    def inflate_one(k):
-                        try:
-                            return zlib.decompress(streams[k])
-                        except zlib.error as e:
-                            raise _lib.DbmError(f"{gf.path}: block {part[k, BlockPlan.INDEX]}: malformed deflate stream ({e})") from None
-                    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
-                        streams = list(pool.map(inflate_one, range(len(streams))))
-                want = part[:, BlockPlan.ROWS] * gf.block_w * itemsize
-                stride = -(-gf.block_h * gf.block_w * itemsize // 16) * 16
-                payload = np.zeros(len(part) * stride, dtype=np.uint8)
-                for k, s in enumerate(streams):
-                    if len(s) < want[k]:
-                        raise _lib.DbmError(f"{gf.path}: block {part[k, BlockPlan.INDEX]}: {len(s)} decoded bytes, {want[k]} expected")
-                    payload[k * stride:k * stride + want[k]] = np.frombuffer(s, dtype=np.uint8, count=int(want[k]))
-                table[:, 0] = np.arange(len(part), dtype=np.int64) * stride
-                table[:, 1] = want
-                mode = 1
-            try:
-                ctx.call("dbm_tiff_decode", devptr(payload), payload.size, devptr(table), len(part), mode, gf.predictor, gf.sample_type, gf.block_w,
-                         gf.block_h, devptr(out), H, W)
-            except _lib.DbmError as e:
-                err = _lib.DbmError(f"{gf.path}: {e}")
-                err.code = e.code
-                raise err from None
+        def read(b):
+            f.seek(int(b[BlockPlan.OFFSET]))
+            s = f.read(int(b[BlockPlan.BYTES]))
+            if len(s) != b[BlockPlan.BYTES]:
+                raise _lib.DbmError(f"{gf.path}: block {b[BlockPlan.INDEX]}: the file ends inside its {b[BlockPlan.BYTES]} bytes")
+            return s
+
+        for payload, table in block_reads.staged_batches(plan, slice(None), gf.dtype.itemsize, workspace_limit, read, on_device,
+                                                         gf.compression != 1, 0, False, gf.path):
+            block_reads.decode_call(ctx, gf.path, "dbm_tiff_decode", devptr(payload), payload.size, devptr(table), len(table), mode,
+                                    gf.predictor, gf.sample_type, gf.block_w, gf.block_h, devptr(out), H, W)
     out.written()
     info = {"pixel_scale": gf.pixel_scale, "tiepoint": gf.tiepoint, "geokeys": gf.geokeys, "nodata": gf.nodata, "bigtiff": gf.bigtiff,
             "compression": gf.compression, "tile": (gf.block_h, gf.block_w), "predictor": gf.predictor, "dtype": gf.dtype,
-            "window": plan.window, "geometry": geometry}
+            "window": plan.window, "geometry": block_reads.window_geometry(geometry, row0, col0)}
     return out, info

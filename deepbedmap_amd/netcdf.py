@@ -22,10 +22,10 @@ import struct
 
 import numpy as np
 
-from . import _lib
+from . import _lib, block_reads
+from .block_reads import BlockPlan as ChunkPlan   # (the plan of a netCDF variable holds all eight columns)
 from .resident import DeviceArray, GridGeometry, devptr
 
-WORKSPACE_DEFAULT = 1 << 30   # bytes of chunk staging per batch of read_netcdf_resident
 INFLATE_DEFAULT = "device"    # where read_netcdf_resident inflates deflated chunks (the measurements that decided it)
 BAND_BYTES = 1 << 24          # contiguous and classic data go through as row bands of about this many bytes (always < 2^31)
 
@@ -37,20 +37,6 @@ _FILTER_NAMES = {1: "deflate", 2: "shuffle", 3: "fletcher32", 4: "szip", 5: "nbi
 _SAMPLE_TYPES = {("u", 1): 0, ("i", 2): 1, ("u", 2): 2, ("i", 4): 3, ("f", 4): 4, ("f", 8): 5, ("i", 1): 6}
 _NEEDED = ("_FillValue", "missing_value", "scale_factor", "add_offset", "node_offset")
 _CLASSIC_TYPES = {1: ">i1", 2: "S1", 3: ">i2", 4: ">i4", 5: ">f4", 6: ">f8"}
-
-
-class ChunkPlan:
-    """What one (windowed) read takes from the file.  `window` = (row0, col0, H, W) in the rows and columns of the variable as it is
-    RETURNED (north-up); `blocks` = int64 (n, 8), one row per chunk or row band that meets the window: file offset, stored bytes, rows
-    held, output row of the block's row 0, output column of its column 0, index, row step (+1, or -1 for a file whose y ascends),
-    filter mask.  `block_shape`: (block_h, block_w) of every block.  Chunks that were never written are absent."""
-    OFFSET, BYTES, ROWS, OUT_ROW, OUT_COL, INDEX, STEP, MASK = range(8)
-
-    def __init__(self, window, blocks, block_shape):
-        self.window, self.blocks, self.block_shape = tuple(int(v) for v in window), blocks, tuple(int(v) for v in block_shape)
-
-    def __len__(self):
-        return len(self.blocks)
 
 
 class _File:
@@ -364,24 +350,12 @@ class NetcdfVariable:
         return max(1, min(self.height, BAND_BYTES // max(row, 1))), self.width
 
     def window(self, window_bound=None):
-        """(row0, col0, H, W) in the returned (north-up) variable: the pixels whose centres lie in [minx, maxx) x (miny, maxy], as
-        GeoTiffFile.window; None: everything."""
-        H, W = self.height, self.width
-        if window_bound is None:
-            return 0, 0, H, W
-        minx, miny, maxx, maxy = (float(v) for v in window_bound)
-        if not all(np.isfinite(v) for v in (minx, miny, maxx, maxy)):
-            raise ValueError("window_bound must be finite")
-        g = self.geometry
-        if g is None:
-            raise ValueError(f"{self.path}: variable {self.name!r} has no coordinates: a window_bound cannot be placed")
-        xc = np.arange(W, dtype=np.float64) * g.dx + g.x0
-        yc = np.arange(H, dtype=np.float64) * g.dy + g.y0
-        cols = np.flatnonzero((xc >= minx) & (xc < maxx))
-        rows = np.flatnonzero((yc > miny) & (yc <= maxy))
-        if cols.size == 0 or rows.size == 0:
-            raise ValueError(f"{self.path}: window_bound {(minx, miny, maxx, maxy)} holds no pixel centre of {self.name!r}")
-        return int(rows[0]), int(cols[0]), int(rows[-1] - rows[0] + 1), int(cols[-1] - cols[0] + 1)
+        """(row0, col0, H, W) in the returned (north-up) variable: `block_reads.pixel_window`, as GeoTiffFile.window; None: everything."""
+        def geometry():
+            if self.geometry is None:
+                raise ValueError(f"{self.path}: variable {self.name!r} has no coordinates: a window_bound cannot be placed")
+            return self.geometry
+        return block_reads.pixel_window(geometry, self.height, self.width, window_bound, self.path, repr(self.name))
 
     def plan(self, window_bound=None):
         """The chunks or row bands a read of `window_bound` (None: everything) needs: a ChunkPlan."""
@@ -836,18 +810,10 @@ def open_netcdf(path, variable=None, coords=("x", "y")):
     return var
 
 
-def _window_geometry(var, plan):
-    g = var.geometry
-    if g is None:
-        return None
-    row0, col0 = plan.window[:2]
-    return dataclasses.replace(g, x0=col0 * g.dx + g.x0, y0=row0 * g.dy + g.y0)
-
-
 def _info(var, plan):
     return {"variable": var.name, "dtype": var.dtype, "layout": var.layout, "tile": plan.block_shape, "chunks": var.chunk_shape,
             "filters": var.filters, "fill": var.fill, "scale": var.scale, "offset": var.offset, "storage_fill": var.storage_fill,
-            "window": plan.window, "geometry": _window_geometry(var, plan), "flipped": var.flipped,
+            "window": plan.window, "geometry": block_reads.window_geometry(var.geometry, *plan.window[:2]), "flipped": var.flipped,
             "compression": 8 if "deflate" in var.filters else 1}
 
 
@@ -883,16 +849,7 @@ def read_netcdf_resident(path, variable=None, window_bound=None, workspace_limit
     DESIGN.md 6l has the measurements behind the default.  window_bound = (minx, miny, maxx, maxy): the pixels whose centres lie in [minx, maxx) x (miny,
     maxy].  workspace_limit: bytes of staging per batch (default 1 GiB; at least one block goes through at a time).  Returns
     (DeviceArray (H, W), info) with read_netcdf's info keys."""
-    import zlib
-    from concurrent.futures import ThreadPoolExecutor
-
-    if workspace_limit is None:
-        workspace_limit = WORKSPACE_DEFAULT
-    workspace_limit = int(workspace_limit)
-    if workspace_limit < 1:
-        raise ValueError("workspace_limit must be positive")
-    if inflate not in ("device", "host"):
-        raise ValueError(f"read_netcdf_resident: inflate {inflate!r}: 'device' or 'host'")
+    workspace_limit = block_reads.read_options(workspace_limit, inflate, "read_netcdf_resident")
     var = open_netcdf(path, variable, coords)
     plan = var.plan(window_bound)
     row0, col0, H, W = plan.window
@@ -906,58 +863,22 @@ def read_netcdf_resident(path, variable=None, window_bound=None, workspace_limit
     if not covered:   # cells that no chunk covers: the storage fill through the value rule
         first = float(convert(np.asarray([var.storage_fill_value()], dtype=native), fill, scale, offset)[0])
         ctx.call("dbm_fill_f32", devptr(out), H * W, first)
-    itemsize = var.dtype.itemsize
-    decoded = -(-bh * bw * itemsize // 16) * 16
+
+    def read(b):
+        return var._f.at(b[ChunkPlan.OFFSET], b[ChunkPlan.BYTES], f"block {b[ChunkPlan.INDEX]} of {var.name!r}")
+
     # groups of blocks that went through the same filters, each cut into batches within the workspace limit
     groups = {}
     for k, b in enumerate(plan.blocks):
         groups.setdefault(var.applied(b[ChunkPlan.MASK]), []).append(k)
     for applied, members in groups.items():
         on_device = "deflate" in applied and inflate == "device"
-        runs, start, used = [], 0, 0
-        for k, m in enumerate(members):
-            cost = decoded + (int(plan.blocks[m, ChunkPlan.BYTES]) if on_device else 16)
-            if k > start and used + cost > workspace_limit:
-                runs.append(members[start:k])
-                start, used = k, 0
-            used += cost
-        runs.append(members[start:])
-        for run in runs:
-            part = plan.blocks[run]
-            streams = [var._f.at(b[ChunkPlan.OFFSET], b[ChunkPlan.BYTES], f"block {b[ChunkPlan.INDEX]} of {var.name!r}") for b in part]
-            if "deflate" in applied and not on_device:
-                def inflate_one(k):
-                    try:
-                        return zlib.decompress(streams[k])
-                    except zlib.error as e:
-                        raise _lib.DbmError(f"{var.path}: block {part[k, ChunkPlan.INDEX]}: malformed deflate stream ({e})") from None
-                with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
-                    streams = list(pool.map(inflate_one, range(len(streams))))
-            table = np.zeros((len(part), 8), dtype=np.int64)
-            table[:, 2:7] = part[:, ChunkPlan.ROWS:ChunkPlan.STEP + 1]
-            sizes = np.array([len(s) for s in streams], dtype=np.int64)
-            if on_device:
-                table[:, 0] = np.cumsum(sizes) - sizes
-                table[:, 1] = sizes
-                payload = np.frombuffer(b"".join(streams), dtype=np.uint8)
-            else:
-                want = (bh if var.layout == "chunked" else part[:, ChunkPlan.ROWS]) * bw * itemsize
-                if (sizes != want).any():
-                    k = int(np.argmax(sizes != want))
-                    raise _lib.DbmError(f"{var.path}: block {part[k, ChunkPlan.INDEX]}: {sizes[k]} decoded bytes, {np.broadcast_to(want, sizes.shape)[k]} expected")
-                table[:, 0] = np.arange(len(part), dtype=np.int64) * decoded
-                table[:, 1] = sizes
-                payload = np.zeros(len(part) * decoded, dtype=np.uint8)
-                for k, s in enumerate(streams):
-                    payload[k * decoded:k * decoded + len(s)] = np.frombuffer(s, dtype=np.uint8)
-            try:
-                ctx.call("dbm_chunk_decode", devptr(payload), payload.size, devptr(table), len(part), 8 if on_device else 1,
-                         1 if "shuffle" in applied else 0, var.sample_type, 1 if var.dtype.byteorder == ">" else 0, bw, bh,
-                         0 if fill is None else 1, 0 if fill is None else _bits(fill, native), 1 if has_scale else 0,
-                         1.0 if scale is None else scale, 0.0 if offset is None else offset, devptr(out), H, W)
-            except _lib.DbmError as e:
-                err = _lib.DbmError(f"{var.path}: {e}")
-                err.code = e.code
-                raise err from None
+        for payload, table in block_reads.staged_batches(plan, members, var.dtype.itemsize, workspace_limit, read, on_device,
+                                                         "deflate" in applied, bh if var.layout == "chunked" else 0, True, var.path):
+            block_reads.decode_call(ctx, var.path, "dbm_chunk_decode", devptr(payload), payload.size, devptr(table), len(table),
+                                    8 if on_device else 1, 1 if "shuffle" in applied else 0, var.sample_type,
+                                    1 if var.dtype.byteorder == ">" else 0, bw, bh, 0 if fill is None else 1,
+                                    0 if fill is None else _bits(fill, native), 1 if has_scale else 0, 1.0 if scale is None else scale,
+                                    0.0 if offset is None else offset, devptr(out), H, W)
     out.written()
     return out, _info(var, plan)
