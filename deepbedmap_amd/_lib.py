@@ -200,6 +200,10 @@ SIGNATURES = {
     "dbm_op_batchnorm_train_backward": [C.c_void_p] + [C.c_void_p] * 9 + [C.c_int] * 4 + [C.POINTER(C.c_int)],
     "dbm_op_disc_head": [C.c_void_p] + [C.c_void_p] * 7 + [C.c_int],
     "dbm_op_disc_head_backward": [C.c_void_p] + [C.c_void_p] * 10 + [C.c_int, C.POINTER(C.c_int)],
+    "dbm_op_input_block": [C.c_void_p] + [C.c_void_p] * 13 + [C.c_int64, C.c_void_p] + [C.c_int] * 4 + [C.POINTER(C.c_int)],
+    "dbm_op_input_block_backward": [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 8 + [C.c_int] * 3 + [C.POINTER(C.c_int)] * 2,
+    "dbm_op_smallcin_wgrad": [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] * 9 + [C.POINTER(C.c_int)],
+    "dbm_op_sumpool2": [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int64, C.c_int, C.c_int],
 }
 
 _lib = None

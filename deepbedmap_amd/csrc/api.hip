@@ -1872,4 +1872,113 @@ int dbm_op_disc_head_backward(dbm_ctx* ctx, const float* x, const float* W1, con
   DBM_API_END
 }
 
+// The two entry points below run the generator's own launch sequences of the input block (generator.hip) on a throw-away model that
+// holds nothing but the block: they copy the caller's tensors in, size the im2col images and call; form choice and launches are there.
+int dbm_op_input_block(dbm_ctx* ctx, const float* x, const float* w1, const float* w2, const float* w3, const float* wx, const float* bx,
+                       const float* ww1, const float* b1, const float* ww2, const float* b2, const float* ww3, const float* b3, float* y,
+                       int64_t ysn, float* yt, int N, int H, int W, int form, int* form_out) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(x && w1 && w2 && w3 && wx && bx && ww1 && b1 && ww2 && b2 && ww3 && b3 && y, "input block op: every input, weight, bias and y are required");
+  DBM_CHECK(N >= 1 && H >= 3 && W >= 3, "input block op: N >= 1 and tiles of at least 3 x 3");
+  DBM_CHECK(form >= -1 && form <= 2, "input block op: form is -1 (the model's choice), 0 (layer-wise), 1 (fused) or 2 (rows)");
+  const long hw = (long)(H - 2) * (W - 2);
+  DBM_CHECK(ysn >= 128 * hw, "input block op: ysn must be at least 128 * (H - 2) * (W - 2)");
+  if (form == IN_FUSED) {
+    DBM_CHECK(input_block_fused_ok(H, W), "input block op: form 1 (the fused kernel) serves 11 x 11 tiles only");
+    DBM_CHECK((reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) % 16 == 0,
+              "input block op: form 1 (the fused kernel) stages w1 / w2 with 16-byte loads, both must be 16-byte aligned");
+  }
+  if (form == IN_ROWS)
+    DBM_CHECK(input_block_rows_ok(H, W), "input block op: form 2 (the rows kernel) needs H >= 3 and planes at least two tiles wide (W - 2 >= 64)");
+  const InputBlockForm f = form < 0 ? input_block_form(H, W, w1, w2, false) : (InputBlockForm)form;
+  DBM_CHECK(!yt || f == IN_ROWS, "input block op: yt (channels-last) is written by form 2 (the rows kernel) only");
+  hipStream_t s = ctx->stream;
+  dbm_model holder;
+  holder.ctx = ctx;
+  const InputBlockIds ib = add_input_block(holder, "op/");
+  holder.alloc_arenas();
+  const float* src[4][2] = {{wx, bx}, {ww1, b1}, {ww2, b2}, {ww3, b3}};
+  for (int i = 0; i < 4; ++i)
+    for (int k = 0; k < 2; ++k)
+      DBM_HIP(hipMemcpyAsync(holder.P(ib.T[i][k]), src[i][k], sizeof(float) * holder.tensors[ib.T[i][k]].n, hipMemcpyDeviceToDevice, s));
+  holder.ensure_packed();
+  ScopedBuf colW1, colW2;
+  if (f == IN_LAYERWISE) {
+    colW1.ensure((size_t)N * holder.layers[ib.L[1]].CinP * hw);
+    colW2.ensure((size_t)N * holder.layers[ib.L[2]].CinP * hw);
+  }
+  input_block_forward(holder, ib, f, N, H, W, x, w1, w2, w3, y, ysn, yt, colW1.p, colW2.p, false, s);
+  DBM_HIP(hipStreamSynchronize(s));
+  if (form_out) *form_out = (int)f;
+  DBM_API_END
+}
+
+int dbm_op_input_block_backward(dbm_ctx* ctx, const float* x, const float* w1, const float* w2, const float* w3, const float* g, int64_t gsn,
+                                float* gwx, float* gbx, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3, int N, int H,
+                                int W, int* cat_out, int* S_out) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(x && w1 && w2 && w3 && g && gwx && gbx && gw1 && gb1 && gw2 && gb2 && gw3 && gb3, "input block op: every input, g and gradient are required");
+  DBM_CHECK(N >= 1 && H >= 3 && W >= 3, "input block op: N >= 1 and tiles of at least 3 x 3");
+  const long hw = (long)(H - 2) * (W - 2);
+  DBM_CHECK(gsn >= 128 * hw, "input block op: gsn must be at least 128 * (H - 2) * (W - 2)");
+  hipStream_t s = ctx->stream;
+  dbm_model holder;
+  holder.ctx = ctx;
+  const InputBlockIds ib = add_input_block(holder, "op/");
+  holder.alloc_arenas();
+  // (the model's launches add into the model's own gradient arena: the caller's gradients go in first and come back with the sums on top)
+  float* dst[4][2] = {{gwx, gbx}, {gw1, gb1}, {gw2, gb2}, {gw3, gb3}};
+  for (int i = 0; i < 4; ++i)
+    for (int k = 0; k < 2; ++k)
+      DBM_HIP(hipMemcpyAsync(holder.G(ib.T[i][k]), dst[i][k], sizeof(float) * holder.tensors[ib.T[i][k]].n, hipMemcpyDeviceToDevice, s));
+  ScopedBuf colW1, colW2;
+  colW1.ensure((size_t)N * holder.layers[ib.L[1]].CinP * hw);
+  colW2.ensure((size_t)N * holder.layers[ib.L[2]].CinP * hw);
+  WgradBatch batch;
+  input_block_queue_wgrads(holder, ib, N, H, W, colW1.p, colW2.p, g, gsn, &batch);
+  ctx->fork_to_side(6);
+  input_block_rebuild_cols(holder, ib, N, H, W, w1, w2, colW1.p, colW2.p, ctx->side);
+  batch.launch(ctx->side);
+  input_block_small_wgrads(holder, ib, N, H, W, x, w3, g, gsn, ctx->side);
+  ctx->join_side();
+  for (int i = 0; i < 4; ++i)
+    for (int k = 0; k < 2; ++k)
+      DBM_HIP(hipMemcpyAsync(dst[i][k], holder.G(ib.T[i][k]), sizeof(float) * holder.tensors[ib.T[i][k]].n, hipMemcpyDeviceToDevice, s));
+  DBM_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < 2; ++i) {
+    if (cat_out) cat_out[i] = batch.desc_cat[i];
+    if (S_out) S_out[i] = batch.desc_S[i];
+  }
+  DBM_API_END
+}
+
+int dbm_op_smallcin_wgrad(dbm_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int N, int C, int H, int W, int O, int k,
+                          int stride, int pad, int with_scratch, int* form_out) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(x && gy && gw, "few-channel wgrad op: x, gy and gw are required");
+  DBM_CHECK(N >= 1 && C >= 1 && O >= 1 && k >= 1 && stride >= 1 && pad >= 0 && H + 2 * pad >= k && W + 2 * pad >= k, "few-channel wgrad op: bad geometry");
+  const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
+  DBM_CHECK((long)N * OH * OW < (1L << 31), "few-channel wgrad op: the kernels count positions in 32 bits");
+  SmallConvDesc q;
+  memset(&q, 0, sizeof(q));
+  q.x = x; q.xsn = (long)C * H * W; q.Cin = C; q.Hin = H; q.Win = W; q.Cout = O; q.OH = OH; q.OW = OW;
+  q.KH = q.KW = k; q.stride = stride; q.pad = pad; q.N = N;
+  ScopedBuf scratch;
+  if (with_scratch) scratch.ensure(smallcin_wgrad_scratch_floats(O));   // (as Discriminator::backward sizes c0_scratch)
+  int form = 0;
+  launch_smallcin_conv_wgrad(q, gy, (long)O * OH * OW, gw, gb, ctx->stream, scratch.p, &form);
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  if (form_out) *form_out = form;
+  DBM_API_END
+}
+
+int dbm_op_sumpool2(dbm_ctx* ctx, const float* g, const float* mask, float* out, int64_t nc, int H, int W) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(g && out && nc >= 1 && H >= 1 && W >= 1, "sumpool2 op: g, out and a non-empty output are required");
+  DBM_CHECK((nc * H * W + 255) / 256 < (1L << 31), "sumpool2 op: too many elements for one launch");
+  launch_sumpool2(g, mask, out, (long)nc, H, W, 0.2f, ctx->stream);
+  DBM_HIP(hipStreamSynchronize(ctx->stream));
+  DBM_API_END
+}
+
 }  // extern "C"

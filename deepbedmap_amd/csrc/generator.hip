@@ -4,6 +4,115 @@
 static const float SLOPE = 0.2f;
 static bool trunk_fused_enabled();
 
+// ---- DeepbedmapInputBlock (srgan_train.py:223-266): the launch sequences Generator::forward / backward and the op-level entry points
+// (dbm_op_input_block, dbm_op_input_block_backward) share ----
+namespace {
+struct InBranch { int Cin, K, stride; };
+const InBranch IN_BR[4] = {{1, 3, 1}, {1, 30, 10}, {2, 6, 2}, {1, 3, 1}};  // on X (H x W), W1 (10H x 10W), W2 (2 x 2H x 2W), W3 (H x W)
+const int IN_SCALE[4] = {1, 10, 2, 1};                                     // the branch's input plane in units of the tile
+}  // namespace
+
+InputBlockIds add_input_block(dbm_model& m, const std::string& prefix) {
+  InputBlockIds ib;
+  const char* names[4] = {"conv_on_X", "conv_on_W1", "conv_on_W2", "conv_on_W3"};
+  for (int i = 0; i < 4; ++i) {
+    m.add_tensor(prefix + names[i] + "/W", {32, IN_BR[i].Cin, IN_BR[i].K, IN_BR[i].K}, DBM_KIND_PARAM);
+    m.add_tensor(prefix + names[i] + "/b", {32}, DBM_KIND_PARAM);
+  }
+  for (int i = 0; i < 4; ++i) {
+    ib.T[i][0] = m.tid(prefix + names[i] + "/W");
+    ib.T[i][1] = m.tid(prefix + names[i] + "/b");
+  }
+  ib.L[1] = m.add_iglayer(prefix + names[1], 32, 1, 30, 1, 0, true, /*as_1x1=*/true);  // GEMM over the 900 im2col rows
+  ib.L[2] = m.add_iglayer(prefix + names[2], 32, 2, 6, 1, 0, true, /*as_1x1=*/true);   // 72 rows
+  return ib;
+}
+
+InputBlockForm input_block_form(int H, int W, const float* w1, const float* w2, bool gemm_bf16) {
+  // training tile: one launch (input_block.hip); the wide branches' im2col images are then rebuilt by backward(), off this path.
+  // DBM_INPUT_FUSED=0: layer by layer (A/B, and the form every other tile size takes)
+  static const int in_fused_env = getenv("DBM_INPUT_FUSED") ? atoi(getenv("DBM_INPUT_FUSED")) : 1;
+  const bool in_rows = in_fused_env && !input_block_fused_ok(H, W) && input_block_rows_ok(H, W) && !gemm_bf16;
+  // (input_block_fused_kernel stages W1 / W2 with 16-byte loads and has no scalar form: 4-byte-aligned caller views take the layer-wise path)
+  const bool in_al16 = (reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) % 16 == 0;
+  if (in_rows) return IN_ROWS;
+  return (in_fused_env && input_block_fused_ok(H, W) && in_al16 && !gemm_bf16) ? IN_FUSED : IN_LAYERWISE;
+}
+
+// four valid convolutions written straight into the 128-channel concat (:256-266)
+void input_block_forward(const dbm_model& m, const InputBlockIds& ib, InputBlockForm form, int N, int H, int W, const float* x, const float* w1,
+                         const float* w2, const float* w3, float* y, long ysn, float* yt, float* colW1, float* colW2, bool gemm_bf16,
+                         hipStream_t s) {
+  const int h = H - 2, w = W - 2;
+  const long hw = (long)h * w;
+  if (form != IN_LAYERWISE) {
+    InputBlockLaunch q;
+    q.yt = yt;
+    q.x = x; q.w1 = w1; q.w2 = w2; q.w3 = w3;
+    q.wx = m.P(ib.T[0][0]); q.bx = m.P(ib.T[0][1]);
+    q.wf1 = m.layers[ib.L[1]].wf; q.b1 = m.P(ib.T[1][1]);
+    q.wf2 = m.layers[ib.L[2]].wf; q.b2 = m.P(ib.T[2][1]);
+    q.w3w = m.P(ib.T[3][0]); q.b3 = m.P(ib.T[3][1]);
+    q.y = y; q.ysn = ysn; q.N = N;
+    if (form == IN_ROWS) launch_input_block_rows(q, H, W, s);
+    else launch_input_block_fused(q, s);
+    return;
+  }
+  const float* in[4] = {x, w1, w2, w3};
+  for (int i = 0; i < 4; ++i) {
+    const int Hin = IN_SCALE[i] * H, Win = IN_SCALE[i] * W;
+    SmallConvDesc d;
+    memset(&d, 0, sizeof(d));
+    d.x = in[i]; d.xsn = (long)IN_BR[i].Cin * Hin * Win; d.Cin = IN_BR[i].Cin; d.Hin = Hin; d.Win = Win;
+    d.w = m.P(ib.T[i][0]); d.bias = m.P(ib.T[i][1]);
+    d.y = y + (long)i * 32 * hw; d.ysn = ysn; d.Cout = 32; d.OH = h; d.OW = w;
+    d.KH = d.KW = IN_BR[i].K; d.stride = IN_BR[i].stride; d.pad = 0; d.N = N; d.act = 0; d.slope = SLOPE;
+    DBM_CHECK((Hin - IN_BR[i].K) / IN_BR[i].stride + 1 == h && (Win - IN_BR[i].K) / IN_BR[i].stride + 1 == w,
+              "input block branch does not produce the (H-2, W-2) grid");
+    if (ib.L[i] >= 0) {  // wide kernels: im2col (0.1 % of the generator's bytes) + MFMA GEMM
+      const IgLayer& L = m.layers[ib.L[i]];
+      float* col = i == 1 ? colW1 : colW2;
+      launch_im2col(in[i], col, N, IN_BR[i].Cin, Hin, Win, IN_BR[i].K, IN_BR[i].K, IN_BR[i].stride, h, w, L.CinP, s);
+      ConvDesc g = m.fwd_desc(L, col, (long)L.CinP * hw, h, w, 0, d.y, ysn, N);
+      if (!gemm_bf16) g.wp16 = nullptr;
+      launch_igemm_conv(g, s);
+    } else {
+      launch_smallcin_conv_fwd(d, s);
+    }
+  }
+}
+
+void input_block_rebuild_cols(const dbm_model& m, const InputBlockIds& ib, int N, int H, int W, const float* w1, const float* w2, float* colW1,
+                              float* colW2, hipStream_t s) {
+  const int h = H - 2, w = W - 2;
+  launch_im2col(w1, colW1, N, 1, 10 * H, 10 * W, 30, 30, 10, h, w, m.layers[ib.L[1]].CinP, s);
+  launch_im2col(w2, colW2, N, 2, 2 * H, 2 * W, 6, 6, 2, h, w, m.layers[ib.L[2]].CinP, s);
+}
+
+void input_block_queue_wgrads(const dbm_model& m, const InputBlockIds& ib, int N, int H, int W, const float* colW1, const float* colW2,
+                              const float* g, long gsn, WgradBatch* batch) {
+  const int h = H - 2, w = W - 2;
+  const long hw = (long)h * w;
+  for (int i = 1; i <= 2; ++i) {
+    const IgLayer& L = m.layers[ib.L[i]];
+    m.run_wgrad(L, i == 1 ? colW1 : colW2, (long)L.CinP * hw, h, w, 0, g + (long)i * 32 * hw, gsn, h, w, N, 1.f, batch);
+  }
+}
+
+void input_block_small_wgrads(const dbm_model& m, const InputBlockIds& ib, int N, int H, int W, const float* x, const float* w3, const float* g,
+                              long gsn, hipStream_t s) {
+  const int h = H - 2, w = W - 2;
+  const long hw = (long)h * w;
+  for (int i = 0; i < 4; i += 3) {  // the two single-channel 3x3 branches
+    SmallConvDesc q;
+    memset(&q, 0, sizeof(q));
+    q.x = i == 0 ? x : w3;
+    q.xsn = (long)H * W; q.Cin = 1; q.Hin = H; q.Win = W;
+    q.Cout = 32; q.OH = h; q.OW = w; q.KH = q.KW = 3; q.stride = 1; q.pad = 0; q.N = N;
+    launch_smallcin_conv_wgrad(q, g + (long)i * 32 * hw, gsn, m.G(ib.T[i][0]), m.G(ib.T[i][1]), s);
+  }
+}
+
 Generator::Generator(dbm_ctx* c, int n, float r, int oc) {
   ctx = c;
   type = 0;
@@ -18,19 +127,7 @@ Generator::Generator(dbm_ctx* c, int n, float r, int oc) {
     add_tensor(name + "/W", {O, C, KH, KW}, DBM_KIND_PARAM);
     add_tensor(name + "/b", {O}, DBM_KIND_PARAM);
   };
-  // DeepbedmapInputBlock  srgan_train.py:223-254
-  const char* in_names[4] = {"input_block/conv_on_X", "input_block/conv_on_W1", "input_block/conv_on_W2",
-                             "input_block/conv_on_W3"};
-  conv(in_names[0], 32, 1, 3, 3);
-  conv(in_names[1], 32, 1, 30, 30);
-  conv(in_names[2], 32, 2, 6, 6);
-  conv(in_names[3], 32, 1, 3, 3);
-  for (int i = 0; i < 4; ++i) {
-    T_in[i][0] = tid(std::string(in_names[i]) + "/W");
-    T_in[i][1] = tid(std::string(in_names[i]) + "/b");
-  }
-  L_in[1] = add_iglayer(in_names[1], 32, 1, 30, 1, 0, true, /*as_1x1=*/true);  // GEMM over the 900 im2col rows
-  L_in[2] = add_iglayer(in_names[2], 32, 2, 6, 1, 0, true, /*as_1x1=*/true);   // 72 rows
+  in_ids = add_input_block(*this, "input_block/");  // DeepbedmapInputBlock  srgan_train.py:223-254
   conv("pre_residual_conv_layer", 64, 128, 3, 3);  // :467-474
   L_pre = add_iglayer("pre_residual_conv_layer", 64, 128, 3, 1, 1, true);
   layers.back().want_x3 = true;
@@ -169,8 +266,8 @@ void Generator::ensure_ws(GenWorkspace& ws, int N, int H, int W, bool train) {
   ws.in_w2.ensure(n * 2 * 4 * H * W);
   ws.in_w3.ensure(n * H * W);
   ws.a0.ensure(n * 128 * hw);
-  ws.colW1.ensure(n * layers[L_in[1]].CinP * hw);
-  ws.colW2.ensure(n * layers[L_in[2]].CinP * hw);
+  ws.colW1.ensure(n * layers[in_ids.L[1]].CinP * hw);
+  ws.colW2.ensure(n * layers[in_ids.L[2]].CinP * hw);
   const int ncat = tr ? nrdb + 1 : 5;
   if ((int)ws.cat.size() < ncat) ws.cat.resize(ncat);
   for (int i = 0; i < ncat; ++i) ws.cat[i].ensure(n * 192 * hw);
@@ -256,52 +353,16 @@ void Generator::forward(GenWorkspace& ws, int N, int H, int W, const float* x, c
   bool pre_x3 = post_x3 && layers[L_pre].wx3 != nullptr && !(bf16_keep32 & 64) && !(getenv("DBM_PRE_X3") && atoi(getenv("DBM_PRE_X3")) == 0);
   // ---- input block: four valid convolutions written straight into the 128-channel concat (:256-266) ----
   {
-    struct { const float* in; int Cin, Hin, Win, K, stride; } br[4] = {
-        {x, 1, H, W, 3, 1}, {w1, 1, 10 * H, 10 * W, 30, 10}, {w2, 2, 2 * H, 2 * W, 6, 2}, {w3, 1, H, W, 3, 1}};
-    // training tile: one launch (input_block.hip); the wide branches' im2col images are then rebuilt by backward(), off this path.
-    // DBM_INPUT_FUSED=0: layer by layer (A/B, and the form every other tile size takes)
-    static const int in_fused_env = getenv("DBM_INPUT_FUSED") ? atoi(getenv("DBM_INPUT_FUSED")) : 1;
-    const bool in_rows = in_fused_env && !input_block_fused_ok(H, W) && input_block_rows_ok(H, W) && !(use_bf16 && !(bf16_keep32 & 1));
-    // (input_block_fused_kernel stages W1 / W2 with 16-byte loads and has no scalar form: 4-byte-aligned caller views take the layer-wise path)
-    const bool in_al16 = (reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) % 16 == 0;
-    const bool in_fused = in_rows || (in_fused_env && input_block_fused_ok(H, W) && in_al16 && !(use_bf16 && !(bf16_keep32 & 1)));
-    ws.col_stale = in_fused && keep;
-    pre_x3 = pre_x3 && in_rows;   // (the split-bf16 pre-residual convolution reads the rows kernel's channels-last output)
-    if (in_fused) {
-      InputBlockLaunch q;
-      q.yt = nullptr;
-      if (pre_x3) {
-        ws.a0t.ensure((size_t)N * 128 * hw);
-        q.yt = ws.a0t.p;
-      }
-      q.x = x; q.w1 = w1; q.w2 = w2; q.w3 = w3;
-      q.wx = P(T_in[0][0]); q.bx = P(T_in[0][1]);
-      q.wf1 = layers[L_in[1]].wf; q.b1 = P(T_in[1][1]);
-      q.wf2 = layers[L_in[2]].wf; q.b2 = P(T_in[2][1]);
-      q.w3w = P(T_in[3][0]); q.b3 = P(T_in[3][1]);
-      q.y = ws.a0.p; q.ysn = 128 * hw; q.N = N;
-      if (in_rows) launch_input_block_rows(q, H, W, s);
-      else launch_input_block_fused(q, s);
+    const bool gemm_bf16 = use_bf16 && !(bf16_keep32 & 1);
+    const InputBlockForm in_form = input_block_form(H, W, w1, w2, gemm_bf16);
+    ws.col_stale = in_form != IN_LAYERWISE && keep;   // (the wide branches' im2col images are then rebuilt by backward(), off this path)
+    pre_x3 = pre_x3 && in_form == IN_ROWS;   // (the split-bf16 pre-residual convolution reads the rows kernel's channels-last output)
+    float* a0t = nullptr;
+    if (pre_x3) {
+      ws.a0t.ensure((size_t)N * 128 * hw);
+      a0t = ws.a0t.p;
     }
-    for (int i = 0; i < 4 && !in_fused; ++i) {
-      SmallConvDesc d;
-      memset(&d, 0, sizeof(d));
-      d.x = br[i].in; d.xsn = (long)br[i].Cin * br[i].Hin * br[i].Win; d.Cin = br[i].Cin; d.Hin = br[i].Hin; d.Win = br[i].Win;
-      d.w = P(T_in[i][0]); d.bias = P(T_in[i][1]);
-      d.y = ws.a0.p + (long)i * 32 * hw; d.ysn = 128 * hw; d.Cout = 32; d.OH = h; d.OW = w;
-      d.KH = d.KW = br[i].K; d.stride = br[i].stride; d.pad = 0; d.N = N; d.act = 0; d.slope = SLOPE;
-      DBM_CHECK((br[i].Hin - br[i].K) / br[i].stride + 1 == h && (br[i].Win - br[i].K) / br[i].stride + 1 == w,
-                "input block branch does not produce the (H-2, W-2) grid");
-      if (L_in[i] >= 0) {  // wide kernels: im2col (0.1 % of the generator's bytes) + MFMA GEMM
-        const IgLayer& L = layers[L_in[i]];
-        float* col = (i == 1 ? ws.colW1 : ws.colW2).p;
-        launch_im2col(br[i].in, col, N, br[i].Cin, br[i].Hin, br[i].Win, br[i].K, br[i].K, br[i].stride, h, w, L.CinP, s);
-        ConvDesc g = prec(fwd_desc(L, col, (long)L.CinP * hw, h, w, 0, d.y, 128 * hw, N), 1);
-        launch_igemm_conv(g, s);
-      } else {
-        launch_smallcin_conv_fwd(d, s);
-      }
-    }
+    input_block_forward(*this, in_ids, in_form, N, H, W, x, w1, w2, w3, ws.a0.p, 128 * hw, a0t, ws.colW1.p, ws.colW2.p, gemm_bf16, s);
   }
   // The 9x9 stage is a chain of ~180 short, latency-bound kernels (162-324 tiles each at batch 64).  The generator
   // has no cross-sample coupling, so the batch is cut into `nsplit` image ranges that run the same chain on
@@ -635,8 +696,8 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
     deform64_wgrad(*this, L, f1, ws.a42t.p, nullptr, ws.off1.p, 32 * P4, ws.g_a51.p, G(L.wi), G(L.bi), ws.dw1_partial.p, N, H4, W4, ctx->side, nullptr);
   }
   if (ws.col_stale) {  // (fused input block: the im2col images the wide branches' weight gradients read -- wbs[6], launched last)
-    launch_im2col(ws.bw_in[1] ? ws.bw_in[1] : ws.in_w1.p, ws.colW1.p, N, 1, 10 * H, 10 * W, 30, 30, 10, h, w, layers[L_in[1]].CinP, ctx->side);
-    launch_im2col(ws.bw_in[2] ? ws.bw_in[2] : ws.in_w2.p, ws.colW2.p, N, 2, 2 * H, 2 * W, 6, 6, 2, h, w, layers[L_in[2]].CinP, ctx->side);
+    input_block_rebuild_cols(*this, in_ids, N, H, W, ws.bw_in[1] ? ws.bw_in[1] : ws.in_w1.p, ws.bw_in[2] ? ws.bw_in[2] : ws.in_w2.p, ws.colW1.p,
+                             ws.colW2.p, ctx->side);
     ws.col_stale = false;
   }
   // Data-parallel run: the gradient arena is in construction order (input block | pre | trunk | tail), and the backward
@@ -781,33 +842,13 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
   join_chains();
   DBM_MARK(s, "G:backward_trunk_chain");
   // ---- pre_residual_conv_layer and the input block ----
-  SmallConvDesc small[4];
-  int small_i[4], nsmall = 0;
   {
     const IgLayer& L = layers[L_pre];
     // (its inputs -- a0 and the chain's last output -- are final when the chain is: the pre-residual weight gradient rides in the
     //  trunk's last launch (same kernel form) instead of being a 50-us launch + fold of its own in the serial tail behind it)
     run_wgrad(L, ws.a0.p, 128 * hw, h, w, 0, ws.dA[0].p, 192 * hw, h, w, N, 1.f, &ws.wbs[prev_grp >= 0 ? prev_grp : 6]);
     run_dgrad(L, dgrad_desc(ws.dA[0].p, 192 * hw, ws.g_a0.p, 128 * hw, N), h, w);
-    struct { const float* in; int Cin, Hin, Win, K, stride; } br[4] = {{ws.in_x.p, 1, H, W, 3, 1},
-                                                                    {ws.in_w1.p, 1, 10 * H, 10 * W, 30, 10},
-                                                                    {ws.in_w2.p, 2, 2 * H, 2 * W, 6, 2},
-                                                                    {ws.in_w3.p, 1, H, W, 3, 1}};
-    for (int i = 0; i < 4; ++i) {
-      SmallConvDesc q;
-      memset(&q, 0, sizeof(q));
-      q.x = ws.bw_in[i] ? ws.bw_in[i] : br[i].in;
-      q.xsn = (long)br[i].Cin * br[i].Hin * br[i].Win; q.Cin = br[i].Cin; q.Hin = br[i].Hin; q.Win = br[i].Win;
-      q.Cout = 32; q.OH = h; q.OW = w; q.KH = q.KW = br[i].K; q.stride = br[i].stride; q.pad = 0; q.N = N;
-      if (L_in[i] >= 0) {
-        const IgLayer& L = layers[L_in[i]];
-        run_wgrad(L, (i == 1 ? ws.colW1 : ws.colW2).p, (long)L.CinP * hw, h, w, 0, ws.g_a0.p + (long)i * 32 * hw, 128 * hw, h, w, N,
-                  1.f, &ws.wbs[6]);
-      } else {
-        small[nsmall] = q;
-        small_i[nsmall++] = i;
-      }
-    }
+    input_block_queue_wgrads(*this, in_ids, N, H, W, ws.colW1.p, ws.colW2.p, ws.g_a0.p, 128 * hw, &ws.wbs[6]);
   }
   DBM_MARK(s, "G:backward_input_block");
   // (Round 4, measured on one box: launching the trunk's weight gradients on the side stream right behind the chain -- before
@@ -820,10 +861,8 @@ void Generator::backward(GenWorkspace& ws, const float* gy, bool cleared, bool u
   if (prev_grp >= 0 && !(iter_abl & 2)) ws.wbs[prev_grp].launch(wgs);
   DBM_MARK(wgs, "G:trunk_weight_gradients");
   ws.wbs[6].launch(wgs);
-  for (int k = 0; k < nsmall; ++k) {  // the two single-channel 3x3 branches of the input block
-    const int i = small_i[k];
-    launch_smallcin_conv_wgrad(small[k], ws.g_a0.p + (long)i * 32 * hw, 128 * hw, G(T_in[i][0]), G(T_in[i][1]), wgs);
-  }
+  input_block_small_wgrads(*this, in_ids, N, H, W, ws.bw_in[0] ? ws.bw_in[0] : ws.in_x.p, ws.bw_in[3] ? ws.bw_in[3] : ws.in_w3.p, ws.g_a0.p,
+                           128 * hw, wgs);
   // input block, pre-residual conv and the trunk group launched last (layer-wise trunk path: the whole trunk)
   if (ctx->comm_in_step) ctx->comm_bucket(grads, rdb_off(final_hi), ctx->side);
   ctx->join_side();  // the optimizer (and the next cleargrads) must see every gradient

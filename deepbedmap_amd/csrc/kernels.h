@@ -14,9 +14,11 @@ struct SmallConvDesc {
   int act; float slope;
 };
 void launch_smallcin_conv_fwd(const SmallConvDesc& d, hipStream_t s);
-// scratch (optional, smallcin_wgrad_scratch_floats(Cout) floats, private to the launch): the read-dy-once form for <= 9 taps
+// scratch (optional, smallcin_wgrad_scratch_floats(Cout) floats, private to the launch): the read-dy-once form (partial sums per
+// position slice + fold) for one input channel, 3 x 3, stride 1, pad 1, Cout % 8 == 0 on >= 16384 positions; everything else, and
+// every call without scratch, takes one workgroup per gradient element.  form_out (op-level tests): 1 = partial + fold, 0 = per element
 void launch_smallcin_conv_wgrad(const SmallConvDesc& d, const float* dy, long dysn, float* gW, float* gb, hipStream_t s,
-                                float* scratch = nullptr);
+                                float* scratch = nullptr, int* form_out = nullptr);
 size_t smallcin_wgrad_scratch_floats(int Cout);
 
 // DeepbedmapInputBlock on the training tile (11 x 11 -> 9 x 9) as one launch (input_block.hip)

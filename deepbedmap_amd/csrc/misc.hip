@@ -134,21 +134,18 @@ __global__ __launch_bounds__(256) void smallcin_conv_wgrad_kernel(const SmallCon
   }
 }
 
-// Few taps (Cin * KH * KW <= 9: conv_layer0 of the discriminator): a workgroup per (output channel, position slice) keeps
-// all nine sums and the bias sum in registers, so dy is read ONCE instead of ten times; the slices' partial sums go to
+// conv_layer0 of the discriminator (one input channel, 3 x 3, stride 1, pad 1): a workgroup per (output channel group, position
+// slice) keeps all nine sums and the bias sum in registers, so dy is read ONCE instead of ten times; the slices' partial sums go to
 // a scratch buffer and a second kernel adds them in slice order (reproducible like the kernel above; 249 -> ~30 us).
 constexpr int SCW_SLICES = 64;
-constexpr int SCW_OG = 8;  // output channels per workgroup of the 3 x 3 form
-// K3 = true: the geometry is known at compile time (one input channel, 3 x 3, stride 1, pad 1 = conv_layer0): without it
-// every tap decodes (c, ky, kx) with runtime integer divisions -- ~600 VALU instructions per position against ten FMAs.
-// The 3 x 3 form also takes SCW_OG output channels per workgroup (blockIdx.x = channel group): a position's nine input
+constexpr int SCW_OG = 8;  // output channels per workgroup
+// The geometry is known at compile time: with (c, ky, kx) decoded per tap by runtime integer divisions a position cost ~600 VALU
+// instructions against ten FMAs.  SCW_OG output channels per workgroup (blockIdx.x = channel group): a position's nine input
 // values are loaded once for all of them (the loads of x, not of dy, were the bulk of the instructions: 49 -> ~15 us).
-template <bool K3>
 __global__ __launch_bounds__(256) void smallcin_wgrad_partial_kernel(const SmallConvDesc d, const float* __restrict__ dy,
                                                                      long dysn, float* __restrict__ partial) {
-  constexpr int OG = K3 ? SCW_OG : 1;
+  constexpr int OG = SCW_OG;
   __shared__ float sh[4][OG * 10];
-  const int K = K3 ? 9 : d.Cin * d.KH * d.KW;  // <= 9
   const int o0 = blockIdx.x * OG, z = blockIdx.y;
   const int plane = d.OH * d.OW;
   const unsigned total = (unsigned)d.N * (unsigned)plane;
@@ -169,36 +166,21 @@ __global__ __launch_bounds__(256) void smallcin_wgrad_partial_kernel(const Small
     if (b >= (unsigned)d.OW) { ++a; b -= (unsigned)d.OW; }
     const float* xn = d.x + (long)n * d.xsn;
     const float* dyp = dy + (long)n * dysn + (long)o0 * plane + r;
-    if constexpr (K3) {
-      const float* xc = xn + (int)a * d.Win + (int)b;
-      float xv[9];
+    const float* xc = xn + (int)a * d.Win + (int)b;
+    float xv[9];
 #pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
+    for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const int iy = (int)a - 1 + ky, ix = (int)b - 1 + kx;
-          xv[ky * 3 + kx] = ((unsigned)iy < (unsigned)d.Hin && (unsigned)ix < (unsigned)d.Win) ? xc[(ky - 1) * d.Win + (kx - 1)] : 0.f;
-        }
-#pragma unroll
-      for (int oo = 0; oo < OG; ++oo) {
-        const float g = dyp[(long)oo * plane];
-        acc[oo][9] += g;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) acc[oo][k] = fmaf(g, xv[k], acc[oo][k]);
+      for (int kx = 0; kx < 3; ++kx) {
+        const int iy = (int)a - 1 + ky, ix = (int)b - 1 + kx;
+        xv[ky * 3 + kx] = ((unsigned)iy < (unsigned)d.Hin && (unsigned)ix < (unsigned)d.Win) ? xc[(ky - 1) * d.Win + (kx - 1)] : 0.f;
       }
-    } else {
-      const float g = dyp[0];
-      acc[0][9] += g;
 #pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        if (k < K) {
-          const int c = k / (d.KH * d.KW), kr = k - c * d.KH * d.KW;
-          const int ky = kr / d.KW, kx = kr - ky * d.KW;
-          const int iy = (int)a * d.stride - d.pad + ky, ix = (int)b * d.stride - d.pad + kx;
-          if ((unsigned)iy < (unsigned)d.Hin && (unsigned)ix < (unsigned)d.Win)
-            acc[0][k] = fmaf(g, xn[(long)c * d.Hin * d.Win + (long)iy * d.Win + ix], acc[0][k]);
-        }
-      }
+    for (int oo = 0; oo < OG; ++oo) {
+      const float g = dyp[(long)oo * plane];
+      acc[oo][9] += g;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) acc[oo][k] = fmaf(g, xv[k], acc[oo][k]);
     }
   }
 #pragma unroll
@@ -231,18 +213,18 @@ __global__ __launch_bounds__(640) void smallcin_wgrad_fold_kernel(const float* _
 size_t smallcin_wgrad_scratch_floats(int Cout) { return (size_t)SCW_SLICES * Cout * 10; }
 
 void launch_smallcin_conv_wgrad(const SmallConvDesc& d, const float* dy, long dysn, float* gW, float* gb,
-                                hipStream_t s, float* scratch) {
+                                hipStream_t s, float* scratch, int* form_out) {
   if (dbm_abl_skip() & 128) return;  // (libdbm_measure.so only)
   const int K = d.Cin * d.KH * d.KW;
-  if (scratch && K <= 9 && (long)d.N * d.OH * d.OW >= 16384) {
-    if (d.Cin == 1 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Cout % SCW_OG == 0)
-      hipLaunchKernelGGL(smallcin_wgrad_partial_kernel<true>, dim3(d.Cout / SCW_OG, SCW_SLICES), dim3(256), 0, s, d, dy, dysn, scratch);
-    else
-      hipLaunchKernelGGL(smallcin_wgrad_partial_kernel<false>, dim3(d.Cout, SCW_SLICES), dim3(256), 0, s, d, dy, dysn, scratch);
+  // (the read-dy-once form serves conv_layer0's geometry only; everything else, and every call without scratch: one workgroup per element)
+  if (scratch && (long)d.N * d.OH * d.OW >= 16384 && d.Cin == 1 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Cout % SCW_OG == 0) {
+    hipLaunchKernelGGL(smallcin_wgrad_partial_kernel, dim3(d.Cout / SCW_OG, SCW_SLICES), dim3(256), 0, s, d, dy, dysn, scratch);
     hipLaunchKernelGGL(smallcin_wgrad_fold_kernel, dim3(d.Cout), dim3(640), 0, s, scratch, d.Cout, K, gW, gb);
     DBM_HIP(hipGetLastError());
+    if (form_out) *form_out = 1;
     return;
   }
+  if (form_out) *form_out = 0;
   hipLaunchKernelGGL(smallcin_conv_wgrad_kernel, dim3(d.Cout * K + (gb ? d.Cout : 0)), dim3(256), 0, s, d, dy, dysn, gW, gb);
   DBM_HIP(hipGetLastError());
 }

@@ -247,6 +247,34 @@ void deform64_backward_data(const dbm_model& m, const IgLayer& L, const DeformFo
 void deform64_wgrad(const dbm_model& m, const IgLayer& L, const DeformForms& f, const float* xt, const float* col, const float* off, long offsn,
                     const float* gy, float* gw, float* gb, float* partial, int N, int H, int W, hipStream_t s, WgradBatch* batch);
 
+// ---- the input block's launch sequences (generator.hip): one copy for Generator::forward / backward and the op-level entry points ----
+// DeepbedmapInputBlock's tensors and layers inside a model: conv_on_X, conv_on_W1, conv_on_W2, conv_on_W3.
+struct InputBlockIds {
+  int T[4][2];                  // (W, b) tensor ids
+  int L[4] = {-1, -1, -1, -1};  // W1 / W2 branches: the layers that run them as im2col + GEMM on the MFMA kernels (1x1 view)
+};
+// Registers the four convolutions `prefix + conv_on_*` (tensors in save_npz order, then the two wide branches' layers) in m.
+InputBlockIds add_input_block(dbm_model& m, const std::string& prefix);
+enum InputBlockForm { IN_LAYERWISE = 0, IN_FUSED = 1, IN_ROWS = 2 };
+// The form the block takes on H x W tiles for these W1 / W2 pointers.  gemm_bf16: the wide branches' GEMMs multiply in bf16 (the sweep
+// with bit 1 of DBM_BF16_FP32_LAYERS cleared): layer-wise only.  The only reader of DBM_INPUT_FUSED.
+InputBlockForm input_block_form(int H, int W, const float* w1, const float* w2, bool gemm_bf16);
+// y (N, 128, (H-2)(W-2)), image stride ysn; yt (IN_ROWS only, or null): the same concat channels-last INSTEAD of y.  IN_LAYERWISE writes
+// the wide branches' im2col images colW1 / colW2 (N * CinP * plane floats each); the other forms leave them alone.
+void input_block_forward(const dbm_model& m, const InputBlockIds& ib, InputBlockForm form, int N, int H, int W, const float* x, const float* w1,
+                         const float* w2, const float* w3, float* y, long ysn, float* yt, float* colW1, float* colW2, bool gemm_bf16,
+                         hipStream_t s);
+// The im2col images the wide branches' weight gradients read, rebuilt from the inputs (behind a forward that was not layer-wise).
+void input_block_rebuild_cols(const dbm_model& m, const InputBlockIds& ib, int N, int H, int W, const float* w1, const float* w2, float* colW1,
+                              float* colW2, hipStream_t s);
+// Weight / bias gradients into m's gradient arena from g (N, >= 128, plane), image stride gsn: the wide branches as 1x1 layers over
+// their im2col images, queued on `batch` ...
+void input_block_queue_wgrads(const dbm_model& m, const InputBlockIds& ib, int N, int H, int W, const float* colW1, const float* colW2,
+                              const float* g, long gsn, WgradBatch* batch);
+// ... and the two single-channel 3x3 branches, launched on s (no scratch: one workgroup per gradient element)
+void input_block_small_wgrads(const dbm_model& m, const InputBlockIds& ib, int N, int H, int W, const float* x, const float* w3, const float* g,
+                              long gsn, hipStream_t s);
+
 // Everything one forward / backward pass of the generator leaves behind or works in: activations, gradients, scratch, the record of
 // the retained graph and the batches planned over these buffers.  Allocates nothing until a pass sizes it (Generator::ensure_ws).
 struct GenWorkspace {
@@ -301,8 +329,7 @@ struct Generator : dbm_model {
   // layer indices into `layers`
   int L_pre, L_post, L_up1, L_up2, L_off1, L_def1, L_off2;
   std::vector<int> L_rdb;  // nrdb*5
-  int T_in[4][2];          // input block (W, b) tensor ids
-  int L_in[4] = {-1, -1, -1, -1};  // W1 / W2 branches run as im2col + GEMM on the MFMA kernels
+  InputBlockIds in_ids;    // input block: tensor ids, and the W1 / W2 branches' layers (im2col + GEMM on the MFMA kernels)
   int T_def2W, T_def2b;
   // Two workspaces on the one set of parameters and weight images.  ws[0] serves every single pass; ws[1] holds the G-step's own
   // retained forward, enqueued while the D-step's discriminator passes are still running (dbm_discriminator_step's prefetch flag,

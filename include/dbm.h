@@ -859,6 +859,33 @@ int dbm_op_disc_head(dbm_ctx* ctx, const float* x, const float* W1, const float*
  * launch while 4 * N * 100 bytes fit 48 KiB of LDS, else one launch per linear layer; *fused_out (HOST, may be NULL) = 1 / 0. */
 int dbm_op_disc_head_backward(dbm_ctx* ctx, const float* x, const float* W1, const float* W2, const float* glogits, const float* l1, float* gx,
                               float* gW1, float* gb1, float* gW2, float* gb2, int N, int* fused_out);
+/* DeepbedmapInputBlock (srgan_train.py:223-266) through the generator's own launch sequences: x (N,1,H,W), w1 (N,1,10H,10W),
+ * w2 (N,2,2H,2W), w3 (N,1,H,W); wx / bx, ww1 / b1, ww2 / b2, ww3 / b3: the OIHW weights (32,1,3,3), (32,1,30,30), (32,2,6,6), (32,1,3,3)
+ * and biases (32) of conv_on_X, _W1, _W2, _W3; all DEVICE -> y (N, 128, plane = (H-2)(W-2)) with image stride ysn >= 128 * plane.  yt (N * plane, 128) or NULL: the concat
+ * channels-last INSTEAD of y (y is then left alone), form 2 only.  form: -1 the model's own choice for these pointers and this shape,
+ * 0 layer-wise (im2col + GEMM for the wide branches, the few-channel kernel for the 3x3 ones), 1 the fused kernel of the 11 x 11
+ * training tile (w1 and w2 16-byte aligned), 2 the rows kernel (H >= 3, W >= 66).  A form that the shape or the alignment does not allow
+ * is refused (DBM_CHECK naming the condition), and so is yt outside form 2.  *form_out (HOST, may be NULL): the form that ran. */
+int dbm_op_input_block(dbm_ctx* ctx, const float* x, const float* w1, const float* w2, const float* w3, const float* wx, const float* bx,
+                       const float* ww1, const float* b1, const float* ww2, const float* b2, const float* ww3, const float* b3, float* y,
+                       int64_t ysn, float* yt, int N, int H, int W, int form, int* form_out);
+/* ... and its weight gradients from g (N, >= 128, plane) with image stride gsn, as Generator::backward runs them behind a fused forward:
+ * the wide branches' im2col images rebuilt from w1 / w2, the two branches as 1x1 layers of 900 / 72 channels in ONE batch (folding by
+ * dbm_set_deterministic), the 3x3 branches through the few-channel kernel without scratch; on the context's side stream.  The four
+ * gradient pairs (gwx / gbx, gw1 / gb1, gw2 / gb2, gw3 / gb3, shapes as the weights above) are ACCUMULATED.  cat_out / S_out (HOST,
+ * 2 ints each, may be NULL): category and K slices of the W1 and the W2 branch, as dbm_op_conv2d_wgrad_batch reports them. */
+int dbm_op_input_block_backward(dbm_ctx* ctx, const float* x, const float* w1, const float* w2, const float* w3, const float* g, int64_t gsn,
+                                float* gwx, float* gbx, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3, int N, int H,
+                                int W, int* cat_out, int* S_out);
+/* Weight gradient of a few-input-channel convolution (the input block's branches, the discriminator's conv_layer0) through
+ * launch_smallcin_conv_wgrad: x (N,C,H,W), gy (N,O,OH,OW) -> gw (O,C,k,k) and gb (O, or NULL) ACCUMULATED.  with_scratch = 1: the launch
+ * is handed a scratch buffer as the discriminator hands it one.  *form_out (HOST, may be NULL): 0 one workgroup per gradient element,
+ * 1 partial sums per position slice + fold (with scratch, one channel, 3x3, stride 1, pad 1, O % 8 == 0, N * OH * OW >= 16384). */
+int dbm_op_smallcin_wgrad(dbm_ctx* ctx, const float* x, const float* gy, float* gw, float* gb, int N, int C, int H, int W, int O, int k,
+                          int stride, int pad, int with_scratch, int* form_out);
+/* Backward of F.resize_images x2 (nearest; srgan_train.py:556-566) with the LeakyReLU(0.2) derivative of the layer below: g (nc, 2H, 2W)
+ * -> out (nc, H, W) = (g00 + g01) + (g10 + g11), times 0.2 where mask (nc, H, W, or NULL) < 0 (both zeros: derivative 1) */
+int dbm_op_sumpool2(dbm_ctx* ctx, const float* g, const float* mask, float* out, int64_t nc, int H, int W);
 
 /* ---- reading survey text tables: the `pandas.read_csv` + `dropna` of ascii_to_xyz (data_prep.py:298-305) ----
  * text: nbytes bytes of one file, host or (DBM_DEVICE_PTRS) device, a device pointer 16-byte aligned; offsets are 64-bit, files above
