@@ -122,6 +122,9 @@ struct ConvDesc {
   unsigned phPlaneM[4], phOwM[4];
 };
 
+// output extent of a convolution along one axis: `in` input positions (after a folded resize), kernel k
+inline int conv_out_extent(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
+
 // What launch_igemm_conv chose for a descriptor (op-level tests: dbm_op_conv2d_launch), written where the launcher decides.
 struct ConvLaunchReport {
   int family;   // 0 igemm_conv_kernel, 1 igemm_pm_kernel, 2 conv_tile_kernel
@@ -177,6 +180,17 @@ void launch_pack_jobs(const PackJob* d_jobs, int njobs, int total_blocks, hipStr
 
 // wgrad (wgrad.hip).  WgradDesc, WgradPlan, the form table and the planner are host-only C++ in wgrad_plan.h.
 #include "wgrad_plan.h"
+// x (N, Cin, Hin, Win) with image stride xsn, read through a nearest x2 resize where ups; dy (N, Cout, OH, OW) with image stride dysn;
+// a k x k layer; gW / gb (gb may be null) receive scale * the gradient
+inline WgradDesc wgrad_desc(const float* x, long xsn, int Cin, int Hin, int Win, int ups, const float* dy, long dysn, int Cout, int OH, int OW,
+                            int k, int stride, int pad, int N, float scale, float* gW, float* gb) {
+  WgradDesc w;
+  memset(&w, 0, sizeof(w));
+  w.x = x; w.xsn = xsn; w.xsc = Hin * Win; w.Cin = Cin; w.Hin = Hin; w.Win = Win; w.ups = ups;
+  w.dy = dy; w.dysn = dysn; w.dysc = OH * OW; w.Cout = Cout; w.OH = OH; w.OW = OW;
+  w.KH = w.KW = k; w.stride = stride; w.pad = pad; w.N = N; w.scale = scale; w.gW = gW; w.gb = gb;
+  return w;
+}
 void launch_wgrad(const WgradDesc& d, hipStream_t s);  // single layer, synchronous (tests / op-level API)
 extern bool g_wgrad_deterministic;  // dbm_set_deterministic: weight gradients are folded without fp32 atomics
 

@@ -82,12 +82,9 @@ void Discriminator::forward(int N, int H, int W, const float* img, float* logits
   const size_t n = (size_t)N;
   c.h[0].ensure(n * 64 * H * W);
   {  // conv_layer0 + LeakyReLU  (:658-659)
-    SmallConvDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x = img; d.xsn = (long)H * W; d.Cin = 1; d.Hin = H; d.Win = W;
+    SmallConvDesc d = small_conv_desc(img, (long)H * W, 1, H, W, 64, 3, 1, 1, N);
     d.w = P(T_c0W); d.bias = P(T_c0b);
-    d.y = c.h[0].p; d.ysn = 64L * H * W; d.Cout = 64; d.OH = H; d.OW = W;
-    d.KH = d.KW = 3; d.stride = 1; d.pad = 1; d.N = N; d.act = 1; d.slope = SLOPE;
+    d.y = c.h[0].p; d.ysn = 64L * H * W; d.act = 1; d.slope = SLOPE;
     launch_smallcin_conv_fwd(d, s);
   }
   // Eval mode (chainer.config.train = False: the G-step's detached pass, :1228, and the dev-set evaluation): BatchNorm is a
@@ -254,10 +251,7 @@ void Discriminator::backward(int slot, const float* glogits, bool join, bool mer
     float* t = gh; gh = gh_next; gh_next = t;
   }
   {  // conv_layer0 weight / bias gradient
-    SmallConvDesc q;
-    memset(&q, 0, sizeof(q));
-    q.x = c.img_src; q.xsn = (long)c.H * c.W; q.Cin = 1; q.Hin = c.H; q.Win = c.W;
-    q.Cout = 64; q.OH = c.H; q.OW = c.W; q.KH = q.KW = 3; q.stride = 1; q.pad = 1; q.N = N;
+    const SmallConvDesc q = small_conv_desc(c.img_src, (long)c.H * c.W, 1, c.H, c.W, 64, 3, 1, 1, N);
     c0_scratch[slot].ensure(smallcin_wgrad_scratch_floats(64));
     launch_smallcin_conv_wgrad(q, gh, 64L * c.H * c.W, G(T_c0W), G(T_c0b), s, c0_scratch[slot].p);
   }

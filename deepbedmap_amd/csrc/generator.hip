@@ -61,14 +61,10 @@ void input_block_forward(const dbm_model& m, const InputBlockIds& ib, InputBlock
   const float* in[4] = {x, w1, w2, w3};
   for (int i = 0; i < 4; ++i) {
     const int Hin = IN_SCALE[i] * H, Win = IN_SCALE[i] * W;
-    SmallConvDesc d;
-    memset(&d, 0, sizeof(d));
-    d.x = in[i]; d.xsn = (long)IN_BR[i].Cin * Hin * Win; d.Cin = IN_BR[i].Cin; d.Hin = Hin; d.Win = Win;
+    // (every branch of IN_BR produces the (H - 2, W - 2) grid: d.OH == h, d.OW == w)
+    SmallConvDesc d = small_conv_desc(in[i], (long)IN_BR[i].Cin * Hin * Win, IN_BR[i].Cin, Hin, Win, 32, IN_BR[i].K, IN_BR[i].stride, 0, N);
     d.w = m.P(ib.T[i][0]); d.bias = m.P(ib.T[i][1]);
-    d.y = y + (long)i * 32 * hw; d.ysn = ysn; d.Cout = 32; d.OH = h; d.OW = w;
-    d.KH = d.KW = IN_BR[i].K; d.stride = IN_BR[i].stride; d.pad = 0; d.N = N; d.act = 0; d.slope = SLOPE;
-    DBM_CHECK((Hin - IN_BR[i].K) / IN_BR[i].stride + 1 == h && (Win - IN_BR[i].K) / IN_BR[i].stride + 1 == w,
-              "input block branch does not produce the (H-2, W-2) grid");
+    d.y = y + (long)i * 32 * hw; d.ysn = ysn; d.act = 0; d.slope = SLOPE;
     if (ib.L[i] >= 0) {  // wide kernels: im2col (0.1 % of the generator's bytes) + MFMA GEMM
       const IgLayer& L = m.layers[ib.L[i]];
       float* col = i == 1 ? colW1 : colW2;
@@ -104,11 +100,7 @@ void input_block_small_wgrads(const dbm_model& m, const InputBlockIds& ib, int N
   const int h = H - 2, w = W - 2;
   const long hw = (long)h * w;
   for (int i = 0; i < 4; i += 3) {  // the two single-channel 3x3 branches
-    SmallConvDesc q;
-    memset(&q, 0, sizeof(q));
-    q.x = i == 0 ? x : w3;
-    q.xsn = (long)H * W; q.Cin = 1; q.Hin = H; q.Win = W;
-    q.Cout = 32; q.OH = h; q.OW = w; q.KH = q.KW = 3; q.stride = 1; q.pad = 0; q.N = N;
+    const SmallConvDesc q = small_conv_desc(i == 0 ? x : w3, (long)H * W, 1, H, W, 32, 3, 1, 0, N);
     launch_smallcin_conv_wgrad(q, g + (long)i * 32 * hw, gsn, m.G(ib.T[i][0]), m.G(ib.T[i][1]), s);
   }
 }

@@ -13,6 +13,16 @@ struct SmallConvDesc {
   int N;
   int act; float slope;
 };
+// Zeroed, with the input, the k x k layer, N and the output extent filled: what the weight gradient reads.  The forward's callers add
+// w, bias, y, ysn, act and slope.
+inline SmallConvDesc small_conv_desc(const float* x, long xsn, int Cin, int Hin, int Win, int Cout, int k, int stride, int pad, int N) {
+  SmallConvDesc d;
+  memset(&d, 0, sizeof(d));
+  d.x = x; d.xsn = xsn; d.Cin = Cin; d.Hin = Hin; d.Win = Win;
+  d.Cout = Cout; d.OH = conv_out_extent(Hin, k, stride, pad); d.OW = conv_out_extent(Win, k, stride, pad);
+  d.KH = d.KW = k; d.stride = stride; d.pad = pad; d.N = N;
+  return d;
+}
 void launch_smallcin_conv_fwd(const SmallConvDesc& d, hipStream_t s);
 // scratch (optional, smallcin_wgrad_scratch_floats(Cout) floats, private to the launch): the read-dy-once form (partial sums per
 // position slice + fold) for one input channel, 3 x 3, stride 1, pad 1, Cout % 8 == 0 on >= 16384 positions; everything else, and

@@ -27,6 +27,9 @@ struct ScopedBuf : DevBuf {
 };
 
 struct dbm_ctx {
+  explicit dbm_ctx(int hip_device) : device(hip_device) {}
+  dbm_ctx(const dbm_ctx&) = delete;
+  ~dbm_ctx();  // (model.hip) frees and destroys everything declared below; dbm_init fills it in, dbm_shutdown drains the streams first
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr;
@@ -108,11 +111,22 @@ struct dbm_ctx {
   DevBuf resample_tmp;        // dbm_grid_rescale: min / max, Gaussian weights and the float64 planes (doubles)
   DevBuf points_tmp;          // dbm_points_region: the workgroups' boxes; dbm_points_blockmedian: block indices, histogram, scan, lists
   long long poly_stats[6] = {};  // list sizes of the last successful dbm_grid_polygon_mask (dbm_grid_polygon_stats)
+  // What the op-level entry points (api_ops.hip) keep from call to call, made on first use on this context's device.
+  struct OpState {
+    // One inbox and one launch counter for both trunk ops: successive calls meet each other's granules, as the passes of a generator's
+    // workspace do.  The counter starts in the middle of the 20-bit range, so that a context crosses the wrap only where a caller
+    // asks for it (epoch0).
+    unsigned long long* trunk_inbox = nullptr;
+    int trunk_epoch = 0x80000;
+    WgradBatch wgrad_batch;                    // dbm_op_conv2d_wgrad_batch: the batch of the previous call ...
+    std::vector<dbm_wgrad_desc> wgrad_key;     // ... and the descriptors it was planned for
+  } op;
 };
 
 void dbm_comm_unique_id_impl(void* out128);  // comm.hip: ncclGetUniqueId
 // A persistent trunk kernel timed out: the layer-by-layer trunk path serves until iteration g_trunk_rearm_at (-1: for good);
 // g_step_serial counts the training iterations entered (api.hip: dbm_step_entry).
+// (These three and g_trunk_local_off (kernels.h) stay process-wide on purpose: a time-out on one context switches every context's trunk path.)
 extern bool g_trunk_fused_off;
 extern long g_step_serial, g_trunk_rearm_at;
 

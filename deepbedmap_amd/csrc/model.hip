@@ -47,6 +47,27 @@ void DevBuf::release() {
   n = 0;
 }
 
+// Everything the struct declares, on the context's device (the caller has set it and drained the streams: dbm_shutdown).  Every member
+// is checked, so that a context dbm_init gave up on half-way destructs cleanly.
+dbm_ctx::~dbm_ctx() {
+  for (void* p : {(void*)zeros, (void*)dev_err_flag, (void*)ssim_win[0], (void*)ssim_win[1], (void*)op.trunk_inbox})
+    if (p) (void)hipFree(p);
+  if (dev_err) (void)hipHostFree(dev_err);
+  for (hipEvent_t e : {ev_timer[0], ev_timer[1], ev_iter[0], ev_iter[1], ev_iter[2], ev_iter[3], ev_persist, ev_comm, ev_comm_done})
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : comm_ev_pool) (void)hipEventDestroy(e);
+  for (DevBuf* b : {&sync_buf, &loss_tmp, &track_tmp, &points_tmp, &tile_tmp, &resample_tmp}) b->release();
+  for (DevBuf& b : stage) b.release();
+  op.wgrad_batch.reset();
+  if (side) (void)hipStreamDestroy(side);
+  for (hipStream_t st : chain)
+    if (st) (void)hipStreamDestroy(st);
+  for (hipEvent_t e : ev_fork)
+    if (e) (void)hipEventDestroy(e);
+  if (ev_join) (void)hipEventDestroy(ev_join);
+  if (own_stream) (void)hipStreamDestroy(own_stream);
+}
+
 dbm_model::~dbm_model() {
   if (ctx)
     for (size_t i = 0; i < ctx->models.size(); ++i)
@@ -310,7 +331,7 @@ ConvDesc dbm_model::fwd_desc(const IgLayer& L, const float* x, long xsn, int Hin
   ConvDesc d;
   memset(&d, 0, sizeof(d));
   const int Hl = Hin << ups, Wl = Win << ups;
-  const int OH = (Hl + 2 * L.pad - L.Kview) / L.stride + 1, OW = (Wl + 2 * L.pad - L.Kview) / L.stride + 1;
+  const int OH = conv_out_extent(Hl, L.Kview, L.stride, L.pad), OW = conv_out_extent(Wl, L.Kview, L.stride, L.pad);
   d.x = x; d.xsn = xsn; d.xsc = Hin * Win; d.Cin = L.CinP; d.Hin = Hin; d.Win = Win; d.ups = ups;
   d.N = N; d.OHl = OH; d.OWl = OW; d.sin = L.stride;
   d.T = L.Kview * L.Kview;
@@ -346,7 +367,7 @@ void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_
     if (reps) reps->push_back(r);
   };
   DBM_CHECK(!bwd_dirty, "run_dgrad: the data-gradient weight images are stale (ensure_packed_bwd was not called)");
-  const int OH = (Hin_fwd + 2 * L.pad - L.Kview) / L.stride + 1, OW = (Win_fwd + 2 * L.pad - L.Kview) / L.stride + 1;
+  const int OH = conv_out_extent(Hin_fwd, L.Kview, L.stride, L.pad), OW = conv_out_extent(Win_fwd, L.Kview, L.stride, L.pad);
   base.xsc = OH * OW; base.Cin = L.OP; base.Hin = OH; base.Win = OW; base.ups = 0;
   static const int cin_live_env = getenv("DBM_CIN_LIVE") ? atoi(getenv("DBM_CIN_LIVE")) : 1;   // (A/B switch)
   base.cin_live = (cin_live_env && L.O < L.OP) ? ((L.O + 7) & ~7) : 0;   // (gradient channels past the layer's O outputs are zero padding)
@@ -392,15 +413,8 @@ void dbm_model::run_dgrad(const IgLayer& L, ConvDesc base, int Hin_fwd, int Win_
 
 WgradDesc dbm_model::wgrad_desc(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, const float* dy, long dysn, int OH,
                                 int OW, int N, float scale) const {
-  WgradDesc w;
-  memset(&w, 0, sizeof(w));
-  w.x = x; w.xsn = xsn; w.xsc = Hin * Win; w.Cin = L.Cview; w.Hin = Hin; w.Win = Win; w.ups = ups;
-  w.dy = dy; w.dysn = dysn; w.dysc = OH * OW; w.Cout = L.O; w.OH = OH; w.OW = OW;
-  w.KH = L.Kview; w.KW = L.Kview; w.stride = L.stride; w.pad = L.Kview == 1 ? 0 : L.pad;
-  w.N = N; w.scale = scale;
-  w.gW = G(L.wi);
-  w.gb = L.bi >= 0 ? G(L.bi) : nullptr;
-  return w;
+  return ::wgrad_desc(x, xsn, L.Cview, Hin, Win, ups, dy, dysn, L.O, OH, OW, L.Kview, L.stride, L.Kview == 1 ? 0 : L.pad, N, scale, G(L.wi),
+                      L.bi >= 0 ? G(L.bi) : nullptr);
 }
 
 void dbm_model::run_wgrad(const IgLayer& L, const float* x, long xsn, int Hin, int Win, int ups, const float* dy,

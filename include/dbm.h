@@ -771,8 +771,8 @@ int dbm_op_conv2d_wgrad_batch(dbm_ctx* ctx, const dbm_wgrad_desc* descs, int L, 
  *   w, b: tables of nrdb * 5 pointers, dense block j's conv_layer(k + 1) at [5 j + k]: (32, 64 + 32 k, 3, 3) / (32), conv_layer5 (64, 192, 3, 3) / (64)
  *   imgs_per_launch: 1 .. the context's images per persistent launch (min(64, CUs / 3)); launch c covers images [c * imgs_per_launch, ...)
  *   only_launch: >= 0 runs that chunk's launch(es) alone (the other images are not touched), -1 all
- *   epoch0: the first launch's epoch, the following launches count up from it (the kernels use its low 20 bits); negative: the op's own
- *           counter goes on.  The two ops share ONE inbox of trunk_fused_inbox_bytes(64) bytes (zeroed once per process) and that counter,
+ *   epoch0: the first launch's epoch, the following launches count up from it (the kernels use its low 20 bits); negative: the context's
+ *           counter goes on.  The two ops share ONE inbox of trunk_fused_inbox_bytes(64) bytes (zeroed once per context) and that counter,
  *           as a generator's workspace does.
  *   agent_stores: 1 = exchange stores at agent scope only (what the kernels do after a time-out), 0 = same-XCD stores may stay in the L2
  * report (HOST, report_cap ints, may be NULL): report[0] = launches made, then per launch {form, workgroups}: form 0 = 27-position tiles,

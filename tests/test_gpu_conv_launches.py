@@ -611,6 +611,11 @@ WGRAD_ROWS = [
      None, "fallback", "alignment fallbacks: x one float off, dysn % 4 != 0 (33-channel stride on 5 x 5), a misaligned 1x1"),
 ]
 WGRAD_IDS = [r[0] for r in WGRAD_ROWS]
+EXTRA_WGRAD_ROWS = {}   # id -> descriptors of rows that other modules run through wgrad_case / WgradRun (not parametrised here)
+
+
+def wgrad_descs(rid):
+    return EXTRA_WGRAD_ROWS[rid] if rid in EXTRA_WGRAD_ROWS else WGRAD_ROWS[WGRAD_IDS.index(rid)][1]
 # what build() is expected to choose -- WGRAD_EXPECT_BEGIN
 WGRAD_EXPECT = {   # row: [(category, S in deterministic mode, S otherwise)] per descriptor
     "cat0": [(0, 1, 1), (0, 1, 1), (0, 1, 1)],
@@ -634,7 +639,7 @@ WGRAD_EXPECT = {   # row: [(category, S in deterministic mode, S otherwise)] per
 @functools.lru_cache(maxsize=None)
 def wgrad_case(rid):
     """Host buffers, float64 references and masses per gradient, the float32 oracle's deviations; shared, never modified"""
-    descs = WGRAD_ROWS[WGRAD_IDS.index(rid)][1]
+    descs = wgrad_descs(rid)
     rs = np.random.RandomState([zlib.crc32(rid.encode())])
     B, ops_, owners = {}, [], []
     for i, q in enumerate(descs):
@@ -696,11 +701,12 @@ def wgrad_tolerances():
 
 
 class WgradRun:
-    """The device side of a row: operands uploaded once; call(cleared) re-fills the gradients and runs the op"""
+    """The device side of a row: operands uploaded once; call(cleared) re-fills the gradients and runs the op (on ctx instead of the
+    default context, where one is given)"""
 
-    def __init__(self, dbm, rid):
-        self.d, self._lib, self.ctx = dbm
-        self.descs = WGRAD_ROWS[WGRAD_IDS.index(rid)][1]
+    def __init__(self, dbm, rid, ctx=None):
+        self.d, self._lib, self.ctx = dbm if ctx is None else (dbm[0], dbm[1], ctx)
+        self.descs = wgrad_descs(rid)
         self.case = wgrad_case(rid)
         d, case = self.d, self.case
         self.dev, self.ptr = {}, {}

@@ -227,9 +227,10 @@ def read_report(report):
     return [(report[1 + 2 * i], report[2 + 2 * i]) for i in range(report[0])]
 
 
-def run_forward(dbm, P, rs, form, keep, imgs=None, ipl=None, only=-1, epoch0=-1, agent=0):
-    """One dbm_op_trunk_forward call on sentinel-filled buffers: (cat list, out or None), every buffer (N, 192, 9, 9)"""
-    _, _lib, ctx = dbm
+def run_forward(dbm, P, rs, form, keep, imgs=None, ipl=None, only=-1, epoch0=-1, agent=0, ctx=None):
+    """One dbm_op_trunk_forward call on sentinel-filled buffers: (cat list, out or None), every buffer (N, 192, 9, 9); ctx: the context
+    to run on instead of the default one"""
+    _, _lib, ctx = dbm if ctx is None else (dbm[0], dbm[1], ctx)
     x = P.x if imgs is None else P.x[imgs]
     N = len(x)
     ipl = N if ipl is None else ipl
