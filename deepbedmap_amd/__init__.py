@@ -23,7 +23,8 @@ from .gridding import mask_far_from_data, tension_surface, to_pixel_registration
 from .ascii_table import TextReader, ascii_to_xyz, parse_pipeline, read_text_table  # noqa: F401
 from .geotiff import (build_overviews, canvas_to_int16, open_geotiff, overview_pyramid, overview_shapes, read_geotiff,  # noqa: F401
                       read_geotiff_resident, save_array_to_grid, write_geotiff_resident)
-from .netcdf import NetcdfVariable, open_netcdf, read_netcdf, read_netcdf_resident  # noqa: F401
+from .netcdf import (NetcdfVariable, open_netcdf, read_netcdf, read_netcdf_resident, save_grid_to_netcdf,  # noqa: F401
+                     write_netcdf_resident)
 from .tiling import Raster, fill_gaps, get_deepbedmap_model_inputs, get_window_bounds, selective_tile, tile_training_set  # noqa: F401
 from .polygons import (Polygons, mask_outside, polygon_mask, read_polygons, read_tiles_geojson, select_tiles,  # noqa: F401
                        tiles_to_geojson)

@@ -100,6 +100,7 @@ SIGNATURES = {
     "dbm_lzw_encode_tiles": [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int],
     "dbm_lzw_decode": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
     "dbm_inflate": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "dbm_deflate_encode_blocks": [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int],
     "dbm_debug_inject_timeout": [C.c_void_p],
     "dbm_debug_inject_timeout_async": [C.c_void_p],
     "dbm_check_timeout": [C.c_void_p],
@@ -158,6 +159,8 @@ SIGNATURES = {
                          C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_long, C.c_long],
     "dbm_tiff_encode": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int,
                         C.c_void_p, C.c_size_t, C.c_void_p],
+    "dbm_chunk_encode": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p,
+                         C.c_size_t, C.c_void_p],
     "dbm_grid_overviews": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p],
     "dbm_grid_rescale": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "dbm_grid_rolling_std": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_void_p],
@@ -215,7 +218,8 @@ class DbmError(RuntimeError):
     # run -- fatal, the replicas have diverged.  9 (dbm_adam_update only): the gradients about to be applied come from a
     # void pass; nothing was applied -- repeat forward + backward, then update.  10 (dbm_grid_tension_surface only): the solve did not
     # converge within max_iter; the output holds the last iterate.  11 (dbm_tiff_decode, dbm_chunk_decode): a block's LZW or deflate stream is malformed.
-    # 12 (dbm_tiff_encode only): a block's LZW stream did not fit its slot (the device encoder's guard; the message names the block).
+    # 12 (dbm_tiff_encode, dbm_chunk_encode): a block's LZW or deflate stream did not fit its slot (the device encoders' guard; the
+    # message names the block).
     code = None
 
 

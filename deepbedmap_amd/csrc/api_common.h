@@ -1,6 +1,6 @@
 // What the extern "C" translation units of libdbm.so share: the exception boundary and the few helpers their entry points have in
 // common.  api.hip holds the training surface (contexts, models, losses, the optimizer, the fused steps), api_data.hip the
-// data-preparation surface (dbm_grid_*, dbm_points_*, dbm_text_*, dbm_tiff_*, dbm_chunk_decode), api_ops.hip the op-level one (dbm_op_*).
+// data-preparation surface (dbm_grid_*, dbm_points_*, dbm_text_*, dbm_tiff_*, dbm_chunk_*), api_ops.hip the op-level one (dbm_op_*).
 #pragma once
 #include "model.h"
 #include <cmath>

@@ -324,6 +324,42 @@ int dbm_chunk_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_byte
   DBM_API_END
 }
 
+// ---- what the block encoders share (dbm_tiff_encode, dbm_chunk_encode): sizes and status words down, the streams packed, one download ----
+// words (ENCODE_WORDS bytes per block): the encoder's {size, status word} (8 bytes per block), then the packer's {offset, size} (16).
+// encoded: the streams lie in slots of slot_cap bytes and their sizes come from the device (a status word, a size of 0 or one beyond
+// the slot: status 12, `codec` names the stream); else table[2 b + 1] holds the sizes already.  The streams go to out_host one behind
+// the other, each at the next even offset; the stream is drained before the call's workspace goes.
+constexpr size_t ENCODE_WORDS = 24;
+static void pack_streams(dbm_ctx* ctx, const std::string& who, const char* codec, long first, size_t nb, bool encoded, uint32_t* words,
+                         const uint8_t* src, size_t src_stride, size_t slot_cap, std::vector<unsigned long long>& table, void* out_host,
+                         size_t out_capacity, size_t* sizes_host) {
+  if (encoded) {
+    std::vector<uint32_t> result(2 * nb);
+    DBM_HIP(hipMemcpyAsync(result.data(), words, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t b = 0; b < nb; ++b) {
+      if (result[2 * b + 1] != 0 || result[2 * b] == 0 || result[2 * b] > slot_cap)
+        throw DbmError(12, who + ": block " + std::to_string(first + (long)b) + ": its " + codec + " stream does not fit the slot of " +
+                               std::to_string(slot_cap) + " bytes; nothing of this call was written");
+      table[2 * b + 1] = result[2 * b];
+    }
+  }
+  size_t total = 0;   // even-aligned offsets: TIFF wants its blocks on word boundaries
+  for (size_t b = 0; b < nb; ++b) {
+    table[2 * b] = total;
+    total += (size_t)((table[2 * b + 1] + 1ull) & ~1ull);
+  }
+  DBM_CHECK(total <= out_capacity, who + ": the streams outgrow the output");   // (implied by the worst-case check)
+  ScopedBuf packed;
+  uint8_t* packed_dev = packed.as<uint8_t>(total + 16);
+  unsigned long long* table_dev = (unsigned long long*)((uint8_t*)words + nb * 8);
+  DBM_HIP(hipMemcpyAsync(table_dev, table.data(), nb * 16, hipMemcpyHostToDevice, ctx->stream));
+  launch_tiff_pack(src, src_stride, table_dev, (int)nb, packed_dev, ctx->stream);
+  DBM_HIP(hipMemcpyAsync(out_host, packed_dev, total, hipMemcpyDeviceToHost, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
+  for (size_t b = 0; b < nb; ++b) sizes_host[b] = (size_t)table[2 * b + 1];
+}
+
 // ---- a float32 plane -> GeoTIFF blocks (tiff_encode.hip) ----
 int dbm_tiff_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sample_type, int block_h, int block_w, int tiled, int predictor,
                     int compression, long first, int n_blocks, void* out_host, size_t out_capacity, size_t* sizes_host) {
@@ -359,26 +395,15 @@ int dbm_tiff_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sa
   a.first = first; a.blocks_x = blocks_x; a.n_blocks = n_blocks;
   a.raw_stride = (long)((block_bytes + 15) / 16 * 16);
   a.slot_cap = slot_cap;
-  ScopedBuf raw, slots, words, packed;   // this call's own, released on every path
+  ScopedBuf raw, slots, words;   // this call's own, released on every path
   const size_t nb = (size_t)n_blocks;
   a.raw = raw.as<uint8_t>(nb * (size_t)a.raw_stride);
-  // per block: the encoder's {size, status word} (8 bytes), then the packer's {offset, size} (16 bytes)
-  a.result = (uint32_t*)words.as<uint8_t>(nb * 24);
-  unsigned long long* table_dev = (unsigned long long*)((uint8_t*)words.p + nb * 8);
+  a.result = (uint32_t*)words.as<uint8_t>(nb * ENCODE_WORDS);
   launch_tiff_blocks(a, ctx->stream);
   std::vector<unsigned long long> table(2 * nb);
   if (lzw) {
     a.slots = slots.as<uint8_t>(nb * slot_cap);
     launch_tiff_lzw_encode(a, ctx->stream);
-    std::vector<uint32_t> result(2 * nb);
-    DBM_HIP(hipMemcpyAsync(result.data(), a.result, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
-    DBM_HIP(hipStreamSynchronize(ctx->stream));
-    for (size_t b = 0; b < nb; ++b) {
-      if (result[2 * b + 1] != 0 || result[2 * b] == 0 || result[2 * b] > slot_cap)
-        throw DbmError(12, "dbm_tiff_encode: block " + std::to_string(first + (long)b) + ": its LZW stream does not fit the slot of " +
-                               std::to_string(slot_cap) + " bytes; nothing of this call was written");
-      table[2 * b + 1] = result[2 * b];
-    }
   } else {
     a.slots = nullptr;
     for (size_t b = 0; b < nb; ++b) {
@@ -387,18 +412,62 @@ int dbm_tiff_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sa
       table[2 * b + 1] = (unsigned long long)rows * (unsigned long long)block_w * (unsigned long long)bytes;
     }
   }
-  size_t total = 0;   // even-aligned offsets: TIFF wants its blocks on word boundaries
-  for (size_t b = 0; b < nb; ++b) {
-    table[2 * b] = total;
-    total += (size_t)((table[2 * b + 1] + 1ull) & ~1ull);
+  pack_streams(ctx, "dbm_tiff_encode", "LZW", first, nb, lzw, a.result, lzw ? a.slots : a.raw, lzw ? slot_cap : (size_t)a.raw_stride, slot_cap,
+               table, out_host, out_capacity, sizes_host);
+  DBM_API_END
+}
+
+// ---- a float32 plane -> netCDF-4 chunks (nc_chunks.hip; deflate through deflate_encode.hip) ----
+int dbm_chunk_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int chunk_h, int chunk_w, int row_step, int shuffle, int compression,
+                     long first, int n_blocks, void* out_host, size_t out_capacity, size_t* sizes_host) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_chunk_encode: NULL context");
+  DBM_CHECK(plane_dev != nullptr, "dbm_chunk_encode: NULL plane");
+  check_plane("dbm_chunk_encode", H, W, 1, "H W must stay below 2^31 samples", "empty plane");
+  DBM_CHECK(compression == 1 || compression == 8, "dbm_chunk_encode: compression must be 1 (the chunk's bytes) or 8 (zlib streams)");
+  DBM_CHECK(shuffle == 0 || shuffle == 1, "dbm_chunk_encode: shuffle must be 0 or 1");
+  DBM_CHECK(row_step == 1 || row_step == -1, "dbm_chunk_encode: the row step must be +1 or -1");
+  DBM_CHECK(chunk_h >= 1 && chunk_w >= 1 && chunk_h <= H && chunk_w <= W, "dbm_chunk_encode: the chunk sides must lie in 1..H and 1..W");
+  DBM_CHECK((long)chunk_h * chunk_w * 4 < (1L << 31), "dbm_chunk_encode: a chunk must hold less than 2^31 bytes");
+  const long chunks_x = (W + chunk_w - 1) / chunk_w, chunks_y = (H + chunk_h - 1) / chunk_h;
+  DBM_CHECK(first >= 0 && n_blocks >= 0 && first + (long)n_blocks <= chunks_x * chunks_y, "dbm_chunk_encode: the chunk range lies outside the image's " +
+                                                                                               std::to_string(chunks_x * chunks_y) + " chunks");
+  const unsigned groups = nc_chunks_groups_per_block(chunk_w, chunk_h);
+  DBM_CHECK((long)n_blocks * groups < (1L << 31), "dbm_chunk_encode: more than 2^31 workgroups in one call");
+  DBM_CHECK(n_blocks == 0 || (out_host != nullptr && sizes_host != nullptr), "dbm_chunk_encode: NULL output or sizes");
+  const bool deflate = compression == 8;
+  const size_t chunk_bytes = (size_t)chunk_h * (size_t)chunk_w * 4;
+  const size_t slot_cap = deflate_slot(chunk_bytes);
+  const size_t worst = deflate ? slot_cap : chunk_bytes;
+  DBM_CHECK(out_capacity / ((worst + 1) & ~(size_t)1) >= (size_t)n_blocks, "dbm_chunk_encode: the output holds " + std::to_string(out_capacity) +
+                                                                                " bytes, the worst case of " + std::to_string(n_blocks) + " chunks is " +
+                                                                                std::to_string((size_t)n_blocks * ((worst + 1) & ~(size_t)1)));
+  if (n_blocks == 0) return 0;
+  ChunkEncodeLaunch a;
+  a.plane = plane_dev;
+  a.H = H; a.W = W;
+  a.chunk_h = chunk_h; a.chunk_w = chunk_w;
+  a.row_step = row_step; a.shuffle = shuffle;
+  a.first = first; a.chunks_x = chunks_x; a.n_blocks = n_blocks;
+  a.groups_per_block = groups;
+  a.raw_stride = (long)((chunk_bytes + 15) / 16 * 16);
+  ScopedBuf raw, slots, words;   // this call's own, released on every path
+  const size_t nb = (size_t)n_blocks;
+  a.raw = raw.as<uint8_t>(nb * (size_t)a.raw_stride);
+  uint32_t* result = (uint32_t*)words.as<uint8_t>(nb * ENCODE_WORDS);
+  launch_nc_chunk_cut(a, ctx->stream);
+  std::vector<unsigned long long> table(2 * nb);
+  DeflateLaunch d;
+  d.raw = a.raw; d.raw_stride = (size_t)a.raw_stride; d.block_bytes = chunk_bytes; d.n_blocks = n_blocks;
+  d.slots = nullptr; d.slot_cap = slot_cap; d.result = result;
+  if (deflate) {
+    d.slots = slots.as<uint8_t>(nb * slot_cap);
+    launch_block_deflate(d, ctx->stream);
+  } else {
+    for (size_t b = 0; b < nb; ++b) table[2 * b + 1] = chunk_bytes;
   }
-  DBM_CHECK(total <= out_capacity, "dbm_tiff_encode: the streams outgrow the output");   // (implied by the worst-case check)
-  uint8_t* packed_dev = packed.as<uint8_t>(total + 16);
-  DBM_HIP(hipMemcpyAsync(table_dev, table.data(), nb * 16, hipMemcpyHostToDevice, ctx->stream));
-  launch_tiff_pack(lzw ? a.slots : a.raw, lzw ? slot_cap : (size_t)a.raw_stride, table_dev, n_blocks, packed_dev, ctx->stream);
-  DBM_HIP(hipMemcpyAsync(out_host, packed_dev, total, hipMemcpyDeviceToHost, ctx->stream));
-  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
-  for (size_t b = 0; b < nb; ++b) sizes_host[b] = (size_t)table[2 * b + 1];
+  pack_streams(ctx, "dbm_chunk_encode", "deflate", first, nb, deflate, result, deflate ? d.slots : a.raw, deflate ? slot_cap : (size_t)a.raw_stride,
+               slot_cap, table, out_host, out_capacity, sizes_host);
   DBM_API_END
 }
 

@@ -413,6 +413,37 @@ struct ChunkDecodeLaunch {
 unsigned nc_chunks_groups_per_block(int block_w, int block_h);
 void launch_nc_chunks(const ChunkDecodeLaunch& a, hipStream_t s);
 
+// A float32 plane -> the chunks of a netCDF-4 variable (nc_chunks.hip; dbm_chunk_encode): the inverse of the above.  The call's chunks
+// are first .. first + n_blocks - 1, row-major over chunks_x columns of chunks.  Chunk row r of the chunk whose first row is r0 is
+// plane row r0 + r (row_step +1) or H - 1 - (r0 + r) (row_step -1: a file whose y ascends); positions beyond the plane are zero
+// bytes; the values are the 32-bit patterns; shuffle: byte k of element i goes to k * n + i, n = chunk_h * chunk_w.
+struct ChunkEncodeLaunch {
+  const float* plane;
+  long H, W;
+  int chunk_h, chunk_w;
+  int row_step, shuffle;
+  long first, chunks_x;
+  int n_blocks;
+  unsigned groups_per_block;   // nc_chunks_groups_per_block(chunk_w, chunk_h)
+  uint8_t* raw;
+  long raw_stride;             // a multiple of 16, >= chunk_h * chunk_w * 4
+};
+void launch_nc_chunk_cut(const ChunkEncodeLaunch& a, hipStream_t s);
+
+// Blocks of bytes -> zlib streams with the fixed Huffman code (deflate_encode.hip), one wavefront per block: block b's block_bytes
+// bytes at raw + b * raw_stride into slots + b * slot_cap; result[2 b] = the stream's size, result[2 b + 1] = its status word (1: it
+// did not fit; size 0), as launch_tiff_lzw_encode.  deflate_slot: the room that always holds a stream (9 bits per byte at most).
+struct DeflateLaunch {
+  const uint8_t* raw;
+  size_t raw_stride, block_bytes;
+  int n_blocks;
+  uint8_t* slots;
+  size_t slot_cap;
+  uint32_t* result;
+};
+inline size_t deflate_slot(size_t n) { return n + n / 8 + 16; }
+void launch_block_deflate(const DeflateLaunch& a, hipStream_t s);
+
 // numpy.ndarray.astype(int16) of a float32 on x86-64: truncation to int32 (cvttss2si: NaN and |x| >= 2^31 give INT32_MIN), then the low
 // 16 bits -- NaN (the canvas frame that no tile covers), +-inf and out-of-range values become 0.  The one cast of f32_to_i16_kernel
 // (tiff_lzw.hip) and tiff_blocks_kernel (tiff_encode.hip).

@@ -103,7 +103,44 @@ __global__ __launch_bounds__(NC_THREADS) void nc_chunks_kernel(ChunkDecodeLaunch
   }
 }
 
+// The inverse (dbm_chunk_encode, stage (a)): chunk b of the call as the bytes an HDF5 file holds before deflate.  The same mapping as
+// above: the chunk is the flat run of its n elements, thread t of workgroup g takes elements (g * PASSES + p) * THREADS + t, so a
+// wavefront loads runs of min(chunk_w, 64) consecutive floats of a plane row and stores 64 consecutive bytes to each byte plane (64
+// consecutive words without shuffle).  The values are loaded as integers: NaN payloads and -0.0 pass unchanged.
+__global__ __launch_bounds__(NC_THREADS) void nc_chunk_cut_kernel(ChunkEncodeLaunch a) {
+  const long b = (long)(blockIdx.x / a.groups_per_block);
+  const unsigned g = blockIdx.x - (unsigned)b * a.groups_per_block;
+  const long index = a.first + b, cy = index / a.chunks_x, cx = index - cy * a.chunks_x;
+  const long r0 = cy * a.chunk_h, c0 = cx * a.chunk_w;
+  const unsigned cw = (unsigned)a.chunk_w;
+  const unsigned n = (unsigned)a.chunk_h * cw;       // n * 4 < 2^31 (checked by the caller)
+  uint8_t* out = a.raw + b * a.raw_stride;
+  const uint32_t* plane = (const uint32_t*)a.plane;
+#pragma unroll
+  for (int p = 0; p < NC_PASSES; ++p) {
+    const unsigned i = (g * NC_PASSES + p) * NC_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const unsigned r = i / cw, c = i - r * cw;
+    const long row = r0 + (long)r, col = c0 + (long)c;
+    uint32_t bits = 0u;   // the padding of an edge chunk
+    if (row < a.H && col < a.W) bits = plane[(a.row_step > 0 ? row : a.H - 1 - row) * a.W + col];
+    if (a.shuffle) {
+      for (int k = 0; k < 4; ++k) out[(size_t)k * n + i] = (uint8_t)(bits >> (8 * k));
+    } else {
+      ((uint32_t*)out)[i] = bits;   // (raw_stride is a multiple of 16: aligned)
+    }
+  }
+}
+
 }  // namespace
+
+void launch_nc_chunk_cut(const ChunkEncodeLaunch& a, hipStream_t s) {
+  const long groups = (long)a.n_blocks * a.groups_per_block;
+  if (groups <= 0) return;
+  DBM_CHECK(groups < (1L << 31), "dbm_chunk_encode: more than 2^31 workgroups in one call");
+  hipLaunchKernelGGL(nc_chunk_cut_kernel, dim3((unsigned)groups), dim3(NC_THREADS), 0, s, a);
+  DBM_HIP(hipGetLastError());
+}
 
 unsigned nc_chunks_groups_per_block(int block_w, int block_h) {
   const long n = (long)block_w * block_h, per = (long)NC_THREADS * NC_PASSES;

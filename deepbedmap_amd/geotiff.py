@@ -384,9 +384,9 @@ def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=
     as they are and no tag): every block row is differenced on the host before it is encoded, and Predictor (317) = 2 is written.
     overviews (int16 and float32 files): the number of reduced-resolution images written behind the first one, or "auto"
     (`overview_shapes`); each halves the one before (`overview_pyramid`: `gdaladdo -r average` in spirit) and is cut, differenced
-    and compressed as the first one is.  0: the file is byte for byte what it always was."""
-    if save_netcdf:
-        raise NotImplementedError("NetCDF output (xarray) is outside this framework; convert the GeoTIFF with GDAL")
+    and compressed as the first one is.  0: the file is byte for byte what it always was.
+    save_netcdf (data_prep.py:826-830; float32 files only): `{outfilepath}.nc` is written next to the .tif from the band as the TIFF
+    holds it (`netcdf.save_grid_to_netcdf`, its defaults); the .tif and the return value are what they are without it."""
     assert len(array.shape) == 3 and array.shape[0] == 1  # one band, CHW (data_prep.py:800-801)
     predictor = _predictor_of(predictor, "save_array_to_grid")
     dt = np.dtype(dtype if dtype is not None else getattr(array, "dtype", np.float32))
@@ -401,6 +401,8 @@ def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=
     H, W = band.shape
     if dt.kind not in "fiu":
         raise ValueError(f"unsupported dtype {dt}")
+    if save_netcdf and dt != np.dtype(np.float32):
+        raise ValueError(f"save_array_to_grid: dtype {dt.name}: save_netcdf writes float32 files only")
     epsg = _epsg_of(crs)
     comp = _compression_of(compression, "save_array_to_grid")
     if comp == 1:
@@ -416,7 +418,12 @@ def save_array_to_grid(outfilepath, window_bound, array, save_netcdf=False, crs=
         level = np.ascontiguousarray(level.astype(dt.newbyteorder("<"), copy=False))
         lh, lw, level_streams = _host_blocks(level, dt, comp, predictor, tiled, nthreads)
         images.append((_image_tags(h, w, dt, comp, predictor, tiled, lh, lw, None, nodataval, None, bigtiff, overview=True), level_streams))
-    return _write_container(f"{outfilepath}.tif", bigtiff, tags, streams, images)
+    written = _write_container(f"{outfilepath}.tif", bigtiff, tags, streams, images)
+    if save_netcdf:
+        from .netcdf import save_grid_to_netcdf
+
+        save_grid_to_netcdf(f"{outfilepath}.nc", window_bound, band, nthreads=nthreads)
+    return written
 
 
 def write_geotiff_resident(outfilepath, window_bound, array, dtype=None, nodataval=-2000, tiled=True, compression="lzw", predictor=1,

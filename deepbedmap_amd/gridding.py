@@ -302,13 +302,15 @@ def to_pixel_registration(grid, geometry, threshold=0.5, download=None, ctx=None
     return (out.get() if download else out), pixel
 
 
-def xyz_to_grid(xyz_data, region, spacing=250, tension=0.35, mask_cell_radius=3, download=True, ctx=None):
-    """xyz_to_grid (data_prep.py:381-441) without its `outfile`: block medians on the gridline grid of `spacing` over `region`
+def xyz_to_grid(xyz_data, region, spacing=250, tension=0.35, mask_cell_radius=3, download=True, ctx=None, outfile=None):
+    """xyz_to_grid (data_prep.py:381-441): block medians on the gridline grid of `spacing` over `region`
     (`blockmedian_grid`), the tension surface through them (`tension_surface`, its defaults for tol and max_iter), the distance mask
     (`mask_far_from_data`; mask_cell_radius=None skips it) and the pixel-registered resampling (`to_pixel_registration`).  Nothing
     leaves the device between the stages.  xyz_data: (n, 3) array, DataFrame with columns x, y, z, or DevicePoints.  Returns
-    (grid (H - 1, W - 1), GridGeometry, pixel-registered): a float32 array, or a DeviceArray with download=False.  Write it with
-    `save_array_to_grid`.  The result is this project's surface, not GMT's (DESIGN.md "Tension surface")."""
+    (grid (H - 1, W - 1), GridGeometry, pixel-registered): a float32 array, or a DeviceArray with download=False.  outfile
+    (data_prep.py:410-441): the result is also written as a netCDF-4 grid of that path, from the device and before any download
+    (`netcdf.write_netcdf_resident`: variable z, y ascending as GMT writes it, chunked, shuffled, deflated on the GPU); the return
+    value is the same.  The result is this project's surface, not GMT's (DESIGN.md "Tension surface")."""
     if mask_cell_radius is not None:
         mask_cell_radius = _mask_radius(mask_cell_radius)
     _surface_arguments(block_shape(region, spacing), tension, 1e-9, 20000)
@@ -316,4 +318,12 @@ def xyz_to_grid(xyz_data, region, spacing=250, tension=0.35, mask_cell_radius=3,
     surface, _ = tension_surface(medians, tension=tension, download=False)
     if mask_cell_radius is not None:
         mask_far_from_data(surface, medians, mask_cell_radius)
-    return to_pixel_registration(surface, geometry, download=download)
+    if outfile is None:
+        return to_pixel_registration(surface, geometry, download=download)
+    from .netcdf import write_netcdf_resident
+
+    grid, pixel = to_pixel_registration(surface, geometry, download=False)
+    H, W = grid.shape
+    west, north = pixel.x0 - pixel.dx / 2, pixel.y0 - pixel.dy / 2     # (dy < 0: the grid is north-up)
+    write_netcdf_resident(outfile, (west, north + H * pixel.dy, west + W * pixel.dx, north), grid, y_ascending=True)
+    return (grid.get() if download else grid), pixel

@@ -15,6 +15,11 @@ VALUE in its stored type becomes NaN (-0.0 equals 0.0; a NaN fill matches every 
 sample is float32(float64(v) * scale + offset), two rounded float64 operations and one rounding to float32; otherwise
 v.astype(float32) (float32 keeps its bits).  A chunk that was never written reads as the storage fill value through the same rule
 (0 if none is defined).  A file whose y ascends is returned north-up.
+
+Writing (reference data_prep.py:826-830: `save_array_to_grid(save_netcdf=True)`; data_prep.py:410-441: `xyz_to_grid(outfile=...)`;
+DESIGN.md 6m): `save_grid_to_netcdf` (host) and `write_netcdf_resident` (dbm_chunk_encode: chunks cut, shuffled and deflated on the
+GPU, only the stored bytes cross PCIe) write one float32 variable over y, x as a netCDF-4 file of the dialect above, byte for byte the
+same file from either; the second half of this module.
 """
 import dataclasses
 import os
@@ -708,14 +713,16 @@ def convert(raw, fill=None, scale=None, offset=None, mask_and_scale=True):
 
 
 def _coordinates(f, name, get):
-    """The values of the 1-D variable `name` as float64, or None if the file has none."""
+    """(the values of the 1-D variable `name` as float64, its attribute `actual_range` as (low, high) or None), or None if the file has
+    no such variable."""
     var = get(name, (1,))
     if not isinstance(var, NetcdfVariable):
         return None
     import zlib
 
     raw = _raw_plane(var, var.plan(None), lambda data, index: zlib.decompress(data))
-    return raw.reshape(-1).astype(np.float64)
+    span = np.asarray(var.attrs.get("actual_range", ()), dtype=np.float64).ravel()
+    return raw.reshape(-1).astype(np.float64), (span if span.size == 2 and np.isfinite(span).all() and span[1] > span[0] else None)
 
 
 def open_netcdf(path, variable=None, coords=("x", "y")):
@@ -793,6 +800,7 @@ def open_netcdf(path, variable=None, coords=("x", "y")):
     var.global_attrs = gattrs
     x, y = (_coordinates(f, c, get) for c in coords)
     if x is not None and y is not None:
+        (x, xspan), (y, yspan) = x, y
         H, W = var.shape
         if (x.size, y.size) != (W, H):
             raise ValueError(f"{path}: coordinates {coords[0]!r} ({x.size}) and {coords[1]!r} ({y.size}) do not match {variable!r} of shape {var.shape}")
@@ -800,6 +808,12 @@ def open_netcdf(path, variable=None, coords=("x", "y")):
         if node is not None and int(np.asarray(node).ravel()[0]) not in (0, 1):
             raise ValueError(f"{path}: root attribute node_offset = {node!r}: 0 (gridline) or 1 (pixel)")
         registration = "gridline" if node is not None and int(np.asarray(node).ravel()[0]) == 0 else "pixel"
+        # a single pixel has no spacing of its own: `actual_range`, the pixel's edges as GMT and this module's writers record them,
+        # gives one (a second node one pixel further: to the east, to the south)
+        if registration == "pixel" and x.size == 1 and xspan is not None:
+            x = np.array([x[0], x[0] + (xspan[1] - xspan[0])])
+        if registration == "pixel" and y.size == 1 and yspan is not None:
+            y = np.array([y[0], y[0] - (yspan[1] - yspan[0])])
         try:
             g = GridGeometry.from_coords(x, y, registration=registration)
         except ValueError as e:
@@ -882,3 +896,328 @@ def read_netcdf_resident(path, variable=None, window_bound=None, workspace_limit
                                     0.0 if offset is None else offset, devptr(out), H, W)
     out.written()
     return out, _info(var, plan)
+
+
+# ---- writing ----
+# The mirror of the readers above: netCDF-4 files of one float32 variable over the dimensions y, x (reference data_prep.py:826-830:
+# `save_array_to_grid(save_netcdf=True)`; data_prep.py:410-441: `xyz_to_grid(outfile=...)`), written without a library.  The dialect
+# is the one `open_netcdf` reads and libhdf5 writes with the low bound "earliest": superblock 0, version-1 object headers, the root
+# group by symbol table, layout 3, a version-1 B-tree over the chunks.  The file is determined by the arguments: no timestamps.
+_GROUP_LEAF_K, _GROUP_INTERNAL_K, _CHUNK_K = 4, 16, 32    # the superblock's two K; version 0 has no field for the third: 32
+_FILL_BITS = 0x7FC00000                                   # _FillValue and the storage fill value: the quiet NaN
+
+
+def deflate_slot(nbytes):
+    """The bytes that always hold the stream of `nbytes` input bytes: no input byte costs more than 9 bits."""
+    return nbytes + nbytes // 8 + 16
+
+
+def deflate_encode_blocks(blocks, nthreads=None):
+    """blocks: (n, block_bytes) uint8 -> list of bytes objects: one zlib stream each, fixed Huffman code (dbm_deflate_encode_blocks: the
+    device encoder's loop on host threads)."""
+    import ctypes as C
+
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+    nb, nbytes = blocks.shape
+    stride = deflate_slot(nbytes)
+    out = np.empty((nb, stride), dtype=np.uint8)
+    sizes = (C.c_size_t * max(nb, 1))()
+    rc = _lib.lib().dbm_deflate_encode_blocks(blocks.ctypes.data_as(C.c_void_p), nbytes, nb, out.ctypes.data_as(C.c_void_p), stride, sizes,
+                                              int(nthreads or min(16, os.cpu_count() or 1)))
+    if rc != 0:
+        raise _lib.DbmError(f"dbm_deflate_encode_blocks failed ({rc})")
+    return [out[i, :sizes[i]].tobytes() for i in range(nb)]
+
+
+def _pad8(data):
+    return data + b"\0" * (-len(data) % 8)
+
+
+def _message(typ, body, flags=0):
+    body = _pad8(body)
+    return struct.pack("<HHB3x", typ, len(body), flags) + body
+
+
+def _object_header(messages):
+    body = b"".join(messages)
+    return struct.pack("<BxHII4x", 1, len(messages), 1, len(body)) + body
+
+
+def _float_type(size):
+    if size == 4:
+        return struct.pack("<BBBBIHHBBBBI", 0x11, 0x20, 31, 0, 4, 0, 32, 23, 8, 0, 23, 127)
+    return struct.pack("<BBBBIHHBBBBI", 0x11, 0x20, 63, 0, 8, 0, 64, 52, 11, 0, 52, 1023)
+
+
+_INT32_TYPE = struct.pack("<BBBBIHH", 0x10, 0x08, 0, 0, 4, 0, 32)
+
+
+def _dataspace(shape):
+    return struct.pack("<BBBx4x", 1, len(shape), 0) + b"".join(struct.pack("<Q", s) for s in shape)
+
+
+def _attribute_message(name, datatype, shape, data):
+    name = name.encode() + b"\0"
+    space = _dataspace(shape)
+    return _message(0x0C, struct.pack("<BxHHH", 1, len(name), len(datatype), len(space)) + _pad8(name) + _pad8(datatype) + _pad8(space) + data)
+
+
+def _text_attribute(name, text):
+    data = text.encode() + b"\0"
+    return _attribute_message(name, struct.pack("<BBBBI", 0x13, 0, 0, 0, len(data)), (), data)
+
+
+def _chunk_btree(entries, ch, cw, base):
+    """The version-1 B-tree (node type 1) over `entries` = [(bytes, address, row offset, column offset)] in chunk order, built level by
+    level with sibling links, 2K entries per node; its nodes lie from address `base` on.  Returns (the nodes' bytes, the root's address)."""
+    key = lambda nbytes, roff, coff, last=0: struct.pack("<IIQQQ", nbytes, 0, roff, coff, last)   # noqa: E731  (filter mask 0)
+    per, node_bytes = 2 * _CHUNK_K, 24 + (2 * _CHUNK_K + 1) * 32 + 2 * _CHUNK_K * 8
+    end_key = key(0, entries[-1][2] + ch, entries[-1][3] + cw, 4)     # one chunk past the last one in every dimension
+    out, level, at = [], 0, base
+    while True:
+        groups = [entries[k:k + per] for k in range(0, len(entries), per)]
+        address = [at + k * node_bytes for k in range(len(groups))]
+        for k, group in enumerate(groups):
+            left = address[k - 1] if k > 0 else _UNDEF
+            right = address[k + 1] if k + 1 < len(groups) else _UNDEF
+            node = b"TREE" + struct.pack("<BBHQQ", 1, level, len(group), left, right)
+            node += b"".join(key(e[0], e[2], e[3]) + struct.pack("<Q", e[1]) for e in group)
+            node += key(groups[k + 1][0][0], groups[k + 1][0][2], groups[k + 1][0][3]) if k + 1 < len(groups) else end_key
+            out.append(node + b"\0" * (node_bytes - len(node)))
+        at += len(groups) * node_bytes
+        if len(groups) == 1:
+            return b"".join(out), address[0]
+        entries = [(g[0][0], a, g[0][2], g[0][3]) for g, a in zip(groups, address)]    # a child's first key, and the child
+        level += 1
+
+
+def _write_container(path, window_bound, H, W, variable, ch, cw, shuffle, deflate, y_ascending, streams):
+    """The file around the chunk `streams` (an iterable of bytes-like objects in row-major chunk order, consumed one at a time)."""
+    g = GridGeometry.from_bounds(window_bound, H, W)
+    minx, miny, maxx, maxy = (float(v) for v in window_bound)
+    x = g.x0 + np.arange(W, dtype=np.float64) * g.dx
+    y = g.y0 + np.arange(H, dtype=np.float64) * g.dy
+    if y_ascending:
+        y = y[::-1]
+    coords = {"x": (np.ascontiguousarray(x, dtype="<f8"), 0, (minx, maxx)), "y": (np.ascontiguousarray(y, dtype="<f8"), 1, (miny, maxy))}
+    names = sorted(["x", "y", variable])
+    # the local heap's data segment: the empty name at 0, then the names
+    heap_data, name_at = b"\0" * 8, {}
+    for n in names:
+        name_at[n] = len(heap_data)
+        heap_data += _pad8(n.encode() + b"\0")
+    f64, f32 = _float_type(8), _float_type(4)
+
+    def coordinate_header(name, address):
+        values, dimid, span = coords[name]
+        return _object_header([
+            _message(0x01, _dataspace((values.size,))),
+            _message(0x03, f64, 1),
+            _message(0x05, struct.pack("<BBBB", 2, 1, 2, 0), 1),                      # fill value: allocated early, never defined
+            _message(0x08, struct.pack("<BBQQ", 3, 1, address, values.nbytes)),        # contiguous
+            _text_attribute("CLASS", "DIMENSION_SCALE"),
+            _text_attribute("NAME", name),
+            _attribute_message("_Netcdf4Dimid", _INT32_TYPE, (), struct.pack("<i", dimid)),
+            _attribute_message("actual_range", f64, (2,), struct.pack("<dd", *span)),
+        ])
+
+    def variable_header(btree):
+        filters = []
+        if shuffle:
+            filters.append(struct.pack("<HHHH", 2, 8, 1, 1) + b"shuffle\0" + struct.pack("<II", 4, 0))
+        if deflate:
+            filters.append(struct.pack("<HHHH", 1, 8, 1, 1) + b"deflate\0" + struct.pack("<II", 1, 0))
+        messages = [
+            _message(0x01, _dataspace((H, W))),
+            _message(0x03, f32, 1),
+            _message(0x05, struct.pack("<BBBBII", 2, 3, 2, 1, 4, _FILL_BITS), 1),      # allocated incrementally, the fill value NaN
+        ]
+        if filters:
+            messages.append(_message(0x0B, struct.pack("<BB6x", 1, len(filters)) + b"".join(filters), 1))
+        messages += [
+            _message(0x08, struct.pack("<BBBQIII", 3, 2, 3, btree, ch, cw, 4)),       # chunked: a version-1 B-tree
+            _attribute_message("_FillValue", f32, (1,), struct.pack("<I", _FILL_BITS)),
+            _attribute_message("_Netcdf4Coordinates", _INT32_TYPE, (2,), struct.pack("<ii", coords["y"][1], coords["x"][1])),
+        ]
+        return _object_header(messages)
+
+    def root_header(btree, heap):
+        return _object_header([
+            _message(0x11, struct.pack("<QQ", btree, heap)),
+            _text_attribute("Conventions", "CF-1.7"),
+            _attribute_message("node_offset", _INT32_TYPE, (), struct.pack("<i", 1)),
+        ])
+
+    # addresses: superblock, root header, group B-tree, heap, symbol node, the three headers, the coordinates, the chunks, their B-tree
+    root_at = 96
+    btree_at = root_at + len(root_header(0, 0))
+    heap_at = btree_at + 24 + (2 * _GROUP_INTERNAL_K + 1) * 8 + 2 * _GROUP_INTERNAL_K * 8
+    heap_data_at = heap_at + 32
+    snod_at = heap_data_at + len(heap_data)
+    at = snod_at + 8 + 2 * _GROUP_LEAF_K * 40
+    header_at = {}
+    for n in names:
+        header_at[n] = at
+        at += len(variable_header(0)) if n == variable else len(coordinate_header(n, 0))
+    data_at = {}
+    for n in ("x", "y"):
+        data_at[n] = at
+        at += coords[n][0].nbytes
+    chunks_at = at
+
+    def head(btree, end):
+        superblock = _SIGNATURE + struct.pack("<BBBBBBBxHHI", 0, 0, 0, 0, 0, 8, 8, _GROUP_LEAF_K, _GROUP_INTERNAL_K, 0)
+        superblock += struct.pack("<QQQQ", 0, _UNDEF, end, _UNDEF)
+        superblock += struct.pack("<QQI4xQQ", 0, root_at, 1, btree_at, heap_at)        # the root group's symbol table entry
+        group = b"TREE" + struct.pack("<BBHQQ", 0, 0, 1, _UNDEF, _UNDEF) + struct.pack("<QQQ", 0, snod_at, name_at[names[-1]])
+        group += b"\0" * (heap_at - btree_at - len(group))
+        heap = b"HEAP" + struct.pack("<B3xQQQ", 0, len(heap_data), 1, heap_data_at)   # free-list head 1: no free block
+        snod = b"SNOD" + struct.pack("<BxH", 1, len(names))
+        snod += b"".join(struct.pack("<QQI4x16x", name_at[n], header_at[n], 0) for n in names)
+        snod += b"\0" * (8 + 2 * _GROUP_LEAF_K * 40 - len(snod))
+        headers = b"".join(variable_header(btree) if n == variable else coordinate_header(n, data_at[n]) for n in names)
+        out = superblock + root_header(btree_at, heap_at) + group + heap + heap_data + snod + headers + coords["x"][0].tobytes() + coords["y"][0].tobytes()
+        assert len(superblock) == 96 and len(out) == chunks_at
+        return out
+
+    nx = -(-W // cw)
+    entries = []
+    with open(path, "wb") as f:
+        f.write(b"\0" * chunks_at)
+        at = chunks_at
+        for k, stream in enumerate(streams):
+            pad = -at % 8
+            f.write(b"\0" * pad)
+            at += pad
+            f.write(stream)
+            entries.append((len(stream), at, (k // nx) * ch, (k % nx) * cw))
+            at += len(stream)
+        if len(entries) != -(-H // ch) * nx:
+            raise _lib.DbmError(f"{path}: {len(entries)} chunk streams for {-(-H // ch) * nx} chunks")
+        pad = -at % 8
+        nodes, root = _chunk_btree(entries, ch, cw, at + pad)
+        f.write(b"\0" * pad + nodes)
+        end = at + pad + len(nodes)
+        f.seek(0)
+        f.write(head(root, end))
+    return path
+
+
+def _write_arguments(who, window_bound, shape, dtype, variable, chunks, shuffle, compression):
+    """The checks the two writers share (every refusal names its argument): (H, W, chunk_h, chunk_w, deflate)."""
+    if np.dtype(dtype) != np.float32:
+        raise ValueError(f"{who}: array holds {np.dtype(dtype).name}: only float32 planes are written")
+    shape = tuple(shape)
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[0] == 1)) or shape[-2] < 1 or shape[-1] < 1:
+        raise ValueError(f"{who}: array must be (1, H, W) or (H, W) and not empty; got {shape}")
+    H, W = int(shape[-2]), int(shape[-1])
+    try:
+        bound = [float(v) for v in window_bound]
+    except (TypeError, ValueError):
+        bound = []
+    if len(bound) != 4 or not all(np.isfinite(bound)) or bound[2] <= bound[0] or bound[3] <= bound[1]:
+        raise ValueError(f"{who}: window_bound {window_bound!r}: (minx, miny, maxx, maxy), finite, maxx > minx and maxy > miny")
+    if not isinstance(variable, str) or not variable or variable in ("x", "y") or not variable.isascii() or "/" in variable:
+        raise ValueError(f"{who}: variable {variable!r}: an ASCII name other than 'x' and 'y'")
+    try:
+        ch, cw = (int(c) for c in chunks)
+        whole = (ch, cw) == tuple(chunks)
+    except (TypeError, ValueError):
+        ch = cw = 0
+        whole = False
+    if not whole or ch < 1 or cw < 1:
+        raise ValueError(f"{who}: chunks {chunks!r}: two chunk sides of at least 1")
+    ch, cw = min(ch, H), min(cw, W)
+    if ch * cw * 4 >= 1 << 31:
+        raise ValueError(f"{who}: chunks of {ch} x {cw} samples hold 2^31 bytes or more")
+    text = compression.lower() if isinstance(compression, str) else None
+    if text not in ("deflate", "none"):
+        raise ValueError(f"{who}: unsupported compression {compression!r} (\"deflate\", \"none\")")
+    if not isinstance(shuffle, (bool, np.bool_)):
+        raise ValueError(f"{who}: shuffle {shuffle!r}: True or False")
+    return H, W, ch, cw, text == "deflate"
+
+
+def chunk_bytes_of(band, ch, cw, shuffle, y_ascending):
+    """The NumPy statement of dbm_chunk_encode's stage (a): the (H, W) float32 `band` as (chunks, ch * cw * 4) uint8, row-major chunk
+    order, the file's rows reversed for y_ascending, edge chunks zero padded, the 32-bit patterns little endian, shuffled per chunk."""
+    bits = np.ascontiguousarray(band, dtype=np.float32).view(np.uint32)
+    if y_ascending:
+        bits = bits[::-1]
+    H, W = bits.shape
+    ny, nx = -(-H // ch), -(-W // cw)
+    padded = np.zeros((ny * ch, nx * cw), dtype="<u4")
+    padded[:H, :W] = bits
+    raw = np.ascontiguousarray(padded.reshape(ny, ch, nx, cw).transpose(0, 2, 1, 3)).view(np.uint8).reshape(ny * nx, ch * cw, 4)
+    if shuffle:
+        raw = raw.transpose(0, 2, 1)
+    return np.ascontiguousarray(raw).reshape(ny * nx, ch * cw * 4)
+
+
+def save_grid_to_netcdf(path, window_bound, array, variable="z", chunks=(256, 256), shuffle=True, compression="deflate", y_ascending=False,
+                        nthreads=None):
+    """Writes the float32 (H, W) or (1, H, W) NumPy `array` as the netCDF-4 file `path` and returns the path: the host writer.  The
+    variable `variable`(y, x) is chunked (`chunks`, clipped to the plane), shuffled and deflated as asked (compression "deflate" or
+    "none"); x and y hold the pixel centres of `window_bound` = (minx, miny, maxx, maxy), the root attribute node_offset = 1 says pixel
+    registration, _FillValue is NaN.  y_ascending: the file's rows run south to north (GMT's order); the readers return it north-up.
+    NumPy cuts and shuffles, dbm_deflate_encode_blocks encodes on `nthreads` host threads.  `write_netcdf_resident` writes the same
+    file, byte for byte, from a plane in HBM."""
+    who = "save_grid_to_netcdf"
+    if not isinstance(array, np.ndarray):
+        raise ValueError(f"{who}: array must be a float32 NumPy array, not {type(array).__name__} (a DeviceArray is written by write_netcdf_resident)")
+    H, W, ch, cw, deflate = _write_arguments(who, window_bound, array.shape, array.dtype, variable, chunks, shuffle, compression)
+    raw = chunk_bytes_of(array.reshape(H, W), ch, cw, bool(shuffle), bool(y_ascending))
+    streams = deflate_encode_blocks(raw, nthreads) if deflate else (r.tobytes() for r in raw)
+    return _write_container(os.fspath(path), window_bound, H, W, variable, ch, cw, bool(shuffle), deflate, bool(y_ascending), streams)
+
+
+def write_netcdf_resident(path, window_bound, array, variable="z", chunks=(256, 256), shuffle=True, compression="deflate", y_ascending=False,
+                          workspace_limit=None):
+    """The mirror of `read_netcdf_resident`: writes the netCDF-4 file `path` from a plane that lives in HBM and returns the path.
+    Cutting the chunks, the row order, the shuffle and deflate (one wavefront per chunk) run on the GPU (dbm_chunk_encode); only the
+    stored bytes cross PCIe.  The file is byte for byte the one `save_grid_to_netcdf` writes from the downloaded plane with the same
+    arguments.  array: a float32 DeviceArray of shape (1, H, W) or (H, W), or a resident Raster.  workspace_limit:
+    bytes of raw chunks plus stream slots per batch (default 1 GiB; one chunk always goes through).  Anything else raises a
+    ValueError that names the argument, before any device work."""
+    who = "write_netcdf_resident"
+    from .block_reads import WORKSPACE_DEFAULT
+    from .tiling import Raster
+
+    if isinstance(array, Raster):
+        if array._dev is None:
+            raise ValueError(f"{who}: array: the Raster is not resident (a NumPy raster is written by save_grid_to_netcdf)")
+        array = array._dev
+    if not isinstance(array, DeviceArray):
+        raise ValueError(f"{who}: array must be a float32 DeviceArray or a resident Raster, not {type(array).__name__} "
+                         "(a NumPy array is written by save_grid_to_netcdf)")
+    H, W, ch, cw, deflate = _write_arguments(who, window_bound, array.shape, array.dtype, variable, chunks, shuffle, compression)
+    if workspace_limit is None:
+        workspace_limit = WORKSPACE_DEFAULT
+    try:
+        workspace_limit = int(workspace_limit)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: workspace_limit {workspace_limit!r} is not a number of bytes") from None
+    if workspace_limit < 1:
+        raise ValueError(f"{who}: workspace_limit must be positive")
+    ctx = array.ctx
+    chunk_bytes = ch * cw * 4
+    nchunks = -(-H // ch) * -(-W // cw)
+    worst = deflate_slot(chunk_bytes) if deflate else chunk_bytes      # a chunk's bytes in the download, before rounding up to even
+    groups = -(-ch * cw // 1024)                                       # workgroups per chunk of the cutting kernel
+    per_batch = max(1, min(workspace_limit // (chunk_bytes + (worst if deflate else 0)), ((1 << 31) - 1) // groups, nchunks))
+
+    def streams():
+        out = np.empty(per_batch * ((worst + 1) & ~1), dtype=np.uint8)
+        sizes = np.zeros(per_batch, dtype=np.uintp)
+        view = memoryview(out)
+        for first in range(0, nchunks, per_batch):
+            n = min(per_batch, nchunks - first)
+            ctx.call("dbm_chunk_encode", devptr(array), H, W, ch, cw, -1 if y_ascending else 1, 1 if shuffle else 0, 8 if deflate else 1,
+                     first, n, devptr(out), out.size, devptr(sizes))
+            pos = 0
+            for k in range(n):
+                size = int(sizes[k])
+                yield view[pos:pos + size]
+                pos += (size + 1) & ~1
+
+    return _write_container(os.fspath(path), window_bound, H, W, variable, ch, cw, bool(shuffle), deflate, bool(y_ascending), streams())

@@ -22,8 +22,8 @@
  *     the gradients and repeats forward + backward before updating (the step entry points clear them themselves).  Status 8:
  *     the same in a data-parallel run, where a local retry cannot keep the replicas identical -- fatal, abort the job.  Status 10
  *     (dbm_grid_tension_surface only): the solve did not converge within max_iter; the output holds the last iterate.  Status 11
- *     (dbm_tiff_decode only): a block's LZW or deflate stream is malformed.  Status 12 (dbm_tiff_encode only): a block's LZW stream did not fit
- *     its slot (the guard of the device encoder; it cannot occur with the slot the call allocates);
+ *     (dbm_tiff_decode only): a block's LZW or deflate stream is malformed.  Status 12 (dbm_tiff_encode, dbm_chunk_encode): a block's LZW or deflate stream
+ *     did not fit its slot (the guard of the device encoders; it cannot occur with the slot the calls allocate);
  *   - tensors are NCHW float32, C-contiguous; weights OIHW, exactly the arrays stored by
  *     chainer.serializers.save_npz (key layout: SURVEY.md Appendix B);
  *   - pointers are HOST pointers unless flags contains DBM_DEVICE_PTRS, in which case they are
@@ -575,12 +575,19 @@ int dbm_generator_step(dbm_model* g, dbm_model* d, int N, int H, int W, const fl
  * (round-trip check).  dbm_inflate: one zlib stream (RFC 1950 around RFC 1951, dbm_tiff_decode's compression 8) decoded on the host
  * by the device decoder's own loop run with one lane; *out_bytes = the decoded size; non-zero on everything that decoder reports (a
  * malformed stream, more than cap bytes of output).  Host functions: no GPU, no context.  The TIFF container is written by the host
- * shim (deepbedmap_amd/geotiff.py). */
+ * shim (deepbedmap_amd/geotiff.py).
+ * dbm_deflate_encode_blocks: `nblocks` blocks of `block_bytes` bytes each (host memory, block t at blocks + t * block_bytes), each as one
+ * zlib stream -- header 78 01, one final block with the fixed Huffman code, the Adler-32 -- by the matching rule of dbm_chunk_encode
+ * (the device encoder's own loop run with one lane: the bytes are the device's), into out + t * out_stride (out_stride >= block_bytes +
+ * block_bytes / 8 + 16 is always enough), sizes in out_sizes[t]; blocks are spread over `nthreads` host threads.  Status 2: a stream did
+ * not fit out_stride. */
 int dbm_f32_to_i16(dbm_ctx* ctx, const float* src_dev, void* dst_dev, size_t n);
 int dbm_lzw_encode_tiles(const void* tiles, size_t tile_bytes, int ntiles, void* out, size_t out_stride, size_t* out_sizes,
                          int nthreads);
 int dbm_lzw_decode(const void* src, size_t nbytes, void* dst, size_t cap, size_t* out_bytes);
 int dbm_inflate(const void* src, size_t nbytes, void* dst, size_t cap, size_t* out_bytes);
+int dbm_deflate_encode_blocks(const void* blocks, size_t block_bytes, int nblocks, void* out, size_t out_stride, size_t* out_sizes,
+                              int nthreads);
 
 /* ---- opening rasters: GeoTIFF blocks decoded on the device (replaces the rasterio / GDAL reads of data_prep.py:668, :845-877 and
  * deepbedmap.py:164-204; header parsing, the block plan and file reads stay with the host shim deepbedmap_amd/geotiff.py) ----
@@ -678,6 +685,34 @@ int dbm_chunk_decode(dbm_ctx* ctx, const void* streams_host, size_t streams_byte
  * image, n_blocks * block_h >= 2^31, out_capacity below the worst case.  n_blocks = 0 succeeds. */
 int dbm_tiff_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sample_type, int block_h, int block_w, int tiled, int predictor,
                     int compression, long first, int n_blocks, void* out_host, size_t out_capacity, size_t* sizes_host);
+
+/* ---- writing grids as netCDF-4 from HBM: chunks cut, shuffled and deflated on the device (data_prep.py:826-830: `save_array_to_grid(
+ * save_netcdf=True)`, the model's deepbedmap3.nc / elevdiffmap.nc of deepbedmap.py:425-437; data_prep.py:410-441: `xyz_to_grid(outfile=
+ * ...)`, the chunked, deflated highres grids GMT writes; the HDF5 container and the batching stay with the host shim
+ * deepbedmap_amd/netcdf.py: write_netcdf_resident) ----
+ * dbm_chunk_encode turns chunks first .. first + n_blocks - 1 (row-major over the variable's chunks of chunk_h x chunk_w) of the float32
+ * plane plane_dev (H, W), ALWAYS a device pointer, into the bytes an HDF5 file stores for them and downloads only those.
+ * Row r of the chunk whose first row is r0 is plane row r0 + r (row_step +1) or H - 1 - (r0 + r) (row_step -1: a file whose y ascends;
+ * the inverse of dbm_chunk_decode's row step).  Chunks are whole: positions beyond the plane are zero bytes.  The values are the 32-bit
+ * patterns, little endian (NaN payloads and -0.0 kept).  shuffle 1: HDF5's shuffle filter over the whole chunk of n = chunk_h * chunk_w
+ * elements: byte k of element i goes to k * n + i.
+ * compression 8: every chunk becomes one zlib stream (RFC 1950 around RFC 1951): header 78 01, ONE final block with the fixed Huffman
+ * code, the Adler-32; greedy matches of 3..258 bytes at distances 1..32768 from a 16 384-entry hash table (the rule: DESIGN.md 6m), one
+ * wavefront per chunk, byte for byte the stream dbm_deflate_encode_blocks writes for the same bytes.  compression 1: the bytes themselves.
+ * out_host (HOST, out_capacity bytes) receives the chunks one behind the other, each at the next even offset from 0 (an odd stream is
+ * followed by one zero byte); sizes_host (HOST) the n_blocks sizes.  out_capacity must cover the worst case: n_blocks times
+ * chunk_bytes + chunk_bytes / 8 + 16 (compression 8: no input byte costs more than 9 bits) or chunk_bytes (compression 1), each
+ * rounded up to even, chunk_bytes = chunk_h * chunk_w * 4.
+ * The call allocates its workspace (per chunk: the raw chunk rounded up to 16, 24 bytes of bookkeeping, for deflate the slot of the worst
+ * case; plus the packed streams), frees it on every path, synchronises the context's stream, writes no caller-visible device memory and
+ * reads no environment variable; the caller bounds the workspace by batching.
+ * Status 12: a chunk's deflate stream did not fit its slot; the message names the chunk and nothing of this call was written.  It cannot
+ * occur with the slot above and is there as the guard of the device loop.
+ * Refused (status 1, nothing launched): NULL pointers, an empty plane or H * W >= 2^31, compression not 1 or 8, shuffle not 0 or 1, a row
+ * step other than +1 / -1, chunk_h or chunk_w < 1 or larger than H or W, a chunk of 2^31 bytes or more, a chunk range outside the image,
+ * 2^31 workgroups or more (n_blocks * ceil(chunk_h * chunk_w / 1024)), out_capacity below the worst case.  n_blocks = 0 succeeds. */
+int dbm_chunk_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int chunk_h, int chunk_w, int row_step, int shuffle, int compression,
+                     long first, int n_blocks, void* out_host, size_t out_capacity, size_t* sizes_host);
 
 /* ---- the overviews of that file, built next to the canvas (deepbedmap.py:749-756 -> data_prep.py:779-834 write one full-resolution
  * image; its readers then run `gdaladdo -r average`.  The directories and the container stay with deepbedmap_amd/geotiff.py) ----
