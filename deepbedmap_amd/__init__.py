@@ -25,6 +25,8 @@ from .geotiff import (build_overviews, canvas_to_int16, open_geotiff, overview_p
                       read_geotiff_resident, save_array_to_grid, write_geotiff_resident)
 from .netcdf import (NetcdfVariable, open_netcdf, read_netcdf, read_netcdf_resident, save_grid_to_netcdf,  # noqa: F401
                      write_netcdf_resident)
+from .relief import (ColorTable, adler32_combine, grey_cpt, make_cpt, read_cpt, read_png, relief_image,  # noqa: F401
+                     relief_image_host, render_dem, save_png, write_png_resident)
 from .tiling import Raster, fill_gaps, get_deepbedmap_model_inputs, get_window_bounds, selective_tile, tile_training_set  # noqa: F401
 from .polygons import (Polygons, mask_outside, polygon_mask, read_polygons, read_tiles_geojson, select_tiles,  # noqa: F401
                        tiles_to_geojson)

@@ -162,6 +162,13 @@ SIGNATURES = {
     "dbm_chunk_encode": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p,
                          C.c_size_t, C.c_void_p],
     "dbm_grid_overviews": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p],
+    "dbm_grid_relief": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p],
+    "dbm_grid_shade_stats": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_double, C.c_double, C.c_double, C.c_void_p],
+    "dbm_png_encode": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_size_t,
+                       C.c_void_p, C.c_void_p],
+    "dbm_png_encode_host": [C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                            C.c_void_p, C.c_int],
     "dbm_grid_rescale": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "dbm_grid_rolling_std": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_void_p],
     "dbm_points_polar_stereographic": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int],
@@ -218,7 +225,7 @@ class DbmError(RuntimeError):
     # run -- fatal, the replicas have diverged.  9 (dbm_adam_update only): the gradients about to be applied come from a
     # void pass; nothing was applied -- repeat forward + backward, then update.  10 (dbm_grid_tension_surface only): the solve did not
     # converge within max_iter; the output holds the last iterate.  11 (dbm_tiff_decode, dbm_chunk_decode): a block's LZW or deflate stream is malformed.
-    # 12 (dbm_tiff_encode, dbm_chunk_encode): a block's LZW or deflate stream did not fit its slot (the device encoders' guard; the
+    # 12 (dbm_tiff_encode, dbm_chunk_encode, dbm_png_encode): a block's LZW or deflate stream did not fit its slot (the device encoders' guard; the
     # message names the block).
     code = None
 

@@ -499,6 +499,107 @@ int dbm_grid_overviews(dbm_ctx* ctx, const float* plane_dev, long H, long W, int
   DBM_API_END
 }
 
+// ---- colour relief and hillshade of a plane (relief.hip) ----
+int dbm_grid_relief(dbm_ctx* ctx, const float* plane_dev, long H, long W, const double* edges_host, const uint8_t* colors_host, int n_slices,
+                    int channels, int shade, double sin_a, double cos_a, double aspect, double mean, double sigma, double k, uint8_t* out_dev) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_grid_relief: NULL context");
+  note_device_write(ctx);
+  DBM_CHECK(plane_dev != nullptr && out_dev != nullptr, "dbm_grid_relief: NULL plane or output");
+  DBM_CHECK(edges_host != nullptr && colors_host != nullptr, "dbm_grid_relief: NULL edges or colours");
+  check_plane("dbm_grid_relief", H, W, 1, "H W must stay below 2^31 samples", "empty plane");
+  DBM_CHECK(channels == 3 || channels == 4, "dbm_grid_relief: channels must be 3 (RGB) or 4 (RGBA)");
+  DBM_CHECK(n_slices >= 1 && n_slices <= RELIEF_MAX_SLICES, "dbm_grid_relief: the table must hold 1..2048 slices");
+  for (int i = 0; i <= n_slices; ++i)
+    DBM_CHECK(std::isfinite(edges_host[i]) && (i == 0 || edges_host[i] > edges_host[i - 1]),
+              "dbm_grid_relief: the edges must be finite and strictly ascending (edge " + std::to_string(i) + ")");
+  if (shade) {
+    DBM_CHECK(std::isfinite(mean) && std::isfinite(sigma) && std::isfinite(k), "dbm_grid_relief: mean, sigma and k must be finite");
+    DBM_CHECK(sigma > 0.0, "dbm_grid_relief: sigma must be positive");
+    DBM_CHECK(std::fabs(k) <= 0.63661977236758138, "dbm_grid_relief: |k| must not exceed 2 / pi (an amplitude of 1)");
+    DBM_CHECK(std::isfinite(sin_a) && std::isfinite(cos_a) && std::isfinite(aspect), "dbm_grid_relief: sin_a, cos_a and aspect must be finite");
+  }
+  ReliefLaunch a;
+  a.plane = plane_dev;
+  a.H = H; a.W = W;
+  a.n_slices = n_slices; a.channels = channels; a.shade = shade != 0;
+  // the table travels through the context's staging buffers: edges in stage[0]; in stage[1] the 6 n bytes of slice colours
+  a.edges = stage_table(ctx, 0, edges_host, (size_t)n_slices + 1);
+  uint8_t* colors = ctx->stage[1].as<uint8_t>(6 * (size_t)n_slices);
+  DBM_HIP(hipMemcpyAsync(colors, colors_host, 6 * (size_t)n_slices, hipMemcpyHostToDevice, ctx->stream));
+  a.colors = colors;
+  std::memcpy(a.bfn, colors_host + 6 * (size_t)n_slices, 9);   // B, F, N follow the slices
+  a.sin_a = sin_a; a.cos_a = cos_a; a.aspect = aspect;
+  a.mean = mean; a.sigma = sigma; a.k = k;
+  a.out = out_dev;
+  launch_grid_relief(a, ctx->stream);
+  DBM_API_END
+}
+
+int dbm_grid_shade_stats(dbm_ctx* ctx, const float* plane_dev, long H, long W, double sin_a, double cos_a, double aspect, double* out_host) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_grid_shade_stats: NULL context");
+  DBM_CHECK(plane_dev != nullptr && out_host != nullptr, "dbm_grid_shade_stats: NULL plane or output");
+  check_plane("dbm_grid_shade_stats", H, W, 1, "H W must stay below 2^31 samples", "empty plane");
+  DBM_CHECK(std::isfinite(sin_a) && std::isfinite(cos_a) && std::isfinite(aspect), "dbm_grid_shade_stats: sin_a, cos_a and aspect must be finite");
+  ReliefLaunch a{};
+  a.plane = plane_dev;
+  a.H = H; a.W = W;
+  a.sin_a = sin_a; a.cos_a = cos_a; a.aspect = aspect;
+  ScopedBuf ws;   // this call's own, released on every path
+  double* stats = (double*)ws.as<char>(shade_stats_workspace(H, W));
+  launch_shade_stats(a, stats, ctx->stream);
+  DBM_HIP(hipMemcpyAsync(out_host, stats, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
+  DBM_API_END
+}
+
+// ---- an 8-bit image -> the deflated bands of a PNG (png_encode.hip; the segments through deflate_encode.hip) ----
+int dbm_png_encode(dbm_ctx* ctx, const uint8_t* image_dev, long H, long W, int channels, int filter, int band_rows, long first_band, int n_bands,
+                   void* out_host, size_t out_capacity, size_t* sizes_host, uint32_t* adlers_host) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_png_encode: NULL context");
+  const long bands = png_check_arguments("dbm_png_encode", image_dev, H, W, channels, filter, band_rows, first_band, n_bands, out_host,
+                                         out_capacity, sizes_host, adlers_host);
+  if (n_bands == 0) return 0;
+  const long row_bytes = W * channels;
+  const size_t band_bytes = (size_t)(band_rows < H ? band_rows : H) * (size_t)(row_bytes + 1), slot_cap = deflate_slot(band_bytes);
+  const size_t nb = (size_t)n_bands;
+  PngFilterLaunch a;
+  a.image = image_dev;
+  a.H = H; a.row_bytes = row_bytes;
+  a.bpp = channels; a.filter = filter; a.band_rows = band_rows;
+  a.first_band = first_band; a.n_bands = n_bands;
+  a.groups_per_band = png_groups_per_band((long)band_bytes);
+  a.raw_stride = (long)((band_bytes + 15) / 16 * 16);
+  DBM_CHECK((long)n_bands * a.groups_per_band < (1L << 31), "dbm_png_encode: more than 2^31 workgroups in one call");
+  // one workspace, carved: the filtered bands, the segments' slots, the bookkeeping words (pack_streams' 24 bytes per band, then the
+  // segments' {Adler-32, length})
+  ScopedBuf ws;   // this call's own, released on every path
+  const size_t ws_bytes = png_workspace(nullptr, nb, (size_t)a.raw_stride, slot_cap, ENCODE_WORDS).bytes;
+  const PngWorkspace carved = png_workspace(ws.as<char>(ws_bytes), nb, (size_t)a.raw_stride, slot_cap, ENCODE_WORDS);
+  uint8_t *raw = carved.raw, *slots = carved.slots;
+  uint32_t *words = carved.words, *segment_words = carved.segment_words;
+  a.raw = raw;
+  launch_png_filter(a, ctx->stream);
+  DeflateLaunch d;
+  d.raw = raw; d.raw_stride = (size_t)a.raw_stride; d.block_bytes = band_bytes; d.n_blocks = n_bands;
+  d.slots = slots; d.slot_cap = slot_cap; d.result = words;
+  d.segments = 1;
+  d.segment_words = segment_words;
+  if (first_band + n_bands == bands) {   // the image's last band ends the stream and may be short
+    d.last_block = n_bands - 1;
+    d.last_bytes = (size_t)(H - (bands - 1) * band_rows) * (size_t)(row_bytes + 1);
+  }
+  launch_block_deflate(d, ctx->stream);
+  std::vector<unsigned long long> table(2 * nb);
+  std::vector<uint32_t> seg(2 * nb);
+  DBM_HIP(hipMemcpyAsync(seg.data(), segment_words, nb * 8, hipMemcpyDeviceToHost, ctx->stream));   // (drained by pack_streams)
+  pack_streams(ctx, "dbm_png_encode", "deflate", first_band, nb, true, words, slots, slot_cap, slot_cap, table, out_host, out_capacity, sizes_host);
+  for (size_t b = 0; b < nb; ++b) adlers_host[b] = seg[2 * b];
+  DBM_API_END
+}
+
 int dbm_grid_rescale(dbm_ctx* ctx, const float* in_dev, long H, long W, long out_h, long out_w, int order, int anti_aliasing, int clip,
                      int input_cast, float* out_dev) {
   DBM_API_BEGIN(ctx)

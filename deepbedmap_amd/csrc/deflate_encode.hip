@@ -30,6 +30,18 @@
 // hold the stream.
 // deflate_encode_lanes is __host__ __device__: with (lane, lanes) = (0, 1) it is the host encoder.  Only the lane primitives differ
 // between the two compilations: window_byte, equal_run, insert_span and lanes_sum.
+//
+// Framing (the bands of a PNG are segments of ONE zlib stream that the host stitches).  The rule above -- hash, candidate,
+// match, inserts -- is the same in every mode; a segment starts with an empty table, so it never refers to bytes in front of it.
+//   0  the stream described above: 78 01, BFINAL 1, the Adler-32 behind the block.
+//   1  a middle segment: no header; one block BFINAL 0, BTYPE 01; behind its end-of-block symbol an EMPTY STORED block -- the bits 000
+//      (BFINAL 0, BTYPE 00), zero bits up to the next byte boundary, then LEN 00 00 and NLEN FF FF -- so that the segment ends on a
+//      byte boundary and the next one can be appended (what zlib's Z_SYNC_FLUSH writes).  No Adler-32 in the stream.
+//   2  the last segment: no header; BFINAL 1; end-of-block; zero bits up to the byte boundary.  No Adler-32 in the stream.
+// In modes 1 and 2 the Adler-32 of the segment's input goes to *adler_out (the caller joins the segments' sums: adler32_combine).
+// The slot bound holds in every mode: the symbols cost at most 9 n bits; mode 0 adds 2 + 4 bytes and 3 + 7 bits, mode 1 adds 3 + 7 + 3
+// bits, at most 7 bits of padding and 4 bytes, mode 2 adds 3 + 7 bits and the padding: never more than ceil((9 n + 20) / 8) + 6 <=
+// n + n / 8 + 10 bytes, below n + n / 8 + 16.
 #include "model.h"
 #include "data_prims.h"
 #include <thread>
@@ -196,16 +208,20 @@ __host__ __device__ inline uint32_t adler32_lanes(const uint8_t* src, size_t n, 
 
 // Encodes src[0, n) into dst[0, cap).  Returns the encoded size, or 0 if cap is too small.  table: DEFLATE_SLOTS entries,
 // uninitialised.  All lanes of the wave call it with the same arguments but `lane`.
+// framing: 0 a whole zlib stream, 1 a middle segment, 2 the last segment (the head of this file); adler_out: where modes 1 and 2 leave
+// the Adler-32 of src[0, n) (lane 0 stores; may be null in mode 0).
 __host__ __device__ inline size_t deflate_encode_lanes(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, uint16_t* table, uint32_t lane,
-                                                       uint32_t lanes) {
+                                                       uint32_t lanes, uint32_t framing = 0u, uint32_t* adler_out = nullptr) {
   DeflateBitWriter w{dst, cap, 0, 0ull, 0u, lane, false};
   for (uint32_t k = lane; k < DEFLATE_SLOTS; k += lanes) table[k] = 0;
   lanes_fence();
   const uint32_t adler = adler32_lanes(src, n, lane, lanes);
-  w.emit(0x78u);
-  w.emit(0x01u);
-  w.put(1u, 1);   // BFINAL
-  w.put(1u, 2);   // BTYPE 01: the fixed code
+  if (framing == 0u) {
+    w.emit(0x78u);
+    w.emit(0x01u);
+  }
+  w.put(framing == 1u ? 0u : 1u, 1);   // BFINAL
+  w.put(1u, 2);                        // BTYPE 01: the fixed code
   size_t i = 0;
 #pragma unroll 1
   while (i < n && !w.overflow) {
@@ -243,21 +259,38 @@ __host__ __device__ inline size_t deflate_encode_lanes(const uint8_t* src, size_
   }
   if (w.overflow) return 0;
   put_symbol(w, 256u);   // end of block
+  if (framing == 1u) w.put(0u, 3);   // the empty stored block: BFINAL 0, BTYPE 00
   w.flush();
-  w.emit(adler >> 24);
-  w.emit((adler >> 16) & 0xFFu);
-  w.emit((adler >> 8) & 0xFFu);
-  w.emit(adler & 0xFFu);
+  if (framing == 0u) {
+    w.emit(adler >> 24);
+    w.emit((adler >> 16) & 0xFFu);
+    w.emit((adler >> 8) & 0xFFu);
+    w.emit(adler & 0xFFu);
+  } else {
+    if (framing == 1u) {   // LEN 0, NLEN ~0
+      w.emit(0x00u);
+      w.emit(0x00u);
+      w.emit(0xFFu);
+      w.emit(0xFFu);
+    }
+    if (lane == 0 && adler_out) *adler_out = adler;
+  }
   return w.overflow ? 0 : w.count;
 }
 
 __global__ __launch_bounds__(64) void block_deflate_kernel(DeflateLaunch a) {
   __shared__ uint16_t table[DEFLATE_SLOTS];
   const size_t b = blockIdx.x;
-  const size_t got = deflate_encode_lanes(a.raw + b * a.raw_stride, a.block_bytes, a.slots + b * a.slot_cap, a.slot_cap, table, threadIdx.x, 64u);
+  // segments (a.segments: the bands of a PNG): every block is a middle segment but the one that ends the stream, which may be short
+  const bool last = a.segments && (long)b == a.last_block;
+  const size_t n = last ? a.last_bytes : a.block_bytes;
+  const uint32_t framing = a.segments ? (last ? 2u : 1u) : 0u;
+  const size_t got = deflate_encode_lanes(a.raw + b * a.raw_stride, n, a.slots + b * a.slot_cap, a.slot_cap, table, threadIdx.x, 64u, framing,
+                                          a.segments ? a.segment_words + 2 * b : nullptr);
   if (threadIdx.x == 0) {
     a.result[2 * b] = (uint32_t)got;             // (slot_cap < 2^32: block_bytes < 2^31)
     a.result[2 * b + 1] = got == 0 ? 1u : 0u;    // the status word: 1 = the stream did not fit its slot
+    if (a.segments) a.segment_words[2 * b + 1] = (uint32_t)n;   // (behind the segment's Adler-32: its length)
   }
 }
 
@@ -267,6 +300,10 @@ void launch_block_deflate(const DeflateLaunch& a, hipStream_t s) {
   if (a.n_blocks <= 0) return;
   hipLaunchKernelGGL(block_deflate_kernel, dim3((unsigned)a.n_blocks), dim3(64), 0, s, a);
   DBM_HIP(hipGetLastError());
+}
+
+size_t deflate_encode_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, uint16_t* table, int framing, uint32_t* adler_out) {
+  return deflate_encode_lanes(src, n, dst, cap, table, 0u, 1u, (uint32_t)framing, adler_out);
 }
 
 extern "C" int dbm_deflate_encode_blocks(const void* blocks, size_t block_bytes, int nblocks, void* out, size_t out_stride, size_t* out_sizes,

@@ -433,6 +433,9 @@ void launch_nc_chunk_cut(const ChunkEncodeLaunch& a, hipStream_t s);
 // Blocks of bytes -> zlib streams with the fixed Huffman code (deflate_encode.hip), one wavefront per block: block b's block_bytes
 // bytes at raw + b * raw_stride into slots + b * slot_cap; result[2 b] = the stream's size, result[2 b + 1] = its status word (1: it
 // did not fit; size 0), as launch_tiff_lzw_encode.  deflate_slot: the room that always holds a stream (9 bits per byte at most).
+// segments != 0 (the bands of a PNG, dbm_png_encode): the blocks are segments of ONE zlib stream -- no header, no Adler-32 in the
+// stream; block last_block (-1: none of this launch) ends the stream, holds last_bytes bytes and is written with BFINAL 1, every other
+// block ends in an empty stored block -- and segment_words[2 b], [2 b + 1] receive the Adler-32 of block b's bytes and their number.
 struct DeflateLaunch {
   const uint8_t* raw;
   size_t raw_stride, block_bytes;
@@ -440,9 +443,17 @@ struct DeflateLaunch {
   uint8_t* slots;
   size_t slot_cap;
   uint32_t* result;
+  int segments = 0;
+  long last_block = -1;
+  size_t last_bytes = 0;
+  uint32_t* segment_words = nullptr;
 };
 inline size_t deflate_slot(size_t n) { return n + n / 8 + 16; }
 void launch_block_deflate(const DeflateLaunch& a, hipStream_t s);
+// deflate_encode_lanes with one lane on the host (png_encode.hip's host writer): framing 0 a whole zlib stream, 1 a middle segment, 2
+// the last segment; table: 16 384 entries of scratch; *adler_out (framing 1, 2): the Adler-32 of src[0, n).  Returns the size, 0 if
+// cap is too small.
+size_t deflate_encode_twin(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, uint16_t* table, int framing, uint32_t* adler_out);
 
 // numpy.ndarray.astype(int16) of a float32 on x86-64: truncation to int32 (cvttss2si: NaN and |x| >= 2^31 give INT32_MIN), then the low
 // 16 bits -- NaN (the canvas frame that no tile covers), +-inf and out-of-range values become 0.  The one cast of f32_to_i16_kernel
@@ -492,6 +503,53 @@ struct PyramidLaunch {
 };
 int pyramid_max_levels(long H, long W);
 void launch_grid_overviews(const PyramidLaunch& a, hipStream_t s);
+
+// Colour relief and hillshade of a plane (relief.hip; dbm_grid_relief, dbm_grid_shade_stats): the float32 plane -> out, uint8 (H, W,
+// channels).  edges (n_slices + 1 doubles) and colors (6 bytes per slice: the colour at its lower edge, then at its upper edge) are
+// DEVICE pointers; bfn holds the colours below the table, above it and of NaN.  shade: the intensity k atan((g - mean) / sigma) of the
+// gradient g along (sin_a, cos_a), dy scaled by aspect.  launch_shade_stats leaves {n, mean, sigma} of the defined g in the first three
+// doubles of ws (shade_stats_workspace(H, W) bytes); it reads plane, H, W, sin_a, cos_a and aspect only.
+constexpr int RELIEF_MAX_SLICES = 2048;
+struct ReliefLaunch {
+  const float* plane;
+  long H, W;
+  const double* edges;
+  const uint8_t* colors;
+  int n_slices, channels, shade;
+  uint8_t bfn[9];
+  double sin_a, cos_a, aspect, mean, sigma, k;
+  uint8_t* out;
+};
+void launch_grid_relief(const ReliefLaunch& a, hipStream_t s);
+size_t shade_stats_workspace(long H, long W);
+void launch_shade_stats(const ReliefLaunch& a, void* ws, hipStream_t s);
+
+// An 8-bit image -> the bands of a PNG's filtered scanlines (png_encode.hip; dbm_png_encode): band b of the call holds the image rows
+// (first_band + b) * band_rows ..., each as one filter-type byte and row_bytes filtered bytes (filter 0 None, 1 Sub, 2 Up, from the raw
+// image), at raw + b * raw_stride (raw_stride a multiple of 16, >= band_rows * (row_bytes + 1)).  png_check_arguments: what the device
+// and the host entry refuse alike; returns the image's number of bands.
+struct PngFilterLaunch {
+  const uint8_t* image;
+  long H, row_bytes;
+  int bpp, filter, band_rows;
+  long first_band;
+  int n_bands;
+  unsigned groups_per_band;    // png_groups_per_band(band_rows * (row_bytes + 1))
+  uint8_t* raw;
+  long raw_stride;
+};
+unsigned png_groups_per_band(long band_bytes);
+void launch_png_filter(const PngFilterLaunch& a, hipStream_t s);
+// dbm_png_encode's workspace, carved from ws (data_prims.h's carver; ws == nullptr only measures: `bytes`): the filtered bands, the
+// segments' slots, words_per_band bytes of bookkeeping per band, the segments' {Adler-32, length}
+struct PngWorkspace {
+  uint8_t *raw, *slots;
+  uint32_t *words, *segment_words;
+  size_t bytes;
+};
+PngWorkspace png_workspace(void* ws, size_t n_bands, size_t raw_stride, size_t slot_cap, size_t words_per_band);
+long png_check_arguments(const char* who, const void* image, long H, long W, int channels, int filter, int band_rows, long first_band, int n_bands,
+                         const void* out, size_t out_capacity, const void* sizes, const void* adlers);
 
 // Fully filled windows of a raster (tile.hip; dbm_grid_filled_windows): flags[uly * nx + ulx] = 1 iff no node of rows [uly step, uly step
 // + size) x columns [ulx step, ulx step + size) is NaN, rows counted from the north (flip_rows: raster row 0 is the south edge), columns

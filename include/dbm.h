@@ -22,7 +22,7 @@
  *     the gradients and repeats forward + backward before updating (the step entry points clear them themselves).  Status 8:
  *     the same in a data-parallel run, where a local retry cannot keep the replicas identical -- fatal, abort the job.  Status 10
  *     (dbm_grid_tension_surface only): the solve did not converge within max_iter; the output holds the last iterate.  Status 11
- *     (dbm_tiff_decode only): a block's LZW or deflate stream is malformed.  Status 12 (dbm_tiff_encode, dbm_chunk_encode): a block's LZW or deflate stream
+ *     (dbm_tiff_decode only): a block's LZW or deflate stream is malformed.  Status 12 (dbm_tiff_encode, dbm_chunk_encode, dbm_png_encode): a block's LZW or deflate stream
  *     did not fit its slot (the guard of the device encoders; it cannot occur with the slot the calls allocate);
  *   - tensors are NCHW float32, C-contiguous; weights OIHW, exactly the arrays stored by
  *     chainer.serializers.save_npz (key layout: SURVEY.md Appendix B);
@@ -729,6 +729,56 @@ int dbm_chunk_encode(dbm_ctx* ctx, const float* plane_dev, long H, long W, int c
  * plane_dev.  levels = 0 succeeds. */
 int dbm_grid_overviews(dbm_ctx* ctx, const float* plane_dev, long H, long W, int sample_type, const double* nodata, int levels,
                        float* out_dev);
+
+/* ---- rendering the DEM from HBM: colour relief, hillshade, PNG (deepbedmap.py:758-775: `gmt.makecpt(cmap="oleron", series=[-4500,
+ * 4500])`, `fig.grdimage(..., cmap=True, Q=True)`, `fig.savefig("deepbedmap_dem.png")`; paper_figures.py:692-699: the same with
+ * `shading="+d"`.  Colour tables, the PNG container and the batching stay with the host shim deepbedmap_amd/relief.py.  The rules are
+ * this project's own -- GMT's pixels are not claimed: DESIGN.md 6n) ----
+ * dbm_grid_relief (deepbedmap.py:758-775, paper_figures.py:692-699) colours the float32 plane plane_dev (H, W) into out_dev, uint8
+ * (H, W, channels), both DEVICE pointers; the call only enqueues.  edges_host (HOST, n_slices + 1 doubles, strictly ascending) and
+ * colors_host (HOST, 6 n_slices + 9 bytes: per slice the colour r, g, b at its lower edge and at its upper edge, then the colours B
+ * below the table, F above it and N of NaN) are copied up by the call.  Per pixel, v = (double)z, every operation one IEEE float64
+ * operation, never an FMA: NaN gives N (alpha 0 with 4 channels; alpha is 255 everywhere else); v < E_0 gives B, v > E_n gives F (so
+ * -inf and +inf); else i = the largest index <= n - 1 with E_i <= v, t = (v - E_i) / (E_{i+1} - E_i), u = c0 + (c1 - c0) t per
+ * channel (the product rounded, then the sum).  shade != 0: I = k atan((g - mean) / sigma) where the gradient g is defined, else 0; I >= 0:
+ * u' = u + (255 - u) I; I < 0: u' = u + u I; B and F pixels are shaded, N pixels are not.  Byte = floor(u' + 0.5) clamped to 0..255.
+ * g = -(dx sin_a + (dy aspect) cos_a) with dx = (z[r, c + 1] - z[r, c - 1]) / 2 and dy = (z[r - 1, c] - z[r + 1, c]) / 2 (rows
+ * north-up, index units), one-sided (the difference of the two samples that exist, not halved) at the first and last column and row;
+ * defined only where the four samples it reads are finite, nowhere if W == 1 or H == 1.  The caller computes sin_a, cos_a of the
+ * azimuth (the reference's "+d" is azimuth -45 degrees, amplitude 1) and k = amplitude 2 / pi.
+ * Refused (status 1, nothing launched): NULL pointers, an empty plane or H * W >= 2^31, channels not 3 or 4, n_slices outside 1..2048,
+ * edges that are not finite or not strictly ascending; with shade: sigma <= 0, a mean, sigma, k, sin_a, cos_a or aspect that is not
+ * finite, |k| > 2 / pi.
+ * dbm_grid_shade_stats (paper_figures.py:692-699: what `shading="+d"` normalises by) returns out_host[3] = {n, mean, sigma} of the
+ * defined g of the plane: mean = sum g / n, sigma = sqrt(sum (g - mean)^2 / (n - 1)), two passes in float64 in a fixed order (the same
+ * bits from call to call); n == 0 gives mean 0, n < 2 sigma 0.  The call allocates its workspace, frees it on every path and
+ * synchronises.  Refused (status 1): NULL pointers, an empty plane or H * W >= 2^31, sin_a, cos_a or aspect not finite.
+ * dbm_png_encode (deepbedmap.py:758-775: `fig.savefig`) turns bands first_band .. first_band + n_bands - 1 of the uint8 image
+ * image_dev (H, W, channels; channels 1 grey, 3 RGB, 4 RGBA), ALWAYS a device pointer, into segments of the PNG's zlib stream and
+ * downloads only those.  Band b holds rows b band_rows ... (the last band is short): per row one filter-type byte and the W channels
+ * filtered bytes (filter 0 None, 1 Sub, 2 Up as PNG defines them, computed from the raw image: Up reads the row above also across a
+ * band boundary, zeros above row 0).  Every band is deflated by one wavefront with the rule of dbm_chunk_encode, framed as a segment:
+ * no zlib header and no Adler-32; one block with the fixed Huffman code, BFINAL 0, followed by an empty stored block (bits 000, padding
+ * to a byte, 00 00 FF FF) -- or, for the image's last band, BFINAL 1 and padding.  78 01 + the segments in order + the big-endian
+ * Adler-32 of all bands' bytes is one valid zlib stream.  out_host (HOST, out_capacity bytes) receives the segments one behind the
+ * other, each at the next even offset from 0; sizes_host (HOST) their n_bands sizes, adlers_host (HOST) the Adler-32 of each band's
+ * bytes.  out_capacity must cover the worst case: n_bands times n + n / 8 + 16 rounded up to even, n = min(band_rows, H) (W channels
+ * + 1).  The call allocates its workspace (per band: the filtered band rounded up to 16, the slot of the worst case, 32 bytes of
+ * bookkeeping; plus the packed segments), frees it on every path, synchronises the context's stream and writes no caller-visible
+ * device memory; the caller bounds the workspace by batching.
+ * Status 12: a band's segment did not fit its slot (the guard of the device loop; it cannot occur with the slot above).
+ * Refused (status 1, nothing launched): NULL pointers, an empty image or H * W >= 2^31, channels not 1, 3 or 4, filter outside 0..2,
+ * band_rows < 1, a band of 2^31 bytes or more, a band range outside the image, 2^31 workgroups or more, out_capacity below the worst
+ * case.  n_bands = 0 succeeds.
+ * dbm_png_encode_host (deepbedmap.py:758-775): the same bytes from a HOST image on `nthreads` host threads -- the device encoder's own
+ * loop and the same filter text run with one lane.  No GPU, no context. */
+int dbm_grid_relief(dbm_ctx* ctx, const float* plane_dev, long H, long W, const double* edges_host, const uint8_t* colors_host, int n_slices,
+                    int channels, int shade, double sin_a, double cos_a, double aspect, double mean, double sigma, double k, uint8_t* out_dev);
+int dbm_grid_shade_stats(dbm_ctx* ctx, const float* plane_dev, long H, long W, double sin_a, double cos_a, double aspect, double* out_host);
+int dbm_png_encode(dbm_ctx* ctx, const uint8_t* image_dev, long H, long W, int channels, int filter, int band_rows, long first_band, int n_bands,
+                   void* out_host, size_t out_capacity, size_t* sizes_host, uint32_t* adlers_host);
+int dbm_png_encode_host(const void* image, long H, long W, int channels, int filter, int band_rows, long first_band, int n_bands, void* out,
+                        size_t out_capacity, size_t* sizes, uint32_t* adlers, int nthreads);
 
 /* One minibatch of `trainer` (srgan_train.py:1286-1309) as ONE call: train_eval_discriminator (:1084-1166) with its
  * optimizer update, then train_eval_generator (:1170-1263) with its update; both optimizers must have been set up
