@@ -44,6 +44,17 @@ CONV_REPORT_INTS = 41  # launches, then ten ints per launch (at most four)
 CONV_REPORT_FIELDS = ("family", "cfg", "waves", "npb", "row", "ksplit", "nosplit", "nphase", "mt2", "yt")
 
 
+class DeformLaunch(C.Structure):
+    """dbm_deform_launch (include/dbm.h): one deformable forward as the generator launches it, every optional output."""
+    _fields_ = [("form", C.c_int), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("O", C.c_int), ("act", C.c_int),
+                ("x", C.c_void_p), ("off", C.c_void_p), ("offsn", C.c_int64), ("w", C.c_void_p), ("bias", C.c_void_p),
+                ("y", C.c_void_p), ("yt", C.c_void_p), ("colout", C.c_void_p), ("z", C.c_void_p)]
+
+
+# dbm_op_deform_forward_launch's report[0]: the path taken
+DEFORM_PATHS = {1: "fused64", 2: "premul", 3: "gather1", 4: "x3", 5: "sampler+gemv", 6: "sampler+igemm"}
+
+
 class WgradDesc(C.Structure):
     """dbm_wgrad_desc (include/dbm.h): one weight gradient of a dbm_op_conv2d_wgrad_batch call."""
     _fields_ = [("x", C.c_void_p), ("xsn", C.c_int64), ("dy", C.c_void_p), ("dysn", C.c_int64), ("N", C.c_int), ("C", C.c_int),
@@ -206,6 +217,7 @@ SIGNATURES = {
     "dbm_op_deform_conv2d": [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 5,
     "dbm_op_deform_conv2d_form": [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 6,
     "dbm_op_deform_conv2d_backward": [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int] * 5,
+    "dbm_op_deform_forward_launch": [C.c_void_p, C.POINTER(DeformLaunch), C.POINTER(C.c_int)],
     "dbm_op_batchnorm_train": [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int] * 4 + [C.POINTER(C.c_int)],
     "dbm_op_batchnorm_train_backward": [C.c_void_p] + [C.c_void_p] * 9 + [C.c_int] * 4 + [C.POINTER(C.c_int)],
     "dbm_op_disc_head": [C.c_void_p] + [C.c_void_p] * 7 + [C.c_int],

@@ -464,6 +464,96 @@ int dbm_op_deform_conv2d(dbm_ctx* ctx, const float* x, const float* off, const f
   DBM_API_END
 }
 
+// One deformable forward exactly as Generator::forward launches it: the offsets at their own image stride, the activation, the
+// channels-last twin, the retained sample matrix and the retained premultiplied planes, each handed to the launcher as given (null
+// stays null).  Form 0 is the layer's own choice (deform_layer_forms + deform_layer_forward on the packed temporary layer); the other
+// forms name one launcher.  report[0] (HOST, may be NULL): the path taken (include/dbm.h); which kernel a launcher then chose shows
+// in the profiler's tags.
+int dbm_op_deform_forward_launch(dbm_ctx* ctx, const dbm_deform_launch* a, int* report) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(a != nullptr && a->x && a->off && a->w, "dbm_op_deform_forward_launch: x, off and w are required");
+  DBM_CHECK(a->N >= 1 && a->H >= 1 && a->W >= 1 && a->O >= 1, "dbm_op_deform_forward_launch: bad geometry");
+  DBM_CHECK(a->form >= 0 && a->form <= 6, "dbm_op_deform_forward_launch: form 0 .. 6");
+  const int N = a->N, H = a->H, W = a->W, O = a->O, C = 64, form = a->form;
+  const long P = (long)H * W;
+  DBM_CHECK(a->offsn >= 18 * P, "dbm_op_deform_forward_launch: offsn below the 18 offset planes of an image");
+  DBM_CHECK(a->act == 0 || a->act == 1, "dbm_op_deform_forward_launch: act is 0 or 1");
+  hipStream_t s = ctx->stream;
+  DeformForms f = deform_layer_forms(C, O, H, W);
+  if (form == 6) f.fwd_fused = f.premul = false, f.fwd_packed = O != 1;
+  const bool fused = form != 6 && (form != 0 || f.fwd_fused);
+  const bool x3 = form >= 2 && form <= 4, few = fused && !x3 && O <= 16;
+  int path;
+  if (x3) {
+    DBM_CHECK(O == 64, "dbm_op_deform_forward_launch: forms 2, 3, 4 (split-bf16) are the 64 -> 64 layer's");
+    DBM_CHECK(!a->colout && !a->z, "dbm_op_deform_forward_launch: the split-bf16 kernels write neither a sample matrix nor premultiplied planes");
+    path = 4;
+  } else if (form == 1 || form == 5) {
+    DBM_CHECK(O <= 16, "dbm_op_deform_forward_launch: forms 1 and 5 are the few-output-channel layer's (O <= 16)");
+    DBM_CHECK(form == 1 || !a->z, "dbm_op_deform_forward_launch: form 5 (gather, then multiply) has no premultiplied planes");
+    path = form == 1 ? 2 : 3;
+  } else if (fused) {
+    DBM_CHECK(deform_conv_fused_ok(C, O), "dbm_op_deform_forward_launch: the fused forms take 64 or <= 16 output channels");
+    path = O == 64 ? 1 : f.premul ? 2 : 3;
+  } else {
+    DBM_CHECK(O == 1 || O % 32 == 0, "dbm_op_deform_forward_launch: the unfused path takes O == 1 (GEMV) or O % 32 == 0 (implicit GEMM)");
+    DBM_CHECK(!a->z, "dbm_op_deform_forward_launch: the unfused path has no premultiplied planes");
+    path = O == 1 ? 5 : 6;
+  }
+  if (few) {
+    DBM_CHECK(!a->act, "dbm_op_deform_forward_launch: the few-output-channel kernels have no activation");
+    DBM_CHECK(!a->colout, "dbm_op_deform_forward_launch: the few-output-channel kernels write no sample matrix");
+  }
+  if (path == 5) DBM_CHECK(!a->act, "dbm_op_deform_forward_launch: the GEMV has no activation");
+  const bool twin_ok = fused && O == 64;
+  DBM_CHECK(!a->yt || twin_ok, "dbm_op_deform_forward_launch: only the fused 64 -> 64 kernels write the channels-last twin");
+  DBM_CHECK(a->y || (a->yt && twin_ok), "dbm_op_deform_forward_launch: y may be null only where yt is written");
+  DBM_CHECK(!a->z || path == 2, "dbm_op_deform_forward_launch: z belongs to the premultiplied form");
+
+  ScopedBuf xt, col, zs, wx;
+  dbm_model holder;   // (stays empty where the form reads the OIHW tensor itself)
+  if (fused) {
+    xt.ensure((size_t)N * C * P);
+    launch_nchw_to_nhwc64(a->x, xt.p, N, (int)P, s);
+  }
+  if (x3) {
+    wx.ensure((deform_x3_packed_elems() + 1) / 2);
+    launch_pack_deform_x3(a->w, wx.p, s);
+    launch_deform_conv64_x3(xt.p, a->off, wx.p, a->bias, a->y, a->yt, N, H, W, a->offsn, a->act, 0.2f, s, form == 3 ? 1 : form == 4 ? 0 : -1);
+  } else if (form == 1 || form == 5) {
+    float* z = a->z;
+    if (form == 1 && !z) {
+      zs.ensure((size_t)N * 9 * O * P);
+      z = zs.p;
+    }
+    launch_deform_conv_fused(xt.p, a->off, a->w, a->bias, a->y, nullptr, nullptr, N, C, H, W, a->offsn, O, 0, 0.2f, s, z);
+  } else {
+    const float* bias = a->bias;
+    if (f.fwd_packed) {
+      const IgLayer L = make_temp_layer(ctx, holder, a->w, a->bias, O, C, 3, 1, 0, true, /*as_1x1=*/true);
+      if (a->bias) bias = holder.P(L.bi);
+    }
+    float* colp = a->colout;
+    if (!fused && !colp) {   // (the unfused path's scratch, where the caller does not keep it)
+      col.ensure((size_t)N * C * 9 * P);
+      colp = col.p;
+    }
+    float* z = nullptr;
+    if (f.premul) {   // (Generator::forward: ws.zdef whenever the layer premultiplies)
+      z = a->z;
+      if (!z) {
+        zs.ensure((size_t)N * 9 * O * P);
+        z = zs.p;
+      }
+    }
+    deform_layer_forward(holder, f.fwd_packed ? &holder.layers[0] : nullptr, f, a->x, xt.p, a->off, a->offsn, a->w, bias, a->y, a->yt, colp, z, N,
+                         C, H, W, O, a->act, s);
+  }
+  DBM_HIP(hipStreamSynchronize(s));
+  if (report) report[0] = path;
+  DBM_API_END
+}
+
 int dbm_op_deform_conv2d_backward(dbm_ctx* ctx, const float* x, const float* off, const float* w, const float* gy,
                                   float* gx, float* goff, float* gw, float* gb, int N, int C, int H, int W, int O) {
   DBM_API_BEGIN(ctx)

@@ -924,6 +924,32 @@ int dbm_op_deform_conv2d_form(dbm_ctx* ctx, const float* x, const float* off, co
                               int W, int O, int form, int lrelu);
 int dbm_op_deform_conv2d_backward(dbm_ctx* ctx, const float* x, const float* off, const float* w, const float* gy,
                                   float* gx, float* goff, float* gw, float* gb, int N, int C, int H, int W, int O);
+/* One deformable forward (64 input channels, 3x3, pad 1) launched exactly as the generator launches it (srgan_train.py:572-574): the
+ * offsets off (N, >= 18, H, W) at their own image stride offsn in floats (the generator's live in a 32-channel buffer), LeakyReLU 0.2
+ * if act, and the optional outputs, each handed to the launcher as given (NULL stays NULL): y (N, O, H, W); yt (N * H * W, 64), the
+ * same values channels-last (O = 64; y may then be NULL); colout (N, 576, H, W), the sample matrix, row c * 9 + t (O = 64, fp32); z
+ * (N, O, 9, H, W), the premultiplied planes sum_c w[o, c, t] x[c] (O <= 16).  form: 0 the layer's own choice, on the packed temporary
+ * layer (a layer that premultiplies gets a scratch z where z is NULL, as the generator's workspace has one); 1 premultiplied (O <= 16);
+ * 2 / 3 / 4 split-bf16, the launcher's choice / its LDS-window kernel / its gathering kernel (O = 64); 5 gather, then multiply (O <= 16,
+ * z == NULL); 6 the unfused path: the sampler writes the sample matrix (into colout where given), then a GEMV (O = 1) or the implicit
+ * GEMM (O % 32 == 0).  Combinations the launchers do not support are refused.  report (HOST, one int, may be NULL): the path taken --
+ * 1 launch_deform_conv_fused 64 -> 64 (LDS-window kernel without colout on planes within its limit, else the gathering kernel; the
+ * profiler's tag tells: deform64w_... / deform64_...[_keep]), 2 premultiplied, 3 gather-then-multiply, 4 launch_deform_conv64_x3
+ * (deform64x3w_... / deform64x3_...), 5 sampler + GEMV, 6 sampler + implicit GEMM. */
+typedef struct dbm_deform_launch {
+  int form;
+  int N, H, W, O;
+  int act;
+  const float* x;      /* (N, 64, H, W) */
+  const float* off; int64_t offsn;
+  const float* w;      /* OIHW (O, 64, 3, 3) */
+  const float* bias;   /* O, or NULL */
+  float* y;
+  float* yt;
+  float* colout;
+  float* z;
+} dbm_deform_launch;
+int dbm_op_deform_forward_launch(dbm_ctx* ctx, const dbm_deform_launch* args, int* report);
 /* L.BatchNormalization (training mode, eps 1e-5, decay 0.9) + F.leaky_relu(0.2) as the discriminator runs them (srgan_train.py:636-644,
  * 664-689): z (N,C,plane) -> y, per-channel mean / inv_std (C) overwritten; avg_mean / avg_var (C) updated in place with the unbiased
  * correction m / max(m - 1, 1), m = N * plane.  The kernel form is the model's own launch choice for (N, C, plane); *form_out (HOST, may

@@ -14,6 +14,7 @@ the identical goff in every regime.  Asserted below, so that nobody hunts for a 
 import inspect
 import os
 import sys
+import zlib
 
 import numpy as np
 import pytest
@@ -25,7 +26,8 @@ from test_gpu_deform_backward import (BOUNDS, OUTPUTS, REGIMES, check, deviation
                                       reference)
 
 SHAPES = [(2, 36, 36), (3, 7, 15)]
-CASES = [(s, r) for s in SHAPES for r in REGIMES if r != "lattice" or is_exact_plane(*s[1:])]
+CASES = [(s, r) for s in SHAPES for r in REGIMES if r != "window_edge" and (r != "lattice" or is_exact_plane(*s[1:]))]
+CASES += [(s, "window_edge") for s in SHAPES]   # (appended: the cases above keep their ids)
 
 
 def _mutant(edits):
@@ -134,3 +136,72 @@ def test_regimes_put_the_samples_where_they_say(evaluated, shape):
     if (H, W) == (36, 36):
         u = ops._deform_geometry(evaluated[shape, "zero"][0][1], H, W, 3, 3, 1, 1)[0]
         assert 0.05 < (u != np.round(u)).mean() < 0.5 and (u < np.round(u)).mean() > 0.03
+
+
+# ---- the forward table (tests/test_gpu_deform_forward.py): its cases and tolerances, without a GPU ----
+import re  # noqa: E402
+
+import test_gpu_deform_forward as fwd  # noqa: E402
+
+ROOT = os.path.dirname(HERE)
+FWD_PLANES = sorted(set(k[1] for k in fwd.ALL_CASES))
+
+
+def test_window_edge_straddles_both_window_limits_on_every_plane():
+    """offsets in [-2, 3) stay inside the LDS windows: each plane of the forward table has offsets at -2 and just below it, just below 3
+    and at it -- on both axes wherever an axis has room for the six values (N * H * W >= 2)"""
+    lo, hi = np.float32(-2.0), np.float32(3.0)
+    for plane in FWD_PLANES:
+        off = REGIMES["window_edge"](np.random.RandomState(zlib.crc32(repr(plane).encode()) % 2**31), *plane)
+        assert off.dtype == np.float32 and off.shape == (plane[0], 18, plane[1], plane[2])
+        axes = [off] if plane[0] * plane[1] * plane[2] < 2 else [off[:, :9], off[:, 9:]]
+        for o in axes:
+            assert (o == lo).any() and (o == np.nextafter(lo, np.float32(-np.inf))).any() and (o < lo - 0.25).any(), plane
+            assert (o == hi).any() and (o == np.nextafter(hi, np.float32(-np.inf))).any() and (o > hi + 0.25).any(), plane
+            assert ((o > lo) & (o < hi)).mean() > 0.6, plane
+    for key in fwd.ALL_CASES:   # ... and so do the offsets the table's cases really use
+        if key[2] == "window_edge":
+            o = fwd.make_inputs(*key[1:])[1]
+            assert (o < lo).any() and (o == lo).any() and (o >= hi).any() and (o == np.nextafter(hi, np.float32(-np.inf))).any(), key
+
+
+def test_only_all_out_has_no_mass_and_the_float32_oracle_sets_the_forward_tolerances():
+    """`all_out`: every sample of every case has zero mass; every other regime leaves mass in every case's output (but `far` on one pixel).  16 x the float32
+    oracle's worst per-element deviation over the forward table lies above the floor and under the 1e-4 cap for every fp32 quantity:
+    the cap is never what lets a case pass."""
+    for key in fwd.ALL_CASES:
+        m = fwd.figures(*key[1:])["sample_mass_max"]
+        # (the one exception, asserted: the nine normal(0, 6) taps of `far` around the ONE pixel of (1, 1, 1) all miss it -- the GPU
+        #  module then holds y to the bias exactly, as under all_out: its exact check is keyed on the mass, not on the regime's name)
+        assert (m == 0) == (key[2] == "all_out" or key[1:] == ((1, 1, 1), "far")), (key, m)
+    worst, tol = fwd.oracle32_worst(), fwd.tolerances()
+    for q in fwd.QUANTITIES:
+        print(f"forward table, {q}: float32 oracle's worst |d| / mass {worst[q]:.3e}, x 16 = {16 * worst[q]:.3e}, tolerance {tol[q]:.3e}")
+        assert fwd.TOL_FLOOR < 16 * worst[q] < fwd.TOL_CAP, (q, worst[q])
+        assert tol[q] == 16 * worst[q]
+    assert tol["x3"] == 2.0 ** -15 + tol["y"]
+
+
+def _window_form_constants():
+    src = open(os.path.join(ROOT, "deepbedmap_amd", "csrc", "deform_fused.hip")).read()
+    return {k: int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1)) for k in ("DWF_R", "DWF_POS", "DWF_MAXPIX")}
+
+
+def fp32_window_ok(H, W, R, POS, MAXPIX):
+    """launch_deform_conv_fused: (span_rows + 2 R + 3) * (W + 2 R + 3) <= DWF_MAXPIX, span_rows = min(H, (POS - 1 + W - 1) / W + 1)"""
+    span_rows = min(H, (POS - 1 + W - 1) // W + 1)
+    return (span_rows + 2 * R + 3) * (W + 2 * R + 3) <= MAXPIX
+
+
+def test_forward_table_sits_on_both_sides_of_the_window_threshold():
+    k = _window_form_constants()
+    assert k == {"DWF_R": 2, "DWF_POS": 128, "DWF_MAXPIX": 528}, k
+    ok = lambda H, W: fp32_window_ok(H, W, k["DWF_R"], k["DWF_POS"], k["DWF_MAXPIX"])   # noqa: E731
+    for H, last in ((6, 37), (36, 37), (5, 37), (1, 59), (2, 51)):
+        assert ok(H, last) and not ok(H, last + 1), (H, last)
+        assert all(ok(H, w) for w in range(1, last + 1)) and not any(ok(H, w) for w in range(last + 1, 200)), H
+    planes = dict([(p, kern) for p, kern, _ in fwd.FP32_PLANES] + fwd.LATTICE_PLANES)
+    for (N, H, W), kern in planes.items():
+        assert kern == ("w" if ok(H, W) else "g"), (N, H, W)
+    for edge in ((1, 6, 37), (1, 6, 38), (1, 1, 59), (1, 1, 60), (1, 2, 51), (1, 2, 52)):
+        assert edge in planes, edge

@@ -29,7 +29,8 @@ all-float32 NumPy oracle against the same reference):
     goff     7.34e-07   C 64, O 64, (1, 1, 1), normal1            4.21e-07
     gw       1.07e-06   C 64, O 1, (2, 27, 79), converge          1.51e-06
     gb       1.29e-06   C 64, O 1, (1, 22, 97), normal1           3.84e-06
-The module takes 20 s there (154 device calls, twice as many evaluations of the NumPy oracle).
+The module takes 20 s there (154 device calls, twice as many evaluations of the NumPy oracle).  The `window_edge` regime (added with
+tests/test_gpu_deform_forward.py: offsets at the forward's LDS-window limit) brought four more fused rows, none above 4.8e-07.
 
 Found by the bitwise-repeat assertion: past plane 1476 (2133 with C = 64) launch_deform_backward scattered gx with fp32 atomics in
 deterministic mode too, so two identical calls differed in gx on (1, 22, 97) and (1, 7, 211).  It now sorts the sampling lists in
@@ -123,8 +124,25 @@ def regime_converge(rs, N, H, W):
     return _offsets_to(tx, ty, H, W)
 
 
+WINDOW_EDGE_VALUES = np.array([-2.0, np.nextafter(np.float32(-2.0), np.float32(-np.inf)), np.nextafter(np.float32(3.0), np.float32(-np.inf)),
+                               3.0, -2.5, 3.5], np.float32)
+
+
+def regime_window_edge(rs, N, H, W):
+    """normal(0, 0.5) with a third of the offsets at the limit of the forward's LDS windows: both window kernels keep offsets in
+    [-2, 3) and serve the others from memory.  The six values are dealt in turn to randomly chosen entries, the x offsets starting
+    with the first and the y offsets with the fourth, so that even a one-pixel plane holds every one of them."""
+    off = rs.normal(0, 0.5, size=(N, 18, H, W)).astype(np.float32)
+    for axis in (0, 1):
+        part = off[:, 9 * axis:9 * axis + 9].reshape(-1)   # (a copy: the slice is not contiguous)
+        idx = rs.permutation(part.size)[:(part.size + 2) // 3]
+        part[idx] = WINDOW_EDGE_VALUES[(np.arange(idx.size) + 3 * axis) % 6]
+        off[:, 9 * axis:9 * axis + 9] = part.reshape(N, 9, H, W)
+    return off
+
+
 REGIMES = {"zero": regime_zero, "tiny": regime_tiny, "lattice": regime_lattice, "normal1": regime_normal1, "border": regime_border,
-           "far": regime_far, "all_out": regime_all_out, "converge": regime_converge}
+           "far": regime_far, "all_out": regime_all_out, "converge": regime_converge, "window_edge": regime_window_edge}
 
 
 def is_exact_plane(H, W):
@@ -281,8 +299,9 @@ FUSED_SHAPES = [
 def _fused_cases():
     out = [(s, r) for s in FUSED_SHAPES for r in ("normal1", "tiny")]
     for s in ((3, 7, 15), (5, 36, 36)):
-        out += [(s, r) for r in REGIMES if r not in ("normal1", "tiny") and (r != "lattice" or is_exact_plane(*s[1:]))]
+        out += [(s, r) for r in REGIMES if r not in ("normal1", "tiny", "window_edge") and (r != "lattice" or is_exact_plane(*s[1:]))]
     out += [((1, 31, 63), "lattice"), ((1, 1, 7), "lattice"), ((2, 27, 79), "converge"), ((2, 27, 79), "all_out")]
+    out += [((3, 7, 15), "window_edge"), ((5, 36, 36), "window_edge")]   # (appended: the rows above keep their ids)
     return [(s, O, r) for s, r in out for O in (64, 1)]
 
 
