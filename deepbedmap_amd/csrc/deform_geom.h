@@ -1,6 +1,6 @@
 // Sampling geometry of the deformable convolution (reference srgan_train.py:506-523, :572-574; Chainer
 // deformable_convolution_2d_sampler + spatial_transformer_sampler semantics), shared by the sampler
-// kernels of deform_sampler.hip and the fused sampler + GEMM kernels of deform_fused.hip.  Every kernel takes a sample's corners,
+// kernels of deform_sampler.hip and the fused sampler + GEMM kernels of deform_fwd.hip, deform_window.hip and deform_bwd.hip.  Every kernel takes a sample's corners,
 // weights and coordinate gradients from here: the sequence of single float32 operations below IS the reference's (a coordinate next
 // to an integer lands on the side its rounding decides; tests/test_deform_cases_host.py shows what another sequence costs).
 #pragma once

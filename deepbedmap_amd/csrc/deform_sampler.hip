@@ -1,7 +1,7 @@
 // Deformable convolution sampler (reference srgan_train.py:506-523, :572-574; Chainer deformable_convolution_2d_sampler +
 // spatial_transformer_sampler semantics): the unfused half of the two deformable layers -- the sampler and its backward,
 // the transposed sampling operator as CSR lists (built per (image, tap), gathered per input pixel), the 576 -> 1 GEMV.  The fused
-// sampler + GEMM kernels are in deform_fused.hip, the launch sequences of the layers in deform_layer.hip.  Order: helpers, the
+// sampler + GEMM kernels are in deform_fwd.hip / deform_window.hip / deform_bwd.hip, the launch sequences of the layers in deform_layer.hip.  Order: helpers, the
 // position-per-thread kernels, the list builder and its three kernels, the gathers, the launchers.
 #include "dbm_internal.h"
 #include "deform_geom.h"
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(NT) void deform_csr_gather_kernel(const int* __rest
 }
 
 // G[n][t][q] = sum over the list entries of input pixel q of w * gy[n][p]: the transposed sampler applied to ONE value per position and
-// tap (the 64 -> 1 layer's backward in premultiplied form, deform_fused.hip); one thread per (image, tap, input pixel).
+// tap (the 64 -> 1 layer's backward in premultiplied form, deform_bwd.hip); one thread per (image, tap, input pixel).
 __global__ __launch_bounds__(256) void deform_csr_gather1_kernel(const int* __restrict__ g_offs, const int2* __restrict__ g_ent,
                                                                  const float* __restrict__ gy, float* __restrict__ G, int plane) {
   const int n = blockIdx.z, t = blockIdx.y;
@@ -471,7 +471,7 @@ void launch_deform_backward(const float* x, const float* off, const float* gcol,
   DBM_HIP(hipGetLastError());
 }
 
-// Input gradient only: the CSR gather from stored lists, without the offset gradients (which the fused kernels of deform_fused.hip
+// Input gradient only: the CSR gather from stored lists, without the offset gradients (which the fused kernels of deform_bwd.hip
 // produce).  False when a plane does not fit (the caller then takes launch_deform_backward).  The limit counts eight channel planes of
 // LDS beside the lists, which the register-only gather no longer uses: that is where the 2133 positions come from (the lists alone,
 // deform_csr_lists_ok, fit up to 3839).  It stays: it decides which kernels run.

@@ -489,7 +489,7 @@ void Generator::forward(GenWorkspace& ws, int N, int H, int W, const float* x, c
   // ---- nearest x2 + conv + LeakyReLU, twice; the resize is folded into the conv's gather (:556-568) ----
   const int H4 = 4 * h, W4 = 4 * w;
   const long P4 = 16 * hw;
-  // The sampler is fused into the GEMM (deform_fused.hip), fed from a channels-last copy of the layer input; the
+  // The sampler is fused into the GEMM (deform_fwd.hip, deform_window.hip), fed from a channels-last copy of the layer input; the
   // (N, 576, H, W) sample matrices exist only in a retained pass whose backward reads them (deform_layer.hip has the forms).
   const DeformForms f1 = deform_layer_forms(64, 64, H4, W4), f2 = deform_layer_forms(64, out_ch, H4, W4);
   // bf16 sweep mode (x3_tail): the upsampling and offset convolutions -- on the signal path, where plain bf16 costs ~100 m rms at the

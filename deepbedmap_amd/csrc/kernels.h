@@ -55,7 +55,7 @@ void launch_deform_backward(const float* x, const float* off, const float* gcol,
                             float* gx, float* goff, int N, int C, int H, int W, long offsn, hipStream_t s, float* ws);
 // the floats of list workspace `ws` it needs (0: none; in deterministic mode a plane past its LDS kernels sorts its lists in global memory)
 size_t deform_backward_workspace_floats(int N, int C, int H, int W);
-// sampler fused into the GEMM (deform_fused.hip): no column matrix.  C == 64, O == 64 (w = packed [576][64] image) or 1 (w = OIHW).
+// sampler fused into the GEMM (deform_fwd.hip, deform_window.hip; backward: deform_bwd.hip): no column matrix.  C == 64, O == 64 (w = packed [576][64] image) or 1 (w = OIHW).
 // xt = the layer input channels-last (N * H * W, 64); yt (optional, O == 64) = the output channels-last as well;
 // colout (optional, O == 64) = the sample matrix (N, 576, H, W) as a by-product (a retained pass: the weight gradient reads it)
 size_t deform_x3_packed_elems();   // bf16 elements of the split-bf16 weight image of a 64 -> 64 deformable layer

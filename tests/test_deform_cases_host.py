@@ -183,7 +183,7 @@ def test_only_all_out_has_no_mass_and_the_float32_oracle_sets_the_forward_tolera
 
 
 def _window_form_constants():
-    src = open(os.path.join(ROOT, "deepbedmap_amd", "csrc", "deform_fused.hip")).read()
+    src = open(os.path.join(ROOT, "deepbedmap_amd", "csrc", "deform_window.h")).read()
     return {k: int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1)) for k in ("DWF_R", "DWF_POS", "DWF_MAXPIX")}
 
 

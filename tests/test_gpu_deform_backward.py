@@ -307,7 +307,7 @@ def _fused_cases():
 
 @pytest.mark.parametrize("shape,O,regime", _fused_cases())
 def test_fused_forms(dbm, shape, O, regime):
-    """C = 64, O in {1, 64}, deterministic mode (the default): the fused kernels of deform_fused.hip up to plane 2133, the sample-matrix
+    """C = 64, O in {1, 64}, deterministic mode (the default): the fused kernels of deform_bwd.hip up to plane 2133, the sample-matrix
     forms beyond; which side ran is pinned by the profiler tags of the 64 -> 64 layer's launches."""
     tags = run_and_check(dbm, 64, O, shape, regime, repeat=True, profile=O == 64)
     if O == 64:

@@ -11,12 +11,10 @@ quarters of its buffer accesses were dummies on the 9 x 9 planes -- so: a pointe
 """
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "deepbedmap_amd", "csrc")
+from hip_asm import CSRC, compile_to_asm, demangle
+
 STORE = re.compile(r"^\s*(global_store|buffer_store|flat_store|global_atomic|buffer_atomic|flat_atomic)")
 LOAD = re.compile(r"^\s*(global_load|buffer_load|flat_load)")   # (LDS-DMA forms included: they count in vmcnt too)
 WAIT = re.compile(r"s_waitcnt.*vmcnt\((\d+)\)")
@@ -24,42 +22,38 @@ FUNC = re.compile(r"^(_Z\w+):")
 
 
 def scan(path):
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "a.s")
-        r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "-o", asm, path],
-                           capture_output=True, text=True, cwd=CSRC)
-        if r.returncode != 0:
-            print(f"{os.path.basename(path)}: compile failed\n{r.stderr[-400:]}")
-            return
-        func, out = None, {}
-        pending = []   # outstanding vector-memory operations in issue order: 's' or 'l'
-        for line in open(asm):
-            m = FUNC.match(line)
-            if m:
-                func, pending = m.group(1), []
-                continue
-            if func is None:
-                continue
-            if "s_endpgm" in line:
-                func = None
-                continue
-            if STORE.match(line):
-                pending.append("s")
-            elif LOAD.match(line):
-                pending.append("l")
-            else:
-                w = WAIT.search(line)
-                if w:
-                    keep = int(w.group(1))
-                    done, pending = (pending[:len(pending) - keep], pending[len(pending) - keep:]) if keep < len(pending) else ([], pending)
-                    # a drain: the completed prefix holds a store that is FOLLOWED by a load inside the prefix (the wait was for that load)
-                    if "s" in done and "l" in done[done.index("s"):]:
-                        out[func] = out.get(func, 0) + 1
-        name = subprocess.run(["c++filt"] + list(out), capture_output=True, text=True).stdout.split("\n") if out else []
-        for (f, n), d in zip(out.items(), name):
-            print(f"{os.path.basename(path):24s} {n:3d}  {d.replace('(anonymous namespace)::', '').split('(')[0][:110]}")
-        if not out:
-            print(f"{os.path.basename(path):24s}   0")
+    asm, err = compile_to_asm(path)
+    if asm is None:
+        print(f"{os.path.basename(path)}: compile failed\n{err}")
+        return
+    func, out = None, {}
+    pending = []   # outstanding vector-memory operations in issue order: 's' or 'l'
+    for line in asm.splitlines():
+        m = FUNC.match(line)
+        if m:
+            func, pending = m.group(1), []
+            continue
+        if func is None:
+            continue
+        if "s_endpgm" in line:
+            func = None
+            continue
+        if STORE.match(line):
+            pending.append("s")
+        elif LOAD.match(line):
+            pending.append("l")
+        else:
+            w = WAIT.search(line)
+            if w:
+                keep = int(w.group(1))
+                done, pending = (pending[:len(pending) - keep], pending[len(pending) - keep:]) if keep < len(pending) else ([], pending)
+                # a drain: the completed prefix holds a store that is FOLLOWED by a load inside the prefix (the wait was for that load)
+                if "s" in done and "l" in done[done.index("s"):]:
+                    out[func] = out.get(func, 0) + 1
+    for (f, n), d in zip(out.items(), demangle(out)):
+        print(f"{os.path.basename(path):24s} {n:3d}  {d[:110]}")
+    if not out:
+        print(f"{os.path.basename(path):24s}   0")
 
 
 if __name__ == "__main__":
