@@ -180,6 +180,11 @@ SIGNATURES = {
                        C.c_void_p, C.c_void_p],
     "dbm_png_encode_host": [C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                             C.c_void_p, C.c_int],
+    "dbm_grid_minmax": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p],
+    "dbm_grid_perspective": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_void_p],
+    "dbm_grid_perspective_host": [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int],
     "dbm_grid_rescale": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "dbm_grid_rolling_std": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_void_p],
     "dbm_points_polar_stereographic": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_int],

@@ -600,6 +600,44 @@ int dbm_png_encode(dbm_ctx* ctx, const uint8_t* image_dev, long H, long W, int c
   DBM_API_END
 }
 
+// ---- the perspective view of a plane (perspective.hip; the host entry dbm_grid_perspective_host stands there) ----
+int dbm_grid_minmax(dbm_ctx* ctx, const float* plane_dev, long H, long W, double* out_host) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_grid_minmax: NULL context");
+  DBM_CHECK(plane_dev != nullptr && out_host != nullptr, "dbm_grid_minmax: NULL plane or output");
+  check_plane("dbm_grid_minmax", H, W, 1, "H W must stay below 2^31 samples", "empty plane");
+  ScopedBuf ws;   // this call's own, released on every path
+  double* out = (double*)ws.as<char>(grid_minmax_workspace(H, W));
+  launch_grid_minmax(plane_dev, H, W, out, ctx->stream);
+  DBM_HIP(hipMemcpyAsync(out_host, out, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
+  DBM_API_END
+}
+
+int dbm_grid_perspective(dbm_ctx* ctx, const float* plane_dev, long H, long W, const uint8_t* drape_dev, int drape_channels, const double* view_host,
+                         long Wo, long Ho, const uint8_t* facade_rgba, const uint8_t* background_rgba, uint8_t* out_dev, int32_t* hits_dev) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr, "dbm_grid_perspective: NULL context");
+  note_device_write(ctx);
+  PerspLaunch a{};
+  perspective_check_arguments("dbm_grid_perspective", plane_dev, H, W, drape_dev, drape_channels, view_host, Wo, Ho, background_rgba, out_dev, a.v);
+  a.plane = plane_dev;
+  a.H = H; a.W = W;
+  a.drape = drape_dev;
+  a.channels = drape_channels;
+  a.Wo = Wo; a.Ho = Ho;
+  a.facade_on = facade_rgba != nullptr;
+  if (facade_rgba) std::memcpy(a.facade, facade_rgba, 4);
+  std::memcpy(a.background, background_rgba, 4);
+  a.out = out_dev;
+  a.hits = hits_dev;
+  ScopedBuf ws;   // this call's own, released on every path
+  const size_t bytes = grid_perspective_workspace(a);
+  launch_grid_perspective(a, bytes ? ws.as<char>(bytes) : nullptr, ctx->stream);
+  DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
+  DBM_API_END
+}
+
 int dbm_grid_rescale(dbm_ctx* ctx, const float* in_dev, long H, long W, long out_h, long out_w, int order, int anti_aliasing, int clip,
                      int input_cast, float* out_dev) {
   DBM_API_BEGIN(ctx)

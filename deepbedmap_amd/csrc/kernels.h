@@ -524,6 +524,38 @@ void launch_grid_relief(const ReliefLaunch& a, hipStream_t s);
 size_t shade_stats_workspace(long H, long W);
 void launch_shade_stats(const ReliefLaunch& a, void* ws, hipStream_t s);
 
+// Perspective view of a plane (perspective.hip; dbm_grid_perspective, dbm_grid_perspective_host, dbm_grid_minmax; the rule: the head of
+// perspective.hip and DESIGN.md 6o): the float32 plane (H, W) and its drape, uint8 (H, W, channels) at the nodes -> out, uint8 (Ho, Wo,
+// 4), and hits, int32 (Ho, Wo) or null: the id of the visible triangle, -2 a wall, -1 none.  All DEVICE pointers.  The launch fills
+// the block counts and the workspace pointers itself from ws (grid_perspective_workspace(a) bytes; none if H < 2 or W < 2).
+// perspective_check_arguments: what the device and the host entry refuse alike; fills the view from the caller's nine doubles.
+// launch_grid_minmax leaves {count of finite samples, min, max} (NaN, NaN if the count is 0) in the first three doubles of ws.
+struct PerspView {
+  double sin_a, cos_a, sin_e, tan_e, level, zfac, sx0, sy0, step;
+};
+struct PerspLaunch {
+  const float* plane;
+  long H, W;
+  const uint8_t* drape;
+  int channels;
+  PerspView v;
+  long Wo, Ho;
+  int facade_on;
+  uint8_t facade[4], background[4];
+  uint8_t* out;
+  int32_t* hits;
+  float *max8, *max64, *part, *zrange;   // (the launch's own)
+  long n8x, n8y, n64x, n64y;
+};
+size_t grid_perspective_workspace(const PerspLaunch& a);
+void launch_grid_perspective(const PerspLaunch& a, void* ws, hipStream_t s);
+void perspective_check_arguments(const char* who, const void* plane, long H, long W, const void* drape, int drape_channels, const double* view,
+                                 long Wo, long Ho, const void* background, const void* out, PerspView& v);
+// the render on host threads from HOST pointers (no GPU): the plain walk, or with `skipping` the device's own traversal
+void perspective_render_host(const PerspLaunch& a, bool skipping, int nthreads);
+size_t grid_minmax_workspace(long H, long W);
+void launch_grid_minmax(const float* plane, long H, long W, void* ws, hipStream_t s);
+
 // An 8-bit image -> the bands of a PNG's filtered scanlines (png_encode.hip; dbm_png_encode): band b of the call holds the image rows
 // (first_band + b) * band_rows ..., each as one filter-type byte and row_bytes filtered bytes (filter 0 None, 1 Sub, 2 Up, from the raw
 // image), at raw + b * raw_stride (raw_stride a multiple of 16, >= band_rows * (row_bytes + 1)).  png_check_arguments: what the device

@@ -9,8 +9,8 @@ of the same bytes; `write_png_resident`; `read_png`), the NumPy statement of the
 (`relief_image`, `render_dem`).
 
 The rules are this project's own and are stated in DESIGN.md 6n; GMT's pixels are NOT claimed: its HSV illumination, its handling of
-hinges from version to version and its dpi resampling are not restated.  `grdview` 3-D plots, axes, text and histograms stay out of
-scope.  No CPU fallback: the device calls raise DbmError without a GPU; the host calls (`relief_image_host`, `save_png`, `read_png`,
+hinges from version to version and its dpi resampling are not restated.  The `grdview` 3-D view is perspective.py; axes, text and histograms stay
+out of scope.  No CPU fallback: the device calls raise DbmError without a GPU; the host calls (`relief_image_host`, `save_png`, `read_png`,
 the colour tables) need none.
 """
 import dataclasses
@@ -586,25 +586,16 @@ def reduced_geometry(geometry, k):
                                dx=geometry.dx * f, dy=geometry.dy * f)
 
 
-def render_dem(grid, path, cpt, shading=None, reduce=0, max_size=4096, nodata=None, filter=1, world_file=True, ctx=None, aspect=1.0,
-               channels=4, band_rows=None):
-    """The reference's last step (deepbedmap.py:758-775) without GMT and without downloading the plane: `grid` -- a float32 DeviceArray,
-    a Raster (its nodata and geometry are used) or a NumPy array that is uploaded -- coloured by `cpt` (with `shading`) and written as
-    the PNG `path`.
-    nodata: samples that match this finite value by the Raster rule (|v - nodata| <= 1e-8 + 1e-5 |nodata|, dbm_grid_tile) become NaN
-    first, in a copy; NaN samples take the table's NaN colour and alpha 0.
-    reduce = k: level k of `build_overviews` (float32, NaN as nodata: the nodata-aware 2 x 2 mean) is rendered instead of the plane;
-    "auto": the smallest k with max(H_k, W_k) <= max_size.
-    world_file: with a Raster, the .pgw of the rendered level is written next to the file.
-    Returns (path, the GridGeometry of the image or None)."""
+def prepared_plane(who, grid, nodata=None, reduce=0, max_size=4096, ctx=None):
+    """What `render_dem` and `plot_3d_view` do to a grid before they colour it: (the resident float32 plane, its GridGeometry or None).
+    grid: a float32 DeviceArray, a Raster (its nodata and geometry are used) or a NumPy array that is uploaded.  nodata: samples that
+    match this finite value by the Raster rule become NaN, in a copy.  reduce = k: level k of `build_overviews` (float32, NaN as nodata)
+    and its `reduced_geometry`; "auto": the smallest k with max(H_k, W_k) <= max_size.  `who` opens the messages."""
     import ctypes as C
 
     from .geotiff import build_overviews
     from .tiling import Raster
 
-    who = "render_dem"
-    _check_render(who, cpt, channels, aspect)
-    shading_parameters(shading)
     geometry = None
     if isinstance(grid, Raster):
         geometry = grid.geometry
@@ -646,6 +637,24 @@ def render_dem(grid, path, cpt, shading=None, reduce=0, max_size=4096, nodata=No
         plane = build_overviews(plane, k, np.float32, float("nan"))[-1]
         if geometry is not None:
             geometry = reduced_geometry(geometry, k)
+    return plane, geometry
+
+
+def render_dem(grid, path, cpt, shading=None, reduce=0, max_size=4096, nodata=None, filter=1, world_file=True, ctx=None, aspect=1.0,
+               channels=4, band_rows=None):
+    """The reference's last step (deepbedmap.py:758-775) without GMT and without downloading the plane: `grid` -- a float32 DeviceArray,
+    a Raster (its nodata and geometry are used) or a NumPy array that is uploaded -- coloured by `cpt` (with `shading`) and written as
+    the PNG `path`.
+    nodata: samples that match this finite value by the Raster rule (|v - nodata| <= 1e-8 + 1e-5 |nodata|, dbm_grid_tile) become NaN
+    first, in a copy; NaN samples take the table's NaN colour and alpha 0.
+    reduce = k: level k of `build_overviews` (float32, NaN as nodata: the nodata-aware 2 x 2 mean) is rendered instead of the plane;
+    "auto": the smallest k with max(H_k, W_k) <= max_size.
+    world_file: with a Raster, the .pgw of the rendered level is written next to the file.
+    Returns (path, the GridGeometry of the image or None)."""
+    who = "render_dem"
+    _check_render(who, cpt, channels, aspect)
+    shading_parameters(shading)
+    plane, geometry = prepared_plane(who, grid, nodata, reduce, max_size, ctx)
     image = relief_image(plane, cpt, shading=shading, aspect=aspect, channels=channels)
     write_png_resident(path, image, filter=filter, band_rows=band_rows, world_file=geometry if world_file else None)
     return path, geometry

@@ -780,6 +780,38 @@ int dbm_png_encode(dbm_ctx* ctx, const uint8_t* image_dev, long H, long W, int c
 int dbm_png_encode_host(const void* image, long H, long W, int channels, int filter, int band_rows, long first_band, int n_bands, void* out,
                         size_t out_capacity, size_t* sizes, uint32_t* adlers, int nthreads);
 
+/* ---- the 3-D perspective view of the DEM (deepbedmap.py:258-295, `plot_3d_view`: `fig.grdview(..., surftype="sim", plane=zmin,
+ * zscale=0.01, perspective=[202.5, 60])`).  A hidden-surface render of the height field under an orthographic view; the frame, the
+ * view's angles and the product stay with the host shim deepbedmap_amd/perspective.py.  The rule is this project's own -- GMT's pixels
+ * are not claimed -- and is stated operation by operation in DESIGN.md 6o and at the head of csrc/perspective.hip ----
+ * dbm_grid_minmax (deepbedmap.py:258-295: the vertical range the frame is made from) returns out_host[3] = {count of finite samples,
+ * min, max} of the float32 plane plane_dev (H, W), a DEVICE pointer; min and max are order-free and therefore exact; NaN, NaN if the
+ * count is 0.  The call allocates its workspace, frees it on every path and synchronises.  Refused (status 1): NULL pointers, an empty
+ * plane or H * W >= 2^31.
+ * dbm_grid_perspective (deepbedmap.py:258-295) renders the plane plane_dev (H, W; rows north-up; node (r, c) at east c, north -r, height
+ * h = (z - level) zfac) draped with drape_dev, uint8 (H, W, drape_channels) at the nodes (what dbm_grid_relief wrote for the plane; a
+ * fourth channel is not read), into out_dev, uint8 (Ho, Wo, 4), and, unless NULL, the ids of the visible triangles into hits_dev,
+ * int32 (Ho, Wo): 2 (r (W - 1) + c) + t for triangle t of cell (r, c), -2 a wall of the facade, -1 none.  plane, drape, out and hits
+ * are DEVICE pointers.  view_host (HOST, nine doubles): sin A, cos A, sin E, tan E, level, zfac, sx0, sy0, step -- the caller computes
+ * the functions of the azimuth A (clockwise from north, where the viewer stands) and of the elevation E once; pixel (i, j) looks along
+ * the ray through screen point sx = sx0 + (j + 0.5) step, sy = sy0 - (i + 0.5) step.  facade_rgba (HOST, four bytes, or NULL: no
+ * facade): the colour of the vertical walls between height 0 and the boundary profile on the four outer edges; background_rgba
+ * (HOST, four bytes): the colour of a pixel that sees nothing.  Every operation of the pixel rule is one IEEE float64 operation,
+ * never an FMA; the image does not depend on the traversal (blocks of 8 x 8 and 64 x 64 cells are skipped by their maxima; the walk
+ * stops behind the visible hit).  H < 2 or W < 2 renders the background.  The call allocates its workspace (4 bytes per 8 x 8 block,
+ * 12 per 64 x 64 block), frees it on every path and synchronises.
+ * Refused (status 1, nothing launched): NULL pointers (but facade_rgba and hits_dev), drape_channels not 3 or 4, an empty plane or
+ * image, H * W, Wo * Ho or 2 (H - 1) (W - 1) >= 2^31, a view value that is not finite, sin A^2 + cos A^2 off 1 by more than 1e-6,
+ * sin E, tan E, zfac or step <= 0.
+ * dbm_grid_perspective_host (deepbedmap.py:258-295): the same bytes from HOST arrays on `nthreads` host threads -- the kernel's own
+ * cell, wall and colour functions under a PLAIN traversal: every cell the ray's ground line meets, no blocks, no early stop.  No GPU,
+ * no context; the same refusals. */
+int dbm_grid_minmax(dbm_ctx* ctx, const float* plane_dev, long H, long W, double* out_host);
+int dbm_grid_perspective(dbm_ctx* ctx, const float* plane_dev, long H, long W, const uint8_t* drape_dev, int drape_channels, const double* view_host,
+                         long Wo, long Ho, const uint8_t* facade_rgba, const uint8_t* background_rgba, uint8_t* out_dev, int32_t* hits_dev);
+int dbm_grid_perspective_host(const float* plane, long H, long W, const uint8_t* drape, int drape_channels, const double* view, long Wo, long Ho,
+                              const uint8_t* facade_rgba, const uint8_t* background_rgba, uint8_t* out, int32_t* hits, int nthreads);
+
 /* One minibatch of `trainer` (srgan_train.py:1286-1309) as ONE call: train_eval_discriminator (:1084-1166) with its
  * optimizer update, then train_eval_generator (:1170-1263) with its update; both optimizers must have been set up
  * (dbm_adam_setup).  Numerically the two step calls + two dbm_adam_update calls, bit for bit; scheduled as a whole: the
