@@ -28,6 +28,7 @@ from .netcdf import (NetcdfVariable, open_netcdf, read_netcdf, read_netcdf_resid
 from .relief import (ColorTable, adler32_combine, grey_cpt, make_cpt, read_cpt, read_png, relief_image,  # noqa: F401
                      relief_image_host, render_dem, save_png, write_png_resident)
 from .perspective import View, grid_minmax, perspective_frame, perspective_image, perspective_image_host, plot_3d_view  # noqa: F401
+from .overlay import Layer, draw_layers, draw_layers_host, render_map  # noqa: F401
 from .tiling import Raster, fill_gaps, get_deepbedmap_model_inputs, get_window_bounds, selective_tile, tile_training_set  # noqa: F401
 from .polygons import (Polygons, mask_outside, polygon_mask, read_polygons, read_tiles_geojson, select_tiles,  # noqa: F401
                        tiles_to_geojson)

@@ -203,6 +203,9 @@ SIGNATURES = {
     "dbm_grid_polygon_mask": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_long, C.c_long, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p,
                               C.c_size_t, C.c_int],
     "dbm_grid_polygon_stats": [C.c_void_p, C.POINTER(C.c_int64)],
+    "dbm_image_overlay": [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                          C.c_double, C.c_char_p, C.c_int, C.c_size_t, C.c_int],
+    "dbm_image_overlay_stats": [C.c_void_p, C.POINTER(C.c_int64)],
     "dbm_adam_setup": [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double],
     "dbm_adam_update": [C.c_void_p, C.c_double],
     "dbm_discriminator_step": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

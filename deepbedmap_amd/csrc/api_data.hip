@@ -1026,4 +1026,78 @@ int dbm_grid_polygon_stats(dbm_ctx* ctx, int64_t out[6]) {
   DBM_API_END
 }
 
+// ---- vector layers on a resident image (overlay.hip) ----
+int dbm_image_overlay(dbm_ctx* ctx, unsigned char* image_dev, long H, long W, int channels, const double geom[4], const double* prims,
+                      size_t n, int kind, int stride, double size_px, const unsigned char rgba[4], int samples, size_t workspace_limit,
+                      int flags) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && image_dev != nullptr && geom != nullptr && rgba != nullptr, "dbm_image_overlay: NULL context, image, geometry or colour");
+  note_device_write(ctx);
+  check_plane("dbm_image_overlay", H, W, 1, "H W must stay below 2^31 pixels", "empty image");
+  DBM_CHECK(channels == 3 || channels == 4, "dbm_image_overlay: channels must be 3 or 4");
+  DBM_CHECK(n < ((size_t)1 << 31), "dbm_image_overlay: n must stay below 2^31");
+  check_geometry("dbm_image_overlay", geom, "the geometry must be finite with non-zero dx and dy");
+  DBM_CHECK(kind == DBM_OVERLAY_SEGMENTS || kind == DBM_OVERLAY_DISCS, "dbm_image_overlay: kind must be DBM_OVERLAY_SEGMENTS or DBM_OVERLAY_DISCS");
+  DBM_CHECK(kind == DBM_OVERLAY_SEGMENTS ? stride == 4 : (stride == 2 || stride == 3),
+            "dbm_image_overlay: the stride is 4 doubles for segments, 2 or 3 for discs");
+  DBM_CHECK(std::isfinite(size_px) && size_px >= 0.0, "dbm_image_overlay: the size must be finite and not negative");
+  DBM_CHECK(samples == 1 || samples == 2 || samples == 4, "dbm_image_overlay: samples must be 1, 2 or 4");
+  DBM_CHECK(n == 0 || prims != nullptr, "dbm_image_overlay: NULL primitive table");
+  const bool dev = device_ptrs(flags);
+  const int used = kind == DBM_OVERLAY_SEGMENTS ? 4 : 2;   // columns that are coordinates
+  if (!dev)
+    for (size_t i = 0; i < n; ++i)
+      for (int k = 0; k < used; ++k)
+        DBM_CHECK(std::isfinite(prims[i * (size_t)stride + k]), "dbm_image_overlay: primitive " + std::to_string(i) + " has a non-finite coordinate");
+  OverlayLaunch a = {};
+  a.n = (long)n;
+  a.H = H; a.W = W;
+  a.kind = kind; a.stride = stride; a.channels = channels; a.S = samples;
+  a.x0 = geom[0]; a.y0 = geom[1]; a.dx = geom[2]; a.dy = geom[3];
+  a.size = size_px;
+  overlay_geometry(a);
+  a.image = image_dev;
+  memcpy(a.rgba, rgba, 4);
+  a.word_aligned = ((uintptr_t)image_dev & 3u) == 0 ? 1 : 0;
+  long long stats[4] = {0, 0, 0, (long long)n};
+  if (n > 0) {
+    ScopedBuf ws, bins;   // this call's own, released on every path
+    double* staged = overlay_carve(a, ws.as<char>(overlay_workspace(a, !dev)), !dev);
+    a.prims = prims;
+    if (!dev) {
+      DBM_HIP(hipMemcpyAsync(staged, prims, n * (size_t)stride * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      a.prims = staged;
+    }
+    launch_overlay_cull(a, ctx->stream);
+    unsigned long long totals[8];
+    DBM_HIP(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
+    DBM_HIP(hipStreamSynchronize(ctx->stream));
+    DBM_CHECK(totals[2] == 0ull, "dbm_image_overlay: " + std::to_string(totals[2]) + " primitives have a non-finite coordinate; nothing was written");
+    a.kept = (unsigned)totals[0];
+    const unsigned long long entries = totals[1];
+    const size_t limit = workspace_limit ? workspace_limit : DBM_POLY_WORKSPACE_DEFAULT;
+    const bool binned = a.kept > 0u && entries < (1ull << 31) && entries * sizeof(unsigned) <= limit;
+    if (a.kept > 0u) {
+      if (binned) {
+        a.entries = bins.as<unsigned>((size_t)entries);
+        launch_overlay_bin(a, ctx->stream);
+      }
+      launch_overlay_paint(a, ctx->stream);
+    }
+    DBM_HIP(hipStreamSynchronize(ctx->stream));   // the workspace is freed when this scope ends
+    stats[0] = (long long)totals[0];
+    stats[1] = (long long)totals[1];
+    stats[2] = binned ? 1LL : 0LL;
+  }
+  memcpy(ctx->overlay_stats, stats, sizeof(stats));
+  DBM_API_END
+}
+
+int dbm_image_overlay_stats(dbm_ctx* ctx, int64_t out[4]) {
+  DBM_API_BEGIN(ctx)
+  DBM_CHECK(ctx != nullptr && out != nullptr, "dbm_image_overlay_stats: NULL argument");
+  for (int k = 0; k < 4; ++k) out[k] = (int64_t)ctx->overlay_stats[k];
+  DBM_API_END
+}
+
 }  // extern "C"

@@ -753,3 +753,35 @@ double* polygon_carve(PolyLaunch& a, void* ws, bool stage_edges_too);
 void launch_polygon_cull(const PolyLaunch& a, hipStream_t s);
 void launch_polygon_bin(const PolyLaunch& a, hipStream_t s);
 void launch_polygon_classify(const PolyLaunch& a, hipStream_t s);
+
+// Vector layers on a resident image (overlay.hip; dbm_image_overlay): prims (n rows of `stride` float64: xa, ya, xb, yb for segments,
+// x, y[, z] for discs) on the device; image uint8 (H, W, channels), painted in place.  overlay_geometry fills the tiling, the radius,
+// its square and gmag from H, W, size; overlay_carve hands out overlay_workspace bytes (256-byte aligned; returns the staging area for a
+// host table if asked for).  launch_overlay_cull fills conv (the kept primitives in pixel units) and totals = {kept primitives, entries
+// the tile bins would hold, primitives with a non-finite coordinate}; the host reads totals, sets kept and -- if it bins -- entries
+// (totals[1] indices), then launch_overlay_bin; launch_overlay_paint blends the layer into the image.
+struct OverlayLaunch {
+  const double* prims;
+  long n, H, W;
+  int kind, stride, channels, S;     // DBM_OVERLAY_SEGMENTS / _DISCS; doubles per row; 3 or 4; sub-samples per pixel side: 1, 2 or 4
+  double x0, y0, dx, dy, size;
+  double radius, r2, gmag;           // size / 2, its square as rounded, the largest of W, H and the radius
+  long tiles_x, tiles_y, nbins;      // pixel tiles per row, tile rows; tiles_x tiles_y bins
+  double* conv;                      // n rows of 4 (segments) or 2 (discs) doubles: the kept primitives, pixel units
+  unsigned* cnt;                     // nbins
+  unsigned* cursor;                  // nbins
+  unsigned* off;                     // nbins + 1
+  unsigned* part;                    // per scan tile
+  unsigned long long* totals;        // 8
+  unsigned* entries;                 // null: unbinned
+  unsigned kept;
+  unsigned char* image;
+  unsigned char rgba[4];
+  int word_aligned;                  // the image may be read and written as 32-bit words (channels == 4)
+};
+void overlay_geometry(OverlayLaunch& a);
+size_t overlay_workspace(const OverlayLaunch& a, bool stage_prims_too);
+double* overlay_carve(OverlayLaunch& a, void* ws, bool stage_prims_too);
+void launch_overlay_cull(const OverlayLaunch& a, hipStream_t s);
+void launch_overlay_bin(const OverlayLaunch& a, hipStream_t s);
+void launch_overlay_paint(const OverlayLaunch& a, hipStream_t s);

@@ -111,6 +111,7 @@ struct dbm_ctx {
   DevBuf resample_tmp;        // dbm_grid_rescale: min / max, Gaussian weights and the float64 planes (doubles)
   DevBuf points_tmp;          // dbm_points_region: the workgroups' boxes; dbm_points_blockmedian: block indices, histogram, scan, lists
   long long poly_stats[6] = {};  // list sizes of the last successful dbm_grid_polygon_mask (dbm_grid_polygon_stats)
+  long long overlay_stats[4] = {};  // the same of the last successful dbm_image_overlay (dbm_image_overlay_stats)
   // What the op-level entry points (api_ops.hip) keep from call to call, made on first use on this context's device.
   struct OpState {
     // One inbox and one launch counter for both trunk ops: successive calls meet each other's granules, as the passes of a generator's

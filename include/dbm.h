@@ -74,6 +74,14 @@ enum {
   DBM_POLY_TILE = 16,
   DBM_POLY_CHUNK = 256
 };
+/* dbm_image_overlay: the two kinds of primitives, the side of a pixel tile (one 256-thread workgroup paints TILE x TILE pixels) and the
+ * number of primitives a workgroup stages into LDS at a time (overlay.hip).  Listed here so that tests can put images and primitive
+ * counts on both sides of them. */
+enum { DBM_OVERLAY_SEGMENTS = 0, DBM_OVERLAY_DISCS = 1 };
+enum {
+  DBM_OVERLAY_TILE = 16,
+  DBM_OVERLAY_CHUNK = 256
+};
 /* dbm_text_*: bytes of text a workgroup stages and parses the lines of, its threads (text.hip: a thread owns the lines that start in
  * its TILE_BYTES / THREADS bytes), the separator value that stands for runs of spaces and tabs (`\s+`), and the limits of the reader
  * description.  Listed here so that tests can put newlines, numbers and long lines on both sides of every tile edge. */
@@ -527,6 +535,47 @@ int dbm_grid_to_pixel(dbm_ctx* ctx, const float* in_dev, long H, long W, double 
 int dbm_grid_polygon_mask(dbm_ctx* ctx, const double* edges, size_t n_edges, long H, long W, const double geom[4], double buffer,
                           unsigned char* mask_dev, float* grid_dev, size_t workspace_limit, int flags);
 int dbm_grid_polygon_stats(dbm_ctx* ctx, int64_t out[6]);
+
+/* ---- the maps' vector layers (paper_figures.py:533-562, Figure 2: `fig.coast(shorelines="0.25p")` -- the grounding line on the DEM --
+ * and `fig.plot(style="r+s", pen="1p,orange2")` -- the study regions and the training tiles as boxes; paper_figures.py:1039-1045, Figure
+ * 5a: `fig.plot(style="c0.1c", color="orange")` -- the transect's survey points on the Thwaites DEM) ----
+ * dbm_image_overlay paints ONE layer -- primitives of one kind, one size in pixels and one colour -- onto a resident image, in place.
+ * It is this project's own, exactly defined rule, NOT GMT's pixels (deepbedmap_amd/overlay.py: draw_layers_host is its
+ * NumPy statement).
+ * image_dev: uint8 (H, W, channels), channels 3 or 4, C-contiguous, ALWAYS device.  geom = {x0, y0, dx, dy}: pixel (r, c) has its
+ * centre at (x0 + c dx, y0 + r dy); either sign of dx and dy.
+ * prims: n rows of `stride` float64, a host table, or with DBM_DEVICE_PTRS a device table.  kind DBM_OVERLAY_SEGMENTS: rows (xa, ya,
+ * xb, yb), stride 4, drawn with a pen of size_px pixels; a segment of length zero is a dot.  kind DBM_OVERLAY_DISCS: rows (x, y) or
+ * (x, y, z) -- stride 2 or 3, z is not read -- drawn as discs of diameter size_px pixels.
+ * 1. Pixel units: u = (x - x0) / dx, v = (y - y0) / dy: one float64 subtraction and one division, each rounded.  All arithmetic below
+ *    is float64 IEEE, no fused multiply-add, IEEE division.
+ * 2. Pixel (r, c) has samples x samples sub-samples, samples S in {1, 2, 4}; sub-sample (i, j) lies at su = c + ((j + 1/2) / S - 1/2),
+ *    sv = r + ((i + 1/2) / S - 1/2), exactly.
+ * 3. With h = size_px / 2 and h2 = h * h (rounded once), a sub-sample is covered if SOME primitive has d2 <= h2 (closed).  Segments:
+ *    ex = ub - ua, ey = vb - va, px = su - ua, py = sv - va, L = ex ex + ey ey; t = L > 0 ? (px ex + py ey) / L : 0, clamped to [0, 1];
+ *    qx = px - t ex, qy = py - t ey, d2 = qx qx + qy qy -- dbm_grid_polygon_mask's distance in pixel units.  Discs: px = su - u,
+ *    py = sv - v, d2 = px px + py py.  A primitive whose pixel coordinates overflow covers nothing (d2 is inf or NaN).
+ * 4. With m = the number of covered sub-samples of the pixel, A = rgba[3], w = m A and D = S S 255, every colour channel becomes
+ *    (w rgba[ch] + (D - w) dst + D / 2) / D in integers (floor division); a fourth channel by the same formula with 255 in the place of
+ *    rgba[ch].  A pixel with m = 0 is not written.
+ * Layers are painted by successive calls, each over the result of the one before.
+ * The result is order-independent (an "any"): the same bytes from call to call, under any permutation of the primitives, and on either
+ * schedule -- primitives binned per tile of DBM_OVERLAY_TILE^2 pixels, or, when the bins would take more than workspace_limit bytes (0: a
+ * default of 256 MiB), every tile running over the whole list of kept primitives.  Culling never changes a result: boxes are grown by
+ * the radius plus a margin of 2^-30 of the coordinate magnitude, far above the rounding of d2 (overlay.hip).  Integer atomics place list
+ * entries; no float atomics.  Pixels are indexed with 64-bit integers: an image may hold more than 2^31 bytes.  The call allocates its
+ * workspace (32 bytes per segment, 16 per disc, 12 per pixel tile, 4 per bin entry; 8 stride per primitive more for a host table), frees
+ * it on every path, and synchronises the context's stream: once to read the counters back (for a device table, whether a coordinate was
+ * not finite -- before anything is written) and once before the workspace is released.
+ * Refused (status 1, nothing written): NULL ctx, image, geom or rgba, H or W < 1, H W >= 2^31, channels not 3 or 4, n >= 2^31, geom not
+ * finite or dx or dy zero, a kind that is neither, stride not 4 for segments or not 2 or 3 for discs, size_px negative or not finite,
+ * samples not 1, 2 or 4, a non-finite x or y of a primitive, NULL prims with n > 0.
+ * dbm_image_overlay_stats: out (HOST) = {primitives kept by the cull, tile bin entries, schedule (0 unbinned, 1 binned), n} of the
+ * context's last successful call. */
+int dbm_image_overlay(dbm_ctx* ctx, unsigned char* image_dev, long H, long W, int channels, const double geom[4], const double* prims,
+                      size_t n, int kind, int stride, double size_px, const unsigned char rgba[4], int samples, size_t workspace_limit,
+                      int flags);
+int dbm_image_overlay_stats(dbm_ctx* ctx, int64_t out[4]);
 
 /* ---- optimizer ---- */
 /* chainer.optimizers.Adam(alpha, eps=1e-8).setup(model): srgan_train.py:1043-1048 */
