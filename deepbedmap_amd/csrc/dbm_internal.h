@@ -178,6 +178,17 @@ struct PackJob {
 };
 void launch_pack_jobs(const PackJob* d_jobs, int njobs, int total_blocks, hipStream_t s);
 
+// A per-lane LDS base address the compiler knows nothing about: reads at base[constant] then carry the constant as the DS
+// instruction's immediate.  Left to itself hipcc folds every constant of the address into one immediate behind a shared register; where
+// that exceeds a field (8-bit dword offsets of ds_read2_b32) it rebuilds a base with a v_add_u32 in front of the read -- inside fp32
+// MFMA loops, where a vector-ALU instruction is paid in MFMA time (wgrad_wave_dma_9x9_kernel, trunk_fused_bwd_kernel).
+typedef __attribute__((address_space(3))) const float* lds_cf;
+__device__ __forceinline__ lds_cf lds_base(const float* shared) {
+  lds_cf q = (lds_cf)shared;
+  asm("" : "+v"(q));
+  return q;
+}
+
 // wgrad (wgrad.hip).  WgradDesc, WgradPlan, the form table and the planner are host-only C++ in wgrad_plan.h.
 #include "wgrad_plan.h"
 // x (N, Cin, Hin, Win) with image stride xsn, read through a nearest x2 resize where ups; dy (N, Cout, OH, OW) with image stride dysn;
@@ -212,6 +223,7 @@ struct WgradBatch {
   int nplans[NCAT] = {}, total_wg[NCAT] = {}, fold_wgs[NCAT] = {};
   size_t lds[NCAT] = {};
   double flops[NCAT] = {}, abytes[NCAT] = {};
+  bool wave_dma_9x9 = false;  // every plan of the wave-DMA form is a 9 x 9 plane, one image per band: wgrad_wave_dma_9x9_kernel runs them
   // layers on tiny planes (wgrad_s2tiny_kernel): their own plan table, outside the form table
   TinyPlan* d_tiny = nullptr;
   int n_tiny = 0, tiny_wgs = 0, tiny_rowlen = 4;

@@ -124,9 +124,14 @@ DI void issue_unit(float (&A)[AU], const float* p, int lane) {
 
 // The QU * 9 MFMAs of one unit.  The B operands of quad q + 1 are requested before the MFMAs of quad q and pinned there
 // (hipcc otherwise puts every ds_read right in front of its MFMA: one exposed LDS latency per pair of MFMAs).
-DI void mma_unit(const float (&A)[AU], int b, int b_next, float (&bq0)[9], f4v (&acc)[NACC]) {
-  // bq0 holds the operands of this unit's first quad (requested during the previous unit); on return those of the next
-  // unit's first quad (b_next < 0: there is none)
+// B addresses: quad c of the layer's input channels (four channel planes) starts 4 * CS floats behind quad c - 1 -- too far for the
+// 8-bit dword offsets of ds_read2_b32, and hipcc then rebuilt a base with a v_add_u32 in front of every pair, between the MFMAs (fp32
+// MFMAs and vector-ALU instructions exclude each other on a SIMD: paid in MFMA time).  So the layer keeps one base register per quad
+// (layer(): 8 or 16, live for the layer only) and every read below is a base plus the tap's immediate.
+template <int NQ>
+DI void mma_unit(const float (&A)[AU], const lds_cf (&B)[NQ], int c0, float (&bq0)[9], f4v (&acc)[NACC]) {
+  // c0: this unit's first quad.  bq0 holds its operands (requested during the previous unit); on return those of the next
+  // unit's first quad (c0 + QU == NQ: there is none)
   float bq[2][9];
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) bq[0][tap] = bq0[tap];
@@ -134,10 +139,10 @@ DI void mma_unit(const float (&A)[AU], int b, int b_next, float (&bq0)[9], f4v (
   for (int q = 0; q < QU; ++q) {
     if (q < QU - 1) {
 #pragma unroll
-      for (int tap = 0; tap < 9; ++tap) bq[(q + 1) & 1][tap] = lds[b + (q + 1) * 4 * CS + (tap / 3) * 10 + tap % 3];
-    } else if (b_next >= 0) {
+      for (int tap = 0; tap < 9; ++tap) bq[(q + 1) & 1][tap] = B[c0 + q + 1][(tap / 3) * 10 + tap % 3];
+    } else if (c0 + QU < NQ) {
 #pragma unroll
-      for (int tap = 0; tap < 9; ++tap) bq0[tap] = lds[b_next + (tap / 3) * 10 + tap % 3];
+      for (int tap = 0; tap < 9; ++tap) bq0[tap] = B[c0 + QU][(tap / 3) * 10 + tap % 3];
     }
     // (round 2) the nine reads above are dealt out BETWEEN the nine MFMAs below -- one MFMA, one DS read, ... -- instead
     // of standing in front of them: their issue slots disappear in the matrix pipe's shadow
@@ -235,7 +240,7 @@ template <int NCH> DI void halo_finish(const Args& a, const Wave& W, int plane0,
 // with), and the epilogue's own global reads (LeakyReLU masks) and the layer's halo requests follow the first unit.
 template <int KL, int NCH>
 DI void sub_tile(const Args& a, Wave& W, float (&A0)[AU], float (&A1)[AU], int s, int j, int gin_region, int dlow_region,
-                 int serial, const float (&bfirst)[9], HaloReq<NCH>* hq) {
+                 int serial, const float (&bfirst)[9], const lds_cf (&B)[KL == 4 ? 16 : 8], HaloReq<NCH>* hq) {
   constexpr int NU = (KL == 4 ? 16 : 8) / QU;
   constexpr int fin0 = KL == 4 ? 160 : KL == 3 ? 128 : KL == 2 ? 96 : KL == 1 ? 64 : 0;  // first channel that is final
   const int lane = W.lane;
@@ -243,8 +248,6 @@ DI void sub_tile(const Args& a, Wave& W, float (&A0)[AU], float (&A1)[AU], int s
   const int ch0 = 16 * mt + 4 * (lane >> 4);   // this lane's four output channels ch0 .. ch0 + 3
   const bool fin = 16 * mt >= fin0;            // wave-uniform
   const bool third = (j % 3 == 2), first = (j % 3 == 0);
-  // B operand planes: Gout bank (conv5) or D[64 + 32 KL ...]
-  const int breg = (KL == 4 ? gin_region : Q0 + 32 * KL * CS) + W.bofs;
 
   float maskv[4] = {1.f, 1.f, 1.f, 1.f};
   const bool use_mask = fin && (KL > 0 || j == 0);
@@ -276,7 +279,7 @@ DI void sub_tile(const Args& a, Wave& W, float (&A0)[AU], float (&A1)[AU], int s
       if (!DBM_ABL_BIT(a, 4)) W.wp += BUNIT;  // (abl 4: every unit re-reads the same weights -- always cache-hot; results wrong)
     }
     __builtin_amdgcn_sched_barrier(0);
-    mma_unit(cur, breg + u * QU * 4 * CS, u + 1 < NU ? breg + (u + 1) * QU * 4 * CS : -1, bq0, acc);
+    mma_unit(cur, B, u * QU, bq0, acc);
     __builtin_amdgcn_sched_barrier(0);
     if (TFB_LATE_LOADS && u == 0) {
       epilogue_reads();
@@ -360,11 +363,16 @@ template <int KL> DI void layer(const Args& a, Wave& W, float (&A0)[AU], float (
   HaloReq<NCH> hq;
   // the first quad's nine B operands are the same for all of this wavefront's sub-tiles of the layer: requested once
   float bfirst[9];
+  // B operand planes: Gout bank (conv5) or D[64 + 32 KL ...]; one base register per quad of input channels (mma_unit)
+  constexpr int NQ = KL == 4 ? 16 : 8;
+  lds_cf B[NQ];
   {
     TFB_T0();
     const int b0 = (KL == 4 ? gin_region : Q0 + 32 * KL * CS) + W.bofs;
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) bfirst[tap] = lds[b0 + (tap / 3) * 10 + tap % 3];
+    for (int c = 0; c < NQ; ++c) B[c] = lds_base(lds + b0 + c * 4 * CS);
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) bfirst[tap] = B[0][(tap / 3) * 10 + tap % 3];
 #ifdef TFB_TIMING
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) asm volatile("" ::"v"(bfirst[tap]));
@@ -382,7 +390,7 @@ template <int KL> DI void layer(const Args& a, Wave& W, float (&A0)[AU], float (
     }
     if (mine) {
       TFB_T0();
-      sub_tile<KL, NCH>(a, W, A0, A1, s, j, gin_region, dlow_region, serial, bfirst, (s == 0 && fetch) ? &hq : nullptr);
+      sub_tile<KL, NCH>(a, W, A0, A1, s, j, gin_region, dlow_region, serial, bfirst, B, (s == 0 && fetch) ? &hq : nullptr);
       TFB_ACC(0);
     }
   }

@@ -592,6 +592,201 @@ __global__ __launch_bounds__(128, 2) void wgrad_wave_dma_kernel(const WgradPlan*
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The wave-DMA form on 9 x 9 planes with one image per band -- the trunk's 181 layers.  WgradBatch::launch runs this kernel in place
+// of wgrad_wave_dma_kernel when EVERY plan of the launch is one (same plans, same LDS layout minus the position table, same grid).
+// The geometry is a compile-time constant and the K loop is unrolled over the band's 41 steps: every LDS read is a per-lane base
+// register plus an immediate, no position table is built or read, and no vector instruction sits between the MFMAs (fp32 MFMAs and
+// vector-ALU instructions exclude each other on a SIMD, DESIGN 4.1: the general loop's eight per step were paid in MFMA time).
+// The same MFMAs on the same operands in the same order as the general kernel: the same bits
+// (tests/test_gpu_exposed_kernels_bitwise.py).  Staging, bias gradient and epilogues are the general kernel's text.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(128, 2) void wgrad_wave_dma_9x9_kernel(const WgradPlan* __restrict__ plans, const int* __restrict__ starts,
+                                                                   int nplans) {
+  constexpr int T = 9;
+  constexpr int H = 9, W = 9, W1 = W + 1;
+  constexpr int plane = H * W;           // 81
+  constexpr int slab = 32 * plane;       // floats of the image's 32 dy planes
+  constexpr int PS = (H + 2) * W1;       // 110: framed x plane
+  constexpr int STEPS = (plane + 1) / 2; // 41: step s feeds positions 2 s + kh; the last one's kh = 1 half is the padding position 81
+  typedef __attribute__((address_space(3))) void* lds_ptr;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  int lo = 0, hi = nplans - 1;
+  const int wg = blockIdx.x;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (starts[mid] <= wg) lo = mid; else hi = mid - 1;
+  }
+  const WgradPlan& p = plans[lo];
+  const WgradDesc& d = p.d;
+  int local = wg - starts[lo];
+  const int wave = threadIdx.x >> 6;
+  const int ct = 2 * (local % p.groups) + wave;  // two wavefronts = two input tiles share one dy slab
+  local /= p.groups;
+  const int by = local % p.coutTiles;
+  const int bz = local / p.coutTiles;
+  float* ldsY = lds;                         // slab
+  float* ldsX0 = ldsY + slab + 4;            // 2 x 32 * PS, behind a 4-float zero guard (tap (0,0) of cell (0,0))
+  float* ldsX = ldsX0 + wave * 32 * PS;      // this wavefront's framed planes
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int j = lane & 31, kh = lane >> 5;
+  const int cout0 = by * 32, cin_w = ct * 32;
+  f32x16 acc[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  for (int e = tid; e < slab + 4 + 2 * 32 * PS; e += 128) lds[e] = 0.f;  // frames, guard, and the planes of ragged tiles
+  // per-lane source cell of the two DMA instructions that fill one framed plane (cells lane, lane + 64)
+  int soff[2];
+  bool sval[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int r = lane + 64 * k;
+    const int yy = r / W1, xx = r - yy * W1;
+    sval[k] = r < PS && yy >= 1 && yy <= H && xx < W;
+    soff[k] = sval[k] ? (yy - 1) * W + xx : 0;
+  }
+  const int nco = min(32, d.Cout - cout0), nci = max(0, min(32, d.Cin - cin_w));
+  const bool wave_active = nci > 0;
+  const int q4y = (nco * plane) >> 2;
+  float bsum = 0.f;
+#ifdef DBM_WG_TIMING
+  unsigned long long tS = 0, tK = 0;
+#endif
+  WG_T(t00);
+  for (int n = bz; n < p.nbands; n += p.S) {   // a band is an image
+    WG_T(tA);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();  // LDS stores / reads of the previous round (both wavefronts) are done before the DMA lands
+    if (n < d.N) {
+      const float4* srcy = (const float4*)(d.dy + (long)n * d.dysn + (long)cout0 * d.dysc);
+      for (int i0 = 64 * wave; i0 < q4y; i0 += 128)  // the two wavefronts split the shared slab
+        if (i0 + lane < q4y) __builtin_amdgcn_global_load_lds(srcy + i0 + lane, (lds_ptr)(ldsY + 4 * i0), 16, 0, 0);
+      const float* srcx = d.x + (long)n * d.xsn + (long)cin_w * d.xsc;
+      for (int c = 0; c < nci; ++c) {
+        if (sval[0]) __builtin_amdgcn_global_load_lds(srcx + c * plane + soff[0], (lds_ptr)(ldsX + c * PS), 4, 0, 0);
+        if (sval[1]) __builtin_amdgcn_global_load_lds(srcx + c * plane + soff[1], (lds_ptr)(ldsX + c * PS + 64), 4, 0, 0);
+      }
+    } else {  // (nbands == N with one image per band: kept with the general kernel's staging text)
+      for (int e = tid; e < slab; e += 128) ldsY[e] = 0.f;
+      for (int e = lane; e < 32 * PS; e += 64) ldsX[e] = 0.f;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    WG_T(tB);
+    WG_TACC(tS, tA, tB);
+    if (d.gb && ct == 0) {  // bias gradient: lane (j, kh) sums every other position of dy plane j (the general kernel's loop, IB = 1)
+      float part[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) part[u] = 0.f;
+      const float* yp = ldsY + j * plane;
+      int e = kh;
+      for (; e + 14 < plane; e += 16) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) part[u] += yp[e + 2 * u];
+      }
+      for (; e < plane; e += 2) part[0] += yp[e];
+      bsum += ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
+    }
+    if (wave_active) {
+      // Position q has dy offset q and x offset q + q / 9 (rows of W1 = 10 cells, relative to ldsX - 1).  Within a step the kh = 1 lanes
+      // are one cell further than the kh = 0 lanes, or two where 2 s is a row's last position: two base registers, the step's offset an
+      // immediate.  The last step has bases of its own: the padding position reads its A value from the zero guard behind the slab
+      // (the general kernel selects 0.f there) and its B values from position 0's cells, as the general kernel's table entry 0 does.
+      // (lds_base, dbm_internal.h: the slabs' constant offsets stay out of the immediates, which then fit ds_read2_b32)
+      const float* xrow = ldsX - 1 + j * PS;
+      const lds_cf aP = lds_base(ldsY + j * plane + kh);
+      const lds_cf aT = lds_base(kh ? ldsY + slab - (plane - 1) : ldsY + j * plane);
+      const lds_cf bP = lds_base(xrow + kh);
+      const lds_cf bR = lds_base(xrow + 2 * kh);
+      const lds_cf bT = lds_base(kh ? xrow - (plane - 1 + (plane - 1) / W) : xrow);
+      auto fetch = [&](int s, float& an, float (&bn)[T]) {   // operands of step s (s: a constant once unrolled)
+        const int kp = 2 * s, xo = kp + kp / W;
+        const bool last = s == STEPS - 1;
+        const lds_cf ap = last ? aT : aP;
+        const lds_cf bp = last ? bT : (kp % W == W - 1 ? bR : bP);
+        an = ap[kp];
+#pragma unroll
+        for (int t = 0; t < T; ++t) bn[t] = bp[xo + (t / 3) * W1 + (t % 3)];
+      };
+      // software pipelined by one step, as the general loop is: the reads of step s + 1 are dealt out between the MFMAs of step s
+      // (two operand sets in ping-pong; the scheduling barriers pin the order)
+      auto half = [&](int s, float& ac, float (&bc)[T], float& an, float (&bn)[T]) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (s + 1 < STEPS) fetch(s + 1, an, bn);
+#pragma unroll
+        for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, bc[t], acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // one DS read
+        }
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);    // the remaining reads
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      float a0, b0[T], a1, b1[T];
+      fetch(0, a0, b0);
+      static_assert(STEPS % 2 == 1, "the unrolled loop ends on the first operand set");
+#pragma unroll
+      for (int s = 0; s + 1 < STEPS; s += 2) {
+        half(s, a0, b0, a1, b1);
+        half(s + 1, a1, b1, a0, b0);
+      }
+      half(STEPS - 1, a0, b0, a1, b1);
+    }
+#ifdef DBM_WG_TIMING
+    asm volatile("s_nop 0" ::"v"(acc[8][15]));
+#endif
+    WG_T(tC);
+    WG_TACC(tK, tB, tC);
+  }
+  WG_T(tE);
+  if (p.partial) {
+    if (wave_active) store_partial<T>(p, bz, by, ct >> 1, wave, lane, d.scale, acc);
+    if (d.gb && ct == 0) {
+      bsum += __shfl_xor(bsum, 32, 64);
+      if (kh == 0) p.partial_b[((long)bz * p.coutTiles + by) * 32 + j] = d.scale * bsum;
+    }
+    return;
+  }
+  float *gWt, *gbt;
+  pair_targets(p, bz, gWt, gbt);
+  __syncthreads();  // the slabs are dead: each wavefront transposes through its own piece of the LDS
+  if (wave_active) {
+    constexpr int ROWF = 32 * T;
+    float* tw = lds + wave * (8 * ROWF);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) tw[(rr + 4 * kh) * ROWF + j * T + t] = d.scale * acc[t][4 * q + rr];
+      __builtin_amdgcn_wave_barrier();
+      for (int e = lane; e < 8 * ROWF; e += 64) {
+        const int rl = e / ROWF;
+        const int rem = e - rl * ROWF;
+        const int o = cout0 + 8 * q + rl;
+        const int c = cin_w + rem / T;
+        if (o < d.Cout && c < d.Cin) atomicAdd(gWt + ((long)o * d.Cin + cin_w) * T + rem, tw[e]);
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  if (d.gb && ct == 0) {
+    bsum += __shfl_xor(bsum, 32, 64);
+    if (kh == 0 && cout0 + j < d.Cout) atomicAdd(gbt + cout0 + j, d.scale * bsum);
+  }
+#ifdef DBM_WG_TIMING
+  __builtin_amdgcn_s_waitcnt(0);
+  if (tid == 0 && blockIdx.x < 8192) {
+    WG_T(tZ);
+    g_dbg[4 * blockIdx.x] = tS; g_dbg[4 * blockIdx.x + 1] = tK; g_dbg[4 * blockIdx.x + 2] = tZ - tE; g_dbg[4 * blockIdx.x + 3] = tZ - t00;
+  }
+#endif
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Row-band LDS-DMA form: 3x3 and 4x4 layers on planes too large for whole-image bands (the 18x18 / 36x36 layers of
 // the generator tail and of the discriminator), any stride, with or without the folded nearest x2 resize.
 // A band = R output rows of one image.  Both operands land with `global_load_lds_dword` (per-lane source address,
@@ -1310,6 +1505,7 @@ void WgradBatch::reset() {
   d_tiny = nullptr;
   n_tiny = tiny_wgs = 0;
   tiny_flops = 0.0;
+  wave_dma_9x9 = false;
   desc_cat.clear();
   desc_S.clear();
   for (int g = 0; g < NCAT; ++g) {
@@ -1354,6 +1550,10 @@ void WgradBatch::build() {
     total_wg[g] = F.total_wg; fold_wgs[g] = F.fold_wgs;
     lds[g] = F.lds; flops[g] = F.flops; abytes[g] = F.abytes;
     if (F.plans.empty()) continue;
+    if (kWgradKernels[g] == wgrad_wave_dma_kernel) {
+      wave_dma_9x9 = true;
+      for (const WgradPlan& q : F.plans) wave_dma_9x9 = wave_dma_9x9 && q.d.OH == 9 && q.d.OW == 9 && q.IB == 1;
+    }
     if (F.arena_floats) {  // pair buffers: zero between launches (the fold kernel clears what it read)
       DBM_HIP(hipMalloc((void**)&d_arena[g], F.arena_floats * sizeof(float)));
       DBM_HIP(hipMemset(d_arena[g], 0, F.arena_floats * sizeof(float)));
@@ -1396,13 +1596,15 @@ void WgradBatch::launch(hipStream_t s) {
       snprintf(tag, sizeof(tag), "%s_x%d", f.tag, nplans[g]);
       g_profiler.begin(s, 1, flops[g], abytes[g], tag, total_wg[g]);
     }
-    static bool attr_set[NCAT] = {};
-    if (!attr_set[g]) {
-      DBM_HIP(hipFuncSetAttribute((const void*)kWgradKernels[g], hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_attr));
-      attr_set[g] = true;
+    // the kernel symbol of this launch: the table's, or the wave-DMA form's 9 x 9 body where every plan of the launch is one
+    const bool p9 = kWgradKernels[g] == wgrad_wave_dma_kernel && wave_dma_9x9;
+    const WgradKernel kernel = p9 ? wgrad_wave_dma_9x9_kernel : kWgradKernels[g];
+    static bool attr_set[NCAT + 1] = {};
+    if (!attr_set[p9 ? NCAT : g]) {
+      DBM_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, f.lds_attr));
+      attr_set[p9 ? NCAT : g] = true;
     }
-    hipLaunchKernelGGL(kWgradKernels[g], dim3(total_wg[g]), dim3(f.threads), lds[g], s, (const WgradPlan*)d_plans[g], (const int*)d_starts[g],
-                       nplans[g]);
+    hipLaunchKernelGGL(kernel, dim3(total_wg[g]), dim3(f.threads), lds[g], s, (const WgradPlan*)d_plans[g], (const int*)d_starts[g], nplans[g]);
     DBM_HIP(hipGetLastError());
     if (fold_wgs[g]) {
       static const bool abl_fold = (dbm_abl_skip() & 8) != 0;  // (libdbm_measure.so only)
