@@ -12,8 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib
-
-WORKSPACE_DEFAULT = 1 << 30   # bytes of block staging per batch of a resident read
+from .resident import WORKSPACE_DEFAULT   # (block_writes.py takes the same default)
 
 
 class BlockPlan:

@@ -25,8 +25,8 @@ import struct
 
 import numpy as np
 
-from . import _lib, block_reads
-from .block_reads import WORKSPACE_DEFAULT, BlockPlan
+from . import _lib, block_reads, block_writes
+from .block_reads import BlockPlan
 from .resident import DeviceArray, GridGeometry, devptr
 
 TILE = 256  # GDAL's default block size for tiled=True
@@ -435,22 +435,14 @@ def write_geotiff_resident(outfilepath, window_bound, array, dtype=None, nodatav
 
     array: a float32 DeviceArray of shape (1, H, W) or (H, W), or a resident Raster; dtype int16 or float32 (the default);
     compression "lzw" or "none" (the samples as they are: as in save_array_to_grid the predictor then has no effect); predictor 1 or
-    2.  workspace_limit: bytes of raw blocks plus stream slots per batch (default 1 GiB; one block always goes through).
+    2.  workspace_limit: bytes of raw blocks plus their stream slots per batch (block_writes: default 1 GiB; one block always goes).
     overviews: the number of reduced-resolution images behind the first one, or "auto" (`overview_shapes`), as in save_array_to_grid:
     one dbm_grid_overviews call builds them all next to the plane -- float32 planes one behind the other in one allocation of at most
     a third of the plane's size (1/4 + 1/16 + ..., a little more at odd sizes); for int16 the canvas is cast while it is read, never
     copied -- and every level then goes through the same batches as the first image.  Anything else raises a ValueError that names
     the argument, before any device work."""
     who = "write_geotiff_resident"
-    from .tiling import Raster
-
-    if isinstance(array, Raster):
-        if array._dev is None:
-            raise ValueError(f"{who}: array: the Raster is not resident (a NumPy raster is written by save_array_to_grid)")
-        array = array._dev
-    if not isinstance(array, DeviceArray):
-        raise ValueError(f"{who}: array must be a float32 DeviceArray or a resident Raster, not {type(array).__name__} "
-                         "(a NumPy array is written by save_array_to_grid)")
+    array = block_writes.resident_plane_to_write(array, who, "save_array_to_grid")
     if array.dtype != np.float32:
         raise ValueError(f"{who}: array holds {array.dtype.name}: only float32 planes are written")
     shape = tuple(array.shape)
@@ -468,11 +460,7 @@ def write_geotiff_resident(outfilepath, window_bound, array, dtype=None, nodatav
     if comp == 1:
         predictor = 1
     epsg = _epsg_of(crs)
-    if workspace_limit is None:
-        workspace_limit = WORKSPACE_DEFAULT
-    workspace_limit = int(workspace_limit)
-    if workspace_limit < 1:
-        raise ValueError(f"{who}: workspace_limit must be positive")
+    workspace_limit = block_writes.write_options(workspace_limit, who)
     shapes = overview_shapes(H, W, overviews, who, "overviews")
     if shapes and dt == np.int16:
         _finite_nodata(nodataval, who)
@@ -487,22 +475,14 @@ def write_geotiff_resident(outfilepath, window_bound, array, dtype=None, nodatav
             raise ValueError(f"{who}: array: blocks of {th} x {tw} samples hold 2^31 bytes or more")
         nblocks = -(-h // th) * -(-w // tw)
         worst = block_bytes * 3 // 2 + 64 if comp == 5 else block_bytes   # a block's bytes in the download, before rounding up to even
-        per_batch = max(1, min(workspace_limit // (block_bytes + (worst if comp == 5 else 0)), ((1 << 31) - 1) // th, nblocks))
+        per_batch = block_writes.blocks_per_call(workspace_limit, block_bytes, worst if comp == 5 else 0, th, nblocks)
         return th, tw, nblocks, worst, per_batch
 
     def streams(plane, h, w, th, tw, nblocks, worst, per_batch):
-        out = np.empty(per_batch * ((worst + 1) & ~1), dtype=np.uint8)
-        sizes = np.zeros(per_batch, dtype=np.uintp)
-        view = memoryview(out)
-        for first in range(0, nblocks, per_batch):
-            n = min(per_batch, nblocks - first)
+        def encode(first, n, out, sizes):
             ctx.call("dbm_tiff_encode", devptr(plane), h, w, sample_type, th, tw, 1 if tiled else 0, predictor, comp, first, n, devptr(out),
                      out.size, devptr(sizes))
-            pos = 0
-            for k in range(n):
-                size = int(sizes[k])
-                yield view[pos:pos + size]
-                pos += (size + 1) & ~1
+        return block_writes.encoded_batches(nblocks, per_batch, worst, encode)
 
     plans = [plan(h, w) for h, w in [(H, W)] + shapes]   # (every refusal before any device work)
     levels = _device_pyramid(array, H, W, sample_type, nodataval, shapes)

@@ -29,6 +29,7 @@ import numpy as np
 
 from . import _lib, block_reads
 from .block_reads import BlockPlan as ChunkPlan   # (the plan of a netCDF variable holds all eight columns)
+from .block_writes import blocks_per_call, deflate_slot, encoded_batches, resident_plane_to_write, write_options
 from .resident import DeviceArray, GridGeometry, devptr
 
 INFLATE_DEFAULT = "device"    # where read_netcdf_resident inflates deflated chunks (the measurements that decided it)
@@ -907,11 +908,6 @@ _GROUP_LEAF_K, _GROUP_INTERNAL_K, _CHUNK_K = 4, 16, 32    # the superblock's two
 _FILL_BITS = 0x7FC00000                                   # _FillValue and the storage fill value: the quiet NaN
 
 
-def deflate_slot(nbytes):
-    """The bytes that always hold the stream of `nbytes` input bytes: no input byte costs more than 9 bits."""
-    return nbytes + nbytes // 8 + 16
-
-
 def deflate_encode_blocks(blocks, nthreads=None):
     """blocks: (n, block_bytes) uint8 -> list of bytes objects: one zlib stream each, fixed Huffman code (dbm_deflate_encode_blocks: the
     device encoder's loop on host threads)."""
@@ -1176,48 +1172,23 @@ def write_netcdf_resident(path, window_bound, array, variable="z", chunks=(256, 
     """The mirror of `read_netcdf_resident`: writes the netCDF-4 file `path` from a plane that lives in HBM and returns the path.
     Cutting the chunks, the row order, the shuffle and deflate (one wavefront per chunk) run on the GPU (dbm_chunk_encode); only the
     stored bytes cross PCIe.  The file is byte for byte the one `save_grid_to_netcdf` writes from the downloaded plane with the same
-    arguments.  array: a float32 DeviceArray of shape (1, H, W) or (H, W), or a resident Raster.  workspace_limit:
-    bytes of raw chunks plus stream slots per batch (default 1 GiB; one chunk always goes through).  Anything else raises a
+    arguments.  array: a float32 DeviceArray of shape (1, H, W) or (H, W), or a resident Raster.  workspace_limit: bytes
+    of raw blocks plus their stream slots per batch (block_writes: default 1 GiB; one block always goes).  Anything else raises a
     ValueError that names the argument, before any device work."""
     who = "write_netcdf_resident"
-    from .block_reads import WORKSPACE_DEFAULT
-    from .tiling import Raster
-
-    if isinstance(array, Raster):
-        if array._dev is None:
-            raise ValueError(f"{who}: array: the Raster is not resident (a NumPy raster is written by save_grid_to_netcdf)")
-        array = array._dev
-    if not isinstance(array, DeviceArray):
-        raise ValueError(f"{who}: array must be a float32 DeviceArray or a resident Raster, not {type(array).__name__} "
-                         "(a NumPy array is written by save_grid_to_netcdf)")
+    array = resident_plane_to_write(array, who, "save_grid_to_netcdf")
     H, W, ch, cw, deflate = _write_arguments(who, window_bound, array.shape, array.dtype, variable, chunks, shuffle, compression)
-    if workspace_limit is None:
-        workspace_limit = WORKSPACE_DEFAULT
-    try:
-        workspace_limit = int(workspace_limit)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: workspace_limit {workspace_limit!r} is not a number of bytes") from None
-    if workspace_limit < 1:
-        raise ValueError(f"{who}: workspace_limit must be positive")
+    workspace_limit = write_options(workspace_limit, who)
     ctx = array.ctx
     chunk_bytes = ch * cw * 4
     nchunks = -(-H // ch) * -(-W // cw)
     worst = deflate_slot(chunk_bytes) if deflate else chunk_bytes      # a chunk's bytes in the download, before rounding up to even
     groups = -(-ch * cw // 1024)                                       # workgroups per chunk of the cutting kernel
-    per_batch = max(1, min(workspace_limit // (chunk_bytes + (worst if deflate else 0)), ((1 << 31) - 1) // groups, nchunks))
+    per_batch = blocks_per_call(workspace_limit, chunk_bytes, worst if deflate else 0, groups, nchunks)
 
-    def streams():
-        out = np.empty(per_batch * ((worst + 1) & ~1), dtype=np.uint8)
-        sizes = np.zeros(per_batch, dtype=np.uintp)
-        view = memoryview(out)
-        for first in range(0, nchunks, per_batch):
-            n = min(per_batch, nchunks - first)
-            ctx.call("dbm_chunk_encode", devptr(array), H, W, ch, cw, -1 if y_ascending else 1, 1 if shuffle else 0, 8 if deflate else 1,
-                     first, n, devptr(out), out.size, devptr(sizes))
-            pos = 0
-            for k in range(n):
-                size = int(sizes[k])
-                yield view[pos:pos + size]
-                pos += (size + 1) & ~1
+    def encode(first, n, out, sizes):
+        ctx.call("dbm_chunk_encode", devptr(array), H, W, ch, cw, -1 if y_ascending else 1, 1 if shuffle else 0, 8 if deflate else 1,
+                 first, n, devptr(out), out.size, devptr(sizes))
 
-    return _write_container(os.fspath(path), window_bound, H, W, variable, ch, cw, bool(shuffle), deflate, bool(y_ascending), streams())
+    return _write_container(os.fspath(path), window_bound, H, W, variable, ch, cw, bool(shuffle), deflate, bool(y_ascending),
+                            encoded_batches(nchunks, per_batch, worst, encode))

@@ -22,6 +22,7 @@ import zlib
 import numpy as np
 
 from . import _lib
+from .block_writes import blocks_per_call, deflate_slot, encoded_batches, write_options
 from .resident import DeviceArray, GridGeometry, devptr, plane_shape, to_device
 
 MAX_SLICES = 2048                # edges and colours live in LDS (relief.hip)
@@ -375,10 +376,6 @@ def default_band_rows(W, channels):
     return max(1, BAND_BYTES // (int(W) * int(channels) + 1))
 
 
-def deflate_slot(n):
-    return n + n // 8 + 16
-
-
 def _image_shape(who, shape, dtype):
     shape = tuple(int(s) for s in shape)
     if np.dtype(dtype) != np.uint8:
@@ -435,24 +432,11 @@ def _write_container(path, H, W, channels, idat_bytes, segments):
     return path
 
 
-def _batched_segments(H, W, channels, band_rows, per_batch, encode):
-    """The segments of all bands, `per_batch` bands per call of encode(first, n, out, sizes, adlers)."""
+def _segments(H, W, channels, band_rows, per_batch, encode):
+    """(bytes, adler, length of the band) of all bands, `per_batch` bands per call of encode(first, n, out, sizes, adlers)."""
     row = W * channels + 1
-    bands = -(-H // band_rows)
-    worst = (deflate_slot(band_rows * row) + 1) & ~1
-    out = np.empty(per_batch * worst, dtype=np.uint8)
-    sizes = np.zeros(per_batch, dtype=np.uintp)
-    adlers = np.zeros(per_batch, dtype=np.uint32)
-    view = memoryview(out)
-    for first in range(0, bands, per_batch):
-        n = min(per_batch, bands - first)
-        encode(first, n, out, sizes, adlers)
-        pos = 0
-        for k in range(n):
-            size = int(sizes[k])
-            rows = min(band_rows, H - (first + k) * band_rows)
-            yield view[pos:pos + size], int(adlers[k]), rows * row
-            pos += (size + 1) & ~1
+    batches = encoded_batches(-(-H // band_rows), per_batch, deflate_slot(band_rows * row), encode, extras=(np.uint32,))
+    return ((data, adler, min(band_rows, H - k * band_rows) * row) for k, (data, adler) in enumerate(batches))
 
 
 def write_world_file(path, geometry):
@@ -481,14 +465,14 @@ def save_png(path, image, filter=1, band_rows=None, idat_bytes=1 << 20, world_fi
     image = np.ascontiguousarray(image)
     threads = int(nthreads) if nthreads else min(16, os.cpu_count() or 1)
     band_bytes = band_rows * (W * channels + 1)
-    per_batch = max(1, min(-(-H // band_rows), (256 << 20) // band_bytes))
+    per_batch = blocks_per_call(256 << 20, band_bytes, 0, 1, -(-H // band_rows))
     lib = _lib.lib()
 
     def encode(first, n, out, sizes, adlers):
         _lib.check(lib.dbm_png_encode_host(devptr(image), H, W, channels, filter, band_rows, first, n, devptr(out), out.size, devptr(sizes),
                                            devptr(adlers), threads))
 
-    _write_container(os.fspath(path), H, W, channels, idat_bytes, _batched_segments(H, W, channels, band_rows, per_batch, encode))
+    _write_container(os.fspath(path), H, W, channels, idat_bytes, _segments(H, W, channels, band_rows, per_batch, encode))
     if world_file is not None:
         write_world_file(path, world_file)
     return path
@@ -498,33 +482,24 @@ def write_png_resident(path, image, filter=1, band_rows=None, idat_bytes=1 << 20
     """Writes the resident uint8 DeviceArray `image` (H, W) or (H, W, 1 | 3 | 4) as the PNG `path` and returns the path.  Filtering and
     deflate (one wavefront per band of band_rows rows) run on the GPU (dbm_png_encode); only the compressed segments cross PCIe.  The
     file is byte for byte the one `save_png` writes from the downloaded image with the same arguments.
-    workspace_limit: bytes of filtered bands plus segment slots per batch (default 1 GiB; one band always goes through)."""
+    workspace_limit: bytes of raw blocks plus their stream slots per batch (block_writes: default 1 GiB; one block always goes)."""
     who = "write_png_resident"
-    from .block_reads import WORKSPACE_DEFAULT
-
     if not isinstance(image, DeviceArray):
         raise ValueError(f"{who}: image must be a uint8 DeviceArray, not {type(image).__name__} (a NumPy array is written by save_png)")
     H, W, channels, band_rows, idat_bytes = _png_arguments(who, image.shape, image.dtype, filter, band_rows, idat_bytes)
     if world_file is not None and not isinstance(world_file, GridGeometry):
         raise ValueError(f"{who}: world_file must be a GridGeometry, not {type(world_file).__name__}")
-    if workspace_limit is None:
-        workspace_limit = WORKSPACE_DEFAULT
-    try:
-        workspace_limit = int(workspace_limit)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: workspace_limit {workspace_limit!r} is not a number of bytes") from None
-    if workspace_limit < 1:
-        raise ValueError(f"{who}: workspace_limit must be positive")
+    workspace_limit = write_options(workspace_limit, who)
     ctx = image.ctx
     band_bytes = band_rows * (W * channels + 1)
     groups = -(-band_bytes // 16384)                                   # workgroups per band of the filter kernel
-    per_batch = max(1, min(workspace_limit // (band_bytes + deflate_slot(band_bytes)), ((1 << 31) - 1) // groups, -(-H // band_rows)))
+    per_batch = blocks_per_call(workspace_limit, band_bytes, deflate_slot(band_bytes), groups, -(-H // band_rows))
 
     def encode(first, n, out, sizes, adlers):
         ctx.call("dbm_png_encode", devptr(image), H, W, channels, filter, band_rows, first, n, devptr(out), out.size, devptr(sizes),
                  devptr(adlers))
 
-    _write_container(os.fspath(path), H, W, channels, idat_bytes, _batched_segments(H, W, channels, band_rows, per_batch, encode))
+    _write_container(os.fspath(path), H, W, channels, idat_bytes, _segments(H, W, channels, band_rows, per_batch, encode))
     if world_file is not None:
         write_world_file(path, world_file)
     return path

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 
 REGISTRATIONS = {"gridline": 0, "pixel": 1}
+WORKSPACE_DEFAULT = 1 << 30   # bytes of block staging per batch of a resident read (block_reads.py) or write (block_writes.py)
 
 
 class DeviceArray:

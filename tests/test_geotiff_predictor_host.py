@@ -128,8 +128,9 @@ def test_write_geotiff_resident_refusals_need_no_device(tmp_path):
     for compression in ("deflate", "zstd", 8):
         with pytest.raises(ValueError, match="write_geotiff_resident: unsupported compression"):
             write(out, BOUND, good, compression=compression)
-    with pytest.raises(ValueError, match="write_geotiff_resident: workspace_limit"):
-        write(out, BOUND, good, workspace_limit=0)
+    for limit in (0, []):   # (not positive; not a number: the documented ValueError, where a bare int() raised TypeError)
+        with pytest.raises(ValueError, match="write_geotiff_resident: workspace_limit"):
+            write(out, BOUND, good, workspace_limit=limit)
     with pytest.raises(ValueError, match="crs"):
         write(out, BOUND, good, crs="+proj=utm +zone=33")
     assert not os.path.exists(out + ".tif")

@@ -167,6 +167,20 @@ def test_batches_write_the_same_file(dbm, tmp_path, plane, monkeypatch):
     same_bytes(one, whole)
 
 
+def test_a_short_last_batch_writes_the_host_writers_file(dbm, tmp_path, monkeypatch):
+    """Six strips of 8 samples a row (five of 256 rows, one of 20), four per call: the last call takes the two that are left."""
+    a = np.random.default_rng(6).normal(0.0, 300.0, (1300, 8)).astype(np.float32)
+    strip = 256 * 8 * 2
+    calls = []
+    real = dbm.default_context().call
+    monkeypatch.setattr(dbm.default_context(), "call", lambda name, *args: (calls.append((name,) + args[9:11]), real(name, *args))[1],
+                        raising=False)
+    got, want = both_files(dbm, tmp_path, a, dtype="int16", tiled=False, compression="lzw", workspace_limit=4 * (strip + strip * 3 // 2 + 64))
+    monkeypatch.undo()
+    assert [c for c in calls if c[0] == "dbm_tiff_encode"] == [("dbm_tiff_encode", 0, 4), ("dbm_tiff_encode", 4, 2)]
+    same_bytes(got, want)
+
+
 @pytest.mark.parametrize("tiled", [True, False])
 @pytest.mark.parametrize("dtype", ["int16", "float32"])
 def test_uncompressed_with_predictor_2(dbm, tmp_path, plane, dtype, tiled):

@@ -239,6 +239,22 @@ def test_the_png_equals_the_host_writers(dbm, tmp_path, png_sources, shape, band
         assert np.array_equal(np.asarray(im).reshape(shape), image)
 
 
+def test_a_short_last_batch_of_bands_writes_the_host_writers_png(dbm, tmp_path, png_sources, monkeypatch):
+    """37 rows in bands of 8: five bands, the last of 5 rows; four bands per call, so the last call takes one."""
+    shape = (37, 29, 4)
+    image = png_sources(shape)["relief"]
+    dev = dbm.DeviceArray(shape, dtype=np.uint8).set(image)
+    band = 8 * (29 * 4 + 1)
+    calls = []
+    real = dev.ctx.call
+    monkeypatch.setattr(dev.ctx, "call", lambda name, *args: (calls.append((name,) + args[6:8]), real(name, *args))[1], raising=False)
+    got = dbm.write_png_resident(str(tmp_path / "dev.png"), dev, band_rows=8, idat_bytes=4096, workspace_limit=4 * (band + band + band // 8 + 16))
+    monkeypatch.undo()
+    assert [c for c in calls if c[0] == "dbm_png_encode"] == [("dbm_png_encode", 0, 4), ("dbm_png_encode", 4, 1)]
+    want = dbm.save_png(str(tmp_path / "host.png"), dev.get(), band_rows=8, idat_bytes=4096)
+    assert open(got, "rb").read() == open(want, "rb").read()
+
+
 def test_png_refusals_and_the_world_file(dbm, tmp_path):
     from deepbedmap_amd import _lib
 
