@@ -144,8 +144,9 @@ int dbm_op_conv2d_wgrad_batch(dbm_ctx* ctx, const dbm_wgrad_desc* descs, int L, 
     key.assign(descs, descs + L);
     for (int i = 0; i < L; ++i) {
       const dbm_wgrad_desc& q = descs[i];
-      DBM_CHECK(q.x && q.dy && q.gW && q.C % 32 == 0 && q.C >= 32 && q.N >= 1 && (q.ups == 0 || q.ups == 1),
-                "wgrad batch op: x, dy, gW are required; C must be a multiple of 32");
+      // (C % 4: a ragged last input tile, e.g. 36 channels, as far as the 16-byte staging of the LDS-DMA forms takes one)
+      DBM_CHECK(q.x && q.dy && q.gW && q.C % 4 == 0 && q.C >= 32 && q.N >= 1 && (q.ups == 0 || q.ups == 1),
+                "wgrad batch op: x, dy, gW are required; C must be a multiple of 4, at least 32");
       const int OH = conv_out_extent(q.H << q.ups, q.k, q.stride, q.pad), OW = conv_out_extent(q.W << q.ups, q.k, q.stride, q.pad);
       DBM_CHECK(OH >= 1 && OW >= 1, "wgrad batch op: empty output plane");
       batch.add(wgrad_desc(q.x, q.xsn, q.C, q.H, q.W, q.ups, q.dy, q.dysn, q.O, OH, OW, q.k, q.stride, q.pad, q.N, q.scale, q.gW, q.gb));

@@ -23,6 +23,7 @@
 // (later: wgrad_direct_kernel / wgrad_1x1_kernel for large planes, wgrad_s2tiny_kernel for the deep discriminator layers --
 // 4x4 stride 2 AND, round 3, 3x3 stride 1 on planes of <= 4 x 4 -- each described where it is defined)
 #include "dbm_internal.h"
+#include "wgrad_9x9_index.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -593,21 +594,25 @@ __global__ __launch_bounds__(128, 2) void wgrad_wave_dma_kernel(const WgradPlan*
 
 // ---------------------------------------------------------------------------------------------------------------
 // The wave-DMA form on 9 x 9 planes with one image per band -- the trunk's 181 layers.  WgradBatch::launch runs this kernel in place
-// of wgrad_wave_dma_kernel when EVERY plan of the launch is one (same plans, same LDS layout minus the position table, same grid).
+// of wgrad_wave_dma_kernel when EVERY plan of the launch is one (same plans, same grid, same LDS request: this layout needs less).
 // The geometry is a compile-time constant and the K loop is unrolled over the band's 41 steps: every LDS read is a per-lane base
 // register plus an immediate, no position table is built or read, and no vector instruction sits between the MFMAs (fp32 MFMAs and
 // vector-ALU instructions exclude each other on a SIMD, DESIGN 4.1: the general loop's eight per step were paid in MFMA time).
-// The same MFMAs on the same operands in the same order as the general kernel: the same bits
-// (tests/test_gpu_exposed_kernels_bitwise.py).  Staging, bias gradient and epilogues are the general kernel's text.
+// x lands as dy does: an unframed slab [channel][81] per wavefront by 16-byte DMA (eleven instructions for a full tile; the framed
+// plane of the general kernel takes two 4-byte ones per channel).  Without the frame a tap that leaves the plane reads a cell of the
+// neighbouring row or plane; its A value then comes from a zero region (three A bases: both halves from the dy slab, or one of them
+// from the zero region), and an MFMA whose two halves are both outside is not issued -- 339 of the general kernel's 369 per band.
+// wgrad_9x9_index.h holds layout, offsets and the validity table; tools/wgrad_9x9_index_check.cpp replays them on the CPU.
+// The remaining MFMAs are the general kernel's, in its order and on its accumulators, and what changed adds +-0 to accumulators that
+// are never -0: the same bits for finite inputs (tests/test_gpu_exposed_kernels_bitwise.py).  A non-finite x beside a border, which
+// the frame kept out of the tap that leaves the plane there, now meets a zero A value and gives NaN.
+// Bias gradient and epilogues are the general kernel's text.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(128, 2) void wgrad_wave_dma_9x9_kernel(const WgradPlan* __restrict__ plans, const int* __restrict__ starts,
                                                                    int nplans) {
-  constexpr int T = 9;
-  constexpr int H = 9, W = 9, W1 = W + 1;
-  constexpr int plane = H * W;           // 81
-  constexpr int slab = 32 * plane;       // floats of the image's 32 dy planes
-  constexpr int PS = (H + 2) * W1;       // 110: framed x plane
-  constexpr int STEPS = (plane + 1) / 2; // 41: step s feeds positions 2 s + kh; the last one's kh = 1 half is the padding position 81
+  using namespace wgrad9;                // T, PLANE, SLAB, STEPS, the LDS layout and the validity table
+  constexpr int plane = PLANE;           // 81
+  constexpr int slab = SLAB;             // floats of 32 planes
   typedef __attribute__((address_space(3))) void* lds_ptr;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int lo = 0, hi = nplans - 1;
@@ -624,9 +629,8 @@ __global__ __launch_bounds__(128, 2) void wgrad_wave_dma_9x9_kernel(const WgradP
   local /= p.groups;
   const int by = local % p.coutTiles;
   const int bz = local / p.coutTiles;
-  float* ldsY = lds;                         // slab
-  float* ldsX0 = ldsY + slab + 4;            // 2 x 32 * PS, behind a 4-float zero guard (tap (0,0) of cell (0,0))
-  float* ldsX = ldsX0 + wave * 32 * PS;      // this wavefront's framed planes
+  float* ldsY = lds + LDS_Y;                 // slab
+  float* ldsX = lds + lds_x(wave);           // this wavefront's x slab; a zero guard in front of the first, the zero region behind the second
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int j = lane & 31, kh = lane >> 5;
@@ -636,20 +640,11 @@ __global__ __launch_bounds__(128, 2) void wgrad_wave_dma_9x9_kernel(const WgradP
   for (int t = 0; t < T; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  for (int e = tid; e < slab + 4 + 2 * 32 * PS; e += 128) lds[e] = 0.f;  // frames, guard, and the planes of ragged tiles
-  // per-lane source cell of the two DMA instructions that fill one framed plane (cells lane, lane + 64)
-  int soff[2];
-  bool sval[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int r = lane + 64 * k;
-    const int yy = r / W1, xx = r - yy * W1;
-    sval[k] = r < PS && yy >= 1 && yy <= H && xx < W;
-    soff[k] = sval[k] ? (yy - 1) * W + xx : 0;
-  }
+  for (int e = tid; e < LDS_FLOATS; e += 128) lds[e] = 0.f;  // guard, zero region, and the planes of ragged tiles
   const int nco = min(32, d.Cout - cout0), nci = max(0, min(32, d.Cin - cin_w));
   const bool wave_active = nci > 0;
   const int q4y = (nco * plane) >> 2;
+  const int q4x = (nci * plane) >> 2;  // (p.fast: the tile's planes are one 16-byte-aligned run of a multiple of four floats)
   float bsum = 0.f;
 #ifdef DBM_WG_TIMING
   unsigned long long tS = 0, tK = 0;
@@ -663,14 +658,12 @@ __global__ __launch_bounds__(128, 2) void wgrad_wave_dma_9x9_kernel(const WgradP
       const float4* srcy = (const float4*)(d.dy + (long)n * d.dysn + (long)cout0 * d.dysc);
       for (int i0 = 64 * wave; i0 < q4y; i0 += 128)  // the two wavefronts split the shared slab
         if (i0 + lane < q4y) __builtin_amdgcn_global_load_lds(srcy + i0 + lane, (lds_ptr)(ldsY + 4 * i0), 16, 0, 0);
-      const float* srcx = d.x + (long)n * d.xsn + (long)cin_w * d.xsc;
-      for (int c = 0; c < nci; ++c) {
-        if (sval[0]) __builtin_amdgcn_global_load_lds(srcx + c * plane + soff[0], (lds_ptr)(ldsX + c * PS), 4, 0, 0);
-        if (sval[1]) __builtin_amdgcn_global_load_lds(srcx + c * plane + soff[1], (lds_ptr)(ldsX + c * PS + 64), 4, 0, 0);
-      }
+      const float4* srcx = (const float4*)(d.x + (long)n * d.xsn + (long)cin_w * d.xsc);
+      for (int i0 = 0; i0 < q4x; i0 += 64)  // each wavefront lands its own tile
+        if (i0 + lane < q4x) __builtin_amdgcn_global_load_lds(srcx + i0 + lane, (lds_ptr)(ldsX + 4 * i0), 16, 0, 0);
     } else {  // (nbands == N with one image per band: kept with the general kernel's staging text)
       for (int e = tid; e < slab; e += 128) ldsY[e] = 0.f;
-      for (int e = lane; e < 32 * PS; e += 64) ldsX[e] = 0.f;
+      for (int e = lane; e < slab; e += 64) ldsX[e] = 0.f;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -690,44 +683,44 @@ __global__ __launch_bounds__(128, 2) void wgrad_wave_dma_9x9_kernel(const WgradP
       bsum += ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
     }
     if (wave_active) {
-      // Position q has dy offset q and x offset q + q / 9 (rows of W1 = 10 cells, relative to ldsX - 1).  Within a step the kh = 1 lanes
-      // are one cell further than the kh = 0 lanes, or two where 2 s is a row's last position: two base registers, the step's offset an
-      // immediate.  The last step has bases of its own: the padding position reads its A value from the zero guard behind the slab
-      // (the general kernel selects 0.f there) and its B values from position 0's cells, as the general kernel's table entry 0 does.
+      // Position q has dy offset q and x offset q: the kh = 1 lanes are one cell further than the kh = 0 lanes, the step's offset is an
+      // immediate.  One B base (the wavefront's x plane j, a row and a cell back: tap (0, 0)), three A bases by which lane halves read
+      // the dy slab and which the zero region (wgrad_9x9_index.h).  The last step's kh = 1 half is the padding position: the zero
+      // region for every tap (the general kernel selects 0.f there).
       // (lds_base, dbm_internal.h: the slabs' constant offsets stay out of the immediates, which then fit ds_read2_b32)
-      const float* xrow = ldsX - 1 + j * PS;
-      const lds_cf aP = lds_base(ldsY + j * plane + kh);
-      const lds_cf aT = lds_base(kh ? ldsY + slab - (plane - 1) : ldsY + j * plane);
-      const lds_cf bP = lds_base(xrow + kh);
-      const lds_cf bR = lds_base(xrow + 2 * kh);
-      const lds_cf bT = lds_base(kh ? xrow - (plane - 1 + (plane - 1) / W) : xrow);
-      auto fetch = [&](int s, float& an, float (&bn)[T]) {   // operands of step s (s: a constant once unrolled)
-        const int kp = 2 * s, xo = kp + kp / W;
-        const bool last = s == STEPS - 1;
-        const lds_cf ap = last ? aT : aP;
-        const lds_cf bp = last ? bT : (kp % W == W - 1 ? bR : bP);
-        an = ap[kp];
+      lds_cf aB[4];
+      aB[NONE] = nullptr;
+      aB[KH0] = lds_base(lds + a_base(KH0, j, kh));
+      aB[KH1] = lds_base(lds + a_base(KH1, j, kh));
+      aB[BOTH] = lds_base(lds + a_base(BOTH, j, kh));
+      const lds_cf bP = lds_base(lds + b_base(wave, j, kh));
+      auto fetch = [&](int s, float (&an)[4], float (&bn)[T]) {   // operands of step s (s: a constant once unrolled)
 #pragma unroll
-        for (int t = 0; t < T; ++t) bn[t] = bp[xo + (t / 3) * W1 + (t % 3)];
+        for (int v = KH0; v <= BOTH; ++v)
+          if (step_uses(s, v)) an[v] = aB[v][a_off(s)];
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+          if (valid(s, t) != NONE) bn[t] = bP[b_off(s, t)];
       };
       // software pipelined by one step, as the general loop is: the reads of step s + 1 are dealt out between the MFMAs of step s
       // (two operand sets in ping-pong; the scheduling barriers pin the order)
-      auto half = [&](int s, float& ac, float (&bc)[T], float& an, float (&bn)[T]) {
+      auto half = [&](int s, float (&ac)[4], float (&bc)[T], float (&an)[4], float (&bn)[T]) {
         __builtin_amdgcn_sched_barrier(0);
         if (s + 1 < STEPS) fetch(s + 1, an, bn);
 #pragma unroll
-        for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, bc[t], acc[t], 0, 0, 0);
+        for (int t = 0; t < T; ++t)
+          if (valid(s, t) != NONE) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[valid(s, t)], bc[t], acc[t], 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < T; ++t) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // one DS read
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);    // the remaining reads
+        for (int t = 0; t < T; ++t)
+          if (valid(s, t) != NONE) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // one DS read
+          }
+        __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);      // the remaining reads
         __builtin_amdgcn_sched_barrier(0);
       };
-      float a0, b0[T], a1, b1[T];
+      float a0[4], b0[T], a1[4], b1[T];
       fetch(0, a0, b0);
-      static_assert(STEPS % 2 == 1, "the unrolled loop ends on the first operand set");
 #pragma unroll
       for (int s = 0; s + 1 < STEPS; s += 2) {
         half(s, a0, b0, a1, b1);

@@ -913,7 +913,7 @@ typedef struct dbm_conv_launch {
 } dbm_conv_launch;
 int dbm_op_conv2d_launch(dbm_ctx* ctx, const dbm_conv_launch* args, int* report);
 /* L weight gradients as ONE batch, the training step's form: gW (O, C, k, k) += scale * sum dy * x, gb (O, or NULL) += scale * sum dy, for
- * x (N, >= C, H, W) with image stride xsn (ups = 1: the layer sees its nearest x2 resize) and dy (N, >= O, OH, OW) with image stride dysn.
+ * x (N, >= C, H, W; C % 4 == 0, C >= 32) with image stride xsn (ups = 1: the layer sees its nearest x2 resize) and dy (N, >= O, OH, OW) with image stride dysn.
  * Two descriptors may name the same gW / gb (the real and the fake graph).  cleared_target = 1: the caller guarantees every gW / gb is
  * zero and receives nothing else.  dbm_set_deterministic selects the folding; a call with the descriptors of the previous call reuses
  * its batch (a mode switch re-plans it).  cat_out / S_out (HOST, L ints each, may be NULL): per descriptor the kernel category (-1

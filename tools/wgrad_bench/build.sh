@@ -5,5 +5,5 @@ set -e
 cd "$(dirname "$0")"
 sed 's|#include "dbm_internal.h"|#include "../../deepbedmap_amd/csrc/dbm_internal.h"|' ../../deepbedmap_amd/csrc/wgrad.hip > wgrad_abl.hip
 for t in trunk discriminator; do
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip -DDBM_WG_TIMING -o $t $t.cpp
+  hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip -DDBM_WG_TIMING -I ../../deepbedmap_amd/csrc -o $t $t.cpp
 done
